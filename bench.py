@@ -3,7 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W                      # BASELINE configs[1] (the headline)
     python bench.py --dtype bf16 --clips 4                             # configs[2]: bf16 contractions, 4 clips in lock-step
-    python bench.py --interval 1 --maps-per-launch 32                  # configs[4]: every frame a key frame; warp /
+    python bench.py --interval 1 --maps-per-launch 32 --full           # configs[4]: every frame a key frame; warp /
                                                                        #   aggregate roofline on 32 maps per launch (HBM-resident)
 
 Metric (BASELINE.json): frames/sec at 1000x600, key_interval = 10, synthetic VID-shaped clips,
@@ -23,10 +23,16 @@ N > 1: launched by torch.distributed.run, one rank per GPU; rank r runs clip(s) 
 independent: "scaling": "weak", no data-path collective); the only collective is the final
 all_gather of per-frame detection counts over RCCL, outside the per-frame path.
 
-After the timed region rank 0 adds, untimed: `roofline` (HIP events around every launch of the
-hand-written ops, the same frames re-issued eagerly; a captured graph carries no per-launch events),
-`parity` (the first frames of the clip against oracle/graph_ref.py: end to end, and stage by stage on
-the GPU's own inputs) and `cpu_baseline` (the oracle graph timed on the host cores).
+A plain run sets up, warms up, times the --steps steps and prints the line.  With --full, rank 0 adds after
+the timed region, untimed: `value_spread` (the region twice more), the extra regions (`value_uploaded_inputs`,
+`value_exact_fp32`, `value_frame_by_frame`), `roofline` (HIP events around every launch of the hand-written ops,
+the same frames re-issued eagerly; a captured graph carries no per-launch events; --maps-per-launch), `parity`
+(the first frames of the clip against oracle/graph_ref.py: end to end, and stage by stage on the GPU's own inputs)
+and `cpu_baseline` (the oracle graph timed on the host cores).
+
+--dump-outputs DIR writes what the last timed step delivered to the host (rank 0's clips) as DIR/<name>.npy:
+`detections` (K, B, classes, R, 5) float64 [x1, y1, x2, y2, score], rows past a class's count zeroed, and `counts`
+(K, B, classes) float64.  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -63,7 +69,7 @@ def parse():
     ap.add_argument('--clips', type=int, default=1,
                     help='clips per GPU advancing in lock-step, one image of each per frame on the batch axis (configs[2]: 4)')
     ap.add_argument('--maps-per-launch', type=int, default=0,
-                    help='roofline leg on this many feature maps per launch of the warp / aggregate kernels (configs[4]: 32, '
+                    help='--full: roofline leg on this many feature maps per launch of the warp / aggregate kernels (configs[4]: 32, '
                          '942 MB per launch, HBM-resident); 0 = the frame loop\'s own single-map launches')
     ap.add_argument('--settle-s', type=float, default=2.5,
                     help='setup: after graph capture, replay untimed intervals for this long before the W warm-up steps (a fresh '
@@ -101,6 +107,12 @@ def parse():
     ap.add_argument('--no-flow-stream', action='store_true', help='FlowNet after the backbone on the key stream instead of beside it')
     ap.add_argument('--cpu-budget-s', type=float, default=20.0)
     ap.add_argument('--max-unique-steps', type=int, default=16, help='distinct intervals of frames kept in HBM')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: the repeats behind `value_spread`, the uploaded-input, exact-fp32 and frame-by-frame '
+                         'regions, the roofline legs (--maps-per-launch included), parity against the oracle and the CPU baseline.  Off: set up, '
+                         'warm up, time the --steps steps, print the line')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step delivered (detections and per-class counts of its frames) as DIR/<name>.npy')
     return ap.parse_args()
 
 
@@ -137,7 +149,8 @@ class Runner(object):
         # the key frame (uint8 HWC BGR, what a decoder returns) - uploaded `key_group - 1` intervals ahead, because a pass of key fronts needs the
         # images of its whole group - and [the K-1 non-key frames uint8 | their motion vectors fp32 | their residuals fp32], uploaded with the
         # interval.  One copy per block on a copy stream, transform (lib/utils/image.py:296-308) on the GPU behind it, into preallocated rings.
-        self.host_inputs = (not args.resident_inputs) and args.lanes > 0
+        # (they feed `value` under --host-inputs, else only the uploaded-input region of --full)
+        self.host_inputs = (not args.resident_inputs) and args.lanes > 0 and (getattr(args, 'full', False) or getattr(args, 'host_inputs', False))
         self._inputs_resident_now = not (self.host_inputs and getattr(args, 'host_inputs', False))
         if self.host_inputs:
             K, B, H, W = self.K, self.B, args.height, args.width
@@ -244,6 +257,15 @@ class Runner(object):
                         r[:, 0], r[:, 1], r[:, 2], r[:, 3:] = k * self.B + b, j, d[:, 4], d[:, :4]
                         rows.append(r)
         return np.vstack(rows) if rows else np.zeros((0, 7), np.float64)
+
+    def last_step_outputs(self):
+        """What the last step delivered to the host, once the pipeline is drained: per frame of the interval and clip, every class's
+        detections [x1, y1, x2, y2, score] (rows past the class's count zeroed: those slots hold whatever an earlier frame left) and the
+        per-class counts.  -> {name: float64 array}"""
+        counts = self.host_counts.numpy().astype(np.int64)                                 # (K, B, ncls)
+        dets = np.stack([self.host_dets_of(k).numpy() for k in range(self.K)])            # (K, B, ncls, R, 5)
+        valid = np.arange(self._R) < counts[..., None]
+        return {"detections": np.where(valid[..., None], dets, 0.0).astype(np.float64), "counts": counts.astype(np.float64)}
 
     def _deliver(self, bufs, slot):
         seg = getattr(bufs[0], 'lsfa_segment', None)
@@ -855,6 +877,23 @@ def load_launch_counts(args):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: every array as d/<name>.npy.  Above DUMP_LIMIT_BYTES in all, each array is cut to a fixed, seeded sample of its
+    rows (the last axis kept whole), in their order, its share of the limit in proportion to its size."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    budget = DUMP_LIMIT_BYTES - 1024 * len(outputs)          # (room for the .npy headers)
+    for name, a in outputs.items():
+        if total > budget:
+            rows = a.reshape(-1, a.shape[-1])
+            n = max(1, len(rows) * budget // total)
+            a = rows[np.sort(np.random.default_rng(0).choice(len(rows), n, replace=False))]
+        np.save(os.path.join(d, name + '.npy'), a)
+
+
 def main():
     args = parse()
     parity_failed = False
@@ -934,6 +973,9 @@ def main():
             r.fg.drop_fronts()
     if settle_drain:
         drain()
+    # the clip starts over from its first frame: the key features are recurrent, and the W + N steps below then depend on nothing the
+    # time-limited settle left behind - the same arguments give the same outputs in every run (--dump-outputs)
+    r.fg.first_frame(r.frames[0])
     for s in range(args.warmup):
         r.step(s, end=args.warmup)
     drain()
@@ -950,11 +992,13 @@ def main():
     drain()
     barrier()
     elapsed = time.perf_counter() - t0
-    # run-to-run spread: the same K steps twice more, each bracketed like the timed region above (`value` stays the FIRST
+    if args.dump_outputs and rank == 0:          # before anything else runs the pipeline again
+        dump_outputs(args.dump_outputs, r.last_step_outputs())
+    # --full, run-to-run spread: the same K steps twice more, each bracketed like the timed region above (`value` stays the FIRST
     # region's; the driver's fresh-box figure and a builder's warm-box one have differed by ~10 %: this makes that visible)
     repeats = [elapsed]
     host_enqueue = []            # how long the host loop of a repeat took to QUEUE its K steps (the rest of the region is waiting for the GPU)
-    for _ in range(0 if args.no_spread else 2):
+    for _ in range(2 if args.full and not args.no_spread else 0):
         barrier()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -965,22 +1009,23 @@ def main():
         barrier()
         repeats.append(time.perf_counter() - t1)
     batched = hasattr(r.fg, 'lanes') and (r.segment > 0 or r.key_group > 1)
-    prof = (r.eager_profile_batched(args.warmup) if batched else r.eager_profile_step(args.warmup)) if rank == 0 else None
+    extras = args.full and rank == 0             # the untimed legs of --full
+    prof = (r.eager_profile_batched(args.warmup) if batched else r.eager_profile_step(args.warmup)) if extras else None
     # r5: the streaming figure beside the headline: the same clip frame by frame (one extra short region; rank 0, untimed by the driver)
     other_inputs = None
-    if getattr(r, 'host_inputs', False) and rank == 0 and not args.no_frame_by_frame:
+    if getattr(r, 'host_inputs', False) and extras and not args.no_frame_by_frame:
         try:
             other_inputs = r.other_inputs_region(args.steps, args.warmup)
         except Exception as e:
             other_inputs = "failed: %r" % (e,)
     exact = None
-    if rank == 0 and not args.no_frame_by_frame and args.lanes > 0:
+    if extras and not args.no_frame_by_frame and args.lanes > 0:
         try:
             exact = r.exact_fp32_region()
         except Exception as e:
             exact = "failed: %r" % (e,)
     fbf = None
-    if batched and rank == 0 and not args.no_frame_by_frame:
+    if batched and extras and not args.no_frame_by_frame:
         try:
             fbf = r.frame_by_frame_region(args.steps, args.warmup)
         except Exception as e:          # a reported extra: never lose the bench line to it
@@ -1030,77 +1075,78 @@ def main():
         frames = world * B * args.steps * K
         fh, fw = int(np.ceil(args.height / 16.0)), int(np.ceil(args.width / 16.0))
         C = r.cfg.network.DFF_FEAT_DIM
-        # ---- roofline: the HBM-bound hand-written kernel (warp), live from HIP events ---------------------
-        warp_ms, warp_n = prof['warp_bilinear']
-        bytes_per_launch = warp_bytes(B, C, fh * fw)
-        if getattr(r, 'warp_bytes_total', None):       # batched pipeline: launches of one map (key frames) and of a segment's maps (one shared key feature)
-            bytes_per_launch = r.warp_bytes_total // max(warp_n, 1)
-        achieved = bytes_per_launch * warp_n / (warp_ms * 1e-3) / 1e9 if warp_ms > 0 else 0.0
-        ops = {k: {"avg_us": round(v[0] * 1e3 / v[1], 2), "launches": v[1], "total_us": round(v[0] * 1e3, 1)}
-               for k, v in prof.items() if v[1]}
-        hand_total = sum(o["total_us"] for o in ops.values()) or 1.0
-        dom = max(ops, key=lambda k: ops[k]["total_us"]) if ops else None
-        # which kernel lsfa_warp_bilinear runs for this shape (warp.hip's predicate: planes of 1,024-4,096 even pixels go through LDS)
-        staged = (fh * fw) % 2 == 0 and 1024 <= fh * fw <= 4096 and os.environ.get('LSFA_WARP_VARIANT', 'auto') != 'gather'
-        warp_kernel = ("warp_staged_kernel (lsfa_warp_bilinear: MV/flow warp + fused epilogue; planes staged in LDS by DMA)" if staged else
-                       "warp_kernel (lsfa_warp_bilinear: MV/flow warp + fused epilogue; gather form: plane size outside the LDS-staged kernel's range)")
-        mixed = bool(getattr(r, 'warp_bytes_total', None))
-        maps_label = ("a MIX of launches: %d map(s) per key-frame launch (flow warp) and %d maps per segment launch (MV warp, one shared key feature); "
-                      "algorithmic_bytes_per_launch is the mean over both kinds" % (B, B * r.segment)) if mixed and getattr(r, 'segment', 0) > 0 \
-            else "%d map(s) per launch" % B
-        roof_hbm = {"bound": "hbm", "kernel": "%s, %s" % (warp_kernel, maps_label),
-                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": load_traffic("warp_bilinear:N=%d,C=%d,H=%d,W=%d" % (B, C, fh, fw)),
-                "launches": warp_n, "avg_us": round(warp_ms * 1e3 / max(warp_n, 1), 2),
-                "algorithmic_bytes_per_launch": bytes_per_launch,
-                "measured": "HIP events around each launch on its stream, same frames re-issued eagerly right after the "
-                            "timed region (graph replays carry no per-launch events); traffic = FETCH_SIZE x2 + WRITE_SIZE "
-                            "from the rocprofv3 PMC passes under profiles/ for this shape, null if none was taken",
-                "note": "%.0f MB per launch: resident in the 256 MiB Infinity Cache, so this is cache bandwidth against "
-                        "the HBM peak; --maps-per-launch 32 gives the HBM-resident figure" % (bytes_per_launch / 1e6)}
-        # ---- roofline of the dominant hand-written kernel: the split-bf16 convolution (matrix pipe) -----------------
-        conv_ms, conv_n = prof.get('conv_nhwc', (0.0, 0))
-        conv_fl, conv_calls = getattr(r, 'conv_flops', (0.0, 0))
-        if conv_n and conv_fl > 0:
-            tf = conv_fl / (conv_ms * 1e-3) / 1e12
-            # matrix-pipe peak for this mix of calls: six bf16 products per fp32 product (2500 / 6), three fp16 ones on the calls
-            # that ran the two-piece form (2500 / 3): harmonic mix by FLOPs
-            fl3 = float(getattr(r, 'conv_flops3', 0.0))
-            fl1 = float(getattr(r, 'conv_flops1', 0.0))
-            fl6 = conv_fl - fl3 - fl1
-            mfma_work = 6 * fl6 + 3 * fl3 + fl1          # matrix-instruction FLOPs actually issued
-            mix_peak = conv_fl / (mfma_work / MFMA_BF16_PEAK_TFLOPS)
-            roof = {"bound": "mfma", "kernel": "the split-operand convolution family behind lsfa_conv_fwd (ring / direct kernels + their reduce passes): "
-                    "every convolution of ResNet-101 + DCN, feat_conv_3x3, the small net, fuse_reduce_add, FlowNet, the Nq net; %d calls of %d interval(s)%s" %
-                    (conv_n, getattr(r, 'profiled_intervals', 1), " computed the way the pipeline batches them (key fronts x%d, segments of %d frames)" % (r.key_group, r.segment) if batched else ""),
-                    "achieved": round(tf, 1), "peak": round(mix_peak, 1), "unit": "TFLOP/s",
-                    "frac": round(tf / mix_peak, 4),
-                    "flops_share_by_products_per_fp32_product": {"six (three bf16 pieces)": round(fl6 / conv_fl, 3), "three (two fp16 pieces)": round(fl3 / conv_fl, 3),
-                                                                  "one (bf16 mode)": round(fl1 / conv_fl, 3)},
-                    "frac_of_six_product_peak": round(tf / MFMA_SPLIT_PEAK_TFLOPS, 4),     # what rounds 1-2 quoted as `frac` (every call on six products)
-                    "traffic": load_traffic("conv_split:%dx%d,interval=%d,%s%s" % (args.width, args.height, args.interval, args.dtype,
-                                                                                  "" if args.clips == 1 else ",clips=%d" % args.clips)),
-                    "launches": conv_n, "avg_us": round(conv_ms * 1e3 / conv_n, 2),
-                    "algorithmic_flops_per_launch": round(conv_fl / max(conv_n, 1)),       # x launches / (avg_us x launches) = achieved
-                    "algorithmic_bytes_per_launch": round(float(getattr(r, 'conv_bytes', 0.0)) / max(conv_n, 1)),
-                    "flop_counted_calls": conv_calls,      # == launches: FLOPs and time cover the same lsfa_conv_fwd / lsfa_deconv4x4s2_crop_fwd calls (FlowNet included)
-                    "by_kernel": getattr(r, 'conv_by_kernel', None),
-                    "mfma_work": {"achieved": round(mfma_work / (conv_ms * 1e-3) / 1e12, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s"},
-                    "fp32_mfma_pipe_peak": 157.3,
-                    "measured": "HIP events around each lsfa_conv_fwd / lsfa_deconv4x4s2_crop_fwd call (convolution kernel + its reduce pass) re-issued "
-                                "eagerly after the timed region; algorithmic FLOPs = 2*M*N*K and algorithmic bytes = every operand once (input channels read, "
-                                "packed weights, output, residual, stored second output) summed over the SAME calls; by_kernel = the same calls by the kernel "
-                                "instantiation the launch plan picks (lsfa_conv_plan_query; tools/conv_family_roofline.py joins it with the rocprofv3 "
-                                "kernel trace and MFMA-busy counters -> profiles/r5/conv_family_roofline.csv); traffic = HBM bytes "
-                                "per call of the kernel family (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 PMC passes over the eager loop, "
-                                "profiles/traffic.json), null if no profile of this configuration is committed",
-                    "note": "fp32 in / fp32 accumulate; an fp32 product costs three fp16 matrix instructions' worth (two-piece form: the fp32 "
-                            "path's default, peak for fp32-equivalent FLOPs 2500 / 3 = 833.3), six bf16 ones (three-piece form: FlowNet, 416.7) "
-                            "or one (bf16 mode, 2500); `peak` is the dense bf16 / fp16 matrix peak divided by the FLOP-weighted products per "
-                            "fp32 product of this mix; the fp32 matrix instructions peak at 157.3"}
-        else:
-            roof = roof_hbm
+        if args.full:
+            # ---- roofline: the HBM-bound hand-written kernel (warp), live from HIP events ---------------------
+            warp_ms, warp_n = prof['warp_bilinear']
+            bytes_per_launch = warp_bytes(B, C, fh * fw)
+            if getattr(r, 'warp_bytes_total', None):       # batched pipeline: launches of one map (key frames) and of a segment's maps (one shared key feature)
+                bytes_per_launch = r.warp_bytes_total // max(warp_n, 1)
+            achieved = bytes_per_launch * warp_n / (warp_ms * 1e-3) / 1e9 if warp_ms > 0 else 0.0
+            ops = {k: {"avg_us": round(v[0] * 1e3 / v[1], 2), "launches": v[1], "total_us": round(v[0] * 1e3, 1)}
+                   for k, v in prof.items() if v[1]}
+            hand_total = sum(o["total_us"] for o in ops.values()) or 1.0
+            dom = max(ops, key=lambda k: ops[k]["total_us"]) if ops else None
+            # which kernel lsfa_warp_bilinear runs for this shape (warp.hip's predicate: planes of 1,024-4,096 even pixels go through LDS)
+            staged = (fh * fw) % 2 == 0 and 1024 <= fh * fw <= 4096 and os.environ.get('LSFA_WARP_VARIANT', 'auto') != 'gather'
+            warp_kernel = ("warp_staged_kernel (lsfa_warp_bilinear: MV/flow warp + fused epilogue; planes staged in LDS by DMA)" if staged else
+                           "warp_kernel (lsfa_warp_bilinear: MV/flow warp + fused epilogue; gather form: plane size outside the LDS-staged kernel's range)")
+            mixed = bool(getattr(r, 'warp_bytes_total', None))
+            maps_label = ("a MIX of launches: %d map(s) per key-frame launch (flow warp) and %d maps per segment launch (MV warp, one shared key feature); "
+                          "algorithmic_bytes_per_launch is the mean over both kinds" % (B, B * r.segment)) if mixed and getattr(r, 'segment', 0) > 0 \
+                else "%d map(s) per launch" % B
+            roof_hbm = {"bound": "hbm", "kernel": "%s, %s" % (warp_kernel, maps_label),
+                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": load_traffic("warp_bilinear:N=%d,C=%d,H=%d,W=%d" % (B, C, fh, fw)),
+                    "launches": warp_n, "avg_us": round(warp_ms * 1e3 / max(warp_n, 1), 2),
+                    "algorithmic_bytes_per_launch": bytes_per_launch,
+                    "measured": "HIP events around each launch on its stream, same frames re-issued eagerly right after the "
+                                "timed region (graph replays carry no per-launch events); traffic = FETCH_SIZE x2 + WRITE_SIZE "
+                                "from the rocprofv3 PMC passes under profiles/ for this shape, null if none was taken",
+                    "note": "%.0f MB per launch: resident in the 256 MiB Infinity Cache, so this is cache bandwidth against "
+                            "the HBM peak; --maps-per-launch 32 gives the HBM-resident figure" % (bytes_per_launch / 1e6)}
+            # ---- roofline of the dominant hand-written kernel: the split-bf16 convolution (matrix pipe) -----------------
+            conv_ms, conv_n = prof.get('conv_nhwc', (0.0, 0))
+            conv_fl, conv_calls = getattr(r, 'conv_flops', (0.0, 0))
+            if conv_n and conv_fl > 0:
+                tf = conv_fl / (conv_ms * 1e-3) / 1e12
+                # matrix-pipe peak for this mix of calls: six bf16 products per fp32 product (2500 / 6), three fp16 ones on the calls
+                # that ran the two-piece form (2500 / 3): harmonic mix by FLOPs
+                fl3 = float(getattr(r, 'conv_flops3', 0.0))
+                fl1 = float(getattr(r, 'conv_flops1', 0.0))
+                fl6 = conv_fl - fl3 - fl1
+                mfma_work = 6 * fl6 + 3 * fl3 + fl1          # matrix-instruction FLOPs actually issued
+                mix_peak = conv_fl / (mfma_work / MFMA_BF16_PEAK_TFLOPS)
+                roof = {"bound": "mfma", "kernel": "the split-operand convolution family behind lsfa_conv_fwd (ring / direct kernels + their reduce passes): "
+                        "every convolution of ResNet-101 + DCN, feat_conv_3x3, the small net, fuse_reduce_add, FlowNet, the Nq net; %d calls of %d interval(s)%s" %
+                        (conv_n, getattr(r, 'profiled_intervals', 1), " computed the way the pipeline batches them (key fronts x%d, segments of %d frames)" % (r.key_group, r.segment) if batched else ""),
+                        "achieved": round(tf, 1), "peak": round(mix_peak, 1), "unit": "TFLOP/s",
+                        "frac": round(tf / mix_peak, 4),
+                        "flops_share_by_products_per_fp32_product": {"six (three bf16 pieces)": round(fl6 / conv_fl, 3), "three (two fp16 pieces)": round(fl3 / conv_fl, 3),
+                                                                      "one (bf16 mode)": round(fl1 / conv_fl, 3)},
+                        "frac_of_six_product_peak": round(tf / MFMA_SPLIT_PEAK_TFLOPS, 4),     # what rounds 1-2 quoted as `frac` (every call on six products)
+                        "traffic": load_traffic("conv_split:%dx%d,interval=%d,%s%s" % (args.width, args.height, args.interval, args.dtype,
+                                                                                      "" if args.clips == 1 else ",clips=%d" % args.clips)),
+                        "launches": conv_n, "avg_us": round(conv_ms * 1e3 / conv_n, 2),
+                        "algorithmic_flops_per_launch": round(conv_fl / max(conv_n, 1)),       # x launches / (avg_us x launches) = achieved
+                        "algorithmic_bytes_per_launch": round(float(getattr(r, 'conv_bytes', 0.0)) / max(conv_n, 1)),
+                        "flop_counted_calls": conv_calls,      # == launches: FLOPs and time cover the same lsfa_conv_fwd / lsfa_deconv4x4s2_crop_fwd calls (FlowNet included)
+                        "by_kernel": getattr(r, 'conv_by_kernel', None),
+                        "mfma_work": {"achieved": round(mfma_work / (conv_ms * 1e-3) / 1e12, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s"},
+                        "fp32_mfma_pipe_peak": 157.3,
+                        "measured": "HIP events around each lsfa_conv_fwd / lsfa_deconv4x4s2_crop_fwd call (convolution kernel + its reduce pass) re-issued "
+                                    "eagerly after the timed region; algorithmic FLOPs = 2*M*N*K and algorithmic bytes = every operand once (input channels read, "
+                                    "packed weights, output, residual, stored second output) summed over the SAME calls; by_kernel = the same calls by the kernel "
+                                    "instantiation the launch plan picks (lsfa_conv_plan_query; tools/conv_family_roofline.py joins it with the rocprofv3 "
+                                    "kernel trace and MFMA-busy counters -> profiles/r5/conv_family_roofline.csv); traffic = HBM bytes "
+                                    "per call of the kernel family (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 PMC passes over the eager loop, "
+                                    "profiles/traffic.json), null if no profile of this configuration is committed",
+                        "note": "fp32 in / fp32 accumulate; an fp32 product costs three fp16 matrix instructions' worth (two-piece form: the fp32 "
+                                "path's default, peak for fp32-equivalent FLOPs 2500 / 3 = 833.3), six bf16 ones (three-piece form: FlowNet, 416.7) "
+                                "or one (bf16 mode, 2500); `peak` is the dense bf16 / fp16 matrix peak divided by the FLOP-weighted products per "
+                                "fp32 product of this mix; the fp32 matrix instructions peak at 157.3"}
+            else:
+                roof = roof_hbm
         line = {
             "metric": "frames/sec/GPU at 1000x600 key_interval=10 (whole-job frames/s)",
             "value": round(frames / elapsed, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -1128,59 +1174,63 @@ def main():
                                     "--segment 0 --key-group 1 = frame by frame" %
                                     (r.segment, r.key_group, (r.key_group - 1) * K,
                                      "; after the pipeline ran empty the first passes are %s key frames" % args.ramp if args.ramp.strip() else "")) if batched else "none: one frame per pass"},
-            "value_spread": {"min": round(frames / max(repeats), 3), "max": round(frames / min(repeats), 3), "repeats": len(repeats),
-                             "values": [round(frames / t, 3) for t in repeats],
-                             "note": "the timed region run %d times back to back; `value` is the first" % len(repeats),
-                             "host_enqueue_share_of_repeats": [round(h / t, 3) for h, t in zip(host_enqueue, repeats[1:])]},
             "inputs": (("resident in HBM as fp32 when the timed region starts (the bench contract: `value` never includes PCIe); `value_uploaded_inputs` is the "
                         "PCIe-inclusive rate of the same pipeline" if uploads_extra else
                         "host-pinned, uploaded in region (--host-inputs): per interval one pinned block (uint8 BGR frames as a decoder hands them over + fp32 motion "
                         "vectors / residuals, dff_rfcn/core/loader.py:131-141) -> one H2D copy -> transform (lib/utils/image.py:296-308) on the GPU; uploads run "
                         "ahead of the frames by the key group's look-ahead; `value_resident_inputs` is the contract's figure")
                        if getattr(r, 'host_inputs', False)
-                       else "resident in HBM as fp32 before the timed region (--resident-inputs, or a serial / non-pipelined run)"),
-            "value_resident_inputs": (round(frames / elapsed, 3) if uploads_extra or not getattr(r, 'host_inputs', False)
-                                      else (round(other_inputs, 3) if isinstance(other_inputs, float) else other_inputs)),
-            "value_uploaded_inputs": ((round(other_inputs, 3) if isinstance(other_inputs, float) else other_inputs) if uploads_extra
-                                      else (round(frames / elapsed, 3) if getattr(r, 'host_inputs', False) else None)),
-            "value_other_inputs_regions": getattr(r, 'other_inputs_rates', None),
-            "value_uploaded_inputs_note": "frames/s of this GPU with the inputs starting in pinned HOST memory: per interval one pinned block (uint8 BGR frames as a "
-                                          "decoder hands them over + fp32 motion vectors / residuals, dff_rfcn/core/loader.py:131-141) -> one H2D copy inside the "
-                                          "region -> transform (lib/utils/image.py:296-308) on the GPU, uploads ahead of the frames by the key group's look-ahead; "
-                                          "the extra region (rank 0: its own 0.75 s settle, then the region twice - `value_other_inputs_regions` - the second reported), or `value` itself under --host-inputs",
-            "value_exact_fp32": (round(exact, 3) if isinstance(exact, float) else exact),
-            "value_exact_fp32_note": "frames/s, frame by frame, with every convolution on the EXACT fp32 matrix instructions (v_mfma_f32_32x32x2_f32, "
-                                     "157 TFLOP/s peak; Executor pieces = 0, a reference evaluation): what the two-fp16-piece form is compared with in "
-                                     "tests/test_parity_fullres_gpu.py::test_two_fp16_pieces_against_exact_fp32_products_at_1000x600; compare with value_frame_by_frame",
-            "value_frame_by_frame": (round(fbf, 3) if isinstance(fbf, float) else fbf),
-            "value_frame_by_frame_note": "frames/s of this GPU for the same clip with one frame per pass (--segment 0 --key-group 1: no look-ahead, the "
-                                         "streaming case; inputs as for `value`), %d timed intervals after its own graph capture + 0.5 s settle + %d warm-up intervals; null when the "
-                                         "headline configuration is itself unbatched" % (args.steps, args.warmup),
-            "roofline": roof,
+                       else "resident in HBM as fp32 before the timed region (no --full nor --host-inputs, --resident-inputs, or a serial / "
+                            "non-pipelined run)"),
             "multi_gpu": multi,
-            "roofline_hbm_kernel": roof_hbm,
-            "roofline_handwritten_ops": {
-                "per_op": ops, "dominant_by_time": dom,
-                "dominant_share_of_handwritten_time": round(ops[dom]["total_us"] / hand_total, 3) if dom else None,
-                "note": "one eager interval; proposal / det_postprocess / rfcn_head are latency-bound by construction "
-                        "(0.5 MB, 53 KB, 18 MB of algorithmic bytes): judged in us, not as a fraction of HBM peak"},
         }
-        if args.maps_per_launch > 0:
-            M = args.maps_per_launch
-            mm = r.many_maps_leg(M)
-            w = mm['warp_bilinear (x scale map)']
-            line["roofline_single_map"] = roof_hbm
-            line["roofline_mfma_kernel"] = roof
-            del line["roofline_hbm_kernel"]
-            line["roofline"] = {"bound": "hbm", "kernel": "%s, %d maps per launch (x scale map epilogue)" % (warp_kernel, M),
-                                "achieved": w["achieved_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                "frac": round(w["achieved_GBps"] / HBM_PEAK_GBS, 4),
-                                "traffic": load_traffic("warp_bilinear:N=%d,C=%d,H=%d,W=%d" % (M, C, fh, fw)),
-                                "launches": w["launches"], "avg_us": w["avg_us"],
-                                "algorithmic_bytes_per_launch": w["algorithmic_bytes_per_launch"],
-                                "measured": "HIP events around each launch, untimed leg after the frame loop; %d MB per launch "
-                                            "(> 256 MiB Infinity Cache: HBM-resident)" % (w["algorithmic_bytes_per_launch"] // 1000000),
-                                "other_kernels_same_size": {k: v for k, v in mm.items() if k != 'warp_bilinear (x scale map)'}}
+        if args.full:
+            line.update({
+                "value_spread": {"min": round(frames / max(repeats), 3), "max": round(frames / min(repeats), 3), "repeats": len(repeats),
+                                 "values": [round(frames / t, 3) for t in repeats],
+                                 "note": "the timed region run %d times back to back; `value` is the first" % len(repeats),
+                                 "host_enqueue_share_of_repeats": [round(h / t, 3) for h, t in zip(host_enqueue, repeats[1:])]},
+                "value_resident_inputs": (round(frames / elapsed, 3) if uploads_extra or not getattr(r, 'host_inputs', False)
+                                          else (round(other_inputs, 3) if isinstance(other_inputs, float) else other_inputs)),
+                "value_uploaded_inputs": ((round(other_inputs, 3) if isinstance(other_inputs, float) else other_inputs) if uploads_extra
+                                          else (round(frames / elapsed, 3) if getattr(r, 'host_inputs', False) else None)),
+                "value_other_inputs_regions": getattr(r, 'other_inputs_rates', None),
+                "value_uploaded_inputs_note": "frames/s of this GPU with the inputs starting in pinned HOST memory: per interval one pinned block (uint8 BGR frames as a "
+                                              "decoder hands them over + fp32 motion vectors / residuals, dff_rfcn/core/loader.py:131-141) -> one H2D copy inside the "
+                                              "region -> transform (lib/utils/image.py:296-308) on the GPU, uploads ahead of the frames by the key group's look-ahead; "
+                                              "the extra region (rank 0: its own 0.75 s settle, then the region twice - `value_other_inputs_regions` - the second reported), or `value` itself under --host-inputs",
+                "value_exact_fp32": (round(exact, 3) if isinstance(exact, float) else exact),
+                "value_exact_fp32_note": "frames/s, frame by frame, with every convolution on the EXACT fp32 matrix instructions (v_mfma_f32_32x32x2_f32, "
+                                         "157 TFLOP/s peak; Executor pieces = 0, a reference evaluation): what the two-fp16-piece form is compared with in "
+                                         "tests/test_parity_fullres_gpu.py::test_two_fp16_pieces_against_exact_fp32_products_at_1000x600; compare with value_frame_by_frame",
+                "value_frame_by_frame": (round(fbf, 3) if isinstance(fbf, float) else fbf),
+                "value_frame_by_frame_note": "frames/s of this GPU for the same clip with one frame per pass (--segment 0 --key-group 1: no look-ahead, the "
+                                             "streaming case; inputs as for `value`), %d timed intervals after its own graph capture + 0.5 s settle + %d warm-up intervals; null when the "
+                                             "headline configuration is itself unbatched" % (args.steps, args.warmup),
+                "roofline": roof,
+                "roofline_hbm_kernel": roof_hbm,
+                "roofline_handwritten_ops": {
+                    "per_op": ops, "dominant_by_time": dom,
+                    "dominant_share_of_handwritten_time": round(ops[dom]["total_us"] / hand_total, 3) if dom else None,
+                    "note": "one eager interval; proposal / det_postprocess / rfcn_head are latency-bound by construction "
+                            "(0.5 MB, 53 KB, 18 MB of algorithmic bytes): judged in us, not as a fraction of HBM peak"},
+            })
+            if args.maps_per_launch > 0:
+                M = args.maps_per_launch
+                mm = r.many_maps_leg(M)
+                w = mm['warp_bilinear (x scale map)']
+                line["roofline_single_map"] = roof_hbm
+                line["roofline_mfma_kernel"] = roof
+                del line["roofline_hbm_kernel"]
+                line["roofline"] = {"bound": "hbm", "kernel": "%s, %d maps per launch (x scale map epilogue)" % (warp_kernel, M),
+                                    "achieved": w["achieved_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                    "frac": round(w["achieved_GBps"] / HBM_PEAK_GBS, 4),
+                                    "traffic": load_traffic("warp_bilinear:N=%d,C=%d,H=%d,W=%d" % (M, C, fh, fw)),
+                                    "launches": w["launches"], "avg_us": w["avg_us"],
+                                    "algorithmic_bytes_per_launch": w["algorithmic_bytes_per_launch"],
+                                    "measured": "HIP events around each launch, untimed leg after the frame loop; %d MB per launch "
+                                                "(> 256 MiB Infinity Cache: HBM-resident)" % (w["algorithmic_bytes_per_launch"] // 1000000),
+                                    "other_kernels_same_size": {k: v for k, v in mm.items() if k != 'warp_bilinear (x scale map)'}}
         if (args.height, args.width) == (600, 1000):
             # algorithmic FLOPs of the dense contractions, key frame 392.0 G, non-key frame 17.3 G
             gflop = (392.0 + 17.3 * (K - 1)) * B
@@ -1190,7 +1240,7 @@ def main():
                                       "time (whole pipeline, everything overlapped), against the same peak as `roofline`: the dense 16-bit matrix peak / 3 "
                                       "products per fp32 product (f32) or / 1 (bf16)", "achieved": round(tf, 1), "peak": peak,
                                       "unit": "TFLOP/s", "frac": round(tf / peak, 4), "gflop_per_step": round(gflop, 1)}
-        if not (args.no_cpu_baseline and args.no_parity):
+        if args.full and not (args.no_cpu_baseline and args.no_parity):
             try:
                 cpu, parity = r.parity_and_cpu_baseline(args.cpu_budget_s, not args.no_parity)
                 if not args.no_cpu_baseline:

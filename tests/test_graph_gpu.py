@@ -866,14 +866,14 @@ def test_two_clips_interleaved_on_one_gpu_are_isolated(world):
 
 
 def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the contract's keys (small frame size so it is quick)."""
+    """bench.py --full prints ONE JSON line with the contract's keys and every extra (small frame size so it is quick)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--height", "192",
-                          "--width", "320", "--cpu-budget-s", "5", "--settle-s", "0.3"], capture_output=True, text=True, timeout=600,
+                          "--width", "320", "--cpu-budget-s", "5", "--settle-s", "0.3", "--full"], capture_output=True, text=True, timeout=600,
                          cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -897,6 +897,45 @@ def test_bench_line_contract():
     assert v["repeats"] == 3 and len(v["values"]) == 3 and v["values"][0] == d["value"] and v["min"] <= d["value"] <= v["max"]
     assert "settle" in d["config"]["setup_before_warmup"] and d["warmup"] == 1
     assert d["parity"]["handwritten_stage_mismatches_on_gpu_inputs"] == 0
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run prints the headline without the extras of --full; --dump-outputs DIR writes what the last timed step
+    delivered (detections and per-class counts of its ten frames), and a --full run with the same arguments writes the same arrays bit
+    for bit (the outputs do not depend on the run, nor on the extras)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--height", "192", "--width", "320",
+              "--settle-s", "0.3"]
+    lines, dumps = {}, {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-parity"])):
+        d = tmp_path / tag
+        out = subprocess.run(common + extra + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1
+        lines[tag] = json.loads(js[0])
+        assert sorted(os.listdir(str(d))) == ["counts.npy", "detections.npy"]
+        dumps[tag] = {n: np.load(str(d / (n + ".npy"))) for n in ("counts", "detections")}
+    p = lines["plain"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in p, k
+    assert p["steps"] == 3 and p["unit"] == "frames/s" and p["higher_is_better"] is True and p["dtype"] == "f32"
+    assert abs(p["value"] - p["config"]["frames_per_step"] / (p["ms_per_step"] / 1e3)) < 0.01 * p["value"]
+    for k in ("value_spread", "roofline", "roofline_hbm_kernel", "value_frame_by_frame", "value_exact_fp32", "parity", "cpu_baseline"):
+        assert k not in p, k
+    assert lines["full"]["value_spread"]["repeats"] == 3 and "roofline" in lines["full"]
+    counts, dets = dumps["plain"]["counts"], dumps["plain"]["detections"]
+    ncls, R = counts.shape[-1], dets.shape[-2]
+    assert counts.dtype == np.float64 and dets.dtype == np.float64 and counts.shape == (10, 1, ncls) and dets.shape == (10, 1, ncls, R, 5)
+    assert counts.nbytes + dets.nbytes <= 64 * 10 ** 6
+    assert counts.sum() == p["config"]["detections_last_interval"] > 0
+    assert not dets[np.arange(R) >= counts[..., None]].any()          # rows past a class's count are zero
+    for n in ("counts", "detections"):
+        np.testing.assert_array_equal(dumps["plain"][n], dumps["full"][n])
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])

@@ -2,7 +2,7 @@
 run() { name=$1; shift; env "$@" 2>/dev/null | tail -1 > gpurun_out/ab_$name.json
 [ -s gpurun_out/ab_$name.json ] || { echo "$name: no output, stopping (sick box?)"; exit 9; }
 python -c "import json,sys; d=json.load(open('gpurun_out/ab_$name.json')); print('$name', d['value'], d['value_spread']['values'])"; }
-B="timeout 300 python bench.py --no-cpu-baseline --no-parity"
+B="timeout 300 python bench.py --full --no-cpu-baseline --no-parity"
 for i in 1 2; do
 run q4l2_$i $B
 run q8l2_$i GPU_MAX_HW_QUEUES=8 $B

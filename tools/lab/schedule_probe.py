@@ -51,7 +51,7 @@ def report():
 
 
 if __name__ == '__main__':
-    sys.argv = [os.path.join(ROOT, 'bench.py')] + sys.argv[1:] + ['--no-cpu-baseline', '--no-parity', '--no-spread', '--no-frame-by-frame']
+    sys.argv = [os.path.join(ROOT, 'bench.py')] + sys.argv[1:] + ['--full', '--no-cpu-baseline', '--no-parity', '--no-spread', '--no-frame-by-frame']
     real_profile = bench.Runner.eager_profile_batched
 
     def profile_after_report(self, *a, **k):            # the first thing bench.py does after its timed region

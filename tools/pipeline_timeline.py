@@ -3,7 +3,7 @@
 for the last `frac` of the run - per queue: launches, busy time (union of its kernels), idle time inside its span and the largest idle
 gaps with the kernels either side; over all queues: the time during which no kernel at all was running.
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --steps 30 --no-cpu-baseline --no-parity
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --full --steps 30 --no-cpu-baseline --no-parity
     python3 tools/pipeline_timeline.py DIR [frac] [--chart MS [BUCKET_US]]
 
 --chart: a text chart of the window's first MS milliseconds, one row per hardware queue, one character per BUCKET_US (default 250) microseconds:

@@ -10,22 +10,22 @@ export TMPDIR=/tmp
 PY=python3
 
 # 1. the bench lines (default = configs[1], batched passes; the same frame by frame; configs[4]; configs[2])
-timeout 600 $PY bench.py --steps 100 > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
-timeout 300 $PY bench.py --steps 20 --warmup 5 > $OUT/bench_driver_settings_run.json 2> /dev/null                                   # the driver's command line
-timeout 300 $PY bench.py --steps 100 --host-inputs --no-cpu-baseline --no-parity > $OUT/bench_host_inputs_run.json 2> /dev/null          # the PCIe-inclusive rate as `value`
-timeout 400 $PY bench.py --steps 60 --segment 0 --key-group 1 --no-cpu-baseline > $OUT/bench_frame_by_frame_run.json 2> /dev/null
-timeout 400 $PY bench.py --interval 1 --maps-per-launch 32 --steps 60 > $OUT/bench_interval1_maps32_run.json 2> $OUT/bench_interval1_maps32_run.err
-timeout 600 $PY bench.py --dtype bf16 --clips 4 --steps 40 > $OUT/bench_bf16_clips4_run.json 2> $OUT/bench_bf16_clips4_run.err
-timeout 400 $PY bench.py --dtype bf16 --steps 60 --no-cpu-baseline --no-parity > $OUT/bench_bf16_clips1_run.json 2> /dev/null
+timeout 600 $PY bench.py --full --steps 100 > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
+timeout 300 $PY bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_settings_run.json 2> /dev/null                                   # the driver's command line
+timeout 300 $PY bench.py --full --steps 100 --host-inputs --no-cpu-baseline --no-parity > $OUT/bench_host_inputs_run.json 2> /dev/null          # the PCIe-inclusive rate as `value`
+timeout 400 $PY bench.py --full --steps 60 --segment 0 --key-group 1 --no-cpu-baseline > $OUT/bench_frame_by_frame_run.json 2> /dev/null
+timeout 400 $PY bench.py --full --interval 1 --maps-per-launch 32 --steps 60 > $OUT/bench_interval1_maps32_run.json 2> $OUT/bench_interval1_maps32_run.err
+timeout 600 $PY bench.py --full --dtype bf16 --clips 4 --steps 40 > $OUT/bench_bf16_clips4_run.json 2> $OUT/bench_bf16_clips4_run.err
+timeout 400 $PY bench.py --full --dtype bf16 --steps 60 --no-cpu-baseline --no-parity > $OUT/bench_bf16_clips1_run.json 2> /dev/null
 
 # 2. kernel trace of the pipelined timed region (default configuration)
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_pipe -o t -- $PY bench.py --steps 30 --no-cpu-baseline --no-parity --no-frame-by-frame > $OUT/trace_pipe.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_pipe -o t -- $PY bench.py --full --steps 30 --no-cpu-baseline --no-parity --no-frame-by-frame > $OUT/trace_pipe.log 2>&1
 $PY tools/summarize_prof.py trace $OUT/trace_pipe $OUT/bench_pipelined_timed_region_kernels.csv 0.6     # also writes ..._kernels_launches.json
 cp $(find $OUT/trace_pipe -name "*kernel_stats.csv" | head -1) $OUT/bench_pipelined_kernel_stats_whole_run.csv 2>/dev/null
 rm -rf $OUT/trace_pipe
 
 # 3. matrix-pipe duty per kernel, serial eager loop (counters only: no trace domains next to --pmc)
-timeout 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_mfma -o t -- $PY bench.py --steps 12 --warmup 3 --settle-s 0 --no-graph --no-cpu-baseline --no-parity --no-spread --no-frame-by-frame > $OUT/pmc_mfma.log 2>&1
+timeout 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_mfma -o t -- $PY bench.py --full --steps 12 --warmup 3 --settle-s 0 --no-graph --no-cpu-baseline --no-parity --no-spread --no-frame-by-frame > $OUT/pmc_mfma.log 2>&1
 $PY tools/summarize_prof.py pmctable $OUT/pmc_mfma $OUT/bench_eager_pmc_mfma_busy.csv
 rm -rf $OUT/pmc_mfma
 
@@ -46,7 +46,7 @@ timeout 200 rocprofv3 --kernel-trace --output-format csv -d $OUT/pmc_trace -o t 
 $PY tools/traffic_probe.py summarize $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_trace $OUT/traffic.json > $OUT/traffic_summary.log 2>&1
 rm -rf $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_trace
 # 4b. HBM traffic of the split-convolution family per call (the `roofline.traffic` of the default bench line), same two-pass rule
-EAGER="bench.py --steps 12 --warmup 12 --settle-s 0 --no-graph --no-cpu-baseline --no-parity --no-spread --no-frame-by-frame"
+EAGER="bench.py --full --steps 12 --warmup 12 --settle-s 0 --no-graph --no-cpu-baseline --no-parity --no-spread --no-frame-by-frame"
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_cfetch -o t -- $PY $EAGER > $OUT/conv_traffic_fetch.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_cwrite -o t -- $PY $EAGER > $OUT/conv_traffic_write.log 2>&1
 $PY tools/summarize_prof.py convtraffic $OUT/pmc_cfetch $OUT/pmc_cwrite $OUT/traffic.json "conv_split:1000x600,interval=10,f32" > $OUT/conv_traffic_summary.log 2>&1
@@ -91,7 +91,7 @@ timeout 60 $PY tools/kernel_sequence.py $OUT/bb6 8 > $OUT/backbone6_kernel_seque
 timeout 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/bb12 -o t -- $PY tools/backbone_only.py 6 backbone 12 > /dev/null 2>&1     # r6: bench.py's default key group
 timeout 60 $PY tools/kernel_sequence.py $OUT/bb12 6 --by-name > $OUT/backbone12_kernels_by_name.txt 2>&1; rm -rf $OUT/bb12
 # 8. r4: where the pipelined loop's wall time goes per hardware queue
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/tl -o t -- $PY bench.py --steps 30 --no-cpu-baseline --no-parity --no-spread --no-frame-by-frame > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/tl -o t -- $PY bench.py --full --steps 30 --no-cpu-baseline --no-parity --no-spread --no-frame-by-frame > /dev/null 2>&1
 timeout 120 $PY tools/pipeline_timeline.py $OUT/tl 0.5 --chart 60 250 > $OUT/pipeline_timeline.txt 2>&1; rm -rf $OUT/tl
 # 9. r6: ... and the schedule WITHOUT a tracer attached (the traced loop runs its queues one after the other: LABNOTES "Round 6", 13)
 timeout 300 $PY tools/lab/schedule_probe.py --steps 40 2>&1 | grep -A200 "schedule of" > $OUT/schedule_probe.txt
