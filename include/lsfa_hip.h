@@ -111,10 +111,45 @@ int lsfa_warp_bilinear(const float* feat, int feat_n, const float* flow,
 int lsfa_warp_bilinear_cl(const float* feat_cl, int feat_n, const float* flow, int N, int C, int H, int W, const float* add_cl,
                           const float* res, int res_c, const float* res_w, const float* res_b, float* out_cl, unsigned* amax_out,
                           int amax_c0, void* stream);
+/* The small net's `bn_before_fuse` (resnet_v1_101_flownet_rfcn.py:231-235 `add`, :243-246 `addv2`): warp_conv_feat_bn on the warped feature
+ * before `cur_feat + warp_conv_feat` (:236).  The BatchNorm's shift does not commute with the warp's zero padding, so it is an epilogue step:
+ *   r = bilerp(...) [+ rnet_conv0(res)];  r = r * bn_scale[c];  r = r + bn_shift[c];  [r = r + add]        (each step rounded on its own)
+ * bn_scale = gamma / sqrt(moving_var + eps), bn_shift = beta - moving_mean * bn_scale (folded on the host).  NCHW (lsfa_warp_bilinear's
+ * arguments without `mul`; the gather kernel) and channels-last (lsfa_warp_bilinear_cl's, amax_out included). */
+int lsfa_warp_bilinear_bn(const float* feat, int feat_n, const float* flow, int N, int C, int H, int W, const float* add, const float* res,
+                          int res_c, const float* res_w, const float* res_b, const float* bn_scale, const float* bn_shift, float* out,
+                          void* stream);
+int lsfa_warp_bilinear_bn_cl(const float* feat_cl, int feat_n, const float* flow, int N, int C, int H, int W, const float* add_cl,
+                             const float* res, int res_c, const float* res_w, const float* res_b, const float* bn_scale, const float* bn_shift,
+                             float* out_cl, unsigned* amax_out, int amax_c0, void* stream);
 /* Kernel choice (process-wide; results are identical bit for bit): 0 = by shape (default), 1 = the gather kernel only (rounds 1-2),
  * 2 = the LDS-staged kernel (round 3: whole planes copied into LDS by DMA, taps read from LDS) or LSFA_ENOTSUP when the shape or
  * alignment does not allow it (H*W even and <= 4096, 16-byte aligned maps, (C*H*W) % 4 == 0). */
 int lsfa_warp_set_variant(int variant);
+
+/* ------------------------------------------------------------------------ *
+ * Short-term aggregation, channel attention (small_net_fuse_type `concatv1` / `concatv2`).
+ * Replaces: Pooling(global_pool=True, pool_type='avg') "global_pool", s_feat_conv1 (1x1) + relu, s_feat_conv2 (1x1) + sigmoid,
+ *           broadcast_mul + add; resnet_v1_101_flownet_rfcn.py:251-259 (concatv1), :261-271 (concatv2).
+ * Maps are channels-last (N, HW, C), 16-byte aligned, channel counts multiples of 4.  Deterministic: no float atomics, and an image's
+ * result does not depend on the other images of the batch.
+ *
+ * lsfa_channel_mean: mean[n, c] over the HW pixels of image n of the concatenation [x1 | x2] (channel c < C1 reads x1[.., c], else
+ *   x2[.., c - C1]; C2 = 0 / x2 = NULL: x1 alone).  Order: partial[n, k, c] = ((0 + x[16k]) + x[16k + 1]) + ... over the k-th run of 16
+ *   pixels, ascending; mean = ((partial[0] + partial[1]) + ... + partial[last]) / HW.  ws: lsfa_channel_mean_workspace_bytes(N, C1 + C2, HW).
+ * lsfa_channel_gate: gate[n, o] = sigmoid(w2[o, :] . relu(w1[:, :] . m[n, :] + b1) + b2[o]) for N images; w1 (M, K), w2 (O, M) fp32 row-major,
+ *   hidden (N, M) scratch.  Each dot product: lane l of a wave accumulates elements 4(l + 64j) .. +3, j ascending, with fmaf from 0, then the
+ *   64 lane sums meet in a butterfly (distance 32, 16, .., 1), then + bias; sigmoid(v) = 1 / (1 + exp(-v)), exp correctly rounded.  A weight
+ *   row is read once per 8 images.  (No matrix instructions: a GEMV.)
+ * lsfa_gate_apply: out = x * gate[n, c] + y (two roundings); `concatv1` passes x = y.  amax_out (or NULL): 256 zeroed slots that receive
+ *   max|out| over channels [amax_c0, C) (the R-FCN convolution's scale, as lsfa_warp_bilinear_cl leaves it).
+ * ------------------------------------------------------------------------ */
+size_t lsfa_channel_mean_workspace_bytes(int N, int C, int HW);
+int lsfa_channel_mean(const float* x1, int C1, const float* x2, int C2, int N, int HW, float* mean, void* ws, size_t ws_bytes, void* stream);
+int lsfa_channel_gate(const float* m, int N, int K, const float* w1, const float* b1, int M, const float* w2, const float* b2, int O,
+                      float* hidden, float* gate, void* stream);
+int lsfa_gate_apply(const float* x, const float* gate, const float* y, int N, int HW, int C, float* out, unsigned* amax_out, int amax_c0,
+                    void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Long-term aggregation combine (Nq_net tail).

@@ -118,8 +118,10 @@ class FrameGraphs(object):
         self._post_full, self.post_bufs = _alloc_post(B, ncls, R, dev)
         self.prefetch = prefetch and cfg.network.add_small_net
         self.data_next = z(B, 3, height, width)        # image of the frame after the current one
-        self.small_cur = z(B, dim, fh, fw)             # small-net feature of the current non-key frame
-        self.small_next = z(B, dim, fh, fw)
+        # small-net feature (the image-only part of the fuse: small_net_channels wide) of the current / next non-key frame
+        sdim = cur_exec.small_net_channels if cur_exec is not None else dim
+        self.small_cur = z(B, sdim, fh, fw)
+        self.small_next = z(B, sdim, fh, fw)
         self.side = streams.new_stream(dev) if self.prefetch else None
         self.feat = None            # the key graph's output feature (static address once captured)
         self.key_graph = self.cur_graph = None

@@ -150,11 +150,12 @@ extern "C" int lsfa_warp_bilinear(const float* feat, int feat_n, const float* fl
 namespace {
 __device__ __attribute__((aligned(16))) float4 g_warp_zero4 = {0.f, 0.f, 0.f, 0.f};      // (not const: a constant-address-space pointer in the select below turns the loads into flat ones)
 
-template <bool HAS_ADD, bool HAS_RES>
+template <bool HAS_ADD, bool HAS_RES, bool HAS_BN = false>
 __global__ __launch_bounds__(256) void warp_cl_kernel(const float* __restrict__ feat, int feat_n, const float* __restrict__ flow, int N, int C,
                                                       int H, int W, const float* __restrict__ add, const float* __restrict__ res, int res_c,
                                                       const float* __restrict__ res_w, const float* __restrict__ res_b,
-                                                      float* __restrict__ out, unsigned* __restrict__ amax_out, int amax_c0, int pix_per_wg) {
+                                                      float* __restrict__ out, unsigned* __restrict__ amax_out, int amax_c0, int pix_per_wg,
+                                                      const float* __restrict__ bn_s, const float* __restrict__ bn_t) {
   using namespace lsfa::warp;
   const int HW = H * W, C4 = C >> 2;
   const int P = N * HW;                                   // (< 2^31: checked by the host)
@@ -163,10 +164,12 @@ __global__ __launch_bounds__(256) void warp_cl_kernel(const float* __restrict__ 
   const float half_w = (float)((W - 1) / 2.0), half_h = (float)((H - 1) / 2.0);
   float mx = 0.f;
   for (int q = threadIdx.x; q < C4; q += 256) {
-    float rw[4][kResMax], rb[4];
+    float rw[4][kResMax], rb[4], bs[4], bt[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       rb[j] = HAS_RES ? res_b[4 * q + j] : 0.f;
+      bs[j] = HAS_BN ? bn_s[4 * q + j] : 1.f;
+      bt[j] = HAS_BN ? bn_t[4 * q + j] : 0.f;
 #pragma unroll
       for (int k = 0; k < kResMax; ++k) rw[j][k] = (HAS_RES && k < res_c) ? res_w[(size_t)(4 * q + j) * res_c + k] : 0.f;
     }
@@ -214,6 +217,10 @@ __global__ __launch_bounds__(256) void warp_cl_kernel(const float* __restrict__ 
         qv = qv + rb[J_];                                                                                                    \
         O_ = O_ + qv;                                                                                                        \
       }                                                                                                                      \
+      if (HAS_BN) {                                                                                                          \
+        O_ = O_ * bs[J_];                                                                                                    \
+        O_ = O_ + bt[J_];                                                                                                    \
+      }                                                                                                                      \
       if (HAS_ADD) O_ = O_ + A_;                                                                                             \
       if (counts) mx = fmaxf(mx, fabsf(O_));
       LSFA_WARP_CL_ONE(0, tl.x, tr.x, bl.x, br.x, a4.x, o0)
@@ -235,38 +242,107 @@ __global__ __launch_bounds__(256) void warp_cl_kernel(const float* __restrict__ 
 }
 }  // namespace
 
-extern "C" int lsfa_warp_bilinear_cl(const float* feat_cl, int feat_n, const float* flow, int N, int C, int H, int W, const float* add_cl,
-                                     const float* res, int res_c, const float* res_w, const float* res_b, float* out_cl, unsigned* amax_out,
-                                     int amax_c0, void* stream) {
+namespace {
+int warp_cl(const char* who, const float* feat_cl, int feat_n, const float* flow, int N, int C, int H, int W, const float* add_cl, const float* res,
+            int res_c, const float* res_w, const float* res_b, const float* bn_s, const float* bn_t, float* out_cl, unsigned* amax_out, int amax_c0,
+            void* stream) {
   using namespace lsfa;
-  LSFA_REQUIRE(feat_cl && flow && out_cl, "lsfa_warp_bilinear_cl: feat, flow and out must be non-NULL");
-  LSFA_REQUIRE(N > 0 && C > 0 && C % 4 == 0 && H > 1 && W > 1, "lsfa_warp_bilinear_cl: bad shape N=%d C=%d (a multiple of 4) H=%d W=%d", N, C, H, W);
-  LSFA_REQUIRE(feat_n >= 1 && N % feat_n == 0, "lsfa_warp_bilinear_cl: feat batch %d must divide N=%d", feat_n, N);
-  LSFA_REQUIRE(amax_c0 >= 0 && amax_c0 < C && amax_c0 % 4 == 0, "lsfa_warp_bilinear_cl: amax_c0=%d must be a multiple of 4 in [0, C)", amax_c0);
-  LSFA_REQUIRE(aligned(feat_cl, 16) && aligned(add_cl, 16) && aligned(out_cl, 16), "lsfa_warp_bilinear_cl: maps must be 16-byte aligned");
+  LSFA_REQUIRE(feat_cl && flow && out_cl, "%s: feat, flow and out must be non-NULL", who);
+  LSFA_REQUIRE(N > 0 && C > 0 && C % 4 == 0 && H > 1 && W > 1, "%s: bad shape N=%d C=%d (a multiple of 4) H=%d W=%d", who, N, C, H, W);
+  LSFA_REQUIRE(feat_n >= 1 && N % feat_n == 0, "%s: feat batch %d must divide N=%d", who, feat_n, N);
+  LSFA_REQUIRE(amax_c0 >= 0 && amax_c0 < C && amax_c0 % 4 == 0, "%s: amax_c0=%d must be a multiple of 4 in [0, C)", who, amax_c0);
+  LSFA_REQUIRE(aligned(feat_cl, 16) && aligned(add_cl, 16) && aligned(out_cl, 16), "%s: maps must be 16-byte aligned", who);
   if (res) {
-    LSFA_REQUIRE(res_w && res_b, "lsfa_warp_bilinear_cl: res given without res_w/res_b");
+    LSFA_REQUIRE(res_w && res_b, "%s: res given without res_w/res_b", who);
     if (res_c < 1 || res_c > warp::kResMax) {
-      set_error("lsfa_warp_bilinear_cl: res_c=%d not in [1,%d]", res_c, warp::kResMax);
+      set_error("%s: res_c=%d not in [1,%d]", who, res_c, warp::kResMax);
       return LSFA_ENOTSUP;
     }
   }
   hipStream_t s = (hipStream_t)stream;
   const long P = (long)N * H * W;
-  LSFA_REQUIRE(P * C < (1L << 31), "lsfa_warp_bilinear_cl: map of 2^31 elements or more");
+  LSFA_REQUIRE(P * C < (1L << 31), "%s: map of 2^31 elements or more", who);
   long per = P / 1536;                     // ~6 workgroups per CU; a run of pixels amortises the quad's residual weights
   if (per < 1) per = 1;
   if (per > 16) per = 16;
   const dim3 grid((unsigned)((P + per - 1) / per));
   ProfScope prof(LSFA_OP_WARP, s);
-#define LSFA_WARP_CL(A_, R_) hipLaunchKernelGGL((warp_cl_kernel<A_, R_>), grid, dim3(256), 0, s, feat_cl, feat_n, flow, N, C, H, W, add_cl, res, res_c, \
-                                                res_w, res_b, out_cl, amax_out, amax_c0, (int)per)
-  if (add_cl && res) LSFA_WARP_CL(true, true);
-  else if (add_cl) LSFA_WARP_CL(true, false);
-  else if (res) LSFA_WARP_CL(false, true);
-  else LSFA_WARP_CL(false, false);
+#define LSFA_WARP_CL(A_, R_, B_) hipLaunchKernelGGL((warp_cl_kernel<A_, R_, B_>), grid, dim3(256), 0, s, feat_cl, feat_n, flow, N, C, H, W, add_cl, res, \
+                                                    res_c, res_w, res_b, out_cl, amax_out, amax_c0, (int)per, bn_s, bn_t)
+  if (bn_s) {
+    if (add_cl && res) LSFA_WARP_CL(true, true, true);
+    else if (add_cl) LSFA_WARP_CL(true, false, true);
+    else if (res) LSFA_WARP_CL(false, true, true);
+    else LSFA_WARP_CL(false, false, true);
+  } else {
+    if (add_cl && res) LSFA_WARP_CL(true, true, false);
+    else if (add_cl) LSFA_WARP_CL(true, false, false);
+    else if (res) LSFA_WARP_CL(false, true, false);
+    else LSFA_WARP_CL(false, false, false);
+  }
 #undef LSFA_WARP_CL
-  LSFA_LAUNCH_CHECK("lsfa_warp_bilinear_cl");
+  LSFA_LAUNCH_CHECK(who);
   return LSFA_OK;
+}
+}  // namespace
+
+extern "C" int lsfa_warp_bilinear_cl(const float* feat_cl, int feat_n, const float* flow, int N, int C, int H, int W, const float* add_cl,
+                                     const float* res, int res_c, const float* res_w, const float* res_b, float* out_cl, unsigned* amax_out,
+                                     int amax_c0, void* stream) {
+  return warp_cl("lsfa_warp_bilinear_cl", feat_cl, feat_n, flow, N, C, H, W, add_cl, res, res_c, res_w, res_b, nullptr, nullptr, out_cl, amax_out,
+                 amax_c0, stream);
+}
+
+// ---- the small net's `bn_before_fuse` (resnet_v1_101_flownet_rfcn.py:231-235, :243-246): warp_conv_feat_bn between the warp and the addend ----
+// The BatchNorm's shift does not commute with the warp's zero padding (a tap outside the map contributes 0, not 0 * s + t), so it cannot be
+// folded into the key feature; it is an epilogue step instead: r = warp + rnet_conv0(res); r = r * bn_scale[c]; r = r + bn_shift[c]; r = r + add.
+// NCHW: the gather kernel (warp_kernel<.., HAS_BN>); channels-last: warp_cl_kernel<.., HAS_BN> with its amax_out.
+extern "C" int lsfa_warp_bilinear_bn(const float* feat, int feat_n, const float* flow, int N, int C, int H, int W, const float* add, const float* res,
+                                     int res_c, const float* res_w, const float* res_b, const float* bn_scale, const float* bn_shift, float* out,
+                                     void* stream) {
+  using namespace lsfa;
+  LSFA_REQUIRE(feat && flow && out && bn_scale && bn_shift, "lsfa_warp_bilinear_bn: feat, flow, bn_scale, bn_shift and out must be non-NULL");
+  LSFA_REQUIRE(N > 0 && C > 0 && H > 1 && W > 1, "lsfa_warp_bilinear_bn: bad shape N=%d C=%d H=%d W=%d", N, C, H, W);
+  LSFA_REQUIRE(feat_n >= 1 && N % feat_n == 0, "lsfa_warp_bilinear_bn: feat batch %d must divide N=%d", feat_n, N);
+  LSFA_REQUIRE(N <= 65535, "lsfa_warp_bilinear_bn: N=%d exceeds grid.z", N);
+  if (res) {
+    LSFA_REQUIRE(res_w && res_b, "lsfa_warp_bilinear_bn: res given without res_w/res_b");
+    if (res_c < 1 || res_c > kResMax) {
+      set_error("lsfa_warp_bilinear_bn: res_c=%d not in [1,%d]", res_c, kResMax);
+      return LSFA_ENOTSUP;
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int HW = H * W;
+  ProfScope prof(LSFA_OP_WARP, s);
+  int vec = (HW % 4 == 0) ? 4 : (HW % 2 == 0) ? 2 : 1;
+  const size_t al = sizeof(float) * vec;
+  if (!(aligned(flow, al) && aligned(add, al) && aligned(res, al) && aligned(out, al))) vec = 1;
+  const int gx = ceil_div(HW, kThreads * vec);
+  int cpb = 8;
+  while (cpb > 1 && (long)gx * ceil_div(C, cpb) * N < 1024) cpb >>= 1;
+  dim3 grid(gx, ceil_div(C, cpb), N);
+#define LSFA_WARP_BN(V_, A_, R_) hipLaunchKernelGGL((warp_kernel<V_, false, A_, R_, true>), grid, dim3(kThreads), 0, s, feat, feat_n, flow, C, H, W, \
+                                                    nullptr, add, res, res_c, res_w, res_b, out, cpb, bn_scale, bn_shift)
+#define LSFA_WARP_BN_V(V_)                          \
+  if (add && res) LSFA_WARP_BN(V_, true, true);     \
+  else if (add) LSFA_WARP_BN(V_, true, false);      \
+  else if (res) LSFA_WARP_BN(V_, false, true);      \
+  else LSFA_WARP_BN(V_, false, false);
+  if (vec == 4) { LSFA_WARP_BN_V(4) }
+  else if (vec == 2) { LSFA_WARP_BN_V(2) }
+  else { LSFA_WARP_BN_V(1) }
+#undef LSFA_WARP_BN_V
+#undef LSFA_WARP_BN
+  LSFA_LAUNCH_CHECK("lsfa_warp_bilinear_bn");
+  return LSFA_OK;
+}
+
+extern "C" int lsfa_warp_bilinear_bn_cl(const float* feat_cl, int feat_n, const float* flow, int N, int C, int H, int W, const float* add_cl,
+                                        const float* res, int res_c, const float* res_w, const float* res_b, const float* bn_scale,
+                                        const float* bn_shift, float* out_cl, unsigned* amax_out, int amax_c0, void* stream) {
+  LSFA_REQUIRE(bn_scale && bn_shift, "lsfa_warp_bilinear_bn_cl: bn_scale and bn_shift must be non-NULL");
+  return warp_cl("lsfa_warp_bilinear_bn_cl", feat_cl, feat_n, flow, N, C, H, W, add_cl, res, res_c, res_w, res_b, bn_scale, bn_shift, out_cl,
+                 amax_out, amax_c0, stream);
 }
 

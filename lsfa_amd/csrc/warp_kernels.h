@@ -54,12 +54,13 @@ __device__ __forceinline__ void store_vec(float* p, const float (&v)[VEC]) {
   *reinterpret_cast<T*>(p) = t;
 }
 
-template <int VEC, bool HAS_MUL, bool HAS_ADD, bool HAS_RES>
+// HAS_BN (lsfa_warp_bilinear_bn): a per-channel affine r * bn_s[c] + bn_t[c] (two roundings) on warp + rnet_conv0(res), before `add`.
+template <int VEC, bool HAS_MUL, bool HAS_ADD, bool HAS_RES, bool HAS_BN = false>
 __global__ __launch_bounds__(kThreads) void warp_kernel(
     const float* __restrict__ feat, int feat_n, const float* __restrict__ flow, int C, int H, int W,
     const float* __restrict__ mul, const float* __restrict__ add, const float* __restrict__ res,
     int res_c, const float* __restrict__ res_w, const float* __restrict__ res_b,
-    float* __restrict__ out, int ch_per_block) {
+    float* __restrict__ out, int ch_per_block, const float* __restrict__ bn_s = nullptr, const float* __restrict__ bn_t = nullptr) {
   const int HW = H * W;
   const int n = blockIdx.z;
   const int c0 = blockIdx.y * ch_per_block;
@@ -133,6 +134,10 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(
           q = q + res_b[c];
           r = r + q;
         }
+        if (HAS_BN) {
+          r = r * bn_s[c];
+          r = r + bn_t[c];
+        }
         if (HAS_ADD) r = r + a[i];
         v[i] = r;
       }
@@ -162,6 +167,10 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(
           if (k < res_c) q = q + res_w[(size_t)c * res_c + k] * rv[k][i];
         q = q + res_b[c];
         r = r + q;
+      }
+      if (HAS_BN) {
+        r = r * bn_s[c];
+        r = r + bn_t[c];
       }
       if (HAS_ADD) r = r + a[i];
       v[i] = r;

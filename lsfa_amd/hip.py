@@ -45,7 +45,8 @@ def lib():
         L.lsfa_last_error.restype = ctypes.c_char_p
         for name in ("lsfa_proposal_workspace_bytes", "lsfa_nms_workspace_bytes", "lsfa_det_workspace_bytes",
                      "lsfa_mv_workspace_bytes", "lsfa_conv_nhwc_workspace_bytes", "lsfa_conv_weight_bytes",
-                     "lsfa_conv_workspace_bytes", "lsfa_deconv4x4s2_crop_workspace_bytes", "lsfa_stem_weight_bytes"):
+                     "lsfa_conv_workspace_bytes", "lsfa_deconv4x4s2_crop_workspace_bytes", "lsfa_stem_weight_bytes",
+                     "lsfa_channel_mean_workspace_bytes"):
             getattr(L, name).restype = ctypes.c_size_t
         L.lsfa_op_name.restype = ctypes.c_char_p
         L._nms.restype = None
@@ -198,6 +199,105 @@ def warp_bilinear_cl(feat_cl, flow, add_cl=None, res=None, res_w=None, res_b=Non
         out = torch.empty((N, H, W, C), device=feat_cl.device, dtype=torch.float32)
     _check(lib().lsfa_warp_bilinear_cl(_ptr(feat_cl), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W), _ptr(add_cl), _ptr(res), _ci(res_c),
                                        _ptr(res_w), _ptr(res_b), _ptr(out), _ptr(amax_out), _ci(amax_c0), _stream()), "lsfa_warp_bilinear_cl")
+    return out
+
+
+@_on_tensor_device
+def warp_bilinear_bn(feat, flow, bn_scale, bn_shift, add=None, res=None, res_w=None, res_b=None, out=None):
+    """lsfa_warp_bilinear_bn: warp_bilinear (no `mul`) with warp_conv_feat_bn between the warp (+ rnet_conv0(res)) and `add`:
+    r * bn_scale[c] + bn_shift[c], two roundings.  NCHW maps."""
+    feat, flow = _f32c(feat, "feat"), _f32c(flow, "flow")
+    add, res = _f32c(add, "add"), _f32c(res, "res")
+    bn_scale, bn_shift = _f32c(bn_scale, "bn_scale"), _f32c(bn_shift, "bn_shift")
+    N, _, H, W = flow.shape
+    feat_n, C = feat.shape[0], feat.shape[1]
+    if bn_scale.numel() != C or bn_shift.numel() != C:
+        raise LsfaError("warp_bilinear_bn: bn_scale / bn_shift must have %d elements" % C)
+    res_c = 0
+    if res is not None:
+        res_w, res_b = _f32c(res_w, "res_w").reshape(C, -1), _f32c(res_b, "res_b")
+        res_c = res.shape[1]
+    if out is None:
+        out = torch.empty((N, C, H, W), device=feat.device, dtype=torch.float32)
+    _check(lib().lsfa_warp_bilinear_bn(_ptr(feat), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W), _ptr(add), _ptr(res), _ci(res_c),
+                                       _ptr(res_w), _ptr(res_b), _ptr(bn_scale), _ptr(bn_shift), _ptr(out), _stream()), "lsfa_warp_bilinear_bn")
+    return out
+
+
+@_on_tensor_device
+def warp_bilinear_bn_cl(feat_cl, flow, bn_scale, bn_shift, add_cl=None, res=None, res_w=None, res_b=None, out=None, amax_out=None, amax_c0=0):
+    """lsfa_warp_bilinear_bn_cl: warp_bilinear_cl with warp_conv_feat_bn before `add_cl` (the bits of warp_bilinear_bn on the transposed maps)."""
+    feat_cl, flow = _f32c(feat_cl, "feat_cl"), _f32c(flow, "flow")
+    add_cl, res = _f32c(add_cl, "add_cl"), _f32c(res, "res")
+    bn_scale, bn_shift = _f32c(bn_scale, "bn_scale"), _f32c(bn_shift, "bn_shift")
+    N, _, H, W = flow.shape
+    feat_n, C = feat_cl.shape[0], feat_cl.shape[3]
+    if tuple(feat_cl.shape[1:3]) != (H, W) or (add_cl is not None and tuple(add_cl.shape) != (N, H, W, C)):
+        raise LsfaError("warp_bilinear_bn_cl: feat_cl %s / add_cl %s do not match a (%d, 2, %d, %d) flow" % (
+            tuple(feat_cl.shape), None if add_cl is None else tuple(add_cl.shape), N, H, W))
+    if bn_scale.numel() != C or bn_shift.numel() != C:
+        raise LsfaError("warp_bilinear_bn_cl: bn_scale / bn_shift must have %d elements" % C)
+    res_c = 0
+    if res is not None:
+        res_w, res_b = _f32c(res_w, "res_w").reshape(C, -1), _f32c(res_b, "res_b")
+        res_c = res.shape[1]
+    if out is None:
+        out = torch.empty((N, H, W, C), device=feat_cl.device, dtype=torch.float32)
+    _check(lib().lsfa_warp_bilinear_bn_cl(_ptr(feat_cl), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W), _ptr(add_cl), _ptr(res),
+                                          _ci(res_c), _ptr(res_w), _ptr(res_b), _ptr(bn_scale), _ptr(bn_shift), _ptr(out), _ptr(amax_out),
+                                          _ci(amax_c0), _stream()), "lsfa_warp_bilinear_bn_cl")
+    return out
+
+
+@_on_tensor_device
+def channel_mean(x1, x2=None, out=None):
+    """lsfa_channel_mean: per-image channel means of channels-last maps, (N, H, W, C1) [and (N, H, W, C2) read as the concatenation
+    [x1 | x2] without storing it] -> (N, C1 + C2).  Deterministic; the order is documented in include/lsfa_hip.h."""
+    x1, x2 = _f32c(x1, "x1"), _f32c(x2, "x2")
+    N, H, W, C1 = x1.shape
+    C2 = 0
+    if x2 is not None:
+        if tuple(x2.shape[:3]) != (N, H, W):
+            raise LsfaError("channel_mean: x2 %s does not match x1 %s" % (tuple(x2.shape), tuple(x1.shape)))
+        C2 = x2.shape[3]
+    C = C1 + C2
+    if out is None:
+        out = torch.empty((N, C), device=x1.device, dtype=torch.float32)
+    need = lib().lsfa_channel_mean_workspace_bytes(_ci(N), _ci(C), _ci(H * W))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x1.device)
+    _check(lib().lsfa_channel_mean(_ptr(x1), _ci(C1), _ptr(x2), _ci(C2), _ci(N), _ci(H * W), _ptr(out), _ptr(ws), ctypes.c_size_t(need),
+                                   _stream()), "lsfa_channel_mean")
+    return out
+
+
+@_on_tensor_device
+def channel_gate(m, w1, b1, w2, b2, out=None):
+    """lsfa_channel_gate: sigmoid(w2 relu(w1 m + b1) + b2) for the N rows of m (N, K); w1 (M, K), w2 (O, M) fp32 -> (N, O)."""
+    m, w1, b1, w2, b2 = (_f32c(t, n) for t, n in ((m, "m"), (w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")))
+    N, K = m.shape
+    M, O = w1.shape[0], w2.shape[0]
+    if w1.numel() != M * K or w2.numel() != O * M or b1.numel() != M or b2.numel() != O:
+        raise LsfaError("channel_gate: weights %s / %s do not chain from %d inputs" % (tuple(w1.shape), tuple(w2.shape), K))
+    hidden = torch.empty((N, M), device=m.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((N, O), device=m.device, dtype=torch.float32)
+    _check(lib().lsfa_channel_gate(_ptr(m), _ci(N), _ci(K), _ptr(w1), _ptr(b1), _ci(M), _ptr(w2), _ptr(b2), _ci(O), _ptr(hidden), _ptr(out),
+                                   _stream()), "lsfa_channel_gate")
+    return out
+
+
+@_on_tensor_device
+def gate_apply(x, gate, y, out=None, amax_out=None, amax_c0=0):
+    """lsfa_gate_apply: x * gate[n, c] + y (two roundings) on channels-last (N, H, W, C) maps; gate (N, C).  amax_out: a zeroed row of
+    amax_slots() that receives max|out| over channels [amax_c0, C)."""
+    x, gate, y = _f32c(x, "x"), _f32c(gate, "gate"), _f32c(y, "y")
+    N, H, W, C = x.shape
+    if tuple(y.shape) != tuple(x.shape) or tuple(gate.shape) != (N, C):
+        raise LsfaError("gate_apply: x %s, y %s, gate %s" % (tuple(x.shape), tuple(y.shape), tuple(gate.shape)))
+    if out is None:
+        out = torch.empty_like(x)
+    _check(lib().lsfa_gate_apply(_ptr(x), _ptr(gate), _ptr(y), _ci(N), _ci(H * W), _ci(C), _ptr(out), _ptr(amax_out), _ci(amax_c0), _stream()),
+           "lsfa_gate_apply")
     return out
 
 

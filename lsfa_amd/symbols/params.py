@@ -3,8 +3,10 @@
 Names are the MXNet layer names of the reference (SURVEY.md §8b "Symbol API"):
 backbone   dff_rfcn/symbols/resnet.py:138-240 + sym_common.py:92-135, 249-290
 symbols    dff_rfcn/symbols/resnet_v1_101_flownet_rfcn.py:44-236 (helpers), :448-659 (test symbols)
-init       init_weight, :753-870 (normal(0, 0.01) for the new layers, zeros for DCN offsets,
-           Convolution5_scale weight 0 / bias 1, small_net_* copied from the big net)
+init       init_weight, :753-870 (normal(0, 0.01) for the new layers - fuse_reduce_*, cur_scale, s_feat_conv* -, zeros for DCN
+           offsets, Convolution5_scale weight 0 / bias 1, small_net_* copied from the big net, BatchNorms of
+           small_net_bn_before_fuse at gamma 1 / beta 0 / mean 0 / var 1)
+small net  fuse_small_net, :209-274: every small_net_fuse_type x small_net_stride x scale / bn combination (small_net_fuse_spec)
 `arg` holds weights/biases/gamma/beta, `aux` holds moving_mean/moving_var, like MXNet.
 """
 from collections import OrderedDict
@@ -114,6 +116,43 @@ def batch_symbol_spec(cfg):
     return arg, aux
 
 
+SMALL_NET_FUSE_TYPES = ('add', 'addv2', 'concat', 'concatv1', 'concatv2')
+SMALL_NET_STAGES = {4: 1, 8: 2}      # small_net_stride -> stages of the small net (fuse_small_net :214-225: stage 1 / stage 2 output)
+
+
+def small_net_channels(cfg):
+    """Channels of the small net's raw output `cur_feat` (num_filters, :218 / :224)."""
+    return FILTERS[SMALL_NET_STAGES[cfg.network.small_net_stride] - 1]
+
+
+def small_net_fuse_spec(arg, aux, cfg):
+    """The layers of fuse_small_net (:209-274) after the small net itself: cur_scale, the fuse branch of small_net_fuse_type and the
+    BatchNorms of small_net_bn_before_fuse (which only the `add` / `addv2` branches create)."""
+    fuse = cfg.network.small_net_fuse_type
+    if fuse not in SMALL_NET_FUSE_TYPES:
+        raise RuntimeError("unknow small_net_fuse_type: %s" % fuse)
+    C = small_net_channels(cfg)
+    if cfg.network.small_net_scale_before_fuse:
+        _conv(arg, 'cur_scale', C, C, 1)                          # :226-227
+    if fuse == 'add':
+        _conv(arg, 'fuse_reduce_add', 1024, C, 3)                 # :230
+    elif fuse == 'addv2':
+        _conv(arg, 'fuse_reduce_add_conv1', C, C, 3)              # :238
+        _conv(arg, 'fuse_reduce_add_conv2', 1024, C, 1)           # :240
+    elif fuse in ('concat', 'concatv1'):
+        _conv(arg, 'fuse_reduce_c1', 512, C, 3)                   # :248 / :252
+        _conv(arg, 'fuse_reduce_c2', 512, 1024, 3)
+        _conv(arg, 'fuse_reduce', 1024, 1024, 3)
+    else:                                                         # concatv2 :262-266
+        _conv(arg, 'fuse_reduce_c1', 1024, C, 3)
+    if fuse in ('concatv1', 'concatv2'):
+        _conv(arg, 's_feat_conv1', 1024, 1024 if fuse == 'concatv1' else 2048, 1)
+        _conv(arg, 's_feat_conv2', 1024, 1024, 1)
+    if cfg.network.small_net_bn_before_fuse and fuse in ('add', 'addv2'):
+        _bn(arg, aux, 'cur_feat_bn', 1024)
+        _bn(arg, aux, 'warp_conv_feat_bn', 1024)
+
+
 def cur_symbol_spec(cfg):
     arg, aux = OrderedDict(), OrderedDict()
     if cfg.network.rnet_num_conv != 0 or cfg.network.res_diff_bn or cfg.network.fuse_type != 'add' \
@@ -121,11 +160,10 @@ def cur_symbol_spec(cfg):
         raise NotImplementedError("only the trained LSFA configuration (rnet_num_conv 0, fuse 'add', no fnet) is built")
     _conv(arg, 'rnet_conv0', 1024, 3, 1)
     if cfg.network.add_small_net:
-        if cfg.network.small_net_stride != 4 or cfg.network.small_net_fuse_type != 'add' \
-                or cfg.network.small_net_bn_before_fuse or cfg.network.small_net_scale_before_fuse:
-            raise NotImplementedError("only small_net_stride 4 / fuse 'add' is built")
-        resnet_spec(arg, aux, 'small_net_', stages=1, add_dcn=False, tail=False)
-        _conv(arg, 'fuse_reduce_add', 1024, 256, 3)
+        if cfg.network.small_net_stride not in SMALL_NET_STAGES:
+            raise RuntimeError("unknow small_net_tride: %d" % cfg.network.small_net_stride)
+        resnet_spec(arg, aux, 'small_net_', stages=SMALL_NET_STAGES[cfg.network.small_net_stride], add_dcn=False, tail=False)
+        small_net_fuse_spec(arg, aux, cfg)
     head_spec(arg, cfg)
     return arg, aux
 
@@ -150,7 +188,7 @@ def init_params(cfg, seed=0, head_fg_prior=0.02, dcn_offset_std=0.02):
         fan_in = float(np.prod(shape[1:]))
         return (rs.randn(*shape) * (gain * np.sqrt(2.0 / fan_in))).astype(np.float32)
 
-    new_layers = ('feat_conv_3x3', 'rpn_', 'rfcn_', 'Nq_', 'em_', 'rnet_', 'fuse_reduce_add')
+    new_layers = ('feat_conv_3x3', 'rpn_', 'rfcn_', 'Nq_', 'em_', 'rnet_', 'fuse_reduce', 'cur_scale', 's_feat_')
     for name, shape in list(karg.items()) + list(carg.items()):
         if name in arg:
             continue

@@ -342,9 +342,11 @@ class Executor(object):
                                        rpn_post_nms_top_n=cfg.TEST.RPN_POST_NMS_TOP_N, threshold=cfg.TEST.RPN_NMS_THRESH,
                                        rpn_min_size=cfg.TEST.RPN_MIN_SIZE)
         two = self.pieces == 2
-        self._slots = {'backbone': _Slots(128, dev, two), 'small': _Slots(16, dev, two), 'agg': _Slots(8, dev, two), 'flow': _Slots(16, dev, two),
-                       'heads': _Slots(2, dev, two)}
+        small_rows = 16 if cfg.network.small_net_stride == 4 else 32     # the stride-8 small net has stages 1-2: 22 rows + the fuse convolutions
+        self._slots = {'backbone': _Slots(128, dev, two), 'small': _Slots(small_rows, dev, two), 'agg': _Slots(8, dev, two), 'flow': _Slots(16, dev, two),
+                       'heads': _Slots(2, dev, two), 'fuse': _Slots(8, dev, two)}
         W = lambda name: _t(arg[name], dev, f32)
+        self.fuse_type, self.warp_bn, self.cur_scale = None, None, None     # small-net fuse (_fuse_prepare)
         if sym.kind in ('key', 'batch'):
             self.net = _ResNetWeights(arg, aux, '', 4, cfg.network.add_dcn, True, dev, self.pieces)
             self.feat_w, self.feat_b = hip.SplitWeight(W('feat_conv_3x3_weight'), pieces=self.pieces), W('feat_conv_3x3_bias')
@@ -367,8 +369,66 @@ class Executor(object):
             self.rnet_w = _t(arg['rnet_conv0_weight'].reshape(1024, 3), dev, f32)
             self.rnet_b = W('rnet_conv0_bias')
             if cfg.network.add_small_net:
-                self.small = _ResNetWeights(arg, aux, 'small_net_', 1, False, False, dev, self.pieces)
-                self.fuse_w, self.fuse_b = hip.SplitWeight(W('fuse_reduce_add_weight'), pieces=self.pieces), W('fuse_reduce_add_bias')
+                self.small_stages = P.SMALL_NET_STAGES[cfg.network.small_net_stride]
+                self.small = _ResNetWeights(arg, aux, 'small_net_', self.small_stages, False, False, dev, self.pieces)
+                self._fuse_prepare(arg, aux)
+
+    def _fuse_prepare(self, arg, aux):
+        """Weights of fuse_small_net (:209-274) after the small net.  cur_feat_bn folds into the convolution in front of it (like _ResNetWeights'
+        BatchNorms); warp_conv_feat_bn cannot fold into the key feature (its shift does not commute with the warp's zero padding) and stays a
+        per-channel scale and shift in the warp's epilogue (lsfa_warp_bilinear_bn[_cl]).  concat / concatv1: fuse_reduce on [c2 | c1] is
+        split along its input channels into two convolutions that add into one output (the second adds the first as its residual), so the
+        concatenation is never stored and c1 may come from anywhere (computed ahead of the frame, FrameGraphs' prefetch)."""
+        net, dev, f32 = self.cfg.network, self.device, torch.float32
+        self.fuse_type = fuse = net.small_net_fuse_type
+        bn = net.small_net_bn_before_fuse and fuse in ('add', 'addv2')
+
+        def dev_t(a):
+            return _t(np.ascontiguousarray(a, np.float32), dev, f32)
+
+        def split(w):
+            return hip.SplitWeight(dev_t(w), pieces=self.pieces)
+
+        def bn_fold(name):        # (scale, shift) of an inference BatchNorm (eps 2e-5, fix_gamma=False: moving statistics at test time)
+            g, b = arg[name + '_gamma'].astype(np.float64), arg[name + '_beta'].astype(np.float64)
+            m, v = aux[name + '_moving_mean'].astype(np.float64), aux[name + '_moving_var'].astype(np.float64)
+            sc = g / np.sqrt(v + BN_EPS)
+            return sc, b - m * sc
+
+        def last_conv(name):      # the convolution that produces cur_feat, with cur_feat_bn folded in
+            w, b = arg[name + '_weight'].astype(np.float64), arg[name + '_bias'].astype(np.float64)
+            if bn:
+                sc, sh = bn_fold('cur_feat_bn')
+                w, b = w * sc.reshape(-1, 1, 1, 1), b * sc + sh
+            return split(w), dev_t(b)
+
+        self.cur_scale = (split(arg['cur_scale_weight']), dev_t(arg['cur_scale_bias'])) if net.small_net_scale_before_fuse else None
+        if bn:
+            sc, sh = bn_fold('warp_conv_feat_bn')
+            self.warp_bn = (dev_t(sc), dev_t(sh))
+        if fuse == 'add':
+            self.fuse_w, self.fuse_b = last_conv('fuse_reduce_add')
+        elif fuse == 'addv2':
+            self.fuse_c1 = (split(arg['fuse_reduce_add_conv1_weight']), dev_t(arg['fuse_reduce_add_conv1_bias']))
+            self.fuse_w, self.fuse_b = last_conv('fuse_reduce_add_conv2')
+        else:
+            self.fuse_c1 = (split(arg['fuse_reduce_c1_weight']), dev_t(arg['fuse_reduce_c1_bias']))
+        if fuse in ('concat', 'concatv1'):
+            self.fuse_c2 = (split(arg['fuse_reduce_c2_weight']), dev_t(arg['fuse_reduce_c2_bias']))
+            wr = arg['fuse_reduce_weight']
+            self.fuse_r_warp, self.fuse_r_cur, self.fuse_r_b = split(wr[:, :512]), split(wr[:, 512:]), dev_t(arg['fuse_reduce_bias'])
+        if fuse in ('concatv1', 'concatv2'):      # the gate's two 1x1 convolutions on a pooled vector: fp32 GEMVs (lsfa_channel_gate)
+            w1, w2 = arg['s_feat_conv1_weight'], arg['s_feat_conv2_weight']
+            self.gate = (dev_t(w1.reshape(w1.shape[0], -1)), dev_t(arg['s_feat_conv1_bias']), dev_t(w2.reshape(w2.shape[0], -1)),
+                         dev_t(arg['s_feat_conv2_bias']))
+
+    @property
+    def small_net_channels(self):
+        """Channels of small_net_feature's map: the image-only part of the fuse - the addend (1024) for `add` / `addv2`, fuse_reduce_c1's
+        output for the concat types (512; 1024 for `concatv2`)."""
+        if not self.cfg.network.add_small_net:
+            return self.cfg.network.DFF_FEAT_DIM
+        return 512 if self.fuse_type in ('concat', 'concatv1') else 1024
 
     def _tap(self, name, x):
         if self.taps is not None:
@@ -715,11 +775,33 @@ class Executor(object):
         """fuse_small_net's image branch (:209-236): avgpool 4x4 -> small_net_ stem + stage 1 ->
         fuse_reduce_add (3x3 256 -> 1024, written NCHW: the warp kernel's `add` operand; nchw=False: channels-last, the operand of
         lsfa_warp_bilinear_cl).  It depends on the frame image only, so a caller may compute it ahead of the rest of the frame
-        (lsfa_amd/core/graphs.py overlaps it with the previous frame's tail)."""
+        (lsfa_amd/core/graphs.py overlaps it with the previous frame's tail).
+        Other small_net_* settings: everything of fuse_small_net before the first operation that reads the warped feature - stride 8 is
+        avgpool 2x2 -> stem + stages 1-2; then cur_scale (scale_before_fuse); then the addend of `add` / `addv2` (cur_feat_bn folded in) or
+        fuse_reduce_c1's output `c1` of the concat types.  Its channel count is `small_net_channels`."""
         with torch.no_grad():
+            return self._small_net_feature(data, nchw)
+
+    def _small_net_feature(self, data, nchw, amax_out=None):
+        net = self.cfg.network
+        if net.small_net_stride == 4 and self.fuse_type == 'add' and self.cur_scale is None:
             img = hip.avgpool_nchw(data, 4)
             s, am = self._resnet(img, self.small, 1, 'small')
-            return self._conv(s, self.fuse_w, self.fuse_b, 1, 1, 1, amax_in=am, nchw=nchw)
+            return self._conv(s, self.fuse_w, self.fuse_b, 1, 1, 1, amax_in=am, amax_out=amax_out, nchw=nchw)
+        img = hip.avgpool_nchw(data, 4 if net.small_net_stride == 4 else 2)      # resize_data (:213 / :219), pooling_convention 'full'
+        s, am = self._resnet(img, self.small, self.small_stages, 'small')
+        S = self._slots['small']                  # (the section _resnet began goes on)
+        if self.cur_scale is not None:            # cur_scale (:226-227): 1x1 C -> C + bias, no activation
+            am_s = S.new()
+            s = self._conv(s, self.cur_scale[0], self.cur_scale[1], amax_in=am, amax_out=am_s)
+            am = am_s
+        if self.fuse_type == 'add':
+            return self._conv(s, self.fuse_w, self.fuse_b, 1, 1, 1, amax_in=am, amax_out=amax_out, nchw=nchw)
+        if self.fuse_type == 'addv2':             # fuse_reduce_add_conv1 (3x3) + ReLU, fuse_reduce_add_conv2 (1x1)
+            am_h = S.new()
+            h = self._conv(s, self.fuse_c1[0], self.fuse_c1[1], 1, 1, 1, act=1, amax_in=am, amax_out=am_h)
+            return self._conv(h, self.fuse_w, self.fuse_b, amax_in=am_h, amax_out=amax_out, nchw=nchw)
+        return self._conv(s, self.fuse_c1[0], self.fuse_c1[1], 1, 1, 1, amax_in=am, amax_out=amax_out, nchw=nchw)
 
     def cur_channels_last(self, channels):
         """whether a non-key frame whose small-net feature is computed inside forward() runs on channels-last maps (_forward_cur_cl)"""
@@ -737,8 +819,12 @@ class Executor(object):
         add_cl = self.small_net_feature(d['data'], nchw=False)
         self._tap('small_feat', add_cl.permute(0, 3, 1, 2))
         am = S.new()
-        conv_cl = hip.warp_bilinear_cl(feat_cl, d['motion_vector'], add_cl=add_cl, res=d['res_diff'], res_w=self.rnet_w, res_b=self.rnet_b,
-                                       amax_out=am, amax_c0=512)     # the maximum of the channels the R-FCN convolution (two fp16 pieces) reads
+        if self.warp_bn is None:
+            conv_cl = hip.warp_bilinear_cl(feat_cl, d['motion_vector'], add_cl=add_cl, res=d['res_diff'], res_w=self.rnet_w, res_b=self.rnet_b,
+                                           amax_out=am, amax_c0=512)     # the maximum of the channels the R-FCN convolution (two fp16 pieces) reads
+        else:                                     # small_net_bn_before_fuse: warp_conv_feat_bn in the epilogue, before the addend
+            conv_cl = hip.warp_bilinear_bn_cl(feat_cl, d['motion_vector'], self.warp_bn[0], self.warp_bn[1], add_cl=add_cl, res=d['res_diff'],
+                                              res_w=self.rnet_w, res_b=self.rnet_b, amax_out=am, amax_c0=512)
         rois, cls_prob, bbox_pred = self._heads_cl(conv_cl, am, d['im_info'])
         return {'data': d['data'], 'data_key': d.get('data_key'), 'data_key_old': d.get('data_key_old'),
                 'feat_key_old': d.get('feat_key_old'), 'rois_output': rois, 'cls_prob_reshape_output': cls_prob,
@@ -764,8 +850,55 @@ class Executor(object):
         B = cfg.TEST.BATCH_IMAGES
         return rois, cls_p.view(B, -1, cls_p.shape[1]), bbox.view(B, -1, bbox.shape[1])
 
+    def _forward_concat(self, d):
+        """small_net_fuse_type concat / concatv1 / concatv2 (:247-271) on channels-last maps: fuse_reduce_c2 is a 3x3 convolution of the warped
+        feature, so the warp writes (pixel, channel) rows (lsfa_warp_bilinear_cl) like _forward_cur_cl's.
+          concat   out = fuse_reduce([c2 | c1])                         (two convolutions into one output: see _fuse_prepare)
+          concatv1 cat = relu(fuse_reduce([c2 | c1])), s = gate(mean(cat)), out = cat * s + cat
+          concatv2 s = gate(mean([warp | c1])) (the 2048-channel mean reads the two maps in place), out = c1 * s + warp
+        gate = sigmoid(s_feat_conv2(relu(s_feat_conv1(.)))) per image (lsfa_channel_gate); the means and the gate application are
+        lsfa_channel_mean / lsfa_gate_apply, which also leaves the maximum the R-FCN convolution's scale needs."""
+        fuse = self.fuse_type
+        S = self._slots['fuse'].begin()
+        feat_cl = d.get('feat_key_cl')
+        if feat_cl is None:
+            feat_cl = hip.nchw_to_nhwc(d['feat_key'])
+        small = d.get('small_feat')        # c1 (NCHW) computed ahead by the caller, else computed here channels-last
+        am_c1 = S.new()
+        if small is None:
+            c1 = self._small_net_feature(d['data'], False, amax_out=am_c1)
+        else:
+            c1 = hip.nchw_to_nhwc(small, amax_out=am_c1)
+        self._tap('small_feat', c1.permute(0, 3, 1, 2))
+        am_w, am_out = S.new(), S.new()
+        warp = hip.warp_bilinear_cl(feat_cl, d['motion_vector'], res=d['res_diff'], res_w=self.rnet_w, res_b=self.rnet_b, amax_out=am_w)
+        self._tap('warp', warp.permute(0, 3, 1, 2))
+        gate = None
+        if fuse == 'concatv2':
+            gate = hip.channel_gate(hip.channel_mean(warp, c1), *self.gate)
+            out = hip.gate_apply(c1, gate, warp, amax_out=am_out, amax_c0=512)
+        else:
+            am_c2 = S.new()
+            c2 = self._conv(warp, self.fuse_c2[0], self.fuse_c2[1], 1, 1, 1, amax_in=am_w, amax_out=am_c2)
+            am_y = am_out if fuse == 'concat' else S.new()
+            y = self._conv(c1, self.fuse_r_cur, self.fuse_r_b, 1, 1, 1, amax_in=am_c1)
+            y = self._conv(c2, self.fuse_r_warp, None, 1, 1, 1, act=1 if fuse == 'concatv1' else 0, amax_in=am_c2, amax_out=am_y,
+                           out=y, residual=y)
+            out = y
+            if fuse == 'concatv1':
+                gate = hip.channel_gate(hip.channel_mean(y), *self.gate)
+                out = hip.gate_apply(y, gate, y, amax_out=am_out, amax_c0=512)
+        if gate is not None:
+            self._tap('gate', gate)
+        rois, cls_prob, bbox_pred = self._heads_cl(out, am_out, d['im_info'])
+        return {'data': d['data'], 'data_key': d.get('data_key'), 'data_key_old': d.get('data_key_old'),
+                'feat_key_old': d.get('feat_key_old'), 'rois_output': rois, 'cls_prob_reshape_output': cls_prob,
+                'bbox_pred_reshape_output': bbox_pred, 'conv_feat': out.permute(0, 3, 1, 2)}
+
     def _forward_cur(self, d):
         cfg = self.cfg
+        if self.fuse_type in ('concat', 'concatv1', 'concatv2'):
+            return self._forward_concat(d)
         add = d.get('small_feat')          # precomputed by the caller, else computed here
         # r6: the whole non-key frame on channels-last maps (no transposing copy in front of the R-FCN convolution) whenever nothing forces the
         # operator layout: the small net's feature is computed here (not handed over NCHW), C is a multiple of 4, no exact-fp32 reference mode.
@@ -775,8 +908,12 @@ class Executor(object):
         if add is None and cfg.network.add_small_net:
             add = self.small_net_feature(d['data'])
         self._tap('small_feat', add)
-        conv_feat = hip.warp_bilinear(d['feat_key'], d['motion_vector'], add=add, res=d['res_diff'], res_w=self.rnet_w,
-                                      res_b=self.rnet_b)
+        if self.warp_bn is None:
+            conv_feat = hip.warp_bilinear(d['feat_key'], d['motion_vector'], add=add, res=d['res_diff'], res_w=self.rnet_w,
+                                          res_b=self.rnet_b)
+        else:
+            conv_feat = hip.warp_bilinear_bn(d['feat_key'], d['motion_vector'], self.warp_bn[0], self.warp_bn[1], add=add, res=d['res_diff'],
+                                             res_w=self.rnet_w, res_b=self.rnet_b)
         rois, cls_prob, bbox_pred = self._heads(conv_feat, d['im_info'])
         return {'data': d['data'], 'data_key': d.get('data_key'), 'data_key_old': d.get('data_key_old'),
                 'feat_key_old': d.get('feat_key_old'), 'rois_output': rois, 'cls_prob_reshape_output': cls_prob,
