@@ -904,6 +904,9 @@ def upsample_flow(x, w, bias, out, c0, amax_out=None):
     """lsfa_upsample_flow: Deconvolution(4x4, stride 2) + Crop(offset 1) of a (N,Hi,Wi,C) flow into channels [c0, c0+C) of out (N,Hc,Wc,L)."""
     x, w = _f32c(x, "x"), _f32c(w, "w")
     N, Hi, Wi, C = x.shape
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda or out.dim() != 4 or out.shape[0] != N
+            or not out.is_contiguous()):
+        raise LsfaError("upsample_flow: out must be a contiguous float32 CUDA tensor (%d, Hc, Wc, L)" % N)
     _check(lib().lsfa_upsample_flow(_ptr(x), _ci(N), _ci(Hi), _ci(Wi), _ci(C), _ptr(w), _ptr(bias), _ci(out.shape[1]), _ci(out.shape[2]),
                                     _ptr(out), _ci(out.shape[3]), _ci(c0), _ptr(amax_out), _stream()), "lsfa_upsample_flow")
     return out
@@ -932,6 +935,8 @@ def rfcn_head_ps_ld(ps_map, cell_ld, rois, H, W, ncls, nbox, spatial_scale=0.062
     """rfcn_head_ps on a position-sensitive map whose cells are `cell_ld` floats apart (N, H, W, cell_ld)."""
     ps_map, rois = _f32c(ps_map, "ps_map"), _f32c(rois, "rois")
     N, R = ps_map.shape[0], rois.shape[0]
+    if ps_map.shape[-1] != cell_ld or ps_map.numel() != N * H * W * cell_ld:
+        raise LsfaError("rfcn_head_ps_ld: ps_map %s is not (%d, %d, %d, cell_ld = %d)" % (tuple(ps_map.shape), N, H, W, cell_ld))
     cls_prob = torch.empty((R, ncls), device=rois.device, dtype=torch.float32)
     bbox_pred = torch.empty((R, nbox), device=rois.device, dtype=torch.float32)
     if LAB_SKIP_HEAD:
