@@ -557,6 +557,27 @@ int lsfa_image_resize_transform(const void* im_hwc_bgr, int is_u8, int N, int H,
                                 const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw, int out_h, int out_w, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Block-matching motion estimation on decoded frames: the (n, 7) rows lsfa_mv_accumulate takes, computed from two uint8 frames.
+ * Replaces (in function, NOT in arithmetic): the vectors the reference reads out of an MPEG-4 stream - ffmpeg's encoder
+ * (data/reencode_vid.sh) and libav's AVMotionVector side data (external/data_loader_py2/coviar_data_loader.c:88-103).  Neither is part of
+ * this project and no output of them exists to compare with, so these two exports are defined by the specification in
+ * lsfa_amd/csrc/me.hip / DESIGN.md "Motion estimation" (restated in numpy as tests/ref_me.py) and are bit-exact with THAT; parity with an
+ * encoder's search (EPZS, half-pel, 4MV) is unpinned and not claimed.  Out of scope: half-pel refinement, 8x8 partitions, B-frames, reading
+ * a real bitstream.
+ * lsfa_luma_u8: bgr (H, W, 3) uint8, the layout lsfa_mv_residual takes -> luma (H, W) uint8, Y = (29 B + 150 G + 77 R + 128) >> 8.
+ * lsfa_mv_estimate: luma_cur, luma_ref (H, W) uint8, 4-byte aligned; 16 x 16 macroblocks on a ceil(W / 16) x ceil(H / 16) grid, edge blocks
+ * cover what is left of the frame; full search over (dx, dy) in [-search, search]^2 (search 1..32) of the candidates whose shifted covered
+ * rectangle lies inside the frame; cost = SAD + lambda (|dx| + |dy|) (lambda 0..2^24), ties by (|dx| + |dy|, dy, dx); max_sad > 0 turns a
+ * winner whose SAD exceeds it into a zero vector (0: off).  mvs (mbh * mbw, 7) int32 rows {-1, 16, 16, 16 bx + 8 + dx, 16 by + 8 + dy,
+ * 16 bx + 8, 16 by + 8} - EVERY block, zero vectors included (lsfa_mv_accumulate skips those itself), so the row count depends on the frame
+ * size alone and nothing is compacted or read back; sad (mbh, mbw) int32, the winner's SAD, may be NULL.  One launch, no workspace.
+ * ------------------------------------------------------------------------ */
+int lsfa_luma_u8(const unsigned char* bgr, int width, int height, unsigned char* luma, void* stream);
+int lsfa_mv_estimate(const unsigned char* luma_cur, const unsigned char* luma_ref, int width, int height,
+                     int search, int lambda, int max_sad, int* mvs /* (mbh*mbw, 7) */, int* sad /* may be NULL */,
+                     void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Plumbing without a reference counterpart: a hipStream_t that is nobody else's (non-blocking; PyTorch's
  * streams come from a small round-robin pool, and two graphs captured on pool twins share one BLAS
  * workspace — lsfa_amd/core/streams.py wraps these in torch.cuda.ExternalStream for capture and replay).
@@ -581,7 +602,8 @@ int lsfa_ptr_table_set(void** table_dev, int n, const void* const* ptrs_host, vo
 enum {
   LSFA_OP_PSROI = 0, LSFA_OP_RFCN_HEAD = 1, LSFA_OP_WARP = 2, LSFA_OP_AGG = 3,
   LSFA_OP_PROPOSAL = 4, LSFA_OP_NMS = 5, LSFA_OP_DET = 6, LSFA_OP_DCN_IM2COL = 7,
-  LSFA_OP_BNRELU = 8, LSFA_OP_CONV = 9, LSFA_OP_STEM = 10, LSFA_OP_FLOWNET = 11, LSFA_OP_COUNT = 12
+  LSFA_OP_BNRELU = 8, LSFA_OP_CONV = 9, LSFA_OP_STEM = 10, LSFA_OP_FLOWNET = 11,
+  LSFA_OP_MV_ESTIMATE = 12, LSFA_OP_COUNT = 13
 };
 int lsfa_prof_enable(int mask);
 int lsfa_prof_read(double* ms_host /*LSFA_OP_COUNT*/, int* launches_host /*LSFA_OP_COUNT*/);

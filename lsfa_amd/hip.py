@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("LSFA_HIP_LIBRARY") or os.path.join(_HERE, "liblsfa_hi
 # code that runs before the library is loaded and is checked against it there (an out-of-date copy made lsfa_prof_read write one
 # element past the buffers sized by it: r3, after LSFA_OP_FLOWNET was added)
 OP_NAMES = ["psroi_pool", "rfcn_head", "warp_bilinear", "aggregate", "proposal", "nms", "det_postprocess",
-            "deform_im2col", "scale_shift_relu", "conv_nhwc", "stem", "flownet_small"]
+            "deform_im2col", "scale_shift_relu", "conv_nhwc", "stem", "flownet_small", "mv_estimate"]
 
 
 class LsfaError(RuntimeError):
@@ -1403,6 +1403,123 @@ class MotionVectorAccumulator(object):
         """The frame's `motion_vector` (1, 2, h, w) and `res_diff` (1, 3, h, w) as get_image builds them (lib/utils/image.py:52-63): the
         accumulated motion vectors, negated, and the residual through transform_mv_res - three launches, nothing leaves the device."""
         return transform_mv_res(self.motion_vectors(), self.residual(bgr_cur, bgr_ref), im_scale, pixel_means, pixel_scale, rcnn_stride, negate_mv=True)
+
+
+# ---- motion estimation on decoded frames (lsfa_amd/csrc/me.hip) ------------------------------------------------------------------------------
+# Parameters, not tuned values: a search range that covers the synthetic clips' motion, a small cost per pixel of vector length so that flat
+# or noisy blocks stay at rest, no intra threshold.  Nothing was fitted to data (there is no encoder output here to fit to).
+ME_SEARCH, ME_LAMBDA, ME_MAX_SAD = 16, 4, 0
+
+
+@_on_tensor_device
+def luma_u8(bgr, out=None):
+    """lsfa_luma_u8: (H, W, 3) uint8 BGR frame on the device -> (H, W) uint8 luma, Y = (29 B + 150 G + 77 R + 128) >> 8."""
+    if not isinstance(bgr, torch.Tensor) or bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3 or not bgr.is_cuda or not bgr.is_contiguous():
+        raise LsfaError("luma_u8: a contiguous (H, W, 3) uint8 CUDA tensor expected, got %s %s" % (tuple(getattr(bgr, 'shape', ())), getattr(bgr, 'dtype', type(bgr))))
+    H, W = int(bgr.shape[0]), int(bgr.shape[1])
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=bgr.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or out.device != bgr.device or not out.is_contiguous():
+        raise LsfaError("luma_u8: out must be a contiguous (%d, %d) uint8 tensor on %s" % (H, W, bgr.device))
+    _check(lib().lsfa_luma_u8(_ptr(bgr), _ci(W), _ci(H), _ptr(out), _stream()), "lsfa_luma_u8")
+    return out
+
+
+@_on_tensor_device
+def mv_estimate(luma_cur, luma_ref, search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, return_sad=False, out=None, sad_out=None):
+    """lsfa_mv_estimate: two (H, W) uint8 luma planes on the device -> (mbh * mbw, 7) int32 rows {-1, 16, 16, src_x, src_y, dst_x, dst_y}, one per
+    16 x 16 macroblock (zero vectors included), as MotionVectorAccumulator.add_frame takes them; with return_sad also the winners' SAD
+    (mbh, mbw) int32.  Full search over [-search, search]^2, cost = SAD + lam (|dx| + |dy|), ties by (|dx| + |dy|, dy, dx); max_sad > 0 zeroes
+    the vector of a block whose best SAD exceeds it.  Defined by its own specification (include/lsfa_hip.h), not by an encoder's search."""
+    for t in (luma_cur, luma_ref):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or not t.is_cuda or not t.is_contiguous():
+            raise LsfaError("mv_estimate: contiguous (H, W) uint8 CUDA planes expected, got %s %s" % (tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
+    if luma_cur.shape != luma_ref.shape or luma_cur.device != luma_ref.device:
+        raise LsfaError("mv_estimate: the planes differ: %s on %s / %s on %s" % (tuple(luma_cur.shape), luma_cur.device, tuple(luma_ref.shape), luma_ref.device))
+    H, W = int(luma_cur.shape[0]), int(luma_cur.shape[1])
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    if out is None:
+        out = torch.empty((mbh * mbw, 7), dtype=torch.int32, device=luma_cur.device)
+    if return_sad and sad_out is None:
+        sad_out = torch.empty((mbh, mbw), dtype=torch.int32, device=luma_cur.device)
+    for t, shape in ((out, (mbh * mbw, 7)), (sad_out, (mbh, mbw))):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != luma_cur.device or not t.is_contiguous()):
+            raise LsfaError("mv_estimate: an output buffer is not a contiguous %s int32 tensor on %s" % (shape, luma_cur.device))
+    _check(lib().lsfa_mv_estimate(_ptr(luma_cur), _ptr(luma_ref), _ci(W), _ci(H), _ci(int(search)), _ci(int(lam)), _ci(int(max_sad)), _ptr(out),
+                                  _ptr(sad_out), _stream()), "lsfa_mv_estimate")
+    return (out, sad_out) if return_sad else out
+
+
+class MotionEstimator(object):
+    """Decoded uint8 frames in, the network's `motion_vector` / `res_diff` out: block motion estimation (lsfa_luma_u8 + lsfa_mv_estimate) in
+    front of a MotionVectorAccumulator, for clips without compressed-stream side data.
+
+        me = MotionEstimator(width, height, device)
+        me.key_frame(bgr0)                   # the GOP's I-frame: identity accumulation, bgr0 becomes the reference
+        me.next_frame(bgr1)                  # a P-frame: vectors against the PREVIOUS frame (an IPPP chain), accumulated
+        mv, res = me.network_inputs(bgr1, bgr0, im_scale, pixel_means, pixel_scale)
+
+    Every buffer is allocated up front (the outputs of network_inputs at its first call for a scale), nothing is read back and nothing
+    synchronises, so the three calls can be captured in a graph on one stream and replayed on new frame contents written into the same
+    tensors.  The tensors network_inputs returns are reused by the next call."""
+
+    def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD):
+        self.width, self.height, self.device = int(width), int(height), torch.device(device)
+        self.search, self.lam, self.max_sad = int(search), int(lam), int(max_sad)
+        if not 1 <= self.search <= 32 or self.lam < 0 or self.max_sad < 0:
+            raise LsfaError("MotionEstimator: search %d (1..32), lam %d (>= 0), max_sad %d (>= 0)" % (self.search, self.lam, self.max_sad))
+        H, W = self.height, self.width
+        self.mbh, self.mbw = -(-H // 16), -(-W // 16)
+        self.acc = MotionVectorAccumulator(W, H, self.device)
+        self._luma = [torch.empty((H, W), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self._ref = 0                   # index of the previous frame's plane
+        self.rows = torch.empty((self.mbh * self.mbw, 7), dtype=torch.int32, device=self.device)
+        self.sad = torch.empty((self.mbh, self.mbw), dtype=torch.int32, device=self.device)
+        self._mv = torch.empty((H, W, 2), dtype=torch.int32, device=self.device)
+        self._res = torch.empty((H, W, 3), dtype=torch.int32, device=self.device)
+        self._out = {}
+
+    def _frame(self, bgr, who):
+        if not isinstance(bgr, torch.Tensor) or bgr.dtype != torch.uint8 or tuple(bgr.shape) != (self.height, self.width, 3) or bgr.device != self.device or not bgr.is_contiguous():
+            raise LsfaError("MotionEstimator.%s: a contiguous (%d, %d, 3) uint8 frame on %s expected, got %s %s" %
+                            (who, self.height, self.width, self.device, tuple(getattr(bgr, 'shape', ())), getattr(bgr, 'dtype', type(bgr))))
+        return bgr
+
+    def key_frame(self, bgr):
+        luma_u8(self._frame(bgr, 'key_frame'), out=self._luma[self._ref])
+        self.acc.reset()
+
+    def next_frame(self, bgr):
+        """Estimates the frame's vectors against the previous frame and accumulates them; returns the (mbh * mbw, 7) rows (a buffer the
+        next call overwrites; self.sad holds the winners' SAD)."""
+        cur = 1 - self._ref
+        luma_u8(self._frame(bgr, 'next_frame'), out=self._luma[cur])
+        mv_estimate(self._luma[cur], self._luma[self._ref], self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+        self.acc.add_frame(self.rows, max_block_area=256)      # the explicit area: no device-to-host read
+        self._ref = cur
+        return self.rows
+
+    def network_inputs(self, bgr_cur, bgr_key, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16):
+        """`motion_vector` (1, 2, h, w) and `res_diff` (1, 3, h, w) of the current frame against the key frame, as
+        MotionVectorAccumulator.network_inputs builds them (lsfa_mv_field, lsfa_mv_residual, lsfa_transform_mv_res), into buffers of its own."""
+        bgr_cur, bgr_key = self._frame(bgr_cur, 'network_inputs'), self._frame(bgr_key, 'network_inputs')
+        import numpy as _np
+        H, W = self.height, self.width
+        h1, w1 = int(_np.rint(H * float(im_scale))), int(_np.rint(W * float(im_scale)))       # cvRound
+        oh, ow = -(-h1 // rcnn_stride), -(-w1 // rcnn_stride)
+        if (oh, ow) not in self._out:
+            self._out[(oh, ow)] = (torch.empty((1, 2, oh, ow), device=self.device, dtype=torch.float32),
+                                   torch.empty((1, 3, oh, ow), device=self.device, dtype=torch.float32))
+        out_mv, out_res = self._out[(oh, ow)]
+        means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
+        L = lib()
+        with torch.cuda.device(self.device):
+            _check(L.lsfa_mv_field(_ptr(self.acc.accu), _ci(W), _ci(H), _ptr(self._mv), _stream()), "lsfa_mv_field")
+            _check(L.lsfa_mv_residual(_ptr(bgr_cur), _ptr(bgr_key), _ptr(self.acc.accu), _ci(W), _ci(H), _ptr(self._res), _stream()), "lsfa_mv_residual")
+            _check(L.lsfa_transform_mv_res(_ptr(self._mv), _ptr(self._res), _ci(1 | 2), _ci(H), _ci(W), ctypes.c_double(float(im_scale)), _ci(h1), _ci(w1),
+                                           _ci(int(rcnn_stride)), means, ctypes.c_double(float(pixel_scale)), _ptr(out_mv), _ptr(out_res), _ci(oh), _ci(ow),
+                                           _stream()), "lsfa_transform_mv_res")
+        return out_mv, out_res
 
 
 # ---- live timing -----------------------------------------------------------------------

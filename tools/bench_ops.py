@@ -84,6 +84,24 @@ def main():
     mvs = torch.tensor(blocks, dtype=torch.int32, device=dev)
     us = timeit(lambda: acc.add_frame(mvs, max_block_area=256), args.iters)
     out['mv_accumulate(1000x600)'] = dict(us=round(us, 2), bytes=1000 * 600 * (4 + 4 + 8 + 8))
+    # motion estimation from decoded frames: luma of one frame, then the full search of its 63 x 38 macroblocks against the previous frame
+    fr0, fr1 = [torch.from_numpy(rs.randint(0, 256, (600, 1000, 3)).astype(np.uint8)).to(dev) for _ in range(2)]
+    y0, y1 = hip.luma_u8(fr0), hip.luma_u8(fr1)
+    us = timeit(lambda: hip.luma_u8(fr1, out=y1), args.iters)
+    out['luma_u8(1000x600)'] = dict(us=round(us, 2), GBps=round(1000 * 600 * 4 / us / 1e3, 1), bytes=1000 * 600 * 4)
+    me_rows = torch.empty((38 * 63, 7), dtype=torch.int32, device=dev)
+    for search in (16, 32):
+        us = timeit(lambda: hip.mv_estimate(y1, y0, search, 4, 0, out=me_rows), args.iters)
+        n_sad = 38 * 63 * (2 * search + 1) ** 2 * 64          # dword SADs: 64 per candidate of a whole block
+        out['mv_estimate(1000x600, R=%d)' % search] = dict(us=round(us, 2), dword_GSADps=round(n_sad / us / 1e3, 1))
+    est = hip.MotionEstimator(1000, 600, dev)
+    est.key_frame(fr0)
+
+    def me_front_end():
+        est.next_frame(fr1)
+        est.network_inputs(fr1, fr0, 1.0)
+    us = timeit(me_front_end, args.iters)
+    out['me front end: next_frame + network_inputs'] = dict(us=round(us, 2))
     # own fp32 MFMA convolution: stage-3 conv2
     xr = torch.randn(1, H, W, 256, device=dev)
     wk = hip.conv_weight_kc(torch.randn(256, 256, 3, 3, device=dev) * 0.02)

@@ -1,0 +1,135 @@
+#!/usr/bin/env python
+"""Time of the motion-estimation front end for one 1000x600 frame next to the non-key frame it feeds (device events, same process):
+
+    luma_u8, mv_estimate at R = 16 and 32          back to back on one stream, eager and as a replayed graph of `iters` calls
+    next_frame + network_inputs                    hip.MotionEstimator: luma, search, accumulation, field, residual, transform_mv_res
+    one non-key frame                              tools/curframe_only.py's loop body (small net + MV warp + heads + detection post-processing)
+
+The condition to read off: the front end for one frame costs less than the non-key frame.  --kernels-only runs just the front-end
+launches a few times (for `rocprofv3 --kernel-trace --stats -- python tools/me_frontend.py --kernels-only`).  Prints one JSON object."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from lsfa_amd import hip
+from lsfa_amd.utils.synthetic import SyntheticClip
+
+DEV = 'cuda:0'
+W, H = 1000, 600
+
+
+def timed(fn, iters, warmup=5):
+    """microseconds per call: `iters` calls between two events"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters
+
+
+def graphed(fn, iters, rounds=5):
+    """microseconds per call with `iters` calls captured in one graph (no host enqueue between the launches): min and median over rounds"""
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(iters):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(rounds):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        g.replay()
+        b.record()
+        torch.cuda.synchronize()
+        us.append(a.elapsed_time(b) * 1e3 / iters)
+    return dict(min=round(min(us), 2), median=round(float(np.median(us)), 2))
+
+
+def non_key_frame(iters):
+    from lsfa_amd.config.config import lsfa_test_config
+    from lsfa_amd.symbols import params as P
+    from lsfa_amd.symbols.resnet_v1_101_flownet_rfcn import resnet_v1_101_flownet_rfcn
+    cfg = lsfa_test_config(key_frame_interval=10)
+    arg, aux = P.init_params(cfg, seed=0)
+    cur = resnet_v1_101_flownet_rfcn(cfg).get_cur_test_symbol(cfg).bind(arg, aux, DEV)
+    data = torch.rand(1, 3, H, W, device=DEV) * 255
+    im_info = torch.tensor([[H, W, 1.0]], device=DEV)
+    feat = torch.randn(1, 1024, 38, 63, device=DEV)
+    mv, res = torch.randn(1, 2, 38, 63, device=DEV) * 0.5, torch.randn(1, 3, 38, 63, device=DEV)
+    R, ncls = cfg.TEST.RPN_POST_NMS_TOP_N, cfg.dataset.NUM_CLASSES
+    bufs = (torch.zeros((1, ncls, R, 5), dtype=torch.float64, device=DEV), torch.zeros((1, ncls), dtype=torch.int32, device=DEV),
+            torch.full((1, ncls, R), -1, dtype=torch.int32, device=DEV))
+
+    def frame():
+        out = cur.forward(data=data, im_info=im_info, feat_key=feat, motion_vector=mv, res_diff=res)
+        hip.det_postprocess_batch(out['rois_output'], out['bbox_pred_reshape_output'].reshape(R, -1), out['cls_prob_reshape_output'].reshape(R, -1),
+                                  1, H, W, 1.0, bufs, nms_thresh=cfg.TEST.NMS, max_per_image=cfg.TEST.max_per_image, class_agnostic=cfg.CLASS_AGNOSTIC)
+
+    with torch.no_grad():
+        return dict(eager_us=round(timed(frame, iters), 1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=200)
+    ap.add_argument('--kernels-only', action='store_true')
+    ap.add_argument('--skip-non-key', action='store_true')
+    args = ap.parse_args()
+    clip = SyntheticClip(0, 4, H, W)
+    frames = [clip.frame_u8(f).to(DEV) for f in range(3)]
+    y = [hip.luma_u8(f) for f in frames]
+    rows = torch.empty((38 * 63, 7), dtype=torch.int32, device=DEV)
+    sad = torch.empty((38, 63), dtype=torch.int32, device=DEV)
+    me = hip.MotionEstimator(W, H, DEV)
+    me.key_frame(frames[0])
+
+    def front_end():
+        me.next_frame(frames[1])
+        me.network_inputs(frames[1], frames[0], 1.0, (0.0, 0.0, 0.0), 1.0)
+
+    if args.kernels_only:
+        for _ in range(20):
+            hip.luma_u8(frames[1], out=y[1])
+            hip.mv_estimate(y[1], y[0], 16, 4, 0, out=rows, sad_out=sad)
+            hip.mv_estimate(y[2], y[1], 32, 4, 0, out=rows, sad_out=sad)
+            front_end()
+        torch.cuda.synchronize()
+        return
+    out = dict(device=torch.cuda.get_device_name(0), frame='%dx%d' % (W, H), iters=args.iters)
+    blocks = 38 * 63
+    for name, fn, work in (('luma_u8', lambda: hip.luma_u8(frames[1], out=y[1]), None),
+                           ('mv_estimate_R16', lambda: hip.mv_estimate(y[1], y[0], 16, 4, 0, out=rows, sad_out=sad), blocks * 33 * 33 * 64),
+                           ('mv_estimate_R32', lambda: hip.mv_estimate(y[2], y[1], 32, 4, 0, out=rows, sad_out=sad), blocks * 65 * 65 * 64),
+                           ('front_end(next_frame+network_inputs)', front_end, None)):
+        r = dict(eager_us=round(timed(fn, args.iters), 2), graph_us=graphed(fn, args.iters))
+        if work:
+            # the search's arithmetic: one dword SAD (4 pixels) per block dword, row and candidate
+            r['dword_sads'] = work
+            r['dword_sads_per_s'] = round(work / (r['graph_us']['min'] * 1e-6), -9)
+        out[name] = r
+    hip.prof_enable(True, ops=['mv_estimate'])
+    for _ in range(50):
+        hip.mv_estimate(y[1], y[0], 16, 4, 0, out=rows, sad_out=sad)
+    ms, n = hip.prof_read()['mv_estimate']
+    hip.prof_enable(False)
+    out['mv_estimate_R16_prof_read_us'] = round(ms * 1e3 / n, 2)
+    if not args.skip_non_key:
+        out['non_key_frame'] = non_key_frame(30)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
