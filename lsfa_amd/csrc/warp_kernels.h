@@ -1,4 +1,4 @@
-// Device kernel of warp.hip: bilinear feature warp (GridGenerator 'warp' + BilinearSampler) with the
+// Device kernels of warp.hip: bilinear feature warp (GridGenerator 'warp' + BilinearSampler) with the
 // fused key-path (x scale_map) and cur-path (+ rnet_conv0(res_diff) + small-net feature) epilogues.
 //
 // Mapping on CDNA4: a thread owns VEC horizontally adjacent output pixels and a run of channels
@@ -54,6 +54,53 @@ __device__ __forceinline__ void store_vec(float* p, const float (&v)[VEC]) {
   *reinterpret_cast<T*>(p) = t;
 }
 
+// One output pixel's four taps: GridGenerator 'warp' + BilinearSampler, the oracle's arithmetic (orc_warp_bilinear) operation for
+// operation.  Pixel (x, y) moved by the flow (fx, fy) samples the 2 x 2 block whose top-left value sits `off` floats from the plane's start.
+struct Tap {
+  int off;                         // y0 * W + x0, in [-2W - 2, HW + W]: outside the map wherever a validity bit below is false
+  float wx0, wx1, wy0, wy1;
+  bool v00, v01, v10, v11;         // top-left, top-right, bottom-left, bottom-right tap inside the map
+};
+__device__ __forceinline__ Tap tap_of(int x, int y, float fx, float fy, int W, int H, float half_w, float half_h) {
+  Tap t;
+  const float gx = ((float)x + fx) / half_w - 1.0f;
+  const float gy = ((float)y + fy) / half_h - 1.0f;
+  const float x_real = (gx + 1.0f) * (float)(W - 1) / 2.0f;
+  const float y_real = (gy + 1.0f) * (float)(H - 1) / 2.0f;
+  const float fx0 = floorf(x_real), fy0 = floorf(y_real);
+  // clamp before the int conversion so wild flows cannot overflow; clamped values
+  // are outside the map either way
+  const int x0 = (int)fminf(fmaxf(fx0, -2.0f), (float)W);
+  const int y0 = (int)fminf(fmaxf(fy0, -2.0f), (float)H);
+  t.wx0 = 1.0f - (x_real - fx0);
+  t.wy0 = 1.0f - (y_real - fy0);
+  t.wx1 = 1.0f - t.wx0;
+  t.wy1 = 1.0f - t.wy0;
+  const bool vx0 = (x0 >= 0 && x0 <= W - 1), vx1 = (x0 + 1 >= 0 && x0 + 1 <= W - 1);
+  const bool vy0 = (y0 >= 0 && y0 <= H - 1), vy1 = (y0 + 1 >= 0 && y0 + 1 <= H - 1);
+  t.v00 = vx0 && vy0; t.v01 = vx1 && vy0; t.v10 = vx0 && vy1; t.v11 = vx1 && vy1;
+  t.off = y0 * W + x0;
+  return t;
+}
+// the bilinear sum of the four tap values (a tap outside the map is passed as 0)
+__device__ __forceinline__ float blend(float tl, float tr, float bl, float br, float wx0, float wx1, float wy0, float wy1) {
+  return tl * wy0 * wx0 + tr * wy0 * wx1 + bl * wy1 * wx0 + br * wy1 * wx1;
+}
+// The fused epilogue, in the one order every kernel and the oracle share: r = the bilinear sum, m = the scale map's value,
+// q = rnet_conv0(res) at this pixel and channel (each kernel forms it from its own copy of the weights), bs / bt = warp_conv_feat_bn's
+// folded scale and shift (two roundings), a = the small net's feature.  An operand whose flag is off is not read.
+template <bool HAS_MUL, bool HAS_ADD, bool HAS_RES, bool HAS_BN>
+__device__ __forceinline__ float epilogue(float r, float m, float q, float bs, float bt, float a) {
+  if (HAS_MUL) r = r * m;
+  if (HAS_RES) r = r + q;
+  if (HAS_BN) {
+    r = r * bs;
+    r = r + bt;
+  }
+  if (HAS_ADD) r = r + a;
+  return r;
+}
+
 // HAS_BN (lsfa_warp_bilinear_bn): a per-channel affine r * bn_s[c] + bn_t[c] (two roundings) on warp + rnet_conv0(res), before `add`.
 template <int VEC, bool HAS_MUL, bool HAS_ADD, bool HAS_RES, bool HAS_BN = false>
 __global__ __launch_bounds__(kThreads) void warp_kernel(
@@ -72,30 +119,12 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(
   load_vec<VEC>(flow + ((size_t)n * 2 + 1) * HW + p0, fy);
 
   const float half_w = (float)((W - 1) / 2.0), half_h = (float)((H - 1) / 2.0);
-  int off[VEC];
-  bool v00[VEC], v01[VEC], v10[VEC], v11[VEC];
-  float wx0[VEC], wx1[VEC], wy0[VEC], wy1[VEC];
+  Tap tp[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     const int p = p0 + i;
     const int y = p / W, x = p - y * W;
-    const float gx = ((float)x + fx[i]) / half_w - 1.0f;
-    const float gy = ((float)y + fy[i]) / half_h - 1.0f;
-    const float x_real = (gx + 1.0f) * (float)(W - 1) / 2.0f;
-    const float y_real = (gy + 1.0f) * (float)(H - 1) / 2.0f;
-    const float fx0 = floorf(x_real), fy0 = floorf(y_real);
-    // clamp before the int conversion so wild flows cannot overflow; clamped values
-    // are outside the map either way
-    const int x0 = (int)fminf(fmaxf(fx0, -2.0f), (float)W);
-    const int y0 = (int)fminf(fmaxf(fy0, -2.0f), (float)H);
-    wx0[i] = 1.0f - (x_real - fx0);
-    wy0[i] = 1.0f - (y_real - fy0);
-    wx1[i] = 1.0f - wx0[i];
-    wy1[i] = 1.0f - wy0[i];
-    const bool vx0 = (x0 >= 0 && x0 <= W - 1), vx1 = (x0 + 1 >= 0 && x0 + 1 <= W - 1);
-    const bool vy0 = (y0 >= 0 && y0 <= H - 1), vy1 = (y0 + 1 >= 0 && y0 + 1 <= H - 1);
-    v00[i] = vx0 && vy0; v01[i] = vx1 && vy0; v10[i] = vx0 && vy1; v11[i] = vx1 && vy1;
-    off[i] = y0 * W + x0;
+    tp[i] = tap_of(x, y, fx[i], fy[i], W, H, half_w, half_h);
   }
 
   float rv[kResMax][VEC];
@@ -109,7 +138,7 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(
   const int c1 = min(c0 + ch_per_block, C);
   bool interior = true;
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) interior = interior && v00[i] && v01[i] && v10[i] && v11[i];
+  for (int i = 0; i < VEC; ++i) interior = interior && tp[i].v00 && tp[i].v01 && tp[i].v10 && tp[i].v11;
   // wave-uniform split: a wave whose pixels all sample inside the map (nearly all of them) runs
   // the loop without any validity logic; the general loop handles map borders and escaping flows
   if (__all(interior)) {
@@ -122,24 +151,18 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(
       if (HAS_ADD) load_vec<VEC>(add + o, a);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
-        const float2u t = *reinterpret_cast<const float2u*>(plane + off[i]);
-        const float2u b = *reinterpret_cast<const float2u*>(plane + off[i] + W);
-        float r = t.x * wy0[i] * wx0[i] + t.y * wy0[i] * wx1[i] + b.x * wy1[i] * wx0[i] + b.y * wy1[i] * wx1[i];
-        if (HAS_MUL) r = r * m[i];
+        const float2u t = *reinterpret_cast<const float2u*>(plane + tp[i].off);
+        const float2u b = *reinterpret_cast<const float2u*>(plane + tp[i].off + W);
+        const float r = blend(t.x, t.y, b.x, b.y, tp[i].wx0, tp[i].wx1, tp[i].wy0, tp[i].wy1);
+        float q = 0.f;
         if (HAS_RES) {
-          float q = res_w[(size_t)c * res_c] * rv[0][i];
+          q = res_w[(size_t)c * res_c] * rv[0][i];
 #pragma unroll
           for (int k = 1; k < kResMax; ++k)
             if (k < res_c) q = q + res_w[(size_t)c * res_c + k] * rv[k][i];
           q = q + res_b[c];
-          r = r + q;
         }
-        if (HAS_BN) {
-          r = r * bn_s[c];
-          r = r + bn_t[c];
-        }
-        if (HAS_ADD) r = r + a[i];
-        v[i] = r;
+        v[i] = epilogue<HAS_MUL, HAS_ADD, HAS_RES, HAS_BN>(r, HAS_MUL ? m[i] : 0.f, q, HAS_BN ? bn_s[c] : 0.f, HAS_BN ? bn_t[c] : 0.f, HAS_ADD ? a[i] : 0.f);
       }
       store_vec<VEC>(out + o, v);
     }
@@ -154,26 +177,20 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(
     if (HAS_ADD) load_vec<VEC>(add + o, a);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
-      const float tl = v00[i] ? plane[off[i]] : 0.f;
-      const float tr = v01[i] ? plane[off[i] + 1] : 0.f;
-      const float bl = v10[i] ? plane[off[i] + W] : 0.f;
-      const float br = v11[i] ? plane[off[i] + W + 1] : 0.f;
-      float r = tl * wy0[i] * wx0[i] + tr * wy0[i] * wx1[i] + bl * wy1[i] * wx0[i] + br * wy1[i] * wx1[i];
-      if (HAS_MUL) r = r * m[i];
+      const float tl = tp[i].v00 ? plane[tp[i].off] : 0.f;
+      const float tr = tp[i].v01 ? plane[tp[i].off + 1] : 0.f;
+      const float bl = tp[i].v10 ? plane[tp[i].off + W] : 0.f;
+      const float br = tp[i].v11 ? plane[tp[i].off + W + 1] : 0.f;
+      const float r = blend(tl, tr, bl, br, tp[i].wx0, tp[i].wx1, tp[i].wy0, tp[i].wy1);
+      float q = 0.f;
       if (HAS_RES) {
-        float q = res_w[(size_t)c * res_c] * rv[0][i];
+        q = res_w[(size_t)c * res_c] * rv[0][i];
 #pragma unroll
         for (int k = 1; k < kResMax; ++k)
           if (k < res_c) q = q + res_w[(size_t)c * res_c + k] * rv[k][i];
         q = q + res_b[c];
-        r = r + q;
       }
-      if (HAS_BN) {
-        r = r * bn_s[c];
-        r = r + bn_t[c];
-      }
-      if (HAS_ADD) r = r + a[i];
-      v[i] = r;
+      v[i] = epilogue<HAS_MUL, HAS_ADD, HAS_RES, HAS_BN>(r, HAS_MUL ? m[i] : 0.f, q, HAS_BN ? bn_s[c] : 0.f, HAS_BN ? bn_t[c] : 0.f, HAS_ADD ? a[i] : 0.f);
     }
     store_vec<VEC>(out + o, v);
   }
@@ -271,21 +288,10 @@ __global__ __launch_bounds__(THREADS) void warp_staged_kernel(StagedArgs A) {
     for (int j = 0; j < 2; ++j) {
       const int p = p0 + j;
       const int y = p / W, x = p - y * W;
-      const float gx = ((float)x + fxs[j]) / half_w - 1.0f;
-      const float gy = ((float)y + fys[j]) / half_h - 1.0f;
-      const float x_real = (gx + 1.0f) * (float)(W - 1) / 2.0f;
-      const float y_real = (gy + 1.0f) * (float)(H - 1) / 2.0f;
-      const float fx0 = floorf(x_real), fy0 = floorf(y_real);
-      const int x0 = (int)fminf(fmaxf(fx0, -2.0f), (float)W);
-      const int y0 = (int)fminf(fmaxf(fy0, -2.0f), (float)H);
-      wx0[i][j] = 1.0f - (x_real - fx0);
-      wy0[i][j] = 1.0f - (y_real - fy0);
-      wx1[i][j] = 1.0f - wx0[i][j];
-      wy1[i][j] = 1.0f - wy0[i][j];
-      const bool vx0 = (x0 >= 0 && x0 <= W - 1), vx1 = (x0 + 1 >= 0 && x0 + 1 <= W - 1);
-      const bool vy0 = (y0 >= 0 && y0 <= H - 1), vy1 = (y0 + 1 >= 0 && y0 + 1 <= H - 1);
-      bits |= ((unsigned)(vx0 && vy0) | ((unsigned)(vx1 && vy0) << 1) | ((unsigned)(vx0 && vy1) << 2) | ((unsigned)(vx1 && vy1) << 3)) << (4 * j);
-      idx[i][j] = y0 * W + x0;     // in [-2W - 2, HW + W]: the four reads stay inside [plane - guard, plane + HW + W + 2)
+      const Tap tp = tap_of(x, y, fxs[j], fys[j], W, H, half_w, half_h);
+      wx0[i][j] = tp.wx0; wx1[i][j] = tp.wx1; wy0[i][j] = tp.wy0; wy1[i][j] = tp.wy1;
+      bits |= ((unsigned)tp.v00 | ((unsigned)tp.v01 << 1) | ((unsigned)tp.v10 << 2) | ((unsigned)tp.v11 << 3)) << (4 * j);
+      idx[i][j] = tp.off;          // in [-2W - 2, HW + W]: the four reads stay inside [plane - guard, plane + HW + W + 2)
     }
     vb[i] = bits;
   }
@@ -374,18 +380,17 @@ __global__ __launch_bounds__(THREADS) void warp_staged_kernel(StagedArgs A) {
         const float tr = (b & 2u) ? top[i][j].y : 0.f;
         const float bl = (b & 4u) ? bot[i][j].x : 0.f;
         const float br = (b & 8u) ? bot[i][j].y : 0.f;
-        float r = tl * wy0[i][j] * wx0[i][j] + tr * wy0[i][j] * wx1[i][j] + bl * wy1[i][j] * wx0[i][j] + br * wy1[i][j] * wx1[i][j];
-        if (HAS_MUL) r = r * (j == 0 ? mv[i].x : mv[i].y);
+        const float r = blend(tl, tr, bl, br, wx0[i][j], wx1[i][j], wy0[i][j], wy1[i][j]);
+        float q = 0.f;
         if (HAS_RES) {
-          float q = rw[0] * rv[i][0][j];
+          q = rw[0] * rv[i][0][j];
 #pragma unroll
           for (int kk = 1; kk < kRes; ++kk)
             if (kk < res_c) q = q + rw[kk] * rv[i][kk][j];
           q = q + rb;
-          r = r + q;
         }
-        if (HAS_ADD) r = r + (j == 0 ? av[i].x : av[i].y);
-        v[j] = r;
+        v[j] = epilogue<HAS_MUL, HAS_ADD, HAS_RES, false>(r, HAS_MUL ? (j == 0 ? mv[i].x : mv[i].y) : 0.f, q, 0.f, 0.f,
+                                                          HAS_ADD ? (j == 0 ? av[i].x : av[i].y) : 0.f);
       }
       const int pl = praw < HW ? praw : HW - 2;
       *reinterpret_cast<float2*>(A.out + obase + pl) = make_float2(v[0], v[1]);
@@ -395,6 +400,109 @@ __global__ __launch_bounds__(THREADS) void warp_staged_kernel(StagedArgs A) {
   }
 }
 
-
 }  // namespace warp
 }  // namespace lsfa
+
+// ---- r6: the non-key path's warp on CHANNELS-LAST maps --------------------------------------------------------------------------------------
+// On a non-key frame the warped feature is read by two 1x1 convolutions only (the RPN head on channels [0, 512), the R-FCN score maps on
+// [512, 1024): resnet_v1_101_flownet_rfcn.py:479-499) - GEMMs over the channel axis, i.e. consumers of channels-last rows.  With the NCHW
+// operator layout every pass carried a transposing copy of half the map in front of the R-FCN convolution (lsfa_nchw_to_nhwc: 32 us per
+// nine-frame segment, 2.2 % of frames/s, profiles/r6/tail_ablation.txt).  Here the key feature is turned channels-last ONCE per pass (one map
+// instead of one per frame), the small net's fuse convolution writes its natural layout, and the warp reads and writes (pixel, channel) rows:
+// thread t owns the channel quad 4t .. 4t+3 (C = 1024: one quad per thread of a 256-thread workgroup), a workgroup walks a run of pixels,
+// every access is a 4 KB row (256 threads x float4).  The arithmetic is lsfa_warp_bilinear's general path, operation for operation (taps
+// outside the map contribute 0 * w; then + rnet_conv0(res_diff) + add): the two layouts give the same bits (tests/test_hip_ops.py).
+// amax_out (or NULL): 256 zeroed slots that receive max|out| - the next convolution's scale, as the convolutions' own epilogues leave it.
+namespace {      // (file-local, as it was in warp.hip: the kernel's name in profiles and traces stays what it has been)
+__device__ __attribute__((aligned(16))) float4 g_warp_zero4 = {0.f, 0.f, 0.f, 0.f};      // (not const: a constant-address-space pointer in the select below turns the loads into flat ones)
+
+template <bool HAS_ADD, bool HAS_RES, bool HAS_BN = false>
+__global__ __launch_bounds__(256) void warp_cl_kernel(const float* __restrict__ feat, int feat_n, const float* __restrict__ flow, int N, int C,
+                                                      int H, int W, const float* __restrict__ add, const float* __restrict__ res, int res_c,
+                                                      const float* __restrict__ res_w, const float* __restrict__ res_b,
+                                                      float* __restrict__ out, unsigned* __restrict__ amax_out, int amax_c0, int pix_per_wg,
+                                                      const float* __restrict__ bn_s, const float* __restrict__ bn_t) {
+  using namespace lsfa::warp;
+  const int HW = H * W, C4 = C >> 2;
+  const int P = N * HW;                                   // (< 2^31: checked by the host)
+  const int p_begin = blockIdx.x * pix_per_wg;
+  const int p_end = min(p_begin + pix_per_wg, P);
+  const float half_w = (float)((W - 1) / 2.0), half_h = (float)((H - 1) / 2.0);
+  float mx = 0.f;
+  for (int q = threadIdx.x; q < C4; q += 256) {
+    float rw[4][kResMax], rb[4], bs[4], bt[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      rb[j] = HAS_RES ? res_b[4 * q + j] : 0.f;
+      bs[j] = HAS_BN ? bn_s[4 * q + j] : 1.f;
+      bt[j] = HAS_BN ? bn_t[4 * q + j] : 0.f;
+#pragma unroll
+      for (int k = 0; k < kResMax; ++k) rw[j][k] = (HAS_RES && k < res_c) ? res_w[(size_t)(4 * q + j) * res_c + k] : 0.f;
+    }
+    const bool counts = 4 * q >= amax_c0;            // the maximum is taken over channels [amax_c0, C): the ones the scaled consumer reads
+    int n = p_begin / HW;
+    int r = p_begin - n * HW;
+    int y = r / W, x = r - y * W;
+    for (int p = p_begin; p < p_end; ++p) {
+      const float fx = flow[((size_t)n * 2 + 0) * HW + r], fy = flow[((size_t)n * 2 + 1) * HW + r];
+      // tap_of()'s arithmetic in this kernel's own words: the pixel is the same for the whole workgroup, and with the 64-bit `off` below the
+      // compiler keeps the validity tests and the offset on the scalar unit exactly as it did; through tap_of() the one-map launch measured
+      // 0.14 us (0.8 %) slower than before (profiles/r8/warp_refactor_ab.txt).  blend() and epilogue() below are the shared ones.
+      const float gx = ((float)x + fx) / half_w - 1.0f;
+      const float gy = ((float)y + fy) / half_h - 1.0f;
+      const float x_real = (gx + 1.0f) * (float)(W - 1) / 2.0f;
+      const float y_real = (gy + 1.0f) * (float)(H - 1) / 2.0f;
+      const float fx0 = floorf(x_real), fy0 = floorf(y_real);
+      const int x0 = (int)fminf(fmaxf(fx0, -2.0f), (float)W);       // (clamped before the conversion: outside the map either way)
+      const int y0 = (int)fminf(fmaxf(fy0, -2.0f), (float)H);
+      const float wx0 = 1.0f - (x_real - fx0), wy0 = 1.0f - (y_real - fy0);
+      const float wx1 = 1.0f - wx0, wy1 = 1.0f - wy0;
+      const bool vx0 = (x0 >= 0 && x0 <= W - 1), vx1 = (x0 + 1 >= 0 && x0 + 1 <= W - 1);
+      const bool vy0 = (y0 >= 0 && y0 <= H - 1), vy1 = (y0 + 1 >= 0 && y0 + 1 <= H - 1);
+      const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4* fb = reinterpret_cast<const float4*>(feat + (size_t)(n % feat_n) * HW * C) + q;
+      const long off = (long)y0 * W + x0;
+      // (every thread of the workgroup works on the same pixel: the four branches are uniform)
+      // a tap outside the map reads a block of zeros (a select between two GLOBAL addresses: `cond ? load : 0` made hipcc spill a zero to
+      // scratch and load through a flat pointer)
+      const float4 tl = *((vx0 && vy0) ? fb + (size_t)off * C4 : &g_warp_zero4);
+      const float4 tr = *((vx1 && vy0) ? fb + (size_t)(off + 1) * C4 : &g_warp_zero4);
+      const float4 bl = *((vx0 && vy1) ? fb + (size_t)(off + W) * C4 : &g_warp_zero4);
+      const float4 br = *((vx1 && vy1) ? fb + (size_t)(off + W + 1) * C4 : &g_warp_zero4);
+      float4 a4 = zero4;
+      if (HAS_ADD) a4 = reinterpret_cast<const float4*>(add)[(size_t)p * C4 + q];
+      // (named scalars, not arrays: indexed arrays ended up in scratch memory here)
+      const float* rp = res + (size_t)n * res_c * HW + r;
+      const float rv0 = HAS_RES ? rp[0] : 0.f, rv1 = (HAS_RES && res_c > 1) ? rp[HW] : 0.f;
+      const float rv2 = (HAS_RES && res_c > 2) ? rp[2 * (size_t)HW] : 0.f, rv3 = (HAS_RES && res_c > 3) ? rp[3 * (size_t)HW] : 0.f;
+      // one component: the oracle's expression, then the residual's 1x1 convolution and the small net's feature
+#define LSFA_WARP_CL_ONE(J_, TL_, TR_, BL_, BR_, A_, O_)                                                                     \
+      const float s##O_ = blend(TL_, TR_, BL_, BR_, wx0, wx1, wy0, wy1);                                                     \
+      float q##O_ = 0.f;                                                                                                     \
+      if (HAS_RES) {                                                                                                         \
+        q##O_ = rw[J_][0] * rv0;                                                                                             \
+        if (res_c > 1) q##O_ = q##O_ + rw[J_][1] * rv1;                                                                      \
+        if (res_c > 2) q##O_ = q##O_ + rw[J_][2] * rv2;                                                                      \
+        if (res_c > 3) q##O_ = q##O_ + rw[J_][3] * rv3;                                                                      \
+        q##O_ = q##O_ + rb[J_];                                                                                              \
+      }                                                                                                                      \
+      const float O_ = epilogue<false, HAS_ADD, HAS_RES, HAS_BN>(s##O_, 0.f, q##O_, bs[J_], bt[J_], A_);                     \
+      if (counts) mx = fmaxf(mx, fabsf(O_));
+      LSFA_WARP_CL_ONE(0, tl.x, tr.x, bl.x, br.x, a4.x, o0)
+      LSFA_WARP_CL_ONE(1, tl.y, tr.y, bl.y, br.y, a4.y, o1)
+      LSFA_WARP_CL_ONE(2, tl.z, tr.z, bl.z, br.z, a4.z, o2)
+      LSFA_WARP_CL_ONE(3, tl.w, tr.w, bl.w, br.w, a4.w, o3)
+#undef LSFA_WARP_CL_ONE
+      reinterpret_cast<float4*>(out)[(size_t)p * C4 + q] = make_float4(o0, o1, o2, o3);
+      if (++x == W) { x = 0; if (++y == H) { y = 0; ++n; } }
+      if (++r == HW) r = 0;
+    }
+  }
+  if (amax_out) {
+    uint32_t m = __float_as_uint(mx);       // non-negative, or NaN bits (fmaxf drops a NaN: a non-finite output shows in the consumer's own status)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(amax_out + ((blockIdx.x * 4 + (threadIdx.x >> 6)) & 255), m);
+  }
+}
+}  // namespace

@@ -28,6 +28,7 @@ class LsfaError(RuntimeError):
 
 
 _lib = None
+_WARP_VARIANTS = {'auto': 0, 'gather': 1, 'staged': 2}       # lsfa_warp_set_variant
 
 
 def lib():
@@ -61,10 +62,9 @@ def lib():
             OP_NAMES[:] = names              # in place: importers of the list see the library's table
         wv = os.environ.get("LSFA_WARP_VARIANT")         # A/B runs of whole programs: 'gather' | 'staged' | 'auto'
         if wv:
-            variants = {'auto': 0, 'gather': 1, 'staged': 2}
-            if wv not in variants:
-                raise LsfaError("LSFA_WARP_VARIANT=%r: expected one of %s" % (wv, sorted(variants)))
-            L.lsfa_warp_set_variant(ctypes.c_int(variants[wv]))
+            if wv not in _WARP_VARIANTS:
+                raise LsfaError("LSFA_WARP_VARIANT=%r: expected one of %s" % (wv, sorted(_WARP_VARIANTS)))
+            L.lsfa_warp_set_variant(ctypes.c_int(_WARP_VARIANTS[wv]))
         _lib = L
     return _lib
 
@@ -161,92 +161,54 @@ def rfcn_head_ps(ps_map, rois, ncls, nbox, spatial_scale=0.0625, pooled_size=7, 
     return (cls_prob, cls_score, bbox_pred) if want_score else (cls_prob, bbox_pred)
 
 
-@_on_tensor_device
-def warp_bilinear(feat, flow, mul=None, add=None, res=None, res_w=None, res_b=None, out=None):
-    feat, flow = _f32c(feat, "feat"), _f32c(flow, "flow")
-    mul, add, res = _f32c(mul, "mul"), _f32c(add, "add"), _f32c(res, "res")
+def _warp(name, cl, feat, flow, mul, add, res, res_w, res_b, bn, out, amax_out=None, amax_c0=0):
+    """The four lsfa_warp_bilinear* entry points: `cl` picks the layout, `bn` = (scale, shift) the form with warp_conv_feat_bn."""
+    feat, flow = _f32c(feat, "feat_cl" if cl else "feat"), _f32c(flow, "flow")
+    mul, add, res = _f32c(mul, "mul"), _f32c(add, "add_cl" if cl else "add"), _f32c(res, "res")
     N, _, H, W = flow.shape
-    feat_n, C = feat.shape[0], feat.shape[1]
+    feat_n, C = feat.shape[0], feat.shape[3 if cl else 1]
+    if cl and (tuple(feat.shape[1:3]) != (H, W) or (add is not None and tuple(add.shape) != (N, H, W, C))):
+        raise LsfaError("%s: feat_cl %s / add_cl %s do not match a (%d, 2, %d, %d) flow" % (
+            name, tuple(feat.shape), None if add is None else tuple(add.shape), N, H, W))
     res_c = 0
     if res is not None:
         res_w, res_b = _f32c(res_w, "res_w").reshape(C, -1), _f32c(res_b, "res_b")
         res_c = res.shape[1]
     if out is None:
-        out = torch.empty((N, C, H, W), device=feat.device, dtype=torch.float32)
-    _check(lib().lsfa_warp_bilinear(_ptr(feat), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W), _ptr(mul),
-                                    _ptr(add), _ptr(res), _ci(res_c), _ptr(res_w), _ptr(res_b), _ptr(out), _stream()),
-           "lsfa_warp_bilinear")
+        out = torch.empty((N, H, W, C) if cl else (N, C, H, W), device=feat.device, dtype=torch.float32)
+    sym = "lsfa_warp_bilinear" + ("_bn" if bn is not None else "") + ("_cl" if cl else "")
+    args = [_ptr(feat), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W)]
+    if bn is None and not cl:                     # `mul` is an argument of lsfa_warp_bilinear alone
+        args.append(_ptr(mul))
+    args += [_ptr(add), _ptr(res), _ci(res_c), _ptr(res_w), _ptr(res_b)]
+    if bn is not None:
+        bn_scale, bn_shift = _f32c(bn[0], "bn scale"), _f32c(bn[1], "bn shift")
+        if mul is not None:
+            raise LsfaError("%s: mul together with bn: the library has no such kernel" % name)
+        if bn_scale.numel() != C or bn_shift.numel() != C:
+            raise LsfaError("%s: bn scale / shift must have %d elements" % (name, C))
+        args += [_ptr(bn_scale), _ptr(bn_shift)]
+    args.append(_ptr(out))
+    if cl:
+        args += [_ptr(amax_out), _ci(amax_c0)]
+    _check(getattr(lib(), sym)(*args, _stream()), sym)
     return out
 
 
 @_on_tensor_device
-def warp_bilinear_cl(feat_cl, flow, add_cl=None, res=None, res_w=None, res_b=None, out=None, amax_out=None, amax_c0=0):
+def warp_bilinear(feat, flow, mul=None, add=None, res=None, res_w=None, res_b=None, out=None, bn=None):
+    """lsfa_warp_bilinear on NCHW maps.  bn = (scale, shift): lsfa_warp_bilinear_bn, warp_conv_feat_bn between the warp (+ rnet_conv0(res))
+    and `add`: r * scale[c] + shift[c], two roundings; not together with `mul`."""
+    return _warp("warp_bilinear", False, feat, flow, mul, add, res, res_w, res_b, bn, out)
+
+
+@_on_tensor_device
+def warp_bilinear_cl(feat_cl, flow, add_cl=None, res=None, res_w=None, res_b=None, out=None, amax_out=None, amax_c0=0, bn=None):
     """lsfa_warp_bilinear_cl: the non-key path's warp on channels-last maps.  feat_cl (feat_n, H, W, C), flow (N, 2, H, W), add_cl (N, H, W, C),
     res (N, res_c, H, W) -> (N, H, W, C); the bits of warp_bilinear on the transposed maps.  amax_out: a zeroed row of amax_slots() that
-    receives max|out| over channels [amax_c0, C) (the scale of the convolution that reads those)."""
-    feat_cl, flow = _f32c(feat_cl, "feat_cl"), _f32c(flow, "flow")
-    add_cl, res = _f32c(add_cl, "add_cl"), _f32c(res, "res")
-    N, _, H, W = flow.shape
-    feat_n, C = feat_cl.shape[0], feat_cl.shape[3]
-    if tuple(feat_cl.shape[1:3]) != (H, W) or (add_cl is not None and tuple(add_cl.shape) != (N, H, W, C)):
-        raise LsfaError("warp_bilinear_cl: feat_cl %s / add_cl %s do not match a (%d, 2, %d, %d) flow" % (
-            tuple(feat_cl.shape), None if add_cl is None else tuple(add_cl.shape), N, H, W))
-    res_c = 0
-    if res is not None:
-        res_w, res_b = _f32c(res_w, "res_w").reshape(C, -1), _f32c(res_b, "res_b")
-        res_c = res.shape[1]
-    if out is None:
-        out = torch.empty((N, H, W, C), device=feat_cl.device, dtype=torch.float32)
-    _check(lib().lsfa_warp_bilinear_cl(_ptr(feat_cl), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W), _ptr(add_cl), _ptr(res), _ci(res_c),
-                                       _ptr(res_w), _ptr(res_b), _ptr(out), _ptr(amax_out), _ci(amax_c0), _stream()), "lsfa_warp_bilinear_cl")
-    return out
-
-
-@_on_tensor_device
-def warp_bilinear_bn(feat, flow, bn_scale, bn_shift, add=None, res=None, res_w=None, res_b=None, out=None):
-    """lsfa_warp_bilinear_bn: warp_bilinear (no `mul`) with warp_conv_feat_bn between the warp (+ rnet_conv0(res)) and `add`:
-    r * bn_scale[c] + bn_shift[c], two roundings.  NCHW maps."""
-    feat, flow = _f32c(feat, "feat"), _f32c(flow, "flow")
-    add, res = _f32c(add, "add"), _f32c(res, "res")
-    bn_scale, bn_shift = _f32c(bn_scale, "bn_scale"), _f32c(bn_shift, "bn_shift")
-    N, _, H, W = flow.shape
-    feat_n, C = feat.shape[0], feat.shape[1]
-    if bn_scale.numel() != C or bn_shift.numel() != C:
-        raise LsfaError("warp_bilinear_bn: bn_scale / bn_shift must have %d elements" % C)
-    res_c = 0
-    if res is not None:
-        res_w, res_b = _f32c(res_w, "res_w").reshape(C, -1), _f32c(res_b, "res_b")
-        res_c = res.shape[1]
-    if out is None:
-        out = torch.empty((N, C, H, W), device=feat.device, dtype=torch.float32)
-    _check(lib().lsfa_warp_bilinear_bn(_ptr(feat), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W), _ptr(add), _ptr(res), _ci(res_c),
-                                       _ptr(res_w), _ptr(res_b), _ptr(bn_scale), _ptr(bn_shift), _ptr(out), _stream()), "lsfa_warp_bilinear_bn")
-    return out
-
-
-@_on_tensor_device
-def warp_bilinear_bn_cl(feat_cl, flow, bn_scale, bn_shift, add_cl=None, res=None, res_w=None, res_b=None, out=None, amax_out=None, amax_c0=0):
-    """lsfa_warp_bilinear_bn_cl: warp_bilinear_cl with warp_conv_feat_bn before `add_cl` (the bits of warp_bilinear_bn on the transposed maps)."""
-    feat_cl, flow = _f32c(feat_cl, "feat_cl"), _f32c(flow, "flow")
-    add_cl, res = _f32c(add_cl, "add_cl"), _f32c(res, "res")
-    bn_scale, bn_shift = _f32c(bn_scale, "bn_scale"), _f32c(bn_shift, "bn_shift")
-    N, _, H, W = flow.shape
-    feat_n, C = feat_cl.shape[0], feat_cl.shape[3]
-    if tuple(feat_cl.shape[1:3]) != (H, W) or (add_cl is not None and tuple(add_cl.shape) != (N, H, W, C)):
-        raise LsfaError("warp_bilinear_bn_cl: feat_cl %s / add_cl %s do not match a (%d, 2, %d, %d) flow" % (
-            tuple(feat_cl.shape), None if add_cl is None else tuple(add_cl.shape), N, H, W))
-    if bn_scale.numel() != C or bn_shift.numel() != C:
-        raise LsfaError("warp_bilinear_bn_cl: bn_scale / bn_shift must have %d elements" % C)
-    res_c = 0
-    if res is not None:
-        res_w, res_b = _f32c(res_w, "res_w").reshape(C, -1), _f32c(res_b, "res_b")
-        res_c = res.shape[1]
-    if out is None:
-        out = torch.empty((N, H, W, C), device=feat_cl.device, dtype=torch.float32)
-    _check(lib().lsfa_warp_bilinear_bn_cl(_ptr(feat_cl), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W), _ptr(add_cl), _ptr(res),
-                                          _ci(res_c), _ptr(res_w), _ptr(res_b), _ptr(bn_scale), _ptr(bn_shift), _ptr(out), _ptr(amax_out),
-                                          _ci(amax_c0), _stream()), "lsfa_warp_bilinear_bn_cl")
-    return out
+    receives max|out| over channels [amax_c0, C) (the scale of the convolution that reads those).  bn = (scale, shift):
+    lsfa_warp_bilinear_bn_cl, as in warp_bilinear."""
+    return _warp("warp_bilinear_cl", True, feat_cl, flow, None, add_cl, res, res_w, res_b, bn, out, amax_out, amax_c0)
 
 
 @_on_tensor_device
@@ -304,7 +266,7 @@ def gate_apply(x, gate, y, out=None, amax_out=None, amax_c0=0):
 def warp_set_variant(variant):
     """'auto' | 'gather' | 'staged': lsfa_warp_set_variant (process-wide kernel choice of warp_bilinear; same results.  'staged'
     makes shapes the LDS-staged kernel does not take an error instead of falling back)."""
-    _check(lib().lsfa_warp_set_variant(_ci({'auto': 0, 'gather': 1, 'staged': 2}[variant])), "lsfa_warp_set_variant")
+    _check(lib().lsfa_warp_set_variant(_ci(_WARP_VARIANTS[variant])), "lsfa_warp_set_variant")
 
 
 @_on_tensor_device

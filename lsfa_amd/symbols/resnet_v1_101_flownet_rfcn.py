@@ -819,12 +819,10 @@ class Executor(object):
         add_cl = self.small_net_feature(d['data'], nchw=False)
         self._tap('small_feat', add_cl.permute(0, 3, 1, 2))
         am = S.new()
-        if self.warp_bn is None:
-            conv_cl = hip.warp_bilinear_cl(feat_cl, d['motion_vector'], add_cl=add_cl, res=d['res_diff'], res_w=self.rnet_w, res_b=self.rnet_b,
-                                           amax_out=am, amax_c0=512)     # the maximum of the channels the R-FCN convolution (two fp16 pieces) reads
-        else:                                     # small_net_bn_before_fuse: warp_conv_feat_bn in the epilogue, before the addend
-            conv_cl = hip.warp_bilinear_bn_cl(feat_cl, d['motion_vector'], self.warp_bn[0], self.warp_bn[1], add_cl=add_cl, res=d['res_diff'],
-                                              res_w=self.rnet_w, res_b=self.rnet_b, amax_out=am, amax_c0=512)
+        # amax: the maximum of the channels the R-FCN convolution (two fp16 pieces) reads; bn (small_net_bn_before_fuse): warp_conv_feat_bn in
+        # the epilogue, before the addend
+        conv_cl = hip.warp_bilinear_cl(feat_cl, d['motion_vector'], add_cl=add_cl, res=d['res_diff'], res_w=self.rnet_w, res_b=self.rnet_b,
+                                       amax_out=am, amax_c0=512, bn=self.warp_bn)
         rois, cls_prob, bbox_pred = self._heads_cl(conv_cl, am, d['im_info'])
         return {'data': d['data'], 'data_key': d.get('data_key'), 'data_key_old': d.get('data_key_old'),
                 'feat_key_old': d.get('feat_key_old'), 'rois_output': rois, 'cls_prob_reshape_output': cls_prob,
@@ -908,12 +906,8 @@ class Executor(object):
         if add is None and cfg.network.add_small_net:
             add = self.small_net_feature(d['data'])
         self._tap('small_feat', add)
-        if self.warp_bn is None:
-            conv_feat = hip.warp_bilinear(d['feat_key'], d['motion_vector'], add=add, res=d['res_diff'], res_w=self.rnet_w,
-                                          res_b=self.rnet_b)
-        else:
-            conv_feat = hip.warp_bilinear_bn(d['feat_key'], d['motion_vector'], self.warp_bn[0], self.warp_bn[1], add=add, res=d['res_diff'],
-                                             res_w=self.rnet_w, res_b=self.rnet_b)
+        conv_feat = hip.warp_bilinear(d['feat_key'], d['motion_vector'], add=add, res=d['res_diff'], res_w=self.rnet_w, res_b=self.rnet_b,
+                                      bn=self.warp_bn)
         rois, cls_prob, bbox_pred = self._heads(conv_feat, d['im_info'])
         return {'data': d['data'], 'data_key': d.get('data_key'), 'data_key_old': d.get('data_key_old'),
                 'feat_key_old': d.get('feat_key_old'), 'rois_output': rois, 'cls_prob_reshape_output': cls_prob,

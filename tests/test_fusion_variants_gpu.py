@@ -254,11 +254,11 @@ def test_warp_with_batchnorm_bit_exact_in_both_layouts():
     want = ((w * sc.numpy()[None, :, None, None]).astype(np.float32) + sh.numpy()[None, :, None, None]).astype(np.float32)
     want = (want + add.numpy()).astype(np.float32)
     t = lambda a: a.to(DEV)
-    got = hip.warp_bilinear_bn(t(feat), t(flow), t(sc), t(sh), add=t(add), res=t(res), res_w=t(rw), res_b=t(rb))
+    got = hip.warp_bilinear(t(feat), t(flow), add=t(add), res=t(res), res_w=t(rw), res_b=t(rb), bn=(t(sc), t(sh)))
     np.testing.assert_array_equal(np_(got), want)
     slots = hip.amax_slots(1, DEV)
-    got_cl = hip.warp_bilinear_bn_cl(t(feat.permute(0, 2, 3, 1).contiguous()), t(flow), t(sc), t(sh), add_cl=t(add.permute(0, 2, 3, 1).contiguous()),
-                                     res=t(res), res_w=t(rw), res_b=t(rb), amax_out=slots[0], amax_c0=512)
+    got_cl = hip.warp_bilinear_cl(t(feat.permute(0, 2, 3, 1).contiguous()), t(flow), add_cl=t(add.permute(0, 2, 3, 1).contiguous()),
+                                  res=t(res), res_w=t(rw), res_b=t(rb), amax_out=slots[0], amax_c0=512, bn=(t(sc), t(sh)))
     np.testing.assert_array_equal(np_(got_cl).transpose(0, 3, 1, 2), want)
     assert float(slots[0].view(torch.float32).max()) == float(np.abs(want[:, 512:]).max())
 

@@ -302,6 +302,162 @@ def test_warp_identity_property(hip):
     assert torch.allclose(out, feat, rtol=0, atol=2e-5 * feat.abs().max().item())
 
 
+# ---- every kernel instance the warp's dispatch can pick, at the smallest planes that tell its decisions apart -------------------------------
+# N = 2 maps of one shared feature (feat_n = 1), C = 8 (two channel quads of the channels-last kernel):
+#   6 x 8 = 48 pixels: the gather kernel's float4 form; the staged kernel takes it when forced
+#   5 x 6 = 30: the float2 form; staged when forced
+#   5 x 7 = 35: the scalar form; odd, so the staged kernel refuses it
+WARP_PLANES = [(6, 8), (5, 6), (5, 7)]
+WARP_N, WARP_C = 2, 8
+WARP_SUBSETS = [(m, a, rc) for m in (False, True) for a in (False, True) for rc in (0, 3, 4)]      # rc: the residual's channels (3: the
+#                                                                                                    unrolled staged instance), 0 = no residual
+_warp_cache = {}
+
+
+def warp_inputs(hw):
+    """The operands of one plane, built once: a smooth flow of magnitude 2.5 whose first row points 4 px up, so that taps leave the map."""
+    if hw not in _warp_cache:
+        H, W = hw
+        N, C = WARP_N, WARP_C
+        rs = np.random.RandomState(100 * H + W)
+        d = dict(feat=rs.randn(1, C, H, W).astype(np.float32), flow=smooth_flow(rs, N, H, W, 2.5),
+                 mul=(1 + 0.1 * rs.randn(N, C, H, W)).astype(np.float32), add=rs.randn(N, C, H, W).astype(np.float32),
+                 res=(4 * rs.randn(N, 4, H, W)).astype(np.float32), res_w=(0.01 * rs.randn(C, 4)).astype(np.float32),
+                 res_b=(0.01 * rs.randn(C)).astype(np.float32), bn_s=(rs.rand(C) + 0.5).astype(np.float32), bn_t=rs.randn(C).astype(np.float32))
+        d['flow'][:, 1, 0, :] -= 4.0
+        d['want'] = {}
+        _warp_cache[hw] = d
+        assert (warp_want(hw, False, False, 0) == 0).any()          # taps outside the map: the border path runs
+    return _warp_cache[hw]
+
+
+def warp_operands(hw, m, a, rc, conv=lambda x: x):
+    d = warp_inputs(hw)
+    kw = {}
+    if m:
+        kw['mul'] = conv(d['mul'])
+    if a:
+        kw['add'] = conv(d['add'])
+    if rc:
+        kw.update(res=conv(d['res'][:, :rc]), res_w=conv(d['res_w'][:, :rc]), res_b=conv(d['res_b']))
+    return kw
+
+
+def warp_want(hw, m, a, rc):
+    """The oracle's result for one operand subset of one plane, computed once and never written to."""
+    d = warp_inputs(hw)
+    if (m, a, rc) not in d['want']:
+        w = oracle.warp_bilinear(d['feat'], d['flow'], **warp_operands(hw, m, a, rc))
+        w.setflags(write=False)
+        d['want'][(m, a, rc)] = w
+    return d['want'][(m, a, rc)]
+
+
+def warp_want_bn(hw, a, rc):
+    """warp (+ res), then * scale and + shift as two float32 roundings, then + add (test_warp_with_batchnorm_bit_exact_in_both_layouts)."""
+    d = warp_inputs(hw)
+    w = warp_want(hw, False, False, rc)
+    want = ((w * d['bn_s'][None, :, None, None]).astype(np.float32) + d['bn_t'][None, :, None, None]).astype(np.float32)
+    return (want + d['add']).astype(np.float32) if a else want
+
+
+def nhwc(a):
+    return t(np.ascontiguousarray(a.transpose(0, 2, 3, 1)))
+
+
+@pytest.mark.parametrize("subset", WARP_SUBSETS, ids=lambda s: "mul%d-add%d-res%d" % s)
+@pytest.mark.parametrize("hw", WARP_PLANES, ids=lambda hw: "%dx%d" % hw)
+def test_warp_every_operand_subset_in_both_nchw_kernels(hip, hw, subset):
+    """Each of the eight (mul, add, res) subsets, the residual with 3 and with 4 channels, through the gather kernel at all three vector widths
+    and through the staged kernel on the two even planes: the oracle's bits."""
+    d = warp_inputs(hw)
+    want = warp_want(hw, *subset)
+    kw = warp_operands(hw, *subset, conv=t)
+    try:
+        hip.warp_set_variant("gather")
+        np.testing.assert_array_equal(hip.warp_bilinear(t(d['feat']), t(d['flow']), **kw).cpu().numpy(), want)
+        if hw[0] * hw[1] % 2 == 0:
+            hip.warp_set_variant("staged")
+            np.testing.assert_array_equal(hip.warp_bilinear(t(d['feat']), t(d['flow']), **kw).cpu().numpy(), want)
+    finally:
+        hip.warp_set_variant("auto")
+
+
+@pytest.mark.parametrize("subset", [(a, rc) for a in (False, True) for rc in (0, 3)], ids=lambda s: "add%d-res%d" % s)
+@pytest.mark.parametrize("hw", WARP_PLANES, ids=lambda hw: "%dx%d" % hw)
+def test_warp_bn_every_operand_subset_in_both_layouts(hip, hw, subset):
+    """bn = (scale, shift) with each (add, res) subset: NCHW (the gather kernel whatever the variant switch says: under 'staged' a plain call
+    of the odd plane is refused, this one is not) and channels-last with max|out| over channels [4, 8)."""
+    a, rc = subset
+    d = warp_inputs(hw)
+    want = warp_want_bn(hw, a, rc)
+    bn = (t(d['bn_s']), t(d['bn_t']))
+    np.testing.assert_array_equal(hip.warp_bilinear(t(d['feat']), t(d['flow']), bn=bn, **warp_operands(hw, False, a, rc, conv=t)).cpu().numpy(), want)
+    try:
+        hip.warp_set_variant("staged")
+        got = hip.warp_bilinear(t(d['feat']), t(d['flow']), bn=bn, **warp_operands(hw, False, a, rc, conv=t))
+    finally:
+        hip.warp_set_variant("auto")
+    np.testing.assert_array_equal(got.cpu().numpy(), want)
+    kw = warp_operands(hw, False, a, rc, conv=t)
+    if a:
+        kw['add_cl'] = nhwc(d['add'])
+        del kw['add']
+    slots = hip.amax_slots(1, DEV)[0]
+    got_cl = hip.warp_bilinear_cl(nhwc(d['feat']), t(d['flow']), bn=bn, amax_out=slots, amax_c0=4, **kw)
+    np.testing.assert_array_equal(got_cl.permute(0, 3, 1, 2).cpu().numpy(), want)
+    assert slots.view(torch.float32).max().item() == float(np.abs(want[:, 4:]).max())
+
+
+def test_warp_bn_with_mul_is_an_error(hip):
+    d = warp_inputs((6, 8))
+    with pytest.raises(hip.LsfaError):
+        hip.warp_bilinear(t(d['feat']), t(d['flow']), mul=t(d['mul']), bn=(t(d['bn_s']), t(d['bn_t'])))
+
+
+@pytest.mark.parametrize("subset", [(a, rc) for a in (False, True) for rc in (0, 3, 4)], ids=lambda s: "add%d-res%d" % s)
+@pytest.mark.parametrize("hw", WARP_PLANES, ids=lambda hw: "%dx%d" % hw)
+def test_warp_channels_last_every_operand_subset(hip, hw, subset):
+    """The channels-last kernel without bn on each (add, res) subset - the residual alone among them: the oracle's bits, transposed."""
+    a, rc = subset
+    d = warp_inputs(hw)
+    kw = warp_operands(hw, False, a, rc, conv=t)
+    if a:
+        kw['add_cl'] = nhwc(d['add'])
+        del kw['add']
+    got = hip.warp_bilinear_cl(nhwc(d['feat']), t(d['flow']), **kw)
+    np.testing.assert_array_equal(got.permute(0, 3, 1, 2).cpu().numpy(), warp_want(hw, False, a, rc))
+
+
+def test_warp_misaligned_maps_fall_back_to_the_scalar_kernel(hip):
+    """6 x 8 planes ask for float4 accesses; `out` and `add` that start 4 bytes past a 16-byte boundary get the scalar form and the same bits.
+    The channels-last kernel has no such form: it refuses the map."""
+    hw = (6, 8)
+    d = warp_inputs(hw)
+    N, C, (H, W) = WARP_N, WARP_C, hw
+    n = N * C * H * W
+
+    def off4(shape, src=None):                     # a contiguous view one float into a fresh (256-byte aligned) allocation
+        v = torch.empty(n + 1, device=DEV)[1:].view(shape)
+        assert v.data_ptr() % 16 == 4
+        if src is not None:
+            v.copy_(t(src))
+        return v
+    kw = warp_operands(hw, False, False, 3, conv=t)
+    try:
+        hip.warp_set_variant("gather")
+        aligned = hip.warp_bilinear(t(d['feat']), t(d['flow']), add=t(d['add']), **kw)
+        out = off4((N, C, H, W))
+        got = hip.warp_bilinear(t(d['feat']), t(d['flow']), add=off4((N, C, H, W), d['add']), out=out, **kw)
+    finally:
+        hip.warp_set_variant("auto")
+    assert got.data_ptr() == out.data_ptr()
+    assert torch.equal(got, aligned)
+    np.testing.assert_array_equal(aligned.cpu().numpy(), warp_want(hw, False, True, 3))
+    with pytest.raises(hip.LsfaError):
+        hip.warp_bilinear_cl(nhwc(d['feat']), t(d['flow']), out=off4((N, H, W, C)))
+
+
 # ------------------------------------------------------------------ aggregate ---------
 @pytest.mark.parametrize("shape", [(1024, 38, 63), (1024, 36, 63), (20, 8, 8), (3, 5, 7)])
 def test_aggregate_softmax2_bit_exact(hip, shape):

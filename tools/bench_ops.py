@@ -73,6 +73,21 @@ def main():
             ('ref: torch add (2 maps -> 1)', lambda: torch.add(feat, feat2, out=o), b3)):
         us = timeit(fn, args.iters)
         out[name] = dict(us=round(us, 2), GBps=round(nbytes / us / 1e3, 1), bytes=nbytes)
+    # the non-key path's own form: channels-last maps, + small-net feature + rnet_conv0(res), max|out| over the R-FCN convolution's channels;
+    # one map and a nine-frame segment (one key feature for all), without and with warp_conv_feat_bn
+    slots = hip.amax_slots(1, dev)[0]
+    feat_cl = feat.permute(0, 2, 3, 1).contiguous()
+    bn = (torch.rand(C, device=dev) + 0.5, torch.randn(C, device=dev))
+    for n in (1, 9):
+        flow_n = torch.randn(n, 2, H, W, device=dev) * 0.3 + 1.5
+        add_cl, res_n, o_cl = torch.randn(n, H, W, C, device=dev), torch.randn(n, 3, H, W, device=dev), torch.empty(n, H, W, C, device=dev)
+        nbytes = ((1 + 2 * n) * C * HW + 5 * n * HW) * 4
+        for tag, kw in (('warp_cl(+res+add, amax) N=%d' % n, {}), ('warp_cl_bn(+res+add, amax) N=%d' % n, {'bn': bn})):
+            us = timeit(lambda: hip.warp_bilinear_cl(feat_cl, flow_n, add_cl=add_cl, res=res_n, res_w=res_w, res_b=res_b, out=o_cl,
+                                                     amax_out=slots, amax_c0=512, **kw), args.iters)
+            out[tag] = dict(us=round(us, 2), GBps=round(nbytes / us / 1e3, 1), bytes=nbytes)
+    us = timeit(lambda: hip.warp_bilinear(feat, flow, add=feat2, res=res, res_w=res_w, res_b=res_b, out=o, bn=bn), args.iters)
+    out['warp_cur_bn(+res+add)'] = dict(us=round(us, 2), GBps=round(b3 / us / 1e3, 1), bytes=b3)
     # Fgfa cosine weights at LSFA's shape: 2048-channel embeddings on the 38x63 map
     ew, ec = torch.randn(1, 2048, H, W, device=dev), torch.randn(1, 2048, H, W, device=dev)
     us = timeit(lambda: hip.aggregate_cosine(feat, feat2, ew, ec, out=o), args.iters)
