@@ -585,8 +585,6 @@ def _plan_kernel_name(d):
     b = lambda v: "true" if v else "false"
     if kind == 2:
         return "conv_split_direct_kernel<%d>" % pc
-    if kind == 3:
-        return "conv_split3x3_kernel<%d, %d>" % (nt, pc)
     return "conv_ring_kernel<%d, %d, %d, %s, %s, %d>%s" % (nt, pc, st, b(sp), b(af), wv, "" if slices <= 1 else " +split_reduce")
 
 
@@ -1009,11 +1007,6 @@ class SplitWeight(object):
                                            _ci(self.w_exp), _ptr(self.frag), _stream()), "lsfa_conv_weights")
 
 
-def SplitWeightH(weight, **kw):
-    """the fp16 two-piece form by name (r3's class)"""
-    return SplitWeight(weight, pieces=2, **kw)
-
-
 @_on_tensor_device
 def amax_partial(x, out=None):
     """lsfa_amax_partial: 256 partial maxima of |x| (float32, contiguous, numel % 4 == 0): an `amax_in` for a map that no convolution
@@ -1061,31 +1054,36 @@ def check_status(status):
     _check(lib().lsfa_status_check(_ptr(status), _stream()), "lsfa_status_check")
 
 
-def _conv_launch(who, x, lda, N, H, W, cin, sw, bias, stride, pad_h, pad_w, dil, act, nchw, residual, y_ptr, ldy, out2, scale2, shift2,
-                 amax_in, amax_out, status, grid, view, prof_tag, device, x_nchw=False, in_scale=None, in_shift=None, x_offset=0):
-    if sw.pieces == 2 and amax_in is None:
-        raise LsfaError("%s: a two-piece (fp16) weight needs amax_in" % who)
+def _conv_desc(x, sw, N, H, W, y_ptr, x_offset=0, lda=0, cin=None, ldy=0, bias=None, stride=1, pad=(0, 0), dil=1, act=0, nchw=False, residual=None,
+               out2=None, scale2=None, shift2=None, amax_in=None, amax_out=None, status=None, grid=(0, 0), view=(0, 0, 0, 0), prof_tag=0,
+               x_nchw=False, in_scale=None, in_shift=None):
+    """struct lsfa_conv_desc of one launch; what a caller leaves out keeps the header's default (0 / NULL: whole channel rows, the
+    convolution's own output grid, no view)"""
     d = ConvDesc()
-    d.x, d.lda, d.N, d.H, d.W, d.Cin = x.data_ptr() + x_offset, lda, N, H, W, cin
-    d.wfrag, d.pieces, d.w_exp, d.amax_in = sw.frag.data_ptr(), sw.pieces, sw.w_exp, (amax_in.data_ptr() if amax_in is not None else None)
-    d.bias, d.Cout, d.kh, d.kw, d.stride, d.pad_h, d.pad_w, d.dil = (bias.data_ptr() if bias is not None else None), sw.cout, sw.kh, sw.kw, stride, pad_h, pad_w, dil
-    d.act, d.y_nchw, d.residual, d.y, d.ldy = int(act), int(nchw), (residual.data_ptr() if residual is not None else None), y_ptr, ldy
-    d.y2, d.scale2, d.shift2 = (out2.data_ptr() if out2 is not None else None), (scale2.data_ptr() if scale2 is not None else None), (shift2.data_ptr() if shift2 is not None else None)
-    d.amax_out, d.status = (amax_out.data_ptr() if amax_out is not None else None), (status.data_ptr() if status is not None else None)
+    d.x, d.lda, d.N, d.H, d.W, d.Cin = x.data_ptr() + x_offset, lda, N, H, W, sw.cin if cin is None else cin
+    d.wfrag, d.pieces, d.w_exp, d.amax_in = _dp(sw.frag), sw.pieces, sw.w_exp, _dp(amax_in)
+    d.bias, d.Cout, d.kh, d.kw, d.stride, d.pad_h, d.pad_w, d.dil = _dp(bias), sw.cout, sw.kh, sw.kw, stride, pad[0], pad[1], dil
+    d.act, d.y_nchw, d.residual, d.y, d.ldy = int(act), int(nchw), _dp(residual), y_ptr, ldy
+    d.y2, d.scale2, d.shift2, d.amax_out, d.status = _dp(out2), _dp(scale2), _dp(shift2), _dp(amax_out), _dp(status)
     d.Ho, d.Wo = grid
     d.out_H, d.out_W, d.out_sy, d.out_sx = view
-    d.prof_tag = prof_tag
-    d.x_nchw = int(x_nchw)
-    d.in_scale, d.in_shift = (in_scale.data_ptr() if in_scale is not None else None), (in_shift.data_ptr() if in_shift is not None else None)
-    w_scale = getattr(sw, 'w_scale', None)
-    d.w_scale = w_scale.data_ptr() if w_scale is not None else None
+    d.prof_tag, d.x_nchw = prof_tag, int(x_nchw)
+    d.in_scale, d.in_shift, d.w_scale = _dp(in_scale), _dp(in_shift), _dp(getattr(sw, 'w_scale', None))
+    return d
+
+
+def _conv_launch(who, x, sw, N, H, W, y_ptr, **desc):
+    """lsfa_conv_fwd on the descriptor _conv_desc(x, sw, N, H, W, y_ptr, **desc) with its workspace, counted for bench.py's roofline"""
+    if sw.pieces == 2 and desc.get("amax_in") is None:
+        raise LsfaError("%s: a two-piece (fp16) weight needs amax_in" % who)
+    d = _conv_desc(x, sw, N, H, W, y_ptr, **desc)
     need = lib().lsfa_conv_workspace_bytes(ctypes.byref(d))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
     if _conv_flops["count"]:
-        Ho = grid[0] if grid[0] > 0 else (H + 2 * pad_h - dil * (sw.kh - 1) - 1) // stride + 1
-        Wo = grid[1] if grid[1] > 0 else (W + 2 * pad_w - dil * (sw.kw - 1) - 1) // stride + 1
-        outs = 1 + (1 if residual is not None else 0) + (1 if out2 is not None else 0)
-        nbytes = 4.0 * N * H * W * cin + 2.0 * sw.pieces * sw.cout * sw.kh * sw.kw * cin + 4.0 * outs * N * Ho * Wo * sw.cout
+        Ho = d.Ho if d.Ho > 0 else (H + 2 * d.pad_h - d.dil * (sw.kh - 1) - 1) // d.stride + 1
+        Wo = d.Wo if d.Wo > 0 else (W + 2 * d.pad_w - d.dil * (sw.kw - 1) - 1) // d.stride + 1
+        outs = 1 + (1 if d.residual else 0) + (1 if d.y2 else 0)
+        nbytes = 4.0 * N * H * W * d.Cin + 2.0 * sw.pieces * sw.cout * sw.kh * sw.kw * d.Cin + 4.0 * outs * N * Ho * Wo * sw.cout
         _count_conv_launch(_plan_kernel_name(d), 2.0 * N * Ho * Wo * sw.real_cout * sw.real_cin * sw.kh * sw.kw, nbytes)
     _check(lib().lsfa_conv_fwd(ctypes.byref(d), _ptr(ws), ctypes.c_size_t(need), _stream()), who)
 
@@ -1162,15 +1160,10 @@ def conv_split(x, sw, bias=None, stride=1, pad=0, dil=1, relu=False, out=None, r
     if amax_in is None and sw.pieces == 2:
         amax_in = amax_partial(x)
     _count_conv(N, Ho, Wo, sw.real_cout, sw.real_cin, kh, kw, sw.pieces)
-    _conv_launch("lsfa_conv_fwd", x, Ctot, N, H, W, Cin, sw, bias, stride, pad, pad, dil, (1 if relu else 0) if act is None else act, nchw,
-                 residual, out.data_ptr(), Cout, out2, scale2, shift2, amax_in, amax_out, status, (0, 0), (0, 0, 0, 0), 0, x.device,
-                 x_nchw=x_nchw, in_scale=in_scale, in_shift=in_shift)
+    _conv_launch("lsfa_conv_fwd", x, sw, N, H, W, out.data_ptr(), lda=Ctot, ldy=Cout, bias=bias, stride=stride, pad=(pad, pad), dil=dil,
+                 act=(1 if relu else 0) if act is None else act, nchw=nchw, residual=residual, out2=out2, scale2=scale2, shift2=shift2,
+                 amax_in=amax_in, amax_out=amax_out, status=status, x_nchw=x_nchw, in_scale=in_scale, in_shift=in_shift)
     return out if out2 is None else (out, out2)
-
-
-def conv_split_h(x, swh, bias=None, stride=1, pad=0, dil=1, act=0, out=None, nchw=False, amax=None, amax_out=None, status=None):
-    """conv_split with r3's argument names for the fp16 two-piece form (amax: the partial maxima of x or of a map that bounds |x|)"""
-    return conv_split(x, swh, bias, stride, pad, dil, out=out, nchw=nchw, act=act, amax_in=amax, amax_out=amax_out, status=status)
 
 
 @_on_tensor_device
@@ -1213,8 +1206,8 @@ def conv_split_view(x, sw, bias, out, stride=1, pad=(0, 0), dil=1, act=0, cin=No
     first = out.data_ptr() + 4 * ((y0 * Wout + x0) * Lout + c0)
     view = place is not None or (Ho, Wo) != (Hout, Wout)
     _count_conv(N, Ho, Wo, sw.real_cout, sw.real_cin, kh, kw, sw.pieces)
-    _conv_launch("lsfa_conv_fwd (view)", x, L, N, H, W, cin, sw, bias, stride, pad[0], pad[1], dil, act, False, None, first, Lout, None, None,
-                 None, amax_in, amax_out, status, (Ho, Wo), (Hout if view else 0, Wout, sy, sx), 1, x.device, x_offset=4 * cin0)
+    _conv_launch("lsfa_conv_fwd (view)", x, sw, N, H, W, first, x_offset=4 * cin0, lda=L, ldy=Lout, bias=bias, stride=stride, pad=pad, dil=dil, act=act,
+                 amax_in=amax_in, amax_out=amax_out, status=status, grid=(Ho, Wo), view=(Hout if view else 0, Wout, sy, sx), prof_tag=1)
     return out
 
 

@@ -1746,12 +1746,12 @@ def test_conv_split_h_fp16_two_piece_form_vs_float64(hip, case):
     x = torch.relu(torch.randn((nb, H, W, ci), device=DEV, generator=g)) * mag
     w = torch.randn((co, ci, k, k), device=DEV, generator=g) * 0.01
     b = torch.randn(co, device=DEV, generator=g) * mag * 0.1
-    swh, sw = hip.SplitWeightH(w), hip.SplitWeight(w)
-    y = hip.conv_split_h(x, swh, b, 1, pad, dil, act=1, nchw=nchw)
-    y_again = hip.conv_split_h(x, swh, b, 1, pad, dil, act=1, nchw=nchw)
+    swh, sw, am = hip.SplitWeight(w, pieces=2), hip.SplitWeight(w), hip.amax_partial(x)
+    y = hip.conv_split(x, swh, b, 1, pad, dil, act=1, nchw=nchw, amax_in=am)
+    y_again = hip.conv_split(x, swh, b, 1, pad, dil, act=1, nchw=nchw, amax_in=am)
     assert torch.equal(y, y_again)
     if nchw:      # the NCHW reduce pass (tile turned in LDS) against the channels-last one: the same numbers, transposed
-        assert torch.equal(y, hip.conv_split_h(x, swh, b, 1, pad, dil, act=1, nchw=False).permute(0, 3, 1, 2))
+        assert torch.equal(y, hip.conv_split(x, swh, b, 1, pad, dil, act=1, nchw=False, amax_in=am).permute(0, 3, 1, 2))
         assert torch.equal(hip.conv_split(x, sw, b, 1, pad, dil, relu=True, nchw=True),
                            hip.conv_split(x, sw, b, 1, pad, dil, relu=True, nchw=False).permute(0, 3, 1, 2))
     ref = torch.relu(torch.nn.functional.conv2d(x.permute(0, 3, 1, 2).double().cpu(), w.double().cpu(), b.double().cpu(), padding=pad, dilation=dil))
@@ -1928,21 +1928,20 @@ def test_conv_ring_every_plan_gives_the_same_convolution(hip, pieces):
         if pieces < 3:
             plans += [(4, 4, 2), (4, 4, 3)]                                                # 4: 256-pixel tiles, eight mixed-role waves (r5)
         for kern, nt, st in plans:
-            if True:
-                if nt == 4 and pieces == 3 and st == 4:
-                    continue
-                for slices in (1, 2, 5, 7):
-                    hip.conv_plan_override(kernel=kern, nt=nt, st=st, slices=slices)
-                    slots = hip.amax_slots(1, DEV)[0]
-                    y, y2 = hip.conv_split(x, sw, b, 1, dil, dil, residual=res, out2=torch.empty_like(res), scale2=sc2, shift2=sh2,
-                                           amax_in=am, amax_out=slots)
-                    assert float((y.double().cpu() - ref).abs().max()) < tol, (kern, nt, st, slices)
-                    assert torch.equal(y2, torch.relu(y * sc2 + sh2))
-                    assert slots.view(torch.float32).max().item() == y2.max().item()
-                    key = (nt, slices)
-                    if key in by_cut:
-                        assert torch.equal(by_cut[key], y), (kern, nt, st, slices)      # neither ring depth nor wave roles change the arithmetic
-                    by_cut[key] = y
+            if nt == 4 and pieces == 3 and st == 4:
+                continue
+            for slices in (1, 2, 5, 7):
+                hip.conv_plan_override(kernel=kern, nt=nt, st=st, slices=slices)
+                slots = hip.amax_slots(1, DEV)[0]
+                y, y2 = hip.conv_split(x, sw, b, 1, dil, dil, residual=res, out2=torch.empty_like(res), scale2=sc2, shift2=sh2,
+                                       amax_in=am, amax_out=slots)
+                assert float((y.double().cpu() - ref).abs().max()) < tol, (kern, nt, st, slices)
+                assert torch.equal(y2, torch.relu(y * sc2 + sh2))
+                assert slots.view(torch.float32).max().item() == y2.max().item()
+                key = (nt, slices)
+                if key in by_cut:
+                    assert torch.equal(by_cut[key], y), (kern, nt, st, slices)      # neither ring depth nor wave roles change the arithmetic
+                by_cut[key] = y
     finally:
         hip.conv_plan_override()
 
