@@ -578,6 +578,49 @@ int lsfa_mv_estimate(const unsigned char* luma_cur, const unsigned char* luma_re
                      void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip): the planes a decoder hands over - libav, the VCN decode engines, a raw .yuv dump - straight to
+ * the packed BGR frame lsfa_mv_residual / lsfa_luma_u8 / lsfa_image_transform_u8 take, to the luma plane lsfa_mv_estimate searches and to the
+ * network's `data`.  Replaces (in function, NOT in arithmetic): the swscale conversion inside the reference's coviar loader
+ * (external/data_loader_py2/coviar_data_loader.c), which runs on the CPU.  Neither swscale nor OpenCV is part of this project, and both carry
+ * options (chroma siting, bilinear chroma) that change the result, so the conversion is defined by the specification below (DESIGN.md "YUV
+ * intake", restated in numpy as tests/ref_yuv.py) and is bit-exact with THAT; parity with swscale or OpenCV is unpinned and not claimed.
+ *   Pixel (x, y) takes Y[y][x] and the chroma sample (x >> 1, y >> 1): nearest-neighbour chroma, no interpolation.  Chroma planes are
+ *   ceil(W / 2) x ceil(H / 2); odd W and H are allowed.  C = Y - o, D = U - 128, E = V - 128, all int; >> is arithmetic (it floors); clip
+ *   clamps to 0..255.
+ *     matrix 0, BT.601 limited range (what MPEG-4 streams carry), o = 16:
+ *        R = clip((298 C + 409 E + 128) >> 8)   G = clip((298 C - 100 D - 208 E + 128) >> 8)   B = clip((298 C + 516 D + 128) >> 8)
+ *     matrix 1, BT.709 limited range, o = 16:
+ *        R = clip((298 C + 459 E + 128) >> 8)   G = clip((298 C -  55 D - 136 E + 128) >> 8)   B = clip((298 C + 541 D + 128) >> 8)
+ *     matrix 2, BT.601 full range (JFIF), o = 0:
+ *        R = clip((256 C + 359 E + 128) >> 8)   G = clip((256 C -  88 D - 183 E + 128) >> 8)   B = clip((256 C + 454 D + 128) >> 8)
+ * Out of scope: NV21, P010 (10-bit), 4:2:2 and 4:4:4; interpolated chroma; any binding to rocDecode (a decoded surface's base, pitch and
+ * height ARE the arguments: INTEGRATION.md).
+ * Planes: a base pointer, a row pitch in bytes and, for N frames, a frame stride in bytes each; a pitch wider than the row is normal
+ * (y_pitch >= W; c_pitch >= 2 ceil(W / 2) for NV12, >= ceil(W / 2) for I420), a frame stride may be anything that does not overlap.
+ * v == NULL: u_or_uv is the interleaved U, V plane (NV12); otherwise u_or_uv and v are I420's two chroma planes, with one pitch and stride.
+ * One launch each, no workspace.  Dword-aligned planes (half-word aligned I420 chroma) of W % 4 == 0, H % 2 == 0 take the kernel that reads
+ * four pixels of two rows per thread; anything else takes a byte-wise kernel, picked per launch.
+ * lsfa_yuv420_to_bgr_u8: bgr (N, H, W, 3) uint8, packed; y_packed (N, H, W) or NULL: the Y plane with the pitch removed - the contiguous plane
+ *   lsfa_mv_estimate wants, without a copy of its own (limited-range Y is NOT lsfa_luma_u8 of the converted frame: different numbers).
+ * lsfa_image_transform_yuv420: `data` (N, 3, H, W) float32, channel i = (bgr[2 - i] - pixel_means[2 - i]) * pixel_scale, subtraction and product
+ *   in float64, rounded to float32 once: bit-identical to lsfa_image_transform_u8 of lsfa_yuv420_to_bgr_u8's frame, which is never stored.
+ *   No H*W % 4 condition.
+ * lsfa_image_resize_transform_yuv420: lsfa_image_resize_transform with is_u8 = 1 reading its taps from the planes (the converted frame as
+ *   float, interpolated in float, padded to `stride`, the float32 / float64 subtraction rule by `stride` stated there); bit-identical to it
+ *   on lsfa_yuv420_to_bgr_u8's frame.  h1, w1, out_h, out_w as there - checked.  The fixed-point is_u8 = 2 form is not offered for YUV.
+ * ------------------------------------------------------------------------ */
+int lsfa_yuv420_to_bgr_u8(const unsigned char* y, long long y_pitch, long long y_frame_stride, const unsigned char* u_or_uv,
+                          const unsigned char* v /* NULL: NV12 */, long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix,
+                          unsigned char* bgr, unsigned char* y_packed /* may be NULL */, void* stream);
+int lsfa_image_transform_yuv420(const unsigned char* y, long long y_pitch, long long y_frame_stride, const unsigned char* u_or_uv,
+                                const unsigned char* v /* NULL: NV12 */, long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix,
+                                const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw, void* stream);
+int lsfa_image_resize_transform_yuv420(const unsigned char* y, long long y_pitch, long long y_frame_stride, const unsigned char* u_or_uv,
+                                       const unsigned char* v /* NULL: NV12 */, long long c_pitch, long long c_frame_stride, int N, int H, int W,
+                                       int matrix, double im_scale, int h1, int w1, int stride, const double* pixel_means_bgr_host,
+                                       double pixel_scale, float* data_nchw, int out_h, int out_w, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Plumbing without a reference counterpart: a hipStream_t that is nobody else's (non-blocking; PyTorch's
  * streams come from a small round-robin pool, and two graphs captured on pool twins share one BLAS
  * workspace — lsfa_amd/core/streams.py wraps these in torch.cuda.ExternalStream for capture and replay).

@@ -13,6 +13,7 @@
 // Pure int32 index work, HBM/L2-bound, bit-exact with orc_coviar_* by construction.  Maps are (H, W, 2)
 // row-major (the reference's are x-major; only its index arithmetic differs).
 #include "common.h"
+#include "resize_kernels.h"
 
 using namespace lsfa;
 
@@ -96,32 +97,14 @@ __global__ __launch_bounds__(kThreads) void mv_residual_kernel(const unsigned ch
 // 0.5) and each of those on 2 x 2 source pixels: one thread per output element computes exactly that chain - the first resize's four values
 // in float32 (mul, mul, add: the two passes' roundings), everything behind them in float64, one rounding to float32 at the end - instead of
 // materialising three full-resolution maps.  oracle/np_ref.py::transform_mv_res is the same arithmetic statement by statement.
-struct ResizeTap { int i0, i1; float a; };
-
-// resize.cpp: `fx = (float)((dx + 0.5) * scale_x - 0.5); sx = cvFloor(fx); fx -= sx;` with scale = 1. / f; taps clamped into the image
-__device__ __forceinline__ ResizeTap resize_tap(int d, int src_n, double inv_f) {
-  const float f = (float)(((double)d + 0.5) * inv_f - 0.5);
-  int s0 = (int)floorf(f);
-  float a = f - (float)s0;
-  if (s0 < 0) { s0 = 0; a = 0.f; }
-  if (s0 >= src_n - 1) { s0 = src_n - 1; a = 0.f; }
-  ResizeTap t;
-  t.i0 = s0;
-  t.i1 = min(s0 + 1, src_n - 1);
-  t.a = a;
-  return t;
-}
-
+// (ResizeTap, resize_tap, resize_blend and resize_transform_store: resize_kernels.h, shared with yuv.hip)
 template <typename T>
 __device__ __forceinline__ float first_resize(const T* __restrict__ src, int H, int W, int C, int c, int y, int x, double inv_scale, float sign = 1.f) {
   const ResizeTap tx = resize_tap(x, W, inv_scale), ty = resize_tap(y, H, inv_scale);
-  const float bx = 1.f - tx.a, by = 1.f - ty.a;
   // (sign: the reference negates the decoder's motion vectors before the transform, image.py:54 - exact, applied to the source values)
   const float s00 = (float)src[((size_t)ty.i0 * W + tx.i0) * C + c] * sign, s01 = (float)src[((size_t)ty.i0 * W + tx.i1) * C + c] * sign;
   const float s10 = (float)src[((size_t)ty.i1 * W + tx.i0) * C + c] * sign, s11 = (float)src[((size_t)ty.i1 * W + tx.i1) * C + c] * sign;
-  const float h0 = s00 * bx + s01 * tx.a;          // the horizontal pass of the two rows, rounded to float like the work buffer
-  const float h1 = s10 * bx + s11 * tx.a;
-  return h0 * by + h1 * ty.a;
+  return resize_blend(s00, s01, s10, s11, tx, ty);
 }
 
 struct MvResArgs {
@@ -188,19 +171,7 @@ __global__ __launch_bounds__(kThreads) void resize_transform_kernel(const T* __r
     rr = first_resize(src, H, W, 3, 2, y, x, inv_scale);
   }
   float* o = out + (size_t)n * 3 * plane + r;
-  if (sub_f64) {
-    // stride > 0: `resize` copied the float32 frame into np.zeros(...) - a float64 image (image.py:288-293) - so `transform` subtracts in float64
-    // and the executor rounds once
-    o[0] = (float)(((double)rr - m2) * pixel_scale);
-    o[plane] = (float)(((double)g - m1) * pixel_scale);
-    o[2 * plane] = (float)(((double)b - m0) * pixel_scale);
-    return;
-  }
-  // stride == 0: a float32 image minus a Python float is a float32 subtraction (the mean rounded to float32 first); the product with pixel_scale is float64
-  const float tr = rr - (float)m2, tg = g - (float)m1, tb = b - (float)m0;
-  o[0] = (float)((double)tr * pixel_scale);
-  o[plane] = (float)((double)tg * pixel_scale);
-  o[2 * plane] = (float)((double)tb * pixel_scale);
+  resize_transform_store(o, plane, b, g, rr, m0, m1, m2, pixel_scale, sub_f64);
 }
 
 // r6: the LAST frame of a video reaches `resize` as the uint8 image cv2.imread returned (lib/utils/image.py:45), and OpenCV interpolates uint8

@@ -7,6 +7,8 @@ score above 0.7 after per-class NMS.
     python -m lsfa_amd.demo --frames DIR [--mv DIR] [--prefix P --epoch E] [--out dets.json]
     python -m lsfa_amd.demo --frames DIR --estimate-mv [--search 16 --mv-lambda 4] [--dump-mv DIR]
 
+    python -m lsfa_amd.demo --yuv clip.nv12 --size 1280x720 [--yuv-format nv12|i420] [--yuv-matrix bt601|bt709|jpeg] [--estimate-mv ...]
+
 --frames: a directory of *.JPEG / *.jpg / *.png frames in display order (decoded with PIL; the
 reference uses cv2.imread, :75).  --mv: one `<frame stem>.npz` per non-key frame holding `mv`
 (H, W, 2) and `res` (H, W, 3) in source-image pixels, the arrays lib/utils/image.py:get_image reads
@@ -19,6 +21,10 @@ full search, not an MPEG-4 encoder's (DESIGN.md "Motion estimation").  --dump-mv
 estimated as the `<frame stem>.npz` files --mv reads: `mv` (H, W, 2) int32 is the accumulated field as get_image holds it AFTER
 `motion_vector = - motion_vector` (lib/utils/image.py:54), i.e. MINUS lsfa_mv_field's output - the --mv path does not negate -
 and `res` (H, W, 3) int32 is lsfa_mv_residual's output as it stands.  Running --mv on such a dump reproduces --estimate-mv.
+--yuv FILE --size WxH: a raw YUV 4:2:0 file as `-f rawvideo -pix_fmt nv12` (or yuv420p: --yuv-format i420) writes it - frames back to back, no
+header - in place of --frames.  The file is memory-mapped, each frame's 1.5 bytes per pixel are uploaded once and everything behind the
+upload runs on the device: `data` is hip.image_resize_transform_yuv420 of the planes, and with --estimate-mv the estimator's *_yuv
+methods convert and search them (DESIGN.md "YUV intake"; the conversion is this project's own integer specification).
 Drawing boxes into images (draw_boxes, :150-156) is left to the caller: the output is JSON.
 """
 import argparse
@@ -116,6 +122,92 @@ class FrameDirClip(object):
         return transform_mv_res(z['mv'], z['res'], self.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE)
 
 
+class YuvFileClip(object):
+    """Frames of one clip from a raw YUV 4:2:0 file (fmt 'nv12': Y plane, then interleaved U, V; 'i420': Y, U, V planes), frames back to
+    back without a header.  Same interface as FrameDirClip: frame(i) is hip.image_resize_transform_yuv420 of the frame's planes on `device`,
+    mv_res(i, key_i) the estimator's *_yuv chain when `estimate` (a dict of hip.MotionEstimator's parameters) is given, zero motion and
+    zero residual otherwise.  The file is memory-mapped; a frame's bytes are uploaded once and the frames of the current interval are kept."""
+
+    def __init__(self, path, width, height, cfg, fmt='nv12', matrix='bt601', estimate=None, device='cuda:0', dump_mv=None):
+        if fmt not in ('nv12', 'i420'):
+            raise ValueError('fmt %r is not nv12 or i420' % (fmt,))
+        if dump_mv is not None and estimate is None:
+            raise ValueError('dump_mv writes the ESTIMATED motion vectors: it needs estimate')
+        self.src_w, self.src_h, self.fmt, self.matrix, self.cfg = int(width), int(height), fmt, matrix, cfg
+        if self.src_w <= 0 or self.src_h <= 0:
+            raise ValueError('bad frame size %d x %d' % (self.src_w, self.src_h))
+        self.cw, self.ch = -(-self.src_w // 2), -(-self.src_h // 2)
+        self.frame_bytes = self.src_w * self.src_h + 2 * self.cw * self.ch
+        size = os.path.getsize(path)
+        if size == 0 or size % self.frame_bytes:
+            raise ValueError('%s holds %d bytes: not a whole number of %d x %d %s frames of %d bytes' % (path, size, self.src_w, self.src_h, fmt,
+                                                                                                     self.frame_bytes))
+        self._map = np.memmap(path, dtype=np.uint8, mode='r')
+        self.num_frames = size // self.frame_bytes
+        self.names = ['%s/%06d' % (os.path.basename(path), i) for i in range(self.num_frames)]
+        # `resize`'s scale (lib/utils/image.py:266-280) from the frame size alone
+        target, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
+        lo, hi = min(self.src_h, self.src_w), max(self.src_h, self.src_w)
+        self.im_scale = float(target) / float(lo)
+        if np.round(self.im_scale * hi) > max_size:
+            self.im_scale = float(max_size) / float(hi)
+        st = cfg.network.IMAGE_STRIDE
+        h1, w1 = int(np.rint(self.src_h * self.im_scale)), int(np.rint(self.src_w * self.im_scale))
+        self.height, self.width = (-(-h1 // st) * st, -(-w1 // st) * st) if st else (h1, w1)
+        self.estimate, self.device, self.dump_mv = estimate, device, dump_mv
+        self._me, self._me_key, self._me_last, self._dev = None, None, None, {}
+        if dump_mv is not None:
+            os.makedirs(dump_mv, exist_ok=True)
+
+    def planes(self, i):
+        """frame i as the keyword arguments of the hip.*yuv420* functions: views of ONE device tensor holding the frame's bytes"""
+        if i not in self._dev:
+            if self.estimate is None:
+                self._dev.clear()                             # nothing looks back at earlier frames
+            raw = np.array(self._map[i * self.frame_bytes:(i + 1) * self.frame_bytes])         # one read of the mapped pages
+            self._dev[i] = torch.from_numpy(raw).to(self.device)
+        buf, n = self._dev[i], self.src_w * self.src_h
+        y = buf[:n].view(self.src_h, self.src_w)
+        if self.fmt == 'nv12':
+            return dict(y=y, uv=buf[n:].view(self.ch, 2 * self.cw))
+        c = self.ch * self.cw
+        return dict(y=y, u=buf[n:n + c].view(self.ch, self.cw), v=buf[n + c:].view(self.ch, self.cw))
+
+    def frame(self, i):
+        from lsfa_amd import hip
+        cfg = self.cfg
+        return hip.image_resize_transform_yuv420(im_scale=self.im_scale, matrix=self.matrix, pixel_means=cfg.network.PIXEL_MEANS,
+                                                 pixel_scale=cfg.network.PIXEL_SCALE, stride=cfg.network.IMAGE_STRIDE, **self.planes(i))
+
+    def _estimated(self, i, key_i):
+        from lsfa_amd import hip
+        if i <= key_i:
+            raise ValueError('frame %d has no motion vectors against key frame %d' % (i, key_i))
+        if self._me is None:
+            self._me = hip.MotionEstimator(self.src_w, self.src_h, self.device, matrix=self.matrix, **self.estimate)
+        me = self._me
+        if self._me_key != key_i or i < self._me_last:        # a new interval (or a step back): start from the key frame again
+            self._dev = {f: t for f, t in self._dev.items() if key_i <= f <= i}
+            me.key_frame_yuv(**self.planes(key_i))
+            self._me_key, self._me_last = key_i, key_i
+        for f in range(self._me_last + 1, i + 1):             # the P-frame chain: every frame against the one before it
+            me.next_frame_yuv(**self.planes(f))
+        self._me_last = i
+        cfg = self.cfg
+        cur, key = me.bgr_cur, me.bgr_key
+        if self.dump_mv is not None:
+            np.savez(os.path.join(self.dump_mv, '%06d.npz' % i), mv=(-me.acc.motion_vectors()).cpu().numpy(),
+                     res=me.acc.residual(cur, key).cpu().numpy())
+        mv, res = me.network_inputs(cur, key, self.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE)
+        return mv.clone(), res.clone()                        # the estimator reuses its output buffers
+
+    def mv_res(self, i, key_i):
+        if self.estimate is not None:
+            return self._estimated(i, key_i)
+        fh, fw = -(-self.height // 16), -(-self.width // 16)
+        return torch.zeros(1, 2, fh, fw), torch.zeros(1, 3, fh, fw)
+
+
 class _Synthetic(object):
     def __init__(self, n, h, w):
         self.c = SyntheticClip(0, n, h, w)
@@ -134,7 +226,11 @@ def parse_args(argv=None):
     ap.add_argument('--cfg', default=None)
     ap.add_argument('--frames', default=None, help='directory of frames (default: a synthetic clip)')
     ap.add_argument('--mv', default=None, help='directory of per-frame .npz with mv / res arrays')
-    ap.add_argument('--estimate-mv', action='store_true', help='estimate block motion vectors from the frames on the GPU (needs --frames)')
+    ap.add_argument('--yuv', default=None, help='a raw YUV 4:2:0 file (frames back to back, no header) in place of --frames; needs --size')
+    ap.add_argument('--size', default=None, help='--yuv: the frame size as WxH, e.g. 1280x720')
+    ap.add_argument('--yuv-format', default='nv12', choices=('nv12', 'i420'), help='--yuv: semi-planar (interleaved U, V) or planar chroma')
+    ap.add_argument('--yuv-matrix', default='bt601', choices=('bt601', 'bt709', 'jpeg'), help='--yuv: the colour matrix of the stream')
+    ap.add_argument('--estimate-mv', action='store_true', help='estimate block motion vectors from the frames on the GPU (needs --frames or --yuv)')
     ap.add_argument('--search', type=int, default=16, help='--estimate-mv: search range in pixels, 1..32 (a parameter, not a tuned value)')
     ap.add_argument('--mv-lambda', type=int, default=4, help='--estimate-mv: cost per pixel of vector length (a parameter, not a tuned value)')
     ap.add_argument('--dump-mv', default=None, help='--estimate-mv: write the estimated mv / res as the .npz files --mv reads')
@@ -146,8 +242,28 @@ def parse_args(argv=None):
     ap.add_argument('--out', default=None, help='write the detections as JSON here')
     ap.add_argument('--no-graph', action='store_true')
     args = ap.parse_args(argv)
-    if args.estimate_mv and (not args.frames or args.mv):
-        ap.error('--estimate-mv needs --frames and excludes --mv')
+    if args.yuv and args.frames:
+        ap.error('--yuv excludes --frames')
+    if args.yuv and args.mv:
+        ap.error('--mv names the frames of --frames; with --yuv use --estimate-mv')
+    args.yuv_size = None
+    if args.yuv:
+        import re
+        m = re.match(r'^(\d+)x(\d+)$', args.size or '')
+        if not m or int(m.group(1)) <= 0 or int(m.group(2)) <= 0:
+            ap.error('--yuv needs --size WxH (got %r)' % (args.size,))
+        args.yuv_size = (int(m.group(1)), int(m.group(2)))
+        w, h = args.yuv_size
+        frame_bytes = w * h + 2 * (-(-w // 2)) * (-(-h // 2))
+        if not os.path.isfile(args.yuv):
+            ap.error('--yuv: no such file: %s' % args.yuv)
+        size = os.path.getsize(args.yuv)
+        if size == 0 or size % frame_bytes:
+            ap.error('--yuv: %s holds %d bytes, not a whole number of %dx%d frames of %d bytes' % (args.yuv, size, w, h, frame_bytes))
+    elif args.size:
+        ap.error('--size belongs to --yuv')
+    if args.estimate_mv and (not (args.frames or args.yuv) or args.mv):
+        ap.error('--estimate-mv needs --frames or --yuv and excludes --mv')
     if args.dump_mv and not args.estimate_mv:
         ap.error('--dump-mv needs --estimate-mv')
     return args
@@ -163,7 +279,10 @@ def main(argv=None):
     cfg.TEST.KEY_FRAME_INTERVAL = args.interval
     dev = 'cuda:0'
     estimate = dict(search=args.search, lam=args.mv_lambda) if args.estimate_mv else None
-    clip = FrameDirClip(args.frames, args.mv, cfg, estimate, dev, args.dump_mv) if args.frames else _Synthetic(args.num, 600, 1000)
+    if args.yuv:
+        clip = YuvFileClip(args.yuv, args.yuv_size[0], args.yuv_size[1], cfg, args.yuv_format, args.yuv_matrix, estimate, dev, args.dump_mv)
+    else:
+        clip = FrameDirClip(args.frames, args.mv, cfg, estimate, dev, args.dump_mv) if args.frames else _Synthetic(args.num, 600, 1000)
     if args.prefix:
         arg_params, aux_params = load_param(args.prefix, args.epoch, process=True)
     else:

@@ -740,6 +740,121 @@ def image_transform_u8(im, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, out=Non
     return out
 
 
+# ---- YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip) ---------------------------------------------------------------------------------------------
+YUV_MATRICES = {'bt601': 0, 'bt709': 1, 'jpeg': 2}
+_cll = ctypes.c_longlong
+
+
+def _yuv_planes(who, y, uv, u, v, matrix):
+    """The plane arguments of the lsfa_*yuv420* exports from uint8 CUDA tensors: y (H, W) or (N, H, W) and either uv (.., ceil(H/2),
+    2 ceil(W/2)) (NV12) or u, v (.., ceil(H/2), ceil(W/2)) (I420).  Row views of pitched surfaces are taken as they are: pitch and frame
+    stride come from .stride(), only the last dimension must be dense.  Returns (ctypes arguments up to `matrix`, N, H, W, batched)."""
+    def shapes():
+        return ", ".join("%s %s" % (n, (tuple(t.shape), tuple(t.stride())) if isinstance(t, torch.Tensor) else type(t).__name__)
+                         for n, t in (("y", y), ("uv", uv), ("u", u), ("v", v)) if t is not None)
+    if matrix not in YUV_MATRICES:
+        raise LsfaError("%s: matrix %r is not one of %s" % (who, matrix, sorted(YUV_MATRICES)))
+    nv12 = uv is not None
+    if nv12 == (u is not None or v is not None) or (not nv12 and (u is None or v is None)):
+        raise LsfaError("%s: give either uv (NV12) or u and v (I420); got %s" % (who, shapes()))
+    planes = [y, uv] if nv12 else [y, u, v]
+    for t in planes:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() not in (2, 3) or t.dim() != y.dim() or \
+                t.device != y.device or (t.shape[-1] > 1 and t.stride(-1) != 1):
+            raise LsfaError("%s: 2-D or 3-D uint8 CUDA planes of one device and rank with a dense last dimension expected, got %s" % (who, shapes()))
+    batched = y.dim() == 3
+    N = int(y.shape[0]) if batched else 1
+    H, W = int(y.shape[-2]), int(y.shape[-1])
+    ch, cw = -(-H // 2), -(-W // 2)
+    want = (ch, 2 * cw) if nv12 else (ch, cw)
+    for t in planes[1:]:
+        if tuple(t.shape[-2:]) != want or (batched and int(t.shape[0]) != N):
+            raise LsfaError("%s: a %d x %d frame has %s chroma planes of %s%s, got %s" % (who, W, H, "an NV12" if nv12 else "I420", want,
+                                                                                           " per frame, %d frames" % N if batched else "", shapes()))
+    if H < 1 or W < 1 or N < 1:
+        raise LsfaError("%s: empty planes: %s" % (who, shapes()))
+    c = planes[1]
+    if not nv12 and (u.stride() != v.stride()):
+        raise LsfaError("%s: u and v must share one pitch and frame stride, got %s" % (who, shapes()))
+    # a plane of one row (or one frame) has no meaningful stride of its own: the row's (the frame's) size serves
+    y_pitch = int(y.stride(-2)) if H > 1 else max(int(y.stride(-2)), W)
+    c_pitch = int(c.stride(-2)) if ch > 1 else max(int(c.stride(-2)), want[1])
+    y_fs = int(y.stride(0)) if batched and N > 1 else 0
+    c_fs = int(c.stride(0)) if batched and N > 1 else 0
+    if y_pitch < W or c_pitch < want[1]:
+        raise LsfaError("%s: a row pitch is below its row: %s" % (who, shapes()))
+    args = (_ptr(y), _cll(y_pitch), _cll(y_fs), _ptr(c), _ptr(None if nv12 else v), _cll(c_pitch), _cll(c_fs), _ci(N), _ci(H), _ci(W),
+            _ci(YUV_MATRICES[matrix]))
+    return args, N, H, W, batched
+
+
+def _yuv_out(who, name, t, shape, dtype, device):
+    if t.dtype != dtype or tuple(t.shape) != shape or t.device != device or not t.is_contiguous():
+        raise LsfaError("%s: %s must be a contiguous %s %s tensor on %s, got %s %s on %s" % (who, name, shape, dtype, device, tuple(t.shape), t.dtype, t.device))
+    return t
+
+
+@_on_tensor_device
+def yuv420_to_bgr_u8(y, uv=None, u=None, v=None, matrix='bt601', out=None, y_packed=None):
+    """lsfa_yuv420_to_bgr_u8: a decoder's YUV 4:2:0 planes on the device - y (H, W) or (N, H, W) uint8 and either uv (NV12: interleaved U, V,
+    (.., ceil(H/2), 2 ceil(W/2))) or u, v (I420: (.., ceil(H/2), ceil(W/2))), possibly row views of pitched surfaces (`y[:, :W]`) - to packed
+    uint8 BGR (H, W, 3) / (N, H, W, 3), the layout lsfa_mv_residual, luma_u8 and image_transform_u8 take.  matrix: 'bt601' (limited range,
+    the default), 'bt709' (limited range) or 'jpeg' (BT.601 full range); nearest-neighbour chroma, integer arithmetic (include/lsfa_hip.h,
+    "YUV 4:2:0 intake" - this project's own specification, not swscale's or OpenCV's).  y_packed: an optional (.., H, W) uint8 tensor that
+    receives the Y plane with the pitch removed (what mv_estimate wants).  One launch."""
+    who = "yuv420_to_bgr_u8"
+    args, N, H, W, batched = _yuv_planes(who, y, uv, u, v, matrix)
+    lead = (N,) if batched else ()
+    if out is None:
+        out = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=y.device)
+    else:
+        _yuv_out(who, "out", out, lead + (H, W, 3), torch.uint8, y.device)
+    if y_packed is not None:
+        _yuv_out(who, "y_packed", y_packed, lead + (H, W), torch.uint8, y.device)
+    _check(lib().lsfa_yuv420_to_bgr_u8(*(args + (_ptr(out), _ptr(y_packed), _stream()))), "lsfa_yuv420_to_bgr_u8")
+    return out
+
+
+@_on_tensor_device
+def image_transform_yuv420(y, uv=None, u=None, v=None, matrix='bt601', pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, out=None):
+    """lsfa_image_transform_yuv420: the planes of yuv420_to_bgr_u8 -> `data` (N, 3, H, W) float32, channel i = (bgr[2 - i] - pixel_means[2 - i])
+    * pixel_scale in float64, rounded once: bit-identical to image_transform_u8(yuv420_to_bgr_u8(...)) without storing the BGR frame, and
+    without its H*W % 4 condition.  pixel_means in B, G, R order.  One launch."""
+    who = "image_transform_yuv420"
+    args, N, H, W, _ = _yuv_planes(who, y, uv, u, v, matrix)
+    if out is None:
+        out = torch.empty((N, 3, H, W), dtype=torch.float32, device=y.device)
+    else:
+        _yuv_out(who, "out", out, (N, 3, H, W), torch.float32, y.device)
+    means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
+    _check(lib().lsfa_image_transform_yuv420(*(args + (means, _cd(float(pixel_scale)), _ptr(out), _stream()))), "lsfa_image_transform_yuv420")
+    return out
+
+
+@_on_tensor_device
+def image_resize_transform_yuv420(y, uv=None, u=None, v=None, im_scale=1.0, matrix='bt601', pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, stride=0,
+                                  out=None):
+    """lsfa_image_resize_transform_yuv420: the planes of yuv420_to_bgr_u8 -> `data` (N, 3, h, w) float32: image_resize_transform of the
+    converted uint8 frame (converted to float, interpolated in float, padded to `stride`), bit-identical to it, reading the taps from the
+    planes.  One launch.  The fixed-point uint8 form (u8_fixed_point) is not offered for YUV."""
+    who = "image_resize_transform_yuv420"
+    args, N, H, W, _ = _yuv_planes(who, y, uv, u, v, matrix)
+    if not float(im_scale) > 0.0 or int(stride) < 0:
+        raise LsfaError("%s: im_scale %r must be positive and stride %r non-negative" % (who, im_scale, stride))
+    import numpy as _np
+    h1, w1 = int(_np.rint(H * float(im_scale))), int(_np.rint(W * float(im_scale)))       # cvRound
+    stride = int(stride)
+    ph, pw = (-(-h1 // stride) * stride, -(-w1 // stride) * stride) if stride else (h1, w1)
+    if out is None:
+        out = torch.empty((N, 3, ph, pw), dtype=torch.float32, device=y.device)
+    else:
+        _yuv_out(who, "out", out, (N, 3, ph, pw), torch.float32, y.device)
+    means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
+    _check(lib().lsfa_image_resize_transform_yuv420(*(args + (_cd(float(im_scale)), _ci(h1), _ci(w1), _ci(stride), means, _cd(float(pixel_scale)),
+                                                               _ptr(out), _ci(ph), _ci(pw), _stream()))), "lsfa_image_resize_transform_yuv420")
+    return out
+
+
 class ImageTable(object):
     """N images (C, H, W) float32, each ANYWHERE on the device, in place of one (N, C, H, W) tensor: what lsfa_avgpool_nchw_tbl and
     lsfa_stem_conv7x7s2_tbl read.  The reference's loader hands over one array per frame (dff_rfcn/core/loader.py:131-141); a batched pass
@@ -1416,9 +1531,23 @@ class MotionEstimator(object):
 
     Every buffer is allocated up front (the outputs of network_inputs at its first call for a scale), nothing is read back and nothing
     synchronises, so the three calls can be captured in a graph on one stream and replayed on new frame contents written into the same
-    tensors.  The tensors network_inputs returns are reused by the next call."""
+    tensors.  The tensors network_inputs returns are reused by the next call.
 
-    def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD):
+    Frames that arrive as a decoder's YUV 4:2:0 planes (see yuv420_to_bgr_u8) go through key_frame_yuv / next_frame_yuv, which convert into
+    BGR buffers the estimator owns (self.bgr_key; self.bgr_cur, a ping-pong pair - allocated at the first such call, nothing after it) and
+    return that buffer: `me.network_inputs(me.bgr_cur, me.bgr_key, ...)` works unchanged.  luma_from='bgr' (the default) searches
+    lsfa_luma_u8 of the converted frame: the rows are those of feeding the converted frames to key_frame / next_frame.  luma_from='y'
+    searches the decoder's own Y plane (the conversion's y_packed output, no luma launch): DIFFERENT numbers - Y is limited-range (16..235)
+    and weighs the channels by the stream's matrix, lsfa_luma_u8 is full-range with its own weights - so SADs, the lambda trade-off and
+    therefore some vectors differ.  `matrix` is the conversion's."""
+
+    def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr', matrix='bt601'):
+        if luma_from not in ('bgr', 'y'):
+            raise LsfaError("MotionEstimator: luma_from %r is not 'bgr' or 'y'" % (luma_from,))
+        if matrix not in YUV_MATRICES:
+            raise LsfaError("MotionEstimator: matrix %r is not one of %s" % (matrix, sorted(YUV_MATRICES)))
+        self.luma_from, self.matrix = luma_from, matrix
+        self.bgr_key, self._bgr_pp, self._bgr_i = None, None, 0
         self.width, self.height, self.device = int(width), int(height), torch.device(device)
         self.search, self.lam, self.max_sad = int(search), int(lam), int(max_sad)
         if not 1 <= self.search <= 32 or self.lam < 0 or self.max_sad < 0:
@@ -1453,6 +1582,45 @@ class MotionEstimator(object):
         self.acc.add_frame(self.rows, max_block_area=256)      # the explicit area: no device-to-host read
         self._ref = cur
         return self.rows
+
+    @property
+    def bgr_cur(self):
+        """the BGR frame the last next_frame_yuv converted (None before the first)"""
+        return None if self._bgr_pp is None else self._bgr_pp[self._bgr_i]
+
+    def _yuv_buffers(self):
+        if self.bgr_key is None:          # the first *_yuv call: the only allocation
+            self.bgr_key = torch.empty((self.height, self.width, 3), dtype=torch.uint8, device=self.device)
+            self._bgr_pp = [torch.empty_like(self.bgr_key) for _ in range(2)]
+
+    def _yuv_to(self, bgr, luma, y, uv, u, v, who):
+        if not isinstance(y, torch.Tensor) or tuple(y.shape) != (self.height, self.width) or y.device != self.device:
+            raise LsfaError("MotionEstimator.%s: a (%d, %d) uint8 Y plane on %s expected, got %s on %s" %
+                            (who, self.height, self.width, self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
+        if self.luma_from == 'y':
+            yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=bgr, y_packed=luma)
+        else:
+            yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=bgr)
+            luma_u8(bgr, out=luma)
+        return bgr
+
+    def key_frame_yuv(self, y, uv=None, u=None, v=None):
+        """key_frame on a decoder's planes: converts into self.bgr_key and returns it"""
+        self._yuv_buffers()
+        bgr = self._yuv_to(self.bgr_key, self._luma[self._ref], y, uv, u, v, 'key_frame_yuv')
+        self.acc.reset()
+        return bgr
+
+    def next_frame_yuv(self, y, uv=None, u=None, v=None):
+        """next_frame on a decoder's planes: converts into the other buffer of the ping-pong pair, which becomes self.bgr_cur, and returns it
+        (the rows are in self.rows, the winners' SAD in self.sad)"""
+        self._yuv_buffers()
+        cur, nxt = 1 - self._ref, 1 - self._bgr_i
+        bgr = self._yuv_to(self._bgr_pp[nxt], self._luma[cur], y, uv, u, v, 'next_frame_yuv')
+        mv_estimate(self._luma[cur], self._luma[self._ref], self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+        self.acc.add_frame(self.rows, max_block_area=256)
+        self._ref, self._bgr_i = cur, nxt
+        return bgr
 
     def network_inputs(self, bgr_cur, bgr_key, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16):
         """`motion_vector` (1, 2, h, w) and `res_diff` (1, 3, h, w) of the current frame against the key frame, as

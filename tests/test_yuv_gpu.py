@@ -1,0 +1,440 @@
+"""lsfa_yuv420_to_bgr_u8, lsfa_image_transform_yuv420 and lsfa_image_resize_transform_yuv420 (lsfa_amd/csrc/yuv.hip) on the GPU against
+tests/ref_yuv.py and against the packed-BGR entry points they fuse, bit for bit (`==` everywhere); hip.MotionEstimator's *_yuv methods against
+the BGR chain and against ref_me on the Y planes; graph capture; the error paths; the demo's --yuv input.  tests/test_yuv_cpu.py pins the
+reference."""
+import ctypes
+import json
+
+import numpy as np
+import pytest
+import torch
+
+import ref_me
+import ref_yuv
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+FORMATS = ("nv12", "i420")
+MATRICES = ("bt601", "bt709", "jpeg")
+PS = 0.0125                     # a non-trivial pixel_scale
+
+
+def means():
+    from lsfa_amd.config.config import lsfa_test_config
+    return tuple(float(m) for m in lsfa_test_config().network.PIXEL_MEANS)
+
+
+def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def dev_plane(a, pitch=None, gap=0, offset=0):
+    """numpy (rows, cols) or (N, rows, cols) uint8 -> a device VIEW of that shape with rows `pitch` bytes apart, frames `gap` bytes further
+    apart than a frame and the base `offset` bytes into its allocation; everything around the data holds 0xA5"""
+    batched = a.ndim == 3
+    n = a.shape[0] if batched else 1
+    rows, cols = a.shape[-2:]
+    pitch = cols if pitch is None else pitch
+    fs = rows * pitch + gap
+    buf = torch.full((offset + n * fs + 8,), 0xA5, dtype=torch.uint8, device=DEV)
+    view = torch.as_strided(buf, (n, rows, cols), (fs, pitch, 1), offset)
+    view.copy_(t(a.reshape(n, rows, cols)))
+    return view if batched else view[0]
+
+
+def dev_planes(y, u, v, fmt, pitch=None, gap=0, y_offset=0):
+    """keyword arguments of the hip.*yuv420* functions for the numpy planes y, u, v"""
+    if fmt == "nv12":
+        return dict(y=dev_plane(y, pitch, gap, y_offset), uv=dev_plane(ref_yuv.interleave(u, v), pitch, gap))
+    return dict(y=dev_plane(y, pitch, gap, y_offset), u=dev_plane(u, pitch, gap), v=dev_plane(v, pitch, gap))
+
+
+def random_planes(H, W, seed, n=None):
+    """uniform random bytes: both clip ends occur"""
+    rs = np.random.RandomState(seed)
+    ch, cw = ref_yuv.chroma_shape(H, W)
+    lead = () if n is None else (n,)
+    return (rs.randint(0, 256, lead + (H, W)).astype(np.uint8), rs.randint(0, 256, lead + (ch, cw)).astype(np.uint8),
+            rs.randint(0, 256, lead + (ch, cw)).astype(np.uint8))
+
+
+# (H, W, pitch, frames, extra bytes between frames, Y base offset): quad path, byte path (W % 4, odd H, offset base), pitched, batched
+GEOMETRIES = [(2, 2, None, None, 0, 0), (4, 6, None, None, 0, 0), (5, 7, None, None, 0, 0), (16, 16, None, None, 0, 0), (34, 50, 64, None, 0, 0),
+              (16, 24, 32, 3, 100, 0), (16, 16, None, None, 0, 1), (6, 8, 12, 3, 36, 0)]
+_WANT = {}
+
+
+def want_bgr(geo, matrix):
+    """ref_yuv's frame of a geometry's planes, computed once per (geometry, matrix) and shared"""
+    key = (geo, matrix)
+    if key not in _WANT:
+        H, W, _, n, _, _ = geo
+        y, u, v = random_planes(H, W, seed=H * 100 + W, n=n)
+        _WANT[key] = (y, u, v, ref_yuv.to_bgr(y, u=u, v=v, matrix=matrix))
+    return _WANT[key]
+
+
+@pytest.mark.parametrize("matrix", MATRICES)
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_yuv420_to_bgr_u8_equals_the_reference(hip, fmt, matrix):
+    """lsfa_yuv420_to_bgr_u8 == ref_yuv at every geometry; y_packed == the Y plane; the 0xA5 bytes of the pitch never show"""
+    for geo in GEOMETRIES:
+        H, W, pitch, n, gap, off = geo
+        y, u, v, want = want_bgr(geo, matrix)
+        planes = dev_planes(y, u, v, fmt, pitch, gap, off)
+        got = hip.yuv420_to_bgr_u8(matrix=matrix, **planes)
+        assert got.dtype == torch.uint8 and tuple(got.shape) == want.shape, geo
+        np.testing.assert_array_equal(got.cpu().numpy(), want, err_msg=str(geo))
+        out, yp = torch.zeros_like(got), torch.zeros(y.shape, dtype=torch.uint8, device=DEV)
+        assert hip.yuv420_to_bgr_u8(matrix=matrix, out=out, y_packed=yp, **planes) is out
+        assert torch.equal(out, got), geo
+        np.testing.assert_array_equal(yp.cpu().numpy(), y, err_msg=str(geo))
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_yuv420_to_bgr_u8_full_size(hip, fmt):
+    """... and at 600 x 1000, once per format"""
+    geo = (600, 1000, None, None, 0, 0)
+    y, u, v, want = want_bgr(geo, "bt601")
+    yp = torch.zeros((600, 1000), dtype=torch.uint8, device=DEV)
+    got = hip.yuv420_to_bgr_u8(y_packed=yp, **dev_planes(y, u, v, fmt))
+    np.testing.assert_array_equal(got.cpu().numpy(), want)
+    np.testing.assert_array_equal(yp.cpu().numpy(), y)
+    assert want.min() == 0 and want.max() == 255
+
+
+@pytest.mark.parametrize("matrix", MATRICES)
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_image_transform_yuv420_is_the_two_step_path(hip, fmt, matrix):
+    """lsfa_image_transform_yuv420 == image_transform_u8(yuv420_to_bgr_u8(...)) wherever the u8 form runs (H*W % 4 == 0), and == ref_yuv + the
+    float64 formula where it does not (5 x 7) and at the batched, pitched geometries"""
+    mn = means()
+    for geo in GEOMETRIES + [(600, 1000, None, None, 0, 0)]:
+        H, W, pitch, n, gap, off = geo
+        if H == 600 and (matrix != "bt601"):
+            continue
+        y, u, v, want = want_bgr(geo, matrix)
+        planes = dev_planes(y, u, v, fmt, pitch, gap, off)
+        got = hip.image_transform_yuv420(matrix=matrix, pixel_means=mn, pixel_scale=PS, **planes)
+        assert got.dtype == torch.float32 and tuple(got.shape) == (n or 1, 3, H, W)
+        if (H * W) % 4 == 0:
+            bgr = hip.yuv420_to_bgr_u8(matrix=matrix, **planes)
+            assert torch.equal(got, hip.image_transform_u8(bgr if n else bgr.unsqueeze(0), mn, PS)), geo
+        if H < 600:
+            np.testing.assert_array_equal(got.cpu().numpy(), ref_yuv.transform(want if n else want[None], mn, PS), err_msg=str(geo))
+        out = torch.zeros_like(got)
+        assert hip.image_transform_yuv420(matrix=matrix, pixel_means=mn, pixel_scale=PS, out=out, **planes) is out and torch.equal(out, got)
+
+
+@pytest.mark.parametrize("case", [(36, 52, 0.78125, 16, 2, 64), (36, 52, 0.78125, 0, 2, 64), (37, 53, 1.7, 16, None, None), (600, 1000, 1.0, 16, None, None),
+                                  (720, 1280, 0.78125, 16, None, None)])
+def test_image_resize_transform_yuv420_is_the_two_step_path(hip, case):
+    """lsfa_image_resize_transform_yuv420 == image_resize_transform (uint8 frames, float interpolation) of the converted frame: both
+    subtraction rules (stride 16 / 0), two pitched frames per launch at the small size, odd sizes, both formats; the large sizes once"""
+    H, W, scale, stride, n, pitch = case
+    mn = means()
+    y, u, v = random_planes(H, W, seed=H + W, n=n)
+    for fmt, matrix in (("nv12", "bt601"), ("i420", "bt709")) if H < 600 else (("nv12", "bt601"),):
+        planes = dev_planes(y, u, v, fmt, pitch, 40 if n else 0)
+        bgr = hip.yuv420_to_bgr_u8(matrix=matrix, **planes)
+        want = hip.image_resize_transform(bgr, scale, mn, PS, stride=stride)
+        got = hip.image_resize_transform_yuv420(im_scale=scale, matrix=matrix, pixel_means=mn, pixel_scale=PS, stride=stride, **planes)
+        assert got.shape == want.shape and torch.equal(got, want), (case, fmt)
+    assert float(got.abs().max()) > 0
+
+
+def yuv_clip(n, width, height, m, seed):
+    """n frames of a translating texture as (y, u, v) planes, and ref_yuv's BGR frames of them"""
+    planes = [ref_yuv.forward(f) for f in ref_me.translated_clip(n, width, height, m, seed=seed, sigma=2.0)]
+    return planes, [ref_yuv.to_bgr(y, u=u, v=v) for y, u, v in planes]
+
+
+@pytest.mark.parametrize("search", [4, 16])
+@pytest.mark.parametrize("size", [(48, 64), (40, 56)])
+def test_motion_estimator_yuv_chain(hip, size, search):
+    """luma_from='bgr': five frames through key_frame_yuv / next_frame_yuv give the rows, SAD, accumulated field and network_inputs of
+    key_frame / next_frame fed ref_yuv's frames.  luma_from='y': the rows and SAD are ref_me's on the Y planes."""
+    height, width = size
+    planes, frames = yuv_clip(5, width, height, (2, -1), seed=height)
+    mn = means()
+    for fmt in FORMATS:
+        a = hip.MotionEstimator(width, height, DEV, search=search, lam=4)
+        b = hip.MotionEstimator(width, height, DEV, search=search, lam=4)
+        c = hip.MotionEstimator(width, height, DEV, search=search, lam=4, luma_from='y')
+        assert a.bgr_key is None and a.bgr_cur is None
+        dp = [dev_planes(y, u, v, fmt, pitch=64) for y, u, v in planes]
+        df = [t(f) for f in frames]
+        key = a.key_frame_yuv(**dp[0])
+        assert key is a.bgr_key and torch.equal(key, df[0])
+        b.key_frame(df[0])
+        c.key_frame_yuv(**dp[0])
+        for f in range(1, 5):
+            cur = a.next_frame_yuv(**dp[f])
+            assert cur is a.bgr_cur and cur is not a.bgr_key and torch.equal(cur, df[f]), f
+            rows = b.next_frame(df[f])
+            assert torch.equal(a.rows, rows) and torch.equal(a.sad, b.sad), f
+            assert torch.equal(a.acc.accu, b.acc.accu), f
+            a_mv, a_res = a.network_inputs(a.bgr_cur, a.bgr_key, 1.25, mn, PS)
+            b_mv, b_res = b.network_inputs(df[f], df[0], 1.25, mn, PS)
+            assert torch.equal(a_mv, b_mv) and torch.equal(a_res, b_res), f
+            c.next_frame_yuv(**dp[f])
+            want_rows, want_sad = ref_me.estimate(planes[f][0], planes[f - 1][0], search, 4)
+            np.testing.assert_array_equal(c.rows.cpu().numpy(), want_rows, err_msg="frame %d" % f)
+            np.testing.assert_array_equal(c.sad.cpu().numpy(), want_sad, err_msg="frame %d" % f)
+            assert torch.equal(c.bgr_cur, df[f])
+        assert float(a_mv.abs().max()) > 0
+
+
+def test_motion_estimator_yuv_graph_capture(hip):
+    """key_frame_yuv + two next_frame_yuv + network_inputs captured with torch.cuda.graph on one stream, replayed on NEW plane contents
+    written into the same tensors == the eager run on those contents"""
+    width, height = 64, 48
+    mn = means()
+    clips = [yuv_clip(3, width, height, (2, -1), seed=1)[0], yuv_clip(3, width, height, (-3, 2), seed=2)[0]]
+    bufs = [dev_planes(y, u, v, "nv12", pitch=64) for y, u, v in clips[0]]
+    me = hip.MotionEstimator(width, height, DEV, search=16, lam=4)
+
+    def step(m, planes):
+        m.key_frame_yuv(**planes[0])
+        m.next_frame_yuv(**planes[1])
+        m.next_frame_yuv(**planes[2])
+        return m.network_inputs(m.bgr_cur, m.bgr_key, 1.0, mn, 1.0)
+
+    step(me, bufs)                           # warm-up: the BGR buffers and network_inputs' outputs are allocated at the first call
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out_mv, out_res = step(me, bufs)
+    for k, clip in enumerate(clips[::-1] + clips):
+        for buf, (y, u, v) in zip(bufs, clip):
+            buf["y"].copy_(t(y))
+            buf["uv"].copy_(t(ref_yuv.interleave(u, v)))
+        g.replay()
+        torch.cuda.synchronize()
+        eager = hip.MotionEstimator(width, height, DEV, search=16, lam=4)
+        e_mv, e_res = step(eager, [dev_planes(y, u, v, "nv12") for y, u, v in clip])
+        assert torch.equal(me.rows, eager.rows) and torch.equal(me.sad, eager.sad), k
+        assert torch.equal(out_mv, e_mv) and torch.equal(out_res, e_res), k
+    assert float(out_mv.abs().max()) > 0
+
+
+def c_args(planes, n_, h_, w_, **over):
+    """the eleven plane arguments of the C entry points from a dev_planes dict, with overrides by name"""
+    y = planes["y"]
+    c = planes["uv"] if "uv" in planes else planes["u"]
+    a = dict(y=y.data_ptr(), y_pitch=y.stride(-2), y_fs=0, c=c.data_ptr(), v=planes["v"].data_ptr() if "v" in planes else None, c_pitch=c.stride(-2),
+             c_fs=0, N=n_, H=h_, W=w_, matrix=0)
+    a.update(over)
+    vp, ll, ci = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
+    return [vp(a["y"]), ll(a["y_pitch"]), ll(a["y_fs"]), vp(a["c"]), vp(a["v"]), ll(a["c_pitch"]), ll(a["c_fs"]), ci(a["N"]), ci(a["H"]), ci(a["W"]),
+            ci(a["matrix"])]
+
+
+def test_error_paths(hip):
+    """every bad call comes back as an error (a non-zero code with a message from C, LsfaError from the wrappers), launches nothing and
+    leaves a passed output as it was"""
+    H, W = 6, 10
+    y, u, v = random_planes(H, W, seed=5)
+    nv, pl = dev_planes(y, u, v, "nv12", pitch=16), dev_planes(y, u, v, "i420", pitch=16)
+    mn = means()
+    bgr = torch.full((H, W, 3), 7, dtype=torch.uint8, device=DEV)
+    data = torch.full((1, 3, H, W), 7.0, device=DEV)
+    rdata = torch.full((1, 3, 16, 16), 7.0, device=DEV)       # scale 1.25: 8 x 12 (cvRound ties to even), padded to 16
+    L = hip.lib()
+    vp, cd, ci = ctypes.c_void_p, ctypes.c_double, ctypes.c_int
+    mean_arr = (ctypes.c_double * 3)(*mn)
+    bad = [dict(y=None), dict(c=None), dict(W=0), dict(H=0), dict(H=-3), dict(N=0), dict(y_pitch=W - 1), dict(c_pitch=W - 1), dict(matrix=3), dict(matrix=-1)]
+    for over in bad:
+        assert L.lsfa_yuv420_to_bgr_u8(*(c_args(nv, 1, H, W, **over) + [vp(bgr.data_ptr()), None, None])) != 0, over
+        assert b"lsfa_yuv420_to_bgr_u8" in L.lsfa_last_error()
+        assert L.lsfa_image_transform_yuv420(*(c_args(nv, 1, H, W, **over) + [mean_arr, cd(PS), vp(data.data_ptr()), None])) != 0, over
+        assert b"lsfa_image_transform_yuv420" in L.lsfa_last_error()
+        assert L.lsfa_image_resize_transform_yuv420(*(c_args(nv, 1, H, W, **over) + [cd(1.25), ci(8), ci(12), ci(16), mean_arr, cd(PS), vp(rdata.data_ptr()),
+                                                                                   ci(16), ci(16), None])) != 0, over
+        assert b"lsfa_image_resize_transform_yuv420" in L.lsfa_last_error()
+    # I420's chroma pitch bound is ceil(W / 2): 4 is too narrow for W = 10, and 5 - too narrow for NV12 - is enough
+    assert L.lsfa_yuv420_to_bgr_u8(*(c_args(pl, 1, H, W, c_pitch=4) + [vp(bgr.data_ptr()), None, None])) != 0
+    assert b"I420" in L.lsfa_last_error()
+    assert L.lsfa_yuv420_to_bgr_u8(*(c_args(nv, 1, H, W, c_pitch=9) + [vp(bgr.data_ptr()), None, None])) != 0
+    assert b"NV12" in L.lsfa_last_error()
+    # NULL outputs and means
+    assert L.lsfa_yuv420_to_bgr_u8(*(c_args(nv, 1, H, W) + [None, None, None])) != 0
+    assert L.lsfa_image_transform_yuv420(*(c_args(nv, 1, H, W) + [None, cd(PS), vp(data.data_ptr()), None])) != 0
+    assert L.lsfa_image_transform_yuv420(*(c_args(nv, 1, H, W) + [mean_arr, cd(PS), None, None])) != 0
+    # an output shape that does not follow from h1 / w1 / stride
+    assert L.lsfa_image_resize_transform_yuv420(*(c_args(nv, 1, H, W) + [cd(1.25), ci(8), ci(12), ci(16), mean_arr, cd(PS), vp(rdata.data_ptr()), ci(16), ci(32),
+                                                                       None])) != 0
+    assert b"padded to 16 gives 16 x 16" in L.lsfa_last_error()
+    assert L.lsfa_image_resize_transform_yuv420(*(c_args(nv, 1, H, W) + [cd(0.0), ci(8), ci(12), ci(16), mean_arr, cd(PS), vp(rdata.data_ptr()), ci(16), ci(16),
+                                                                       None])) != 0
+    # the wrappers
+    for fn in (hip.yuv420_to_bgr_u8, hip.image_transform_yuv420, hip.image_resize_transform_yuv420):
+        for kw in (dict(y=nv["y"]), dict(y=nv["y"], uv=nv["uv"], u=pl["u"], v=pl["v"]), dict(y=nv["y"], u=pl["u"]), dict(matrix="bt2020", **nv),
+                   dict(y=nv["y"], uv=pl["u"]), dict(y=nv["y"], u=pl["u"], v=pl["v"][:, :4]), dict(y=nv["y"].cpu(), uv=nv["uv"].cpu()),
+                   dict(y=nv["y"].float(), uv=nv["uv"]), dict(y=nv["y"], uv=nv["uv"].unsqueeze(0)), dict(y=nv["y"][:, ::2], uv=nv["uv"][:, :10]),
+                   dict(y=nv["y"], u=pl["u"], v=dev_plane(v, pitch=32))):
+            with pytest.raises(hip.LsfaError):
+                fn(**kw)
+    with pytest.raises(hip.LsfaError, match=r"\(6, 10, 3\)"):
+        hip.yuv420_to_bgr_u8(out=bgr[:4], **nv)
+    with pytest.raises(hip.LsfaError):
+        hip.yuv420_to_bgr_u8(out=bgr, y_packed=torch.zeros((H, W + 2), dtype=torch.uint8, device=DEV)[:, :W], **nv)
+    with pytest.raises(hip.LsfaError):
+        hip.image_transform_yuv420(out=data[:, :, :4], **nv)
+    with pytest.raises(hip.LsfaError):
+        hip.image_resize_transform_yuv420(im_scale=1.25, stride=16, out=data, **nv)
+    with pytest.raises(hip.LsfaError):
+        hip.image_resize_transform_yuv420(im_scale=0.0, **nv)
+    with pytest.raises(hip.LsfaError):
+        hip.MotionEstimator(W, H, DEV, luma_from='u')
+    me = hip.MotionEstimator(W, H, DEV)
+    with pytest.raises(hip.LsfaError):
+        me.key_frame_yuv(y=nv["y"][:4], uv=nv["uv"][:2])
+    with pytest.raises(hip.LsfaError):
+        me.next_frame_yuv(y=nv["y"])
+    torch.cuda.synchronize()
+    assert bool((bgr == 7).all()) and bool((data == 7.0).all()) and bool((rdata == 7.0).all())
+    # ... and the same buffers are written by the good calls
+    hip.yuv420_to_bgr_u8(out=bgr, **nv)
+    hip.image_resize_transform_yuv420(im_scale=1.25, stride=16, out=rdata, **nv)
+    np.testing.assert_array_equal(bgr.cpu().numpy(), ref_yuv.to_bgr(y, u=u, v=v))
+    assert torch.equal(rdata, hip.image_resize_transform_yuv420(im_scale=1.25, stride=16, **nv))
+
+
+def test_prof_scope_counts_one_launch_per_call(hip):
+    y, u, v = random_planes(16, 16, seed=8)
+    nv, odd = dev_planes(y, u, v, "nv12"), dev_planes(*random_planes(5, 7, seed=8), fmt="i420")
+    hip.prof_enable(True, ops=["stem"])
+    try:
+        hip.prof_read()
+        for planes in (nv, odd):              # the quad and the byte-wise kernel
+            hip.yuv420_to_bgr_u8(**planes)
+            hip.image_transform_yuv420(**planes)
+            hip.image_resize_transform_yuv420(im_scale=1.5, stride=16, **planes)
+        ms, n = hip.prof_read()["stem"]
+    finally:
+        hip.prof_enable(False)
+    assert n == 6 and ms > 0.0
+
+
+def write_yuv_clip(tmp_path, n, width, height, m, seed):
+    from PIL import Image
+    planes, frames = yuv_clip(n, width, height, m, seed)
+    for fmt in FORMATS:
+        with open(str(tmp_path / ("clip." + fmt)), "wb") as f:
+            for y, u, v in planes:
+                f.write(ref_yuv.raw_frame_bytes(y, u, v, fmt))
+    (tmp_path / "frames").mkdir()
+    for i, fr in enumerate(frames):
+        Image.fromarray(np.ascontiguousarray(fr[:, :, ::-1])).save(str(tmp_path / "frames" / ("%06d.png" % i)))      # PNG holds RGB; the frames are BGR
+    return planes, frames
+
+
+def test_yuv_file_clip_equals_the_direct_chain(hip, tmp_path):
+    """YuvFileClip.frame / mv_res == image_resize_transform and the MotionEstimator chain on ref_yuv's frames of the same file, for both
+    formats; without `estimate` zero motion and zero residual; a file that is no whole number of frames is refused"""
+    from lsfa_amd import demo
+    from lsfa_amd.config.config import lsfa_test_config
+    cfg = lsfa_test_config()
+    planes, frames = write_yuv_clip(tmp_path, 6, 160, 96, (3, -2), seed=4)
+    df = [t(f) for f in frames]
+    for fmt in FORMATS:
+        clip = demo.YuvFileClip(str(tmp_path / ("clip." + fmt)), 160, 96, cfg, fmt, "bt601", dict(search=16, lam=4), DEV)
+        assert clip.num_frames == 6 and clip.frame_bytes == 160 * 96 * 3 // 2
+        ref_clip = demo.FrameDirClip(str(tmp_path / "frames"), None, cfg)
+        assert (clip.height, clip.width, clip.im_scale) == (ref_clip.height, ref_clip.width, ref_clip.im_scale)
+        me = hip.MotionEstimator(160, 96, DEV, search=16, lam=4)
+        me.key_frame(df[0])
+        for i in range(6):
+            want = hip.image_resize_transform(df[i], clip.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE, stride=cfg.network.IMAGE_STRIDE)
+            got = clip.frame(i)
+            assert torch.equal(got, want), i
+            if i:
+                me.next_frame(df[i])
+                want_mv, want_res = me.network_inputs(df[i], df[0], clip.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE)
+                got_mv, got_res = clip.mv_res(i, 0)
+                assert torch.equal(got_mv, want_mv) and torch.equal(got_res, want_res), i
+        assert float(got_mv.abs().max()) > 0
+        assert sorted(clip._dev) == list(range(6))                      # one upload per frame of the interval, kept
+        b_mv, _ = clip.mv_res(2, 0)                                       # a step back starts over from the key frame
+        assert sorted(clip._dev) == [0, 1, 2]
+        plain = demo.YuvFileClip(str(tmp_path / ("clip." + fmt)), 160, 96, cfg, fmt)
+        z_mv, z_res = plain.mv_res(1, 0)
+        assert tuple(z_mv.shape) == tuple(got_mv.shape) and float(z_mv.abs().max()) == 0 and float(z_res.abs().max()) == 0
+    with pytest.raises(ValueError):
+        demo.YuvFileClip(str(tmp_path / "clip.nv12"), 160, 98, cfg)
+    with pytest.raises(SystemExit):
+        demo.parse_args(["--yuv", str(tmp_path / "clip.nv12"), "--size", "160x98"])
+    with pytest.raises(SystemExit):
+        demo.parse_args(["--yuv", str(tmp_path / "clip.nv12"), "--size", "160x96", "--frames", str(tmp_path / "frames")])
+
+
+class DirectClip(object):
+    """demo's clip interface served by direct calls on BGR frames already converted (by ref_yuv): no YUV code behind it"""
+
+    def __init__(self, hip, frames, cfg, like, estimate):
+        self.hip, self.df, self.cfg, self.estimate = hip, [t(f) for f in frames], cfg, estimate
+        self.num_frames, self.names = len(frames), list(like.names)
+        self.height, self.width, self.im_scale = like.height, like.width, like.im_scale
+
+    def frame(self, i):
+        cfg = self.cfg
+        return self.hip.image_resize_transform(self.df[i], self.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE, stride=cfg.network.IMAGE_STRIDE)
+
+    def mv_res(self, i, key_i):
+        cfg = self.cfg
+        me = self.hip.MotionEstimator(self.df[0].shape[1], self.df[0].shape[0], DEV, **self.estimate)
+        me.key_frame(self.df[key_i])
+        for f in range(key_i + 1, i + 1):
+            me.next_frame(self.df[f])
+        mv, res = me.network_inputs(self.df[i], self.df[key_i], self.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE)
+        return mv.clone(), res.clone()
+
+
+def test_demo_yuv_estimate_dump_and_read_back(hip, tmp_path, monkeypatch):
+    """lsfa_amd.demo --yuv (NV12 and I420) --estimate-mv --dump-mv: the detections of both formats are identical to those of direct calls
+    (image_resize_transform, MotionEstimator.key_frame / next_frame) on ref_yuv's conversion of the same planes, run through the same
+    demo loop; the dump, read back through the existing --mv reader (FrameDirClip on PNG frames saved from the converted BGR), reproduces
+    the estimated `motion_vector` / `res_diff` tensors bit for bit.  The detections of a whole `--frames --mv` run are NOT compared: that
+    path resizes the frame on the host, which agrees with the device's resize to rounding only (tests/test_image_cpu.py), not bit for bit."""
+    from lsfa_amd import demo
+    from lsfa_amd.config.config import lsfa_test_config
+    _, frames = write_yuv_clip(tmp_path, 12, 160, 96, (3, -2), seed=6)
+    outs = {}
+    common = ["--size", "160x96", "--estimate-mv", "--interval", "4", "--score", "0.05"]
+    for fmt in FORMATS:
+        out = tmp_path / (fmt + ".json")
+        demo.main(["--yuv", str(tmp_path / ("clip." + fmt)), "--yuv-format", fmt, "--dump-mv", str(tmp_path / ("mv_" + fmt)), "--out", str(out)] + common)
+        outs[fmt] = json.loads(out.read_text())
+    non_key = [i for i in range(12) if i % 4]
+    for fmt in FORMATS:
+        assert sorted(p.name for p in (tmp_path / ("mv_" + fmt)).iterdir()) == ["%06d.npz" % i for i in non_key]
+    for i in non_key:
+        a, b = np.load(str(tmp_path / "mv_nv12" / ("%06d.npz" % i))), np.load(str(tmp_path / "mv_i420" / ("%06d.npz" % i)))
+        assert (a["mv"] == b["mv"]).all() and (a["res"] == b["res"]).all()
+    assert np.abs(a["mv"]).max() > 0
+    # the same loop over direct calls on the converted frames
+    cfg = lsfa_test_config()
+    like = demo.YuvFileClip(str(tmp_path / "clip.nv12"), 160, 96, cfg)
+    direct = {}
+
+    def direct_clip(path, width, height, cfg_, fmt, matrix, estimate, dev, dump_mv):
+        direct["clip"] = DirectClip(hip, frames, cfg_, like, estimate)
+        return direct["clip"]
+
+    monkeypatch.setattr(demo, "YuvFileClip", direct_clip)
+    out = tmp_path / "direct.json"
+    demo.main(["--yuv", str(tmp_path / "clip.nv12"), "--out", str(out)] + common)
+    outs["direct"] = json.loads(out.read_text())
+    assert [r["key"] for r in outs["nv12"]] == [i % 4 == 0 for i in range(12)]
+    dets = {k: [(r["key"], r["dets"]) for r in v] for k, v in outs.items()}          # (the frame names carry the file's name)
+    assert dets["nv12"] == dets["i420"] == dets["direct"]
+    assert sum(len(r["dets"]) for r in outs["nv12"]) > 0
+    # the dump through the --mv reader
+    reader = demo.FrameDirClip(str(tmp_path / "frames"), str(tmp_path / "mv_nv12"), cfg)
+    assert reader.im_scale == like.im_scale
+    for i in (1, 3, 6, 11):
+        r_mv, r_res = reader.mv_res(i, i - i % 4)
+        d_mv, d_res = direct["clip"].mv_res(i, i - i % 4)
+        assert torch.equal(r_mv, d_mv.cpu()) and torch.equal(r_res, d_res.cpu()), i

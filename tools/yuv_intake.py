@@ -1,0 +1,158 @@
+#!/usr/bin/env python
+"""Frame intake at 1000 x 600, packed BGR against NV12, N = 1, 9, 12 frames per call, in ONE process on one device (device events,
+`--iters` calls per figure after a warm-up, `--rounds` rounds with the two paths alternating; every figure is printed as min / median / max
+over the rounds, which IS the run-to-run spread to judge a difference by):
+
+    upload + intake      pinned host memory -> device copy -> `data`:  3 B/pixel + lsfa_image_transform_u8  against
+                         1.5 B/pixel + lsfa_image_transform_yuv420
+    kernels alone        each intake kernel as a replayed graph of `--iters` launches (no host enqueue between them), with the bytes the
+                         algorithm reads and writes over that time: lsfa_image_transform_u8, lsfa_image_transform_yuv420 (NV12, I420),
+                         lsfa_yuv420_to_bgr_u8 (with and without y_packed), lsfa_luma_u8 (what y_packed saves), and the resize forms
+                         lsfa_image_resize_transform (uint8) / lsfa_image_resize_transform_yuv420 at scale 1, stride 16
+
+The one expectation: the NV12 transform kernel is not slower than the u8 one beyond the spread - it writes the same bytes and reads half.
+Prints one JSON object per line.  Ends itself after --time-limit seconds."""
+import argparse
+import ctypes
+import json
+import os
+import signal
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from lsfa_amd import hip
+
+DEV = 'cuda:0'
+W, H = 1000, 600
+MEANS, SCALE = (102.9801, 115.9465, 122.7717), 0.0125
+
+
+def stats(us):
+    return dict(min=round(min(us), 2), median=round(float(np.median(us)), 2), max=round(max(us), 2))
+
+
+def eager_rounds(fns, iters, rounds, warmup=10):
+    """microseconds per call of each fn in `fns`: `iters` calls between two events, the fns alternating within every round"""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    us = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            us[k].append(a.elapsed_time(b) * 1e3 / iters)
+    return {k: stats(v) for k, v in us.items()}
+
+
+def graph_rounds(fns, iters, rounds):
+    """the same with `iters` calls of a fn captured in one graph: kernel time without the host's enqueue"""
+    graphs = {}
+    for k, fn in fns.items():
+        fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(iters):
+                fn()
+        g.replay()
+        graphs[k] = g
+    torch.cuda.synchronize()
+    us = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, g in graphs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            g.replay()
+            b.record()
+            torch.cuda.synchronize()
+            us[k].append(a.elapsed_time(b) * 1e3 / iters)
+    return {k: stats(v) for k, v in us.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=200)
+    ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--frames', type=int, nargs='*', default=[1, 9, 12])
+    ap.add_argument('--time-limit', type=int, default=240, help='seconds after which the process ends itself')
+    args = ap.parse_args()
+    signal.alarm(args.time_limit)
+    if not torch.cuda.is_available():
+        raise SystemExit('no GPU: nothing to measure')
+    print(json.dumps(dict(device=torch.cuda.get_device_name(0), frame='%dx%d' % (W, H), iters=args.iters, rounds=args.rounds,
+                          unit='microseconds per call: min / median / max over the rounds')), flush=True)
+    rs = np.random.RandomState(0)
+    px = H * W
+    means_c = (ctypes.c_double * 3)(*MEANS)
+    for N in args.frames:
+        # host side: what a decoder (NV12: Y rows, then interleaved chroma rows, one surface per frame) or a host colour conversion (BGR) leaves
+        h_bgr = torch.from_numpy(rs.randint(0, 256, (N, H, W, 3)).astype(np.uint8)).pin_memory()
+        h_nv12 = torch.from_numpy(rs.randint(0, 256, (N, H * 3 // 2, W)).astype(np.uint8)).pin_memory()
+        d_bgr = torch.empty((N, H, W, 3), dtype=torch.uint8, device=DEV)
+        d_nv12 = torch.empty((N, H * 3 // 2, W), dtype=torch.uint8, device=DEV)
+        d_bgr.copy_(h_bgr)
+        d_nv12.copy_(h_nv12)
+        y, uv = d_nv12[:, :H], d_nv12[:, H:]
+        d_i420 = d_nv12.clone()
+        u = d_i420[:, H:].reshape(N, 2, H // 2, W // 2)[:, 0]
+        v = d_i420[:, H:].reshape(N, 2, H // 2, W // 2)[:, 1]
+        yi = d_i420[:, :H]
+        data = torch.empty((N, 3, H, W), dtype=torch.float32, device=DEV)
+        rdata = torch.empty((N, 3, 608, 1008), dtype=torch.float32, device=DEV)
+        bgr_out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=DEV)
+        y_packed = torch.empty((N, H, W), dtype=torch.uint8, device=DEV)
+        luma = torch.empty((H, W), dtype=torch.uint8, device=DEV)
+        assert torch.equal(hip.image_transform_yuv420(y, uv, pixel_means=MEANS, pixel_scale=SCALE),
+                           hip.image_transform_u8(hip.yuv420_to_bgr_u8(y, uv), MEANS, SCALE))
+
+        def up_bgr():
+            d_bgr.copy_(h_bgr, non_blocking=True)
+            hip.image_transform_u8(d_bgr, MEANS, SCALE, out=data)
+
+        def up_nv12():
+            d_nv12.copy_(h_nv12, non_blocking=True)
+            hip.image_transform_yuv420(y, uv, pixel_means=MEANS, pixel_scale=SCALE, out=data)
+
+        r = eager_rounds(dict(bgr_upload_transform_u8=up_bgr, nv12_upload_transform_yuv420=up_nv12,
+                              bgr_upload_only=lambda: d_bgr.copy_(h_bgr, non_blocking=True),
+                              nv12_upload_only=lambda: d_nv12.copy_(h_nv12, non_blocking=True)), args.iters, args.rounds)
+        print(json.dumps(dict(N=N, what='upload + intake, eager', upload_bytes=dict(bgr=3 * px * N, nv12=px * N * 3 // 2), us=r)), flush=True)
+
+        def resize_u8():          # the C entry point itself: hip.image_resize_transform allocates its output at every call
+            hip._check(hip.lib().lsfa_image_resize_transform(hip._ptr(d_bgr), 1, N, H, W, ctypes.c_double(1.0), H, W, 16, means_c, ctypes.c_double(SCALE),
+                                                             hip._ptr(rdata), 608, 1008, hip._stream()), 'lsfa_image_resize_transform')
+
+        kernels = {
+            # name: (fn, bytes read + written by the algorithm)
+            'image_transform_u8': (lambda: hip.image_transform_u8(d_bgr, MEANS, SCALE, out=data), (3 + 12) * px * N),
+            'image_transform_yuv420_nv12': (lambda: hip.image_transform_yuv420(y, uv, pixel_means=MEANS, pixel_scale=SCALE, out=data), (1.5 + 12) * px * N),
+            'image_transform_yuv420_i420': (lambda: hip.image_transform_yuv420(yi, u=u, v=v, pixel_means=MEANS, pixel_scale=SCALE, out=data), (1.5 + 12) * px * N),
+            'yuv420_to_bgr_u8': (lambda: hip.yuv420_to_bgr_u8(y, uv, out=bgr_out), (1.5 + 3) * px * N),
+            'yuv420_to_bgr_u8+y_packed': (lambda: hip.yuv420_to_bgr_u8(y, uv, out=bgr_out, y_packed=y_packed), (1.5 + 4) * px * N),
+            'luma_u8(one frame)': (lambda: hip.luma_u8(d_bgr[0], out=luma), (3 + 1) * px),
+            'image_resize_transform_u8': (resize_u8, (3 * px + 12 * 608 * 1008) * N),
+            'image_resize_transform_yuv420': (lambda: hip.image_resize_transform_yuv420(y, uv, im_scale=1.0, pixel_means=MEANS, pixel_scale=SCALE, stride=16,
+                                                                                       out=rdata), (1.5 * px + 12 * 608 * 1008) * N),
+        }
+        r = graph_rounds({k: f for k, (f, _) in kernels.items()}, args.iters, args.rounds)
+        for k, (_, nbytes) in kernels.items():
+            r[k]['bytes'] = int(nbytes)
+            r[k]['GB_per_s_at_median'] = round(nbytes / (r[k]['median'] * 1e-6) / 1e9, 1)
+        print(json.dumps(dict(N=N, what='kernels alone, replayed graph', us=r)), flush=True)
+        a, b = r['image_transform_u8'], r['image_transform_yuv420_nv12']
+        print(json.dumps(dict(N=N, what='expectation: NV12 transform not slower than u8 beyond the spread',
+                              u8=a['median'], nv12=b['median'], u8_spread=round(a['max'] - a['min'], 2), nv12_spread=round(b['max'] - b['min'], 2),
+                              holds=bool(b['median'] <= a['median'] + max(a['max'] - a['min'], b['max'] - b['min'])))), flush=True)
+
+
+if __name__ == '__main__':
+    main()
