@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import oracle
+import ref_bf16
 from oracle import np_ref
 
 pytestmark = pytest.mark.gpu
@@ -788,6 +789,10 @@ def test_rpn_head_on_the_nchw_map(hip, shape, pieces):
     assert float((bbox.double().cpu() - logits[:, 2 * A:]).abs().max()) < tol
     assert float((cls_prob.double().cpu() - want_p).abs().max()) < tol
     assert float((cls_prob[:, :A] + cls_prob[:, A:] - 1.0).abs().max()) < 3e-7
+    if pieces == 1:      # the bf16 mode's logits against the convolution of the ROUNDED operands (tests/ref_bf16.py): the derived bound and the fp32 criterion
+        ref, ref_abs = ref_bf16.conv_ref(feat[:, :512].permute(0, 2, 3, 1).cpu().numpy(), w64.cpu().numpy(), b64.cpu().numpy(), 1, (0, 0), 1, 0)
+        r_gamma, r_fp32 = ref_bf16.bound_ratios(logits_g.cpu().numpy(), ref, ref_abs, 512)
+        assert r_gamma <= 1.0 and r_fp32 < 1.0, (r_gamma, r_fp32)
     # the same numbers as the channels-last form of the same convolution
     rows = hip.conv_split(feat[:, :512].permute(0, 2, 3, 1).contiguous(), sw, b64)
     assert torch.equal(rows, logits_g)
@@ -1443,6 +1448,10 @@ def test_conv_split_vs_float64_and_fp32_mfma(hip, cfg, pieces):
     err_split = np.abs(g - want).max()
     if pieces == 1:
         assert err_split < 1e-2 * scale, err_split         # one bf16 product per fp32 product: 2^-8 per term
+        # ... and, against the convolution of the ROUNDED operands (tests/ref_bf16.py), the derived bound and the fp32 forms' criterion below
+        ref, ref_abs = ref_bf16.conv_ref(x.transpose(0, 2, 3, 1), w, b, stride, (pad, pad), dil, 1)
+        r_gamma, r_fp32 = ref_bf16.bound_ratios(g, ref, ref_abs, Cin * k * k)
+        assert r_gamma <= 1.0 and r_fp32 < 1.0, (r_gamma, r_fp32)
         return
     assert err_split < 2e-6 * np.sqrt(Cin * k * k) * scale
     ref32 = hip.conv_nhwc(xt, hip.conv_weight_kc(t(w)), t(b), k, k, stride, pad, dil, relu=True).cpu().numpy()
