@@ -40,7 +40,7 @@ def new_stream(device, high_priority=False):
         return s
     ptr = ctypes.c_void_p()
     with torch.cuda.device(dev):
-        hip._check(hip.lib().lsfa_stream_create(ctypes.byref(ptr), ctypes.c_int(1 if high_priority else 0)), "lsfa_stream_create")
+        hip._check(hip.lib().lsfa_stream_create(ctypes.byref(ptr), 1 if high_priority else 0), "lsfa_stream_create")
     s = torch.cuda.ExternalStream(ptr.value, device=dev)
     _OWNED.append(ptr.value)
     return s

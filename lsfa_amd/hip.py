@@ -8,8 +8,12 @@ eager fallback — if the library is missing or a call fails, LsfaError is raise
 import ctypes
 import math
 import os
+import re
 
+import numpy as np
 import torch  # must be imported before the .so so that both share one libamdhip64
+
+from lsfa_amd import build as _build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LSFA_HIP_LIBRARY: another build of the same library (tools/lab/drop_product_check.sh runs the parity suite against a deliberately
@@ -30,6 +34,59 @@ class LsfaError(RuntimeError):
 _lib = None
 _WARP_VARIANTS = {'auto': 0, 'gather': 1, 'staged': 2}       # lsfa_warp_set_variant
 
+# ---- the ABI, as include/lsfa_hip.h states it ---------------------------------------------------------------------------------------------
+# The header is the one statement of the C ABI on this side too: `ConvDesc` is built from its struct and lib() gives every export the
+# restype / argtypes of its prototype, so a call with a missing argument, a float for an int or a size_t read as an int is refused by
+# ctypes instead of reaching the library.  Call sites pass plain Python values; None is NULL.
+_HEADER = os.path.join(_build.INCLUDE, "lsfa_hip.h")
+_C_TYPES = {"void": None, "int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double,
+            "long": ctypes.c_long, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t}
+
+
+def _ctype(decl, named=True):
+    """ctypes type of one declaration of the header: a parameter or struct field (`named`) or a return type.  Pointers are c_void_p
+    but for a returned const char* and a const lsfa_conv_desc*; a scalar type outside _C_TYPES is an error."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if named:
+        words.pop()
+    if "*" in words:
+        if words == ["char", "*"] and not named:
+            return ctypes.c_char_p
+        return ctypes.POINTER(ConvDesc) if words == ["lsfa_conv_desc", "*"] else ctypes.c_void_p
+    if " ".join(words) not in _C_TYPES or (named and words == ["void"]):
+        raise LsfaError("%s: no ctypes type for %r; extend _C_TYPES in lsfa_amd/hip.py" % (_HEADER, decl))
+    return _C_TYPES[" ".join(words)]
+
+
+def _parse_header():
+    """-> (the fields of struct lsfa_conv_desc as ctypes _fields_, {export: (return type, [parameter, ...])} as the header spells them)"""
+    try:
+        text = open(_HEADER).read()
+    except OSError as e:
+        raise LsfaError("the binding is derived from %s, which cannot be read (%s); there is no fallback" % (_HEADER, e))
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    struct = re.search(r"struct\s+lsfa_conv_desc\s*\{(.*?)\}", text, flags=re.S)
+    if not struct:
+        raise LsfaError("%s does not define struct lsfa_conv_desc" % _HEADER)
+    fields = []
+    for stmt in filter(str.strip, struct.group(1).split(";")):
+        first, *more = [d.strip() for d in stmt.split(",")]          # `int N, H, W, Cin`: one type, several declarators
+        if more and "*" in stmt:
+            raise LsfaError("%s: pointer fields are declared one by one: %r" % (_HEADER, stmt.strip()))
+        fields += [(name, _ctype(first)) for name in [first.replace("*", " ").split()[-1]] + more]
+    protos = {m.group(2): (m.group(1), [] if m.group(3).strip() == "void" else m.group(3).split(","))
+              for m in re.finditer(r"([\w\s*]+?)\b(lsfa_\w+|_nms)\s*\(([^()]*)\)\s*;", text)}
+    return fields, protos
+
+
+_CONV_DESC_FIELDS, _PROTOTYPES = _parse_header()
+
+
+class ConvDesc(ctypes.Structure):
+    """struct lsfa_conv_desc (include/lsfa_hip.h), field for field"""
+    _fields_ = _CONV_DESC_FIELDS
+
 
 def lib():
     global _lib
@@ -37,23 +94,17 @@ def lib():
         if not os.path.exists(LIB_PATH):
             # not a fallback: build the real library if the toolchain is here, else fail loudly
             try:
-                from lsfa_amd import build as _build
                 _build.build_hip()
             except Exception as e:
                 raise LsfaError("liblsfa_hip.so is not built (%s) and building it failed (%r); run "
                                 "`python -m lsfa_amd.build` — there is no fallback path" % (LIB_PATH, e))
         L = ctypes.CDLL(LIB_PATH)
-        L.lsfa_last_error.restype = ctypes.c_char_p
-        for name in ("lsfa_proposal_workspace_bytes", "lsfa_nms_workspace_bytes", "lsfa_det_workspace_bytes",
-                     "lsfa_mv_workspace_bytes", "lsfa_conv_nhwc_workspace_bytes", "lsfa_conv_weight_bytes",
-                     "lsfa_conv_workspace_bytes", "lsfa_deconv4x4s2_crop_workspace_bytes", "lsfa_stem_weight_bytes",
-                     "lsfa_channel_mean_workspace_bytes"):
-            getattr(L, name).restype = ctypes.c_size_t
-        L.lsfa_op_name.restype = ctypes.c_char_p
-        L._nms.restype = None
+        for name, (ret, params) in _PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = _ctype(ret, named=False), [_ctype(p) for p in params]
         names, i = [], 0
         while True:
-            nm = L.lsfa_op_name(ctypes.c_int(i))
+            nm = L.lsfa_op_name(i)
             if not nm or nm == b"?" or i >= 64:          # "?" is what the library returns past the last id
                 break
             names.append(nm.decode())
@@ -64,7 +115,7 @@ def lib():
         if wv:
             if wv not in _WARP_VARIANTS:
                 raise LsfaError("LSFA_WARP_VARIANT=%r: expected one of %s" % (wv, sorted(_WARP_VARIANTS)))
-            L.lsfa_warp_set_variant(ctypes.c_int(_WARP_VARIANTS[wv]))
+            L.lsfa_warp_set_variant(_WARP_VARIANTS[wv])
         _lib = L
     return _lib
 
@@ -74,18 +125,12 @@ def _check(rc, what):
         raise LsfaError("%s failed (code %d): %s" % (what, rc, lib().lsfa_last_error().decode()))
 
 
-_vp = ctypes.c_void_p
-_ci = ctypes.c_int
-_cf = ctypes.c_float
-_cd = ctypes.c_double
-
-
 def _ptr(t):
-    return _vp(t.data_ptr()) if t is not None else None
+    return t.data_ptr() if t is not None else None
 
 
 def _stream():
-    return _vp(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _on_tensor_device(fn):
@@ -112,6 +157,18 @@ def _f32c(t, name):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _means(pixel_means):
+    """config.network.PIXEL_MEANS (B, G, R) as the three host doubles the image transforms read"""
+    return (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
+
+
+def _resized(H, W, im_scale, stride):
+    """-> h1, w1 = cvRound(H * im_scale), cvRound(W * im_scale) as numpy rounds them, then the two padded up to multiples of `stride`
+    (0: as they are)"""
+    h1, w1 = int(np.rint(H * float(im_scale))), int(np.rint(W * float(im_scale)))
+    return (h1, w1, -(-h1 // stride) * stride, -(-w1 // stride) * stride) if stride else (h1, w1, h1, w1)
+
+
 # ------------------------------------------------------------------------------------
 @_on_tensor_device
 def psroi_pool(data, rois, spatial_scale, output_dim, pooled_size, group_size, with_mapping=False):
@@ -120,9 +177,8 @@ def psroi_pool(data, rois, spatial_scale, output_dim, pooled_size, group_size, w
     R = rois.shape[0]
     out = torch.empty((R, output_dim, pooled_size, pooled_size), device=data.device, dtype=torch.float32)
     mc = torch.empty_like(out) if with_mapping else None
-    _check(lib().lsfa_psroi_pool_fwd(_ptr(data), _ptr(rois), _ci(N), _ci(C), _ci(H), _ci(W), _ci(R),
-                                     _cf(spatial_scale), _ci(output_dim), _ci(pooled_size), _ci(group_size),
-                                     _ptr(out), _ptr(mc), _stream()), "lsfa_psroi_pool_fwd")
+    _check(lib().lsfa_psroi_pool_fwd(_ptr(data), _ptr(rois), N, C, H, W, R, spatial_scale, output_dim, pooled_size, group_size, _ptr(out), _ptr(mc),
+                                     _stream()), "lsfa_psroi_pool_fwd")
     return (out, mc) if with_mapping else out
 
 
@@ -140,8 +196,7 @@ def rfcn_head(cls_map, box_map, rois, spatial_scale=0.0625, pooled_size=7, group
     else:
         cls_prob, bbox_pred = out
     cls_score = torch.empty((R, ncls), device=rois.device, dtype=torch.float32) if want_score else None
-    _check(lib().lsfa_rfcn_head_fwd(_ptr(cls_map), _ptr(box_map), _ptr(rois), _ci(N), _ci(H), _ci(W), _ci(R),
-                                    _ci(ncls), _ci(nbox), _cf(spatial_scale), _ci(pooled_size), _ci(group_size),
+    _check(lib().lsfa_rfcn_head_fwd(_ptr(cls_map), _ptr(box_map), _ptr(rois), N, H, W, R, ncls, nbox, spatial_scale, pooled_size, group_size,
                                     _ptr(cls_prob), _ptr(cls_score), _ptr(bbox_pred), _stream()), "lsfa_rfcn_head_fwd")
     return (cls_prob, cls_score, bbox_pred) if want_score else (cls_prob, bbox_pred)
 
@@ -155,8 +210,7 @@ def rfcn_head_ps(ps_map, rois, ncls, nbox, spatial_scale=0.0625, pooled_size=7, 
     cls_prob = torch.empty((R, ncls), device=rois.device, dtype=torch.float32)
     bbox_pred = torch.empty((R, nbox), device=rois.device, dtype=torch.float32)
     cls_score = torch.empty((R, ncls), device=rois.device, dtype=torch.float32) if want_score else None
-    _check(lib().lsfa_rfcn_head_ps_fwd(_ptr(ps_map), _ptr(rois), _ci(N), _ci(H), _ci(W), _ci(R), _ci(ncls), _ci(nbox),
-                                       _cf(spatial_scale), _ci(pooled_size), _ci(group_size), _ptr(cls_prob),
+    _check(lib().lsfa_rfcn_head_ps_fwd(_ptr(ps_map), _ptr(rois), N, H, W, R, ncls, nbox, spatial_scale, pooled_size, group_size, _ptr(cls_prob),
                                        _ptr(cls_score), _ptr(bbox_pred), _stream()), "lsfa_rfcn_head_ps_fwd")
     return (cls_prob, cls_score, bbox_pred) if want_score else (cls_prob, bbox_pred)
 
@@ -177,10 +231,10 @@ def _warp(name, cl, feat, flow, mul, add, res, res_w, res_b, bn, out, amax_out=N
     if out is None:
         out = torch.empty((N, H, W, C) if cl else (N, C, H, W), device=feat.device, dtype=torch.float32)
     sym = "lsfa_warp_bilinear" + ("_bn" if bn is not None else "") + ("_cl" if cl else "")
-    args = [_ptr(feat), _ci(feat_n), _ptr(flow), _ci(N), _ci(C), _ci(H), _ci(W)]
+    args = [_ptr(feat), feat_n, _ptr(flow), N, C, H, W]
     if bn is None and not cl:                     # `mul` is an argument of lsfa_warp_bilinear alone
         args.append(_ptr(mul))
-    args += [_ptr(add), _ptr(res), _ci(res_c), _ptr(res_w), _ptr(res_b)]
+    args += [_ptr(add), _ptr(res), res_c, _ptr(res_w), _ptr(res_b)]
     if bn is not None:
         bn_scale, bn_shift = _f32c(bn[0], "bn scale"), _f32c(bn[1], "bn shift")
         if mul is not None:
@@ -190,7 +244,7 @@ def _warp(name, cl, feat, flow, mul, add, res, res_w, res_b, bn, out, amax_out=N
         args += [_ptr(bn_scale), _ptr(bn_shift)]
     args.append(_ptr(out))
     if cl:
-        args += [_ptr(amax_out), _ci(amax_c0)]
+        args += [_ptr(amax_out), amax_c0]
     _check(getattr(lib(), sym)(*args, _stream()), sym)
     return out
 
@@ -225,10 +279,9 @@ def channel_mean(x1, x2=None, out=None):
     C = C1 + C2
     if out is None:
         out = torch.empty((N, C), device=x1.device, dtype=torch.float32)
-    need = lib().lsfa_channel_mean_workspace_bytes(_ci(N), _ci(C), _ci(H * W))
+    need = lib().lsfa_channel_mean_workspace_bytes(N, C, H * W)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x1.device)
-    _check(lib().lsfa_channel_mean(_ptr(x1), _ci(C1), _ptr(x2), _ci(C2), _ci(N), _ci(H * W), _ptr(out), _ptr(ws), ctypes.c_size_t(need),
-                                   _stream()), "lsfa_channel_mean")
+    _check(lib().lsfa_channel_mean(_ptr(x1), C1, _ptr(x2), C2, N, H * W, _ptr(out), _ptr(ws), need, _stream()), "lsfa_channel_mean")
     return out
 
 
@@ -243,8 +296,8 @@ def channel_gate(m, w1, b1, w2, b2, out=None):
     hidden = torch.empty((N, M), device=m.device, dtype=torch.float32)
     if out is None:
         out = torch.empty((N, O), device=m.device, dtype=torch.float32)
-    _check(lib().lsfa_channel_gate(_ptr(m), _ci(N), _ci(K), _ptr(w1), _ptr(b1), _ci(M), _ptr(w2), _ptr(b2), _ci(O), _ptr(hidden), _ptr(out),
-                                   _stream()), "lsfa_channel_gate")
+    _check(lib().lsfa_channel_gate(_ptr(m), N, K, _ptr(w1), _ptr(b1), M, _ptr(w2), _ptr(b2), O, _ptr(hidden), _ptr(out), _stream()),
+           "lsfa_channel_gate")
     return out
 
 
@@ -258,15 +311,14 @@ def gate_apply(x, gate, y, out=None, amax_out=None, amax_c0=0):
         raise LsfaError("gate_apply: x %s, y %s, gate %s" % (tuple(x.shape), tuple(y.shape), tuple(gate.shape)))
     if out is None:
         out = torch.empty_like(x)
-    _check(lib().lsfa_gate_apply(_ptr(x), _ptr(gate), _ptr(y), _ci(N), _ci(H * W), _ci(C), _ptr(out), _ptr(amax_out), _ci(amax_c0), _stream()),
-           "lsfa_gate_apply")
+    _check(lib().lsfa_gate_apply(_ptr(x), _ptr(gate), _ptr(y), N, H * W, C, _ptr(out), _ptr(amax_out), amax_c0, _stream()), "lsfa_gate_apply")
     return out
 
 
 def warp_set_variant(variant):
     """'auto' | 'gather' | 'staged': lsfa_warp_set_variant (process-wide kernel choice of warp_bilinear; same results.  'staged'
     makes shapes the LDS-staged kernel does not take an error instead of falling back)."""
-    _check(lib().lsfa_warp_set_variant(_ci(_WARP_VARIANTS[variant])), "lsfa_warp_set_variant")
+    _check(lib().lsfa_warp_set_variant(_WARP_VARIANTS[variant]), "lsfa_warp_set_variant")
 
 
 @_on_tensor_device
@@ -283,18 +335,17 @@ def aggregate_softmax2(a, b, logits, out=None, logit_row_stride=None):
                 logits.numel() < (2 * N - 1) * logit_row_stride + H * W):
             raise LsfaError("aggregate_softmax2: logits %s (%s, %s) must be contiguous float32 on %s with %d rows of %d logits >= %d floats apart, got stride %d" % (
                 tuple(logits.shape), logits.dtype, logits.device, a.device, 2 * N, H * W, H * W, logit_row_stride))
-        _check(lib().lsfa_aggregate_softmax2_rows(_ptr(a), _ptr(b), _ptr(logits), ctypes.c_long(logit_row_stride), _ci(N), _ci(C), _ci(H), _ci(W),
-                                                  _ptr(out), _stream()), "lsfa_aggregate_softmax2_rows")
+        _check(lib().lsfa_aggregate_softmax2_rows(_ptr(a), _ptr(b), _ptr(logits), logit_row_stride, N, C, H, W, _ptr(out), _stream()),
+               "lsfa_aggregate_softmax2_rows")
         return out
     logits = _f32c(logits, "logits")
     if logits.numel() != 2 * N * H * W:
         raise LsfaError("aggregate_softmax2: logits %s do not match a %s" % (tuple(logits.shape), tuple(a.shape)))
     if N == 1:
-        _check(lib().lsfa_aggregate_softmax2(_ptr(a), _ptr(b), _ptr(logits), _ci(C), _ci(H), _ci(W), _ptr(out), _stream()),
-               "lsfa_aggregate_softmax2")
+        _check(lib().lsfa_aggregate_softmax2(_ptr(a), _ptr(b), _ptr(logits), C, H, W, _ptr(out), _stream()), "lsfa_aggregate_softmax2")
     else:
-        _check(lib().lsfa_aggregate_softmax2_batched(_ptr(a), _ptr(b), _ptr(logits), _ci(N), _ci(C), _ci(H), _ci(W),
-                                                     _ptr(out), _stream()), "lsfa_aggregate_softmax2_batched")
+        _check(lib().lsfa_aggregate_softmax2_batched(_ptr(a), _ptr(b), _ptr(logits), N, C, H, W, _ptr(out), _stream()),
+               "lsfa_aggregate_softmax2_batched")
     return out
 
 
@@ -305,8 +356,8 @@ def aggregate_cosine(a, b, emb_warp, emb_cur, out=None):
     _, C, H, W = a.shape
     if out is None:
         out = torch.empty_like(a)
-    _check(lib().lsfa_aggregate_cosine(_ptr(a), _ptr(b), _ptr(emb_warp), _ptr(emb_cur), _ci(C), _ci(emb_warp.shape[1]),
-                                       _ci(H), _ci(W), _ptr(out), _stream()), "lsfa_aggregate_cosine")
+    _check(lib().lsfa_aggregate_cosine(_ptr(a), _ptr(b), _ptr(emb_warp), _ptr(emb_cur), C, emb_warp.shape[1], H, W, _ptr(out), _stream()),
+           "lsfa_aggregate_cosine")
     return out
 
 
@@ -334,7 +385,7 @@ class ProposalOp(object):
         if bbox_pred.shape != (B, 4 * A, H, W) or im_info.shape != (B, 3):
             raise LsfaError("Proposal: expected bbox_pred %s and im_info %s, got %s and %s (multi_proposal-inl.h:179-187)"
                             % ((B, 4 * A, H, W), (B, 3), tuple(bbox_pred.shape), tuple(im_info.shape)))
-        need = lib().lsfa_proposal_workspace_bytes(_ci(B), _ci(A), _ci(H), _ci(W), _ci(self.pre_n))
+        need = lib().lsfa_proposal_workspace_bytes(B, A, H, W, self.pre_n)
         ws = torch.empty(need, dtype=torch.uint8, device=cls_prob.device)
         count = A * H * W
         pre_n = min(self.pre_n if self.pre_n > 0 else count, count)
@@ -344,18 +395,16 @@ class ProposalOp(object):
             scores = torch.empty((B * post_n, 1), device=cls_prob.device, dtype=torch.float32)
         else:
             rois, scores = out
-        _check(lib().lsfa_proposal(_ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ci(B), _ci(A), _ci(H), _ci(W),
-                                   _ci(self.feature_stride), self.scales, _ci(len(self.scales)), self.ratios,
-                                   _ci(len(self.ratios)), _ci(self.pre_n), _ci(self.post_n), _cf(self.threshold),
-                                   _ci(self.min_size), _ptr(rois), _ptr(scores), _ptr(ws),
-                                   ctypes.c_size_t(ws.numel()), _stream()), "lsfa_proposal")
+        _check(lib().lsfa_proposal(_ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), B, A, H, W, self.feature_stride, self.scales, len(self.scales),
+                                   self.ratios, len(self.ratios), self.pre_n, self.post_n, self.threshold, self.min_size, _ptr(rois), _ptr(scores),
+                                   _ptr(ws), ws.numel(), _stream()), "lsfa_proposal")
         return (rois, scores) if self.output_score else rois
 
 
 @_on_tensor_device
 def proposal_set_plan(plan):
     """'auto' | 'single' | 'chip' | 'chip-box-sweep': lsfa_proposal_set_plan (process-wide launch plan; same results)."""
-    _check(lib().lsfa_proposal_set_plan(_ci({'auto': 0, 'single': 1, 'chip': 2, 'chip-box-sweep': 3, 'lab-no-nms': 99}[plan])), "lsfa_proposal_set_plan")
+    _check(lib().lsfa_proposal_set_plan({'auto': 0, 'single': 1, 'chip': 2, 'chip-box-sweep': 3, 'lab-no-nms': 99}[plan]), "lsfa_proposal_set_plan")
 
 
 # Ablation switches (tools/lab/tail_ablation.sh; VERDICT r5 items 4 and 5): LSFA_LAB_SKIP=tail,copy,nhwc drops launches from every frame so that
@@ -379,10 +428,9 @@ def nms_sorted(boxes, thresh):
     n, d = boxes.shape
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=boxes.device)
     num = torch.zeros(1, dtype=torch.int32, device=boxes.device)
-    need = lib().lsfa_nms_workspace_bytes(_ci(n))
+    need = lib().lsfa_nms_workspace_bytes(n)
     ws = torch.empty(need, dtype=torch.uint8, device=boxes.device)
-    _check(lib().lsfa_nms_sorted(_ptr(boxes), _ci(n), _ci(d), _cf(thresh), _ptr(keep), _ptr(num), _ptr(ws),
-                                 ctypes.c_size_t(need), _stream()), "lsfa_nms_sorted")
+    _check(lib().lsfa_nms_sorted(_ptr(boxes), n, d, thresh, _ptr(keep), _ptr(num), _ptr(ws), need, _stream()), "lsfa_nms_sorted")
     return keep, num
 
 
@@ -396,22 +444,19 @@ def nms_sorted_f64(boxes, thresh):
     n, d = boxes.shape
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=boxes.device)
     num = torch.zeros(1, dtype=torch.int32, device=boxes.device)
-    need = lib().lsfa_nms_workspace_bytes(_ci(n))
+    need = lib().lsfa_nms_workspace_bytes(n)
     ws = torch.empty(need, dtype=torch.uint8, device=boxes.device)
-    _check(lib().lsfa_nms_sorted_f64(_ptr(boxes), _ci(n), _ci(d), _cd(thresh), _ptr(keep), _ptr(num), _ptr(ws),
-                                     ctypes.c_size_t(need), _stream()), "lsfa_nms_sorted_f64")
+    _check(lib().lsfa_nms_sorted_f64(_ptr(boxes), n, d, thresh, _ptr(keep), _ptr(num), _ptr(ws), need, _stream()), "lsfa_nms_sorted_f64")
     return keep, num
 
 
 def nms_host(boxes_np, thresh, device_id=0):
     """The reference's `_nms` C entry point (lib/nms/gpu_nms.hpp:14-15): host numpy in, host list out."""
-    import numpy as np
     boxes_np = np.ascontiguousarray(boxes_np, dtype=np.float32)
     n, d = boxes_np.shape
     keep = np.zeros(max(n, 1), dtype=np.int32)
-    num = ctypes.c_int(0)
-    lib()._nms(keep.ctypes.data_as(_vp), ctypes.byref(num), boxes_np.ctypes.data_as(_vp), _ci(n), _ci(d),
-               _cf(thresh), _ci(device_id))
+    num = ctypes.c_int()
+    lib()._nms(keep.ctypes.data_as(ctypes.c_void_p), ctypes.byref(num), boxes_np.ctypes.data_as(ctypes.c_void_p), n, d, thresh, device_id)
     return keep[:num.value]
 
 
@@ -421,8 +466,7 @@ def bbox_pred_clip(rois, deltas, im_h, im_w, scale):
     R = rois.shape[0]
     nreg = deltas.shape[1] // 4
     out = torch.empty((R, 4 * nreg), dtype=torch.float64, device=rois.device)
-    _check(lib().lsfa_bbox_pred_clip(_ptr(rois), _ptr(deltas), _ci(R), _ci(nreg), _cd(im_h), _cd(im_w), _cd(scale),
-                                     _ptr(out), _stream()), "lsfa_bbox_pred_clip")
+    _check(lib().lsfa_bbox_pred_clip(_ptr(rois), _ptr(deltas), R, nreg, im_h, im_w, scale, _ptr(out), _stream()), "lsfa_bbox_pred_clip")
     return out
 
 
@@ -440,10 +484,9 @@ def det_postprocess(rois, deltas, probs, im_h, im_w, scale, score_thresh=1e-4, n
         dets, counts, keep_idx = out
     if LAB_SKIP_DET:
         return dets, counts, keep_idx
-    _check(lib().lsfa_det_postprocess(_ptr(rois), _ptr(deltas), _ptr(probs), _ci(R), _ci(ncls), _ci(nreg),
-                                      _ci(int(class_agnostic)), _cd(im_h), _cd(im_w), _cd(scale), _cd(score_thresh),
-                                      _cd(nms_thresh), _ci(max_per_image), _ptr(dets), _ptr(counts), _ptr(keep_idx),
-                                      None, ctypes.c_size_t(0), _stream()), "lsfa_det_postprocess")
+    _check(lib().lsfa_det_postprocess(_ptr(rois), _ptr(deltas), _ptr(probs), R, ncls, nreg, int(class_agnostic), im_h, im_w, scale, score_thresh,
+                                      nms_thresh, max_per_image, _ptr(dets), _ptr(counts), _ptr(keep_idx), None, 0, _stream()),
+           "lsfa_det_postprocess")
     return dets, counts, keep_idx
 
 
@@ -455,8 +498,7 @@ def rpn_softmax_split(logits, A):
     N, H, W, L = logits.shape
     cls_prob = torch.empty((N, 2 * A, H, W), device=logits.device, dtype=torch.float32)
     bbox = torch.empty((N, 4 * A, H, W), device=logits.device, dtype=torch.float32)
-    _check(lib().lsfa_rpn_softmax_split(_ptr(logits), _ci(N), _ci(H), _ci(W), _ci(L), _ci(A), _ptr(cls_prob), _ptr(bbox), _stream()),
-           "lsfa_rpn_softmax_split")
+    _check(lib().lsfa_rpn_softmax_split(_ptr(logits), N, H, W, L, A, _ptr(cls_prob), _ptr(bbox), _stream()), "lsfa_rpn_softmax_split")
     return cls_prob, bbox
 
 
@@ -474,10 +516,9 @@ def det_postprocess_batch(rois, deltas, probs, B, im_h, im_w, scale, out, score_
         raise LsfaError("det_postprocess_batch: out must be contiguous (B, ncls, R, 5) / (B, ncls) / (B, ncls, R) buffers")
     if LAB_SKIP_DET:
         return dets, counts, keep_idx
-    _check(lib().lsfa_det_postprocess_batch(_ptr(rois), _ptr(deltas), _ptr(probs), _ci(B), _ci(R), _ci(ncls), _ci(nreg),
-                                            _ci(int(class_agnostic)), _cd(im_h), _cd(im_w), _cd(scale), _cd(score_thresh),
-                                            _cd(nms_thresh), _ci(max_per_image), _ptr(dets), _ptr(counts), _ptr(keep_idx),
-                                            None, ctypes.c_size_t(0), _stream()), "lsfa_det_postprocess_batch")
+    _check(lib().lsfa_det_postprocess_batch(_ptr(rois), _ptr(deltas), _ptr(probs), B, R, ncls, nreg, int(class_agnostic), im_h, im_w, scale,
+                                            score_thresh, nms_thresh, max_per_image, _ptr(dets), _ptr(counts), _ptr(keep_idx), None, 0, _stream()),
+           "lsfa_det_postprocess_batch")
     return dets, counts, keep_idx
 
 
@@ -488,9 +529,8 @@ def deform_im2col(data, offset, kh, kw, pad, stride, dilate, deform_groups, out=
     Ho, Wo = offset.shape[2], offset.shape[3]
     if out is None:
         out = torch.empty((N, C * kh * kw, Ho * Wo), dtype=torch.float32, device=data.device)
-    _check(lib().lsfa_deform_im2col(_ptr(data), _ptr(offset), _ci(N), _ci(C), _ci(H), _ci(W), _ci(kh), _ci(kw),
-                                    _ci(pad), _ci(stride), _ci(dilate), _ci(deform_groups), _ci(Ho), _ci(Wo),
-                                    _ptr(out), _stream()), "lsfa_deform_im2col")
+    _check(lib().lsfa_deform_im2col(_ptr(data), _ptr(offset), N, C, H, W, kh, kw, pad, stride, dilate, deform_groups, Ho, Wo, _ptr(out), _stream()),
+           "lsfa_deform_im2col")
     return out
 
 
@@ -505,9 +545,8 @@ def deform_im2col_cl(data, offset, kh, kw, pad, stride, dilate, deform_groups, o
         raise LsfaError("deform_im2col_cl: offset has %d channels, expected %d" % (offset.shape[3], 2 * kh * kw * deform_groups))
     if out is None:
         out = torch.empty((N, Ho * Wo, kh * kw * C), dtype=torch.float32, device=data.device)
-    _check(lib().lsfa_deform_im2col_cl_ld(_ptr(data), _ptr(offset), _ci(offset.shape[3]), _ci(N), _ci(C), _ci(H), _ci(W),
-                                          _ci(kh), _ci(kw), _ci(pad), _ci(stride), _ci(dilate), _ci(deform_groups), _ci(Ho),
-                                          _ci(Wo), _ptr(out), _stream()), "lsfa_deform_im2col_cl_ld")
+    _check(lib().lsfa_deform_im2col_cl_ld(_ptr(data), _ptr(offset), offset.shape[3], N, C, H, W, kh, kw, pad, stride, dilate, deform_groups, Ho, Wo,
+                                          _ptr(out), _stream()), "lsfa_deform_im2col_cl_ld")
     return out
 
 
@@ -518,8 +557,7 @@ def scale_shift_relu(x, scale, shift, relu=True, out=None):
     HW = x.numel() // (N * C)
     if out is None:
         out = torch.empty_like(x)
-    _check(lib().lsfa_scale_shift_relu(_ptr(x), _ptr(scale), _ptr(shift), _ci(N), _ci(C), _ci(HW), _ci(int(relu)),
-                                       _ptr(out), _stream()), "lsfa_scale_shift_relu")
+    _check(lib().lsfa_scale_shift_relu(_ptr(x), _ptr(scale), _ptr(shift), N, C, HW, int(relu), _ptr(out), _stream()), "lsfa_scale_shift_relu")
     return out
 
 
@@ -530,8 +568,7 @@ def scale_shift_leaky(x, scale, shift, slope, out=None):
     HW = x.numel() // (N * C)
     if out is None:
         out = torch.empty_like(x)
-    _check(lib().lsfa_scale_shift_leaky(_ptr(x), _ptr(scale), _ptr(shift), _ci(N), _ci(C), _ci(HW), _cf(slope),
-                                        _ptr(out), _stream()), "lsfa_scale_shift_leaky")
+    _check(lib().lsfa_scale_shift_leaky(_ptr(x), _ptr(scale), _ptr(shift), N, C, HW, slope, _ptr(out), _stream()), "lsfa_scale_shift_leaky")
     return out
 
 
@@ -543,8 +580,7 @@ def scale_shift_relu_cl(x, scale, shift, relu=True, out=None):
     rows = x.numel() // C
     if out is None:
         out = torch.empty_like(x)
-    _check(lib().lsfa_scale_shift_relu_cl(_ptr(x), _ptr(scale), _ptr(shift), ctypes.c_longlong(rows), _ci(C),
-                                          _ci(int(relu)), _ptr(out), _stream()), "lsfa_scale_shift_relu_cl")
+    _check(lib().lsfa_scale_shift_relu_cl(_ptr(x), _ptr(scale), _ptr(shift), rows, C, int(relu), _ptr(out), _stream()), "lsfa_scale_shift_relu_cl")
     return out
 
 
@@ -637,12 +673,10 @@ def conv_nhwc(x, w_kc, bias, kh, kw, stride=1, pad=0, dil=1, relu=False, out=Non
         if t is not None and (t.numel() != N * Ho * Wo * Cout or not t.is_contiguous() or t.dtype != torch.float32):
             raise LsfaError("conv_nhwc: %s must be a contiguous float32 tensor of %d elements" % (name, N * Ho * Wo * Cout))
     _count_conv(N, Ho, Wo, Cout, Cin, kh, kw)
-    need = lib().lsfa_conv_nhwc_workspace_bytes(_ci(N), _ci(H), _ci(W), _ci(Cout), _ci(kh), _ci(kw), _ci(stride), _ci(pad), _ci(dil))
+    need = lib().lsfa_conv_nhwc_workspace_bytes(N, H, W, Cout, kh, kw, stride, pad, dil)
     ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-    _check(lib().lsfa_conv_nhwc_fused_fwd(_ptr(x), _ci(N), _ci(H), _ci(W), _ci(Cin), _ptr(w_kc), _ptr(bias), _ci(Cout), _ci(kh),
-                                          _ci(kw), _ci(stride), _ci(pad), _ci(dil), _ci(int(relu)), _ptr(residual), _ptr(out),
-                                          _ptr(out2), _ptr(scale2), _ptr(shift2), _ptr(ws), ctypes.c_size_t(need), _stream()),
-           "lsfa_conv_nhwc_fused_fwd")
+    _check(lib().lsfa_conv_nhwc_fused_fwd(_ptr(x), N, H, W, Cin, _ptr(w_kc), _ptr(bias), Cout, kh, kw, stride, pad, dil, int(relu), _ptr(residual),
+                                          _ptr(out), _ptr(out2), _ptr(scale2), _ptr(shift2), _ptr(ws), need, _stream()), "lsfa_conv_nhwc_fused_fwd")
     return out if out2 is None else (out, out2)
 
 
@@ -675,7 +709,7 @@ def copy_many(pairs):
     src = (ctypes.c_void_p * n)(*[(s.data_ptr() if s is not None else None) for _, s in pairs])
     cnt = (ctypes.c_long * n)(*[d.numel() for d, _ in pairs])
     with torch.cuda.device(pairs[0][0].device):
-        _check(lib().lsfa_copy_many(_ci(n), dst, src, cnt, _stream()), "lsfa_copy_many")
+        _check(lib().lsfa_copy_many(n, dst, src, cnt, _stream()), "lsfa_copy_many")
 
 
 @_on_tensor_device
@@ -689,15 +723,13 @@ def transform_mv_res(motion_vector, res_diff, im_scale, pixel_means=(0.0, 0.0, 0
     if mv.dim() != 3 or res.dim() != 3 or mv.shape[2] != 2 or res.shape[2] != 3 or mv.shape[:2] != res.shape[:2] or not (mv.is_contiguous() and res.is_contiguous()):
         raise LsfaError("transform_mv_res: contiguous (H, W, 2) and (H, W, 3) expected, got %s / %s" % (tuple(mv.shape), tuple(res.shape)))
     H, W = int(mv.shape[0]), int(mv.shape[1])
-    import numpy as _np
-    h1, w1 = int(_np.rint(H * float(im_scale))), int(_np.rint(W * float(im_scale)))       # cvRound
-    oh, ow = -(-h1 // rcnn_stride), -(-w1 // rcnn_stride)
+    h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
+    oh, ow = ph // rcnn_stride, pw // rcnn_stride
     out_mv = torch.empty((1, 2, oh, ow), device=mv.device, dtype=torch.float32)
     out_res = torch.empty((1, 3, oh, ow), device=mv.device, dtype=torch.float32)
-    means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
-    _check(lib().lsfa_transform_mv_res(_ptr(mv), _ptr(res), _ci(int(mv.dtype == torch.int32) | (2 if negate_mv else 0)), _ci(H), _ci(W), ctypes.c_double(float(im_scale)), _ci(h1), _ci(w1),
-                                       _ci(int(rcnn_stride)), means, ctypes.c_double(float(pixel_scale)), _ptr(out_mv), _ptr(out_res), _ci(oh), _ci(ow),
-                                       _stream()), "lsfa_transform_mv_res")
+    _check(lib().lsfa_transform_mv_res(_ptr(mv), _ptr(res), int(mv.dtype == torch.int32) | (2 if negate_mv else 0), H, W, float(im_scale), h1, w1,
+                                       int(rcnn_stride), _means(pixel_means), float(pixel_scale), _ptr(out_mv), _ptr(out_res), oh, ow, _stream()),
+           "lsfa_transform_mv_res")
     return out_mv, out_res
 
 
@@ -712,15 +744,12 @@ def image_resize_transform(im, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scal
     if im.dtype not in (torch.uint8, torch.float32) or im.dim() != 4 or im.shape[3] != 3 or not im.is_contiguous():
         raise LsfaError("image_resize_transform: (N, H, W, 3) contiguous uint8 or float32 expected, got %s %s" % (tuple(im.shape), im.dtype))
     N, H, W, _ = [int(v) for v in im.shape]
-    import numpy as _np
-    h1, w1 = int(_np.rint(H * float(im_scale))), int(_np.rint(W * float(im_scale)))       # cvRound
-    ph, pw = (-(-h1 // stride) * stride, -(-w1 // stride) * stride) if stride else (h1, w1)
+    h1, w1, ph, pw = _resized(H, W, im_scale, stride)
     out = torch.empty((N, 3, ph, pw), device=im.device, dtype=torch.float32)
-    means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
     if u8_fixed_point and im.dtype != torch.uint8:
         raise LsfaError("image_resize_transform: u8_fixed_point needs uint8 frames")
-    _check(lib().lsfa_image_resize_transform(_ptr(im), _ci(2 if u8_fixed_point else int(im.dtype == torch.uint8)), _ci(N), _ci(H), _ci(W), ctypes.c_double(float(im_scale)), _ci(h1), _ci(w1),
-                                             _ci(int(stride)), means, ctypes.c_double(float(pixel_scale)), _ptr(out), _ci(ph), _ci(pw), _stream()),
+    _check(lib().lsfa_image_resize_transform(_ptr(im), 2 if u8_fixed_point else int(im.dtype == torch.uint8), N, H, W, float(im_scale), h1, w1,
+                                             int(stride), _means(pixel_means), float(pixel_scale), _ptr(out), ph, pw, _stream()),
            "lsfa_image_resize_transform")
     return out
 
@@ -734,15 +763,12 @@ def image_transform_u8(im, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, out=Non
     N, H, W, _ = im.shape
     if out is None:
         out = torch.empty((N, 3, H, W), device=im.device, dtype=torch.float32)
-    means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
-    _check(lib().lsfa_image_transform_u8(_vp(im.data_ptr()), _ci(N), _ci(H), _ci(W), means, ctypes.c_double(pixel_scale), _ptr(out), _stream()),
-           "lsfa_image_transform_u8")
+    _check(lib().lsfa_image_transform_u8(_ptr(im), N, H, W, _means(pixel_means), pixel_scale, _ptr(out), _stream()), "lsfa_image_transform_u8")
     return out
 
 
 # ---- YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip) ---------------------------------------------------------------------------------------------
 YUV_MATRICES = {'bt601': 0, 'bt709': 1, 'jpeg': 2}
-_cll = ctypes.c_longlong
 
 
 def _yuv_planes(who, y, uv, u, v, matrix):
@@ -783,8 +809,7 @@ def _yuv_planes(who, y, uv, u, v, matrix):
     c_fs = int(c.stride(0)) if batched and N > 1 else 0
     if y_pitch < W or c_pitch < want[1]:
         raise LsfaError("%s: a row pitch is below its row: %s" % (who, shapes()))
-    args = (_ptr(y), _cll(y_pitch), _cll(y_fs), _ptr(c), _ptr(None if nv12 else v), _cll(c_pitch), _cll(c_fs), _ci(N), _ci(H), _ci(W),
-            _ci(YUV_MATRICES[matrix]))
+    args = (_ptr(y), y_pitch, y_fs, _ptr(c), _ptr(None if nv12 else v), c_pitch, c_fs, N, H, W, YUV_MATRICES[matrix])
     return args, N, H, W, batched
 
 
@@ -826,8 +851,8 @@ def image_transform_yuv420(y, uv=None, u=None, v=None, matrix='bt601', pixel_mea
         out = torch.empty((N, 3, H, W), dtype=torch.float32, device=y.device)
     else:
         _yuv_out(who, "out", out, (N, 3, H, W), torch.float32, y.device)
-    means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
-    _check(lib().lsfa_image_transform_yuv420(*(args + (means, _cd(float(pixel_scale)), _ptr(out), _stream()))), "lsfa_image_transform_yuv420")
+    _check(lib().lsfa_image_transform_yuv420(*(args + (_means(pixel_means), float(pixel_scale), _ptr(out), _stream()))),
+           "lsfa_image_transform_yuv420")
     return out
 
 
@@ -841,17 +866,15 @@ def image_resize_transform_yuv420(y, uv=None, u=None, v=None, im_scale=1.0, matr
     args, N, H, W, _ = _yuv_planes(who, y, uv, u, v, matrix)
     if not float(im_scale) > 0.0 or int(stride) < 0:
         raise LsfaError("%s: im_scale %r must be positive and stride %r non-negative" % (who, im_scale, stride))
-    import numpy as _np
-    h1, w1 = int(_np.rint(H * float(im_scale))), int(_np.rint(W * float(im_scale)))       # cvRound
     stride = int(stride)
-    ph, pw = (-(-h1 // stride) * stride, -(-w1 // stride) * stride) if stride else (h1, w1)
+    h1, w1, ph, pw = _resized(H, W, im_scale, stride)
     if out is None:
         out = torch.empty((N, 3, ph, pw), dtype=torch.float32, device=y.device)
     else:
         _yuv_out(who, "out", out, (N, 3, ph, pw), torch.float32, y.device)
-    means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
-    _check(lib().lsfa_image_resize_transform_yuv420(*(args + (_cd(float(im_scale)), _ci(h1), _ci(w1), _ci(stride), means, _cd(float(pixel_scale)),
-                                                               _ptr(out), _ci(ph), _ci(pw), _stream()))), "lsfa_image_resize_transform_yuv420")
+    _check(lib().lsfa_image_resize_transform_yuv420(*(args + (float(im_scale), h1, w1, stride, _means(pixel_means), float(pixel_scale), _ptr(out),
+                                                               ph, pw, _stream()))),
+           "lsfa_image_resize_transform_yuv420")
     return out
 
 
@@ -892,7 +915,7 @@ class ImageTable(object):
                     c, h, w, self.device, tuple(t.shape), t.dtype, t.device))
         arr = (ctypes.c_void_p * n)(*[t.data_ptr() for t in images])
         with torch.cuda.device(self.device):
-            _check(lib().lsfa_ptr_table_set(_vp(self.ptrs.data_ptr()), _ci(n), arr, _stream()), "lsfa_ptr_table_set")
+            _check(lib().lsfa_ptr_table_set(_ptr(self.ptrs), n, arr, _stream()), "lsfa_ptr_table_set")
         self.held = images
         return self
 
@@ -914,9 +937,9 @@ def avgpool_nchw(x, k, out=None):
         out = torch.empty((N, C, Ho, Wo), device=x.device, dtype=torch.float32)
     if tbl:
         with torch.cuda.device(x.device):
-            _check(lib().lsfa_avgpool_nchw_tbl(_vp(x.ptrs.data_ptr()), _ci(N), _ci(C), _ci(H), _ci(W), _ci(k), _ptr(out), _stream()), "lsfa_avgpool_nchw_tbl")
+            _check(lib().lsfa_avgpool_nchw_tbl(_ptr(x.ptrs), N, C, H, W, k, _ptr(out), _stream()), "lsfa_avgpool_nchw_tbl")
         return out
-    _check(lib().lsfa_avgpool_nchw(_ptr(x), _ci(N), _ci(C), _ci(H), _ci(W), _ci(k), _ptr(out), _stream()), "lsfa_avgpool_nchw")
+    _check(lib().lsfa_avgpool_nchw(_ptr(x), N, C, H, W, k, _ptr(out), _stream()), "lsfa_avgpool_nchw")
     return out
 
 
@@ -950,11 +973,11 @@ def stem_conv(x, w_l, bias, in_scale=None, in_shift=None, out=None, accum=None, 
         raise LsfaError("stem_conv: accum must be a contiguous %s tensor" % (tuple(out.shape),))
     if tbl:
         with torch.cuda.device(x.device):
-            _check(lib().lsfa_stem_conv7x7s2_tbl(_vp(x.ptrs.data_ptr()), _ci(N), _ci(H), _ci(W), _ptr(in_scale), _ptr(in_shift), _ptr(w_l), _ptr(bias),
-                                                 _ptr(accum), _ci(act), _ptr(out), _ptr(amax_out), _stream()), "lsfa_stem_conv7x7s2_tbl")
+            _check(lib().lsfa_stem_conv7x7s2_tbl(_ptr(x.ptrs), N, H, W, _ptr(in_scale), _ptr(in_shift), _ptr(w_l), _ptr(bias), _ptr(accum), act,
+                                                 _ptr(out), _ptr(amax_out), _stream()), "lsfa_stem_conv7x7s2_tbl")
         return out
-    _check(lib().lsfa_stem_conv7x7s2_ex(_ptr(x), _ci(N), _ci(H), _ci(W), _ptr(in_scale), _ptr(in_shift), _ptr(w_l), _ptr(bias),
-                                        _ptr(accum), _ci(act), _ptr(out), _ptr(amax_out), _stream()), "lsfa_stem_conv7x7s2_ex")
+    _check(lib().lsfa_stem_conv7x7s2_ex(_ptr(x), N, H, W, _ptr(in_scale), _ptr(in_shift), _ptr(w_l), _ptr(bias), _ptr(accum), act, _ptr(out),
+                                        _ptr(amax_out), _stream()), "lsfa_stem_conv7x7s2_ex")
     return out
 
 
@@ -969,8 +992,8 @@ def head_conv3x3(x, w, bias, cin=None, mul=1.0, out=None, c0=0, nchw=False):
         raise LsfaError("head_conv3x3: weight %s does not fit %d input channels of %d" % (tuple(w.shape), cin, L))
     if out is None:
         out = torch.empty((N, Cout, H, W) if nchw else (N, H, W, Cout), device=x.device, dtype=torch.float32)
-    _check(lib().lsfa_head_conv3x3(_ptr(x), _ci(L), _ci(N), _ci(H), _ci(W), _ci(cin), _ptr(w), _ptr(bias), _ci(Cout), _cf(mul), _ptr(out),
-                                   _ci(int(nchw)), _ci(out.shape[3] if not nchw else 0), _ci(c0), _stream()), "lsfa_head_conv3x3")
+    _check(lib().lsfa_head_conv3x3(_ptr(x), L, N, H, W, cin, _ptr(w), _ptr(bias), Cout, mul, _ptr(out), int(nchw), out.shape[3] if not nchw else 0,
+                                   c0, _stream()), "lsfa_head_conv3x3")
     return out
 
 
@@ -982,8 +1005,8 @@ def upsample_flow(x, w, bias, out, c0, amax_out=None):
     if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda or out.dim() != 4 or out.shape[0] != N
             or not out.is_contiguous()):
         raise LsfaError("upsample_flow: out must be a contiguous float32 CUDA tensor (%d, Hc, Wc, L)" % N)
-    _check(lib().lsfa_upsample_flow(_ptr(x), _ci(N), _ci(Hi), _ci(Wi), _ci(C), _ptr(w), _ptr(bias), _ci(out.shape[1]), _ci(out.shape[2]),
-                                    _ptr(out), _ci(out.shape[3]), _ci(c0), _ptr(amax_out), _stream()), "lsfa_upsample_flow")
+    _check(lib().lsfa_upsample_flow(_ptr(x), N, Hi, Wi, C, _ptr(w), _ptr(bias), out.shape[1], out.shape[2], _ptr(out), out.shape[3], c0,
+                                    _ptr(amax_out), _stream()), "lsfa_upsample_flow")
     return out
 
 
@@ -1001,8 +1024,7 @@ def nchw_to_nhwc(x, c0=0, c=None, out=None, amax_out=None):
     if 'nhwc' in LAB_SKIP and out.data_ptr() in _lab_filled:
         return out
     _lab_filled.add(out.data_ptr())
-    _check(lib().lsfa_nchw_to_nhwc(_ptr(x), _ci(N), _ci(C), _ci(H * W), _ci(c0), _ci(c), _ptr(out), _ptr(amax_out), _stream()),
-           "lsfa_nchw_to_nhwc")
+    _check(lib().lsfa_nchw_to_nhwc(_ptr(x), N, C, H * W, c0, c, _ptr(out), _ptr(amax_out), _stream()), "lsfa_nchw_to_nhwc")
     return out
 
 
@@ -1017,9 +1039,8 @@ def rfcn_head_ps_ld(ps_map, cell_ld, rois, H, W, ncls, nbox, spatial_scale=0.062
     if LAB_SKIP_HEAD:
         return cls_prob, bbox_pred
     with torch.cuda.device(ps_map.device):
-        _check(lib().lsfa_rfcn_head_ps_ld_fwd(_ptr(ps_map), _ci(cell_ld), _ptr(rois), _ci(N), _ci(H), _ci(W), _ci(R), _ci(ncls), _ci(nbox),
-                                              _cf(spatial_scale), _ci(pooled_size), _ci(group_size), _ptr(cls_prob), None,
-                                              _ptr(bbox_pred), _stream()), "lsfa_rfcn_head_ps_ld_fwd")
+        _check(lib().lsfa_rfcn_head_ps_ld_fwd(_ptr(ps_map), cell_ld, _ptr(rois), N, H, W, R, ncls, nbox, spatial_scale, pooled_size, group_size,
+                                              _ptr(cls_prob), None, _ptr(bbox_pred), _stream()), "lsfa_rfcn_head_ps_ld_fwd")
     return cls_prob, bbox_pred
 
 
@@ -1029,7 +1050,7 @@ def avgpool2_nhwc(x):
     x = _f32c(x, "x")
     N, H, W, C = x.shape
     y = torch.empty((N, (H + 1) // 2, (W + 1) // 2, C), device=x.device, dtype=torch.float32)
-    _check(lib().lsfa_avgpool2_nhwc(_ptr(x), _ci(N), _ci(H), _ci(W), _ci(C), _ptr(y), _stream()), "lsfa_avgpool2_nhwc")
+    _check(lib().lsfa_avgpool2_nhwc(_ptr(x), N, H, W, C, _ptr(y), _stream()), "lsfa_avgpool2_nhwc")
     return y
 
 
@@ -1045,27 +1066,9 @@ def maxpool3x3s2_nhwc(x, out=None, scale2=None, shift2=None, amax_out=None):
     if out is None:
         out = torch.empty((N, Ho, Wo, C), device=x.device, dtype=torch.float32)
     out2 = torch.empty_like(out) if scale2 is not None else None
-    _check(lib().lsfa_maxpool3x3s2_nhwc(_ptr(x), _ci(N), _ci(H), _ci(W), _ci(C), _ptr(out), _ptr(out2), _ptr(scale2), _ptr(shift2),
-                                        _ptr(amax_out), _stream()), "lsfa_maxpool3x3s2_nhwc")
+    _check(lib().lsfa_maxpool3x3s2_nhwc(_ptr(x), N, H, W, C, _ptr(out), _ptr(out2), _ptr(scale2), _ptr(shift2), _ptr(amax_out), _stream()),
+           "lsfa_maxpool3x3s2_nhwc")
     return out if out2 is None else (out, out2)
-
-
-class ConvDesc(ctypes.Structure):
-    """struct lsfa_conv_desc (include/lsfa_hip.h)"""
-    _fields_ = [("x", ctypes.c_void_p), ("lda", ctypes.c_int), ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("Cin", ctypes.c_int),
-                ("wfrag", ctypes.c_void_p), ("pieces", ctypes.c_int), ("w_exp", ctypes.c_int), ("amax_in", ctypes.c_void_p),
-                ("bias", ctypes.c_void_p), ("Cout", ctypes.c_int), ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("stride", ctypes.c_int),
-                ("pad_h", ctypes.c_int), ("pad_w", ctypes.c_int), ("dil", ctypes.c_int),
-                ("act", ctypes.c_int), ("y_nchw", ctypes.c_int), ("residual", ctypes.c_void_p), ("y", ctypes.c_void_p), ("ldy", ctypes.c_int),
-                ("y2", ctypes.c_void_p), ("scale2", ctypes.c_void_p), ("shift2", ctypes.c_void_p),
-                ("amax_out", ctypes.c_void_p), ("status", ctypes.c_void_p),
-                ("Ho", ctypes.c_int), ("Wo", ctypes.c_int), ("out_H", ctypes.c_int), ("out_W", ctypes.c_int), ("out_sy", ctypes.c_int),
-                ("out_sx", ctypes.c_int), ("prof_tag", ctypes.c_int), ("x_nchw", ctypes.c_int),
-                ("in_scale", ctypes.c_void_p), ("in_shift", ctypes.c_void_p), ("w_scale", ctypes.c_void_p)]
-
-
-def _dp(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 # SplitWeight's default form: three bf16 pieces (exact cut, no scale needed).  The frame path binds its fp32 convolutions with
@@ -1092,7 +1095,7 @@ class SplitWeight(object):
                 raise LsfaError("SplitWeight: Cin=%d must be a multiple of 32, Cout=%d of 64" % (self.cin, self.cout))
             self.w_exp, self.frag, self.w_kc = 0, None, w_kc
             return
-        need = lib().lsfa_conv_weight_bytes(_ci(self.cout), _ci(self.kh), _ci(self.kw), _ci(self.cin), _ci(self.pieces))
+        need = lib().lsfa_conv_weight_bytes(self.cout, self.kh, self.kw, self.cin, self.pieces)
         if need == 0:
             raise LsfaError("SplitWeight: Cin=%d must be a multiple of 32, Cout=%d of 64, pieces=%d one of 1, 2, 3" % (self.cin, self.cout, self.pieces))
         self.w_exp, self.w_scale = 0, None
@@ -1110,16 +1113,16 @@ class SplitWeight(object):
             self.w_exp_pc = e
             self.w_scale = torch.ldexp(torch.ones(self.cout, dtype=torch.float32, device=weight.device), -e).contiguous()
             with torch.cuda.device(weight.device):
-                _check(lib().lsfa_conv_weights_pc(_ptr(w_kc), _ci(self.cout), _ci(self.kh), _ci(self.kw), _ci(self.cin), _ptr(e), _ptr(self.frag),
-                                                  _stream()), "lsfa_conv_weights_pc")
+                _check(lib().lsfa_conv_weights_pc(_ptr(w_kc), self.cout, self.kh, self.kw, self.cin, _ptr(e), _ptr(self.frag), _stream()),
+                       "lsfa_conv_weights_pc")
             return
         if self.pieces == 2:
             amax = float(weight.abs().max().item())              # bind time: a host synchronisation is fine here
             self.w_exp = 0 if not (amax > 0 and math.isfinite(amax)) else 13 - int(math.floor(math.log2(amax)))
             self.w_exp = max(-100, min(100, self.w_exp))
         with torch.cuda.device(weight.device):
-            _check(lib().lsfa_conv_weights(_ptr(w_kc), _ci(self.cout), _ci(self.kh), _ci(self.kw), _ci(self.cin), _ci(self.pieces),
-                                           _ci(self.w_exp), _ptr(self.frag), _stream()), "lsfa_conv_weights")
+            _check(lib().lsfa_conv_weights(_ptr(w_kc), self.cout, self.kh, self.kw, self.cin, self.pieces, self.w_exp, _ptr(self.frag), _stream()),
+                   "lsfa_conv_weights")
 
 
 @_on_tensor_device
@@ -1129,31 +1132,29 @@ def amax_partial(x, out=None):
     x = _f32c(x, "x")
     if out is None:
         out = torch.empty(AMAX_SLOTS, device=x.device, dtype=torch.float32)
-    _check(lib().lsfa_amax_partial(_ptr(x), ctypes.c_longlong(x.numel()), _ptr(out), _stream()), "lsfa_amax_partial")
+    _check(lib().lsfa_amax_partial(_ptr(x), x.numel(), _ptr(out), _stream()), "lsfa_amax_partial")
     return out
 
 
-def amax_slots(n, device):
-    """n zeroed amax_out slot arrays (n, 256) - uint32 bit patterns of non-negative floats, readable as float32 through .view()
-    (cleared by lsfa_copy_many's zero-fill job on the current stream: no PyTorch kernel in a captured frame section)"""
-    t = torch.empty((n, AMAX_SLOTS), dtype=torch.int32, device=device)
+def _zeros(shape, dtype, device):
+    """torch.zeros cleared by lsfa_copy_many's zero-fill job on the current stream: no PyTorch kernel in a captured frame section"""
+    t = torch.empty(shape, dtype=dtype, device=device)
     if t.is_cuda:
         with torch.cuda.device(t.device):
             copy_many([(t, None)])
     else:
         t.zero_()
     return t
+
+
+def amax_slots(n, device):
+    """n zeroed amax_out slot arrays (n, 256) - uint32 bit patterns of non-negative floats, readable as float32 through .view()"""
+    return _zeros((n, AMAX_SLOTS), torch.int32, device)
 
 
 def zeros_f32(shape, device):
-    """torch.zeros(shape, float32) cleared by lsfa_copy_many's zero-fill job (see amax_slots)"""
-    t = torch.empty(shape, dtype=torch.float32, device=device)
-    if t.is_cuda:
-        with torch.cuda.device(t.device):
-            copy_many([(t, None)])
-    else:
-        t.zero_()
-    return t
+    """torch.zeros(shape, float32) (see _zeros)"""
+    return _zeros(shape, torch.float32, device)
 
 
 def new_status(device):
@@ -1176,14 +1177,14 @@ def _conv_desc(x, sw, N, H, W, y_ptr, x_offset=0, lda=0, cin=None, ldy=0, bias=N
     convolution's own output grid, no view)"""
     d = ConvDesc()
     d.x, d.lda, d.N, d.H, d.W, d.Cin = x.data_ptr() + x_offset, lda, N, H, W, sw.cin if cin is None else cin
-    d.wfrag, d.pieces, d.w_exp, d.amax_in = _dp(sw.frag), sw.pieces, sw.w_exp, _dp(amax_in)
-    d.bias, d.Cout, d.kh, d.kw, d.stride, d.pad_h, d.pad_w, d.dil = _dp(bias), sw.cout, sw.kh, sw.kw, stride, pad[0], pad[1], dil
-    d.act, d.y_nchw, d.residual, d.y, d.ldy = int(act), int(nchw), _dp(residual), y_ptr, ldy
-    d.y2, d.scale2, d.shift2, d.amax_out, d.status = _dp(out2), _dp(scale2), _dp(shift2), _dp(amax_out), _dp(status)
+    d.wfrag, d.pieces, d.w_exp, d.amax_in = _ptr(sw.frag), sw.pieces, sw.w_exp, _ptr(amax_in)
+    d.bias, d.Cout, d.kh, d.kw, d.stride, d.pad_h, d.pad_w, d.dil = _ptr(bias), sw.cout, sw.kh, sw.kw, stride, pad[0], pad[1], dil
+    d.act, d.y_nchw, d.residual, d.y, d.ldy = int(act), int(nchw), _ptr(residual), y_ptr, ldy
+    d.y2, d.scale2, d.shift2, d.amax_out, d.status = _ptr(out2), _ptr(scale2), _ptr(shift2), _ptr(amax_out), _ptr(status)
     d.Ho, d.Wo = grid
     d.out_H, d.out_W, d.out_sy, d.out_sx = view
     d.prof_tag, d.x_nchw = prof_tag, int(x_nchw)
-    d.in_scale, d.in_shift, d.w_scale = _dp(in_scale), _dp(in_shift), _dp(getattr(sw, 'w_scale', None))
+    d.in_scale, d.in_shift, d.w_scale = _ptr(in_scale), _ptr(in_shift), _ptr(getattr(sw, 'w_scale', None))
     return d
 
 
@@ -1200,7 +1201,7 @@ def _conv_launch(who, x, sw, N, H, W, y_ptr, **desc):
         outs = 1 + (1 if d.residual else 0) + (1 if d.y2 else 0)
         nbytes = 4.0 * N * H * W * d.Cin + 2.0 * sw.pieces * sw.cout * sw.kh * sw.kw * d.Cin + 4.0 * outs * N * Ho * Wo * sw.cout
         _count_conv_launch(_plan_kernel_name(d), 2.0 * N * Ho * Wo * sw.real_cout * sw.real_cin * sw.kh * sw.kw, nbytes)
-    _check(lib().lsfa_conv_fwd(ctypes.byref(d), _ptr(ws), ctypes.c_size_t(need), _stream()), who)
+    _check(lib().lsfa_conv_fwd(ctypes.byref(d), _ptr(ws), need, _stream()), who)
 
 
 def _conv_exact(x, sw, bias, stride, pad, dil, act, out, residual, out2, scale2, shift2, nchw, x_nchw, in_scale, in_shift):
@@ -1339,7 +1340,7 @@ def deconv_phase_weights(wt, cin_pad=None, pieces=None):
     pieces = int(DEFAULT_PIECES if pieces is None else pieces)
     if pieces == 0:
         pieces = 3      # exact-fp32 reference mode: the four-phase launch exists on the split kernels only; three bf16 pieces cut the operands exactly
-    per = lib().lsfa_conv_weight_bytes(_ci(cout), _ci(2), _ci(2), _ci(cpad), _ci(pieces))
+    per = lib().lsfa_conv_weight_bytes(cout, 2, 2, cpad, pieces)
     if per == 0:
         raise LsfaError("deconv_phase_weights: Cin=%d must be a multiple of 32 and Cout=%d of 64" % (cpad, cout))
     frag4 = torch.empty(4 * per, dtype=torch.uint8, device=wt.device)
@@ -1358,8 +1359,8 @@ def deconv_phase_weights(wt, cin_pad=None, pieces=None):
             sw.real_cout, sw.real_cin = cout, cin
             sw.frag = frag4[(py * 2 + px) * per:(py * 2 + px + 1) * per]
             with torch.cuda.device(wt.device):
-                _check(lib().lsfa_conv_weights(_ptr(_f32c(conv_weight_kc(wp), "weight")), _ci(cout), _ci(2), _ci(2), _ci(cpad), _ci(pieces),
-                                               _ci(w_exp), _ptr(sw.frag), _stream()), "lsfa_conv_weights")
+                _check(lib().lsfa_conv_weights(_ptr(_f32c(conv_weight_kc(wp), "weight")), cout, 2, 2, cpad, pieces, w_exp, _ptr(sw.frag), _stream()),
+                       "lsfa_conv_weights")
             out.append(sw)
     out.frag4, out.pieces, out.w_exp = frag4, pieces, w_exp
     return out
@@ -1383,7 +1384,7 @@ def deconv4x4s2_crop(x, sw4, bias, out, c0=0, act=0, amax_in=None, amax_out=None
         raise LsfaError("deconv4x4s2_crop: the phase weights must come from hip.deconv_phase_weights (one allocation)")
     if amax_in is None and sw4.pieces == 2:
         amax_in = amax_partial(x)
-    need = lib().lsfa_deconv4x4s2_crop_workspace_bytes(_ci(N), _ci(Hi), _ci(Wi), _ci(cin), _ci(cout), _ci(Hc), _ci(Wc), _ci(sw4.pieces))
+    need = lib().lsfa_deconv4x4s2_crop_workspace_bytes(N, Hi, Wi, cin, cout, Hc, Wc, sw4.pieces)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
     for i, s in enumerate(sw4):      # four phases, ONE launch
         _count_conv(N, (Hc + 1) // 2, (Wc + 1) // 2, s.real_cout, s.real_cin, 2, 2, sw4.pieces, launches=1 if i == 0 else 0)
@@ -1391,21 +1392,21 @@ def deconv4x4s2_crop(x, sw4, bias, out, c0=0, act=0, amax_in=None, amax_out=None
         _count_conv_launch("conv_ring_kernel (the four phases of a stride-2 transposed convolution)",
                            sum(2.0 * N * ((Hc + 1) // 2) * ((Wc + 1) // 2) * s.real_cout * s.real_cin * 4 for s in sw4),
                            4.0 * N * Hi * Wi * cin + 4 * 2.0 * sw4.pieces * cout * 4 * cin + 4.0 * N * Hc * Wc * cout)
-    _check(lib().lsfa_deconv4x4s2_crop_fwd(_ptr(x), _ci(L), _ci(N), _ci(Hi), _ci(Wi), _ci(cin), _ptr(frags), _ci(sw4.pieces), _ci(sw4.w_exp),
-                                           _ptr(amax_in), _ptr(bias), _ci(cout), _ci(act), _vp(out.data_ptr() + 4 * c0), _ci(Lout), _ci(Hc), _ci(Wc),
-                                           _ptr(amax_out), _ptr(status), _ptr(ws), ctypes.c_size_t(need), _stream()), "lsfa_deconv4x4s2_crop_fwd")
+    _check(lib().lsfa_deconv4x4s2_crop_fwd(_ptr(x), L, N, Hi, Wi, cin, _ptr(frags), sw4.pieces, sw4.w_exp, _ptr(amax_in), _ptr(bias), cout, act,
+                                           out.data_ptr() + 4 * c0, Lout, Hc, Wc, _ptr(amax_out), _ptr(status), _ptr(ws), need, _stream()),
+           "lsfa_deconv4x4s2_crop_fwd")
     return out
 
 
 def conv_plan_override(kernel=0, nt=0, st=0, slices=0):
     """lsfa_conv_plan_override (lab): force the ring kernel (kernel=1), its tile width / ring depth / K slices; zeros = the plan decides"""
-    _check(lib().lsfa_conv_plan_override(_ci(kernel), _ci(nt), _ci(st), _ci(slices)), "lsfa_conv_plan_override")
+    _check(lib().lsfa_conv_plan_override(kernel, nt, st, slices), "lsfa_conv_plan_override")
 
 
 def conv_order_override(tile_order=-1, k_order=-1):
     """lsfa_conv_order_override (lab / tests): workgroup -> tile numbering (0 pixel tile fastest, 1 channel tile fastest) and the ring kernel's walk
     of K (0 tap by tap, 1 channel chunk by channel chunk); -1 = the default"""
-    _check(lib().lsfa_conv_order_override(_ci(tile_order), _ci(k_order)), "lsfa_conv_order_override")
+    _check(lib().lsfa_conv_order_override(tile_order, k_order), "lsfa_conv_order_override")
 
 
 class MotionVectorAccumulator(object):
@@ -1421,7 +1422,7 @@ class MotionVectorAccumulator(object):
     def __init__(self, width, height, device='cuda:0'):
         self.width, self.height, self.device = int(width), int(height), torch.device(device)
         self._bufs = [torch.empty((height, width, 2), dtype=torch.int32, device=self.device) for _ in range(2)]
-        self._ws = torch.empty(lib().lsfa_mv_workspace_bytes(_ci(width), _ci(height)), dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(lib().lsfa_mv_workspace_bytes(width, height), dtype=torch.uint8, device=self.device)
         self._cur = 0
         self.reset()
 
@@ -1431,8 +1432,7 @@ class MotionVectorAccumulator(object):
 
     def reset(self):
         with torch.cuda.device(self.device):
-            _check(lib().lsfa_mv_identity(_ptr(self._bufs[self._cur]), _ci(self.width), _ci(self.height), _stream()),
-                   "lsfa_mv_identity")
+            _check(lib().lsfa_mv_identity(_ptr(self._bufs[self._cur]), self.width, self.height, _stream()), "lsfa_mv_identity")
 
     def add_frame(self, mvs, max_block_area=None):
         """mvs (n, 7) int32.  max_block_area: an upper bound of w*h over the blocks (256 for 16x16 macroblocks);
@@ -1447,15 +1447,14 @@ class MotionVectorAccumulator(object):
         mvs = mvs.to(self.device).contiguous()
         old, new = self._bufs[self._cur], self._bufs[1 - self._cur]
         with torch.cuda.device(self.device):
-            _check(lib().lsfa_mv_accumulate(_ptr(mvs), _ci(n), _ci(area), _ptr(old), _ptr(new), _ci(self.width),
-                                            _ci(self.height), _ptr(self._ws), ctypes.c_size_t(self._ws.numel()), _stream()),
-                   "lsfa_mv_accumulate")
+            _check(lib().lsfa_mv_accumulate(_ptr(mvs), n, area, _ptr(old), _ptr(new), self.width, self.height, _ptr(self._ws), self._ws.numel(),
+                                            _stream()), "lsfa_mv_accumulate")
         self._cur = 1 - self._cur
 
     def motion_vectors(self):
         mv = torch.empty((self.height, self.width, 2), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            _check(lib().lsfa_mv_field(_ptr(self.accu), _ci(self.width), _ci(self.height), _ptr(mv), _stream()), "lsfa_mv_field")
+            _check(lib().lsfa_mv_field(_ptr(self.accu), self.width, self.height, _ptr(mv), _stream()), "lsfa_mv_field")
         return mv
 
     def residual(self, bgr_cur, bgr_ref):
@@ -1465,8 +1464,8 @@ class MotionVectorAccumulator(object):
         bgr_cur, bgr_ref = bgr_cur.to(self.device).contiguous(), bgr_ref.to(self.device).contiguous()
         res = torch.empty((self.height, self.width, 3), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            _check(lib().lsfa_mv_residual(_ptr(bgr_cur), _ptr(bgr_ref), _ptr(self.accu), _ci(self.width), _ci(self.height),
-                                          _ptr(res), _stream()), "lsfa_mv_residual")
+            _check(lib().lsfa_mv_residual(_ptr(bgr_cur), _ptr(bgr_ref), _ptr(self.accu), self.width, self.height, _ptr(res), _stream()),
+                   "lsfa_mv_residual")
         return res
 
     def network_inputs(self, bgr_cur, bgr_ref, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16):
@@ -1491,7 +1490,7 @@ def luma_u8(bgr, out=None):
         out = torch.empty((H, W), dtype=torch.uint8, device=bgr.device)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or out.device != bgr.device or not out.is_contiguous():
         raise LsfaError("luma_u8: out must be a contiguous (%d, %d) uint8 tensor on %s" % (H, W, bgr.device))
-    _check(lib().lsfa_luma_u8(_ptr(bgr), _ci(W), _ci(H), _ptr(out), _stream()), "lsfa_luma_u8")
+    _check(lib().lsfa_luma_u8(_ptr(bgr), W, H, _ptr(out), _stream()), "lsfa_luma_u8")
     return out
 
 
@@ -1515,8 +1514,8 @@ def mv_estimate(luma_cur, luma_ref, search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_
     for t, shape in ((out, (mbh * mbw, 7)), (sad_out, (mbh, mbw))):
         if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != luma_cur.device or not t.is_contiguous()):
             raise LsfaError("mv_estimate: an output buffer is not a contiguous %s int32 tensor on %s" % (shape, luma_cur.device))
-    _check(lib().lsfa_mv_estimate(_ptr(luma_cur), _ptr(luma_ref), _ci(W), _ci(H), _ci(int(search)), _ci(int(lam)), _ci(int(max_sad)), _ptr(out),
-                                  _ptr(sad_out), _stream()), "lsfa_mv_estimate")
+    _check(lib().lsfa_mv_estimate(_ptr(luma_cur), _ptr(luma_ref), W, H, int(search), int(lam), int(max_sad), _ptr(out), _ptr(sad_out), _stream()),
+           "lsfa_mv_estimate")
     return (out, sad_out) if return_sad else out
 
 
@@ -1626,22 +1625,20 @@ class MotionEstimator(object):
         """`motion_vector` (1, 2, h, w) and `res_diff` (1, 3, h, w) of the current frame against the key frame, as
         MotionVectorAccumulator.network_inputs builds them (lsfa_mv_field, lsfa_mv_residual, lsfa_transform_mv_res), into buffers of its own."""
         bgr_cur, bgr_key = self._frame(bgr_cur, 'network_inputs'), self._frame(bgr_key, 'network_inputs')
-        import numpy as _np
         H, W = self.height, self.width
-        h1, w1 = int(_np.rint(H * float(im_scale))), int(_np.rint(W * float(im_scale)))       # cvRound
-        oh, ow = -(-h1 // rcnn_stride), -(-w1 // rcnn_stride)
+        h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
+        oh, ow = ph // rcnn_stride, pw // rcnn_stride
         if (oh, ow) not in self._out:
             self._out[(oh, ow)] = (torch.empty((1, 2, oh, ow), device=self.device, dtype=torch.float32),
                                    torch.empty((1, 3, oh, ow), device=self.device, dtype=torch.float32))
         out_mv, out_res = self._out[(oh, ow)]
-        means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
         L = lib()
         with torch.cuda.device(self.device):
-            _check(L.lsfa_mv_field(_ptr(self.acc.accu), _ci(W), _ci(H), _ptr(self._mv), _stream()), "lsfa_mv_field")
-            _check(L.lsfa_mv_residual(_ptr(bgr_cur), _ptr(bgr_key), _ptr(self.acc.accu), _ci(W), _ci(H), _ptr(self._res), _stream()), "lsfa_mv_residual")
-            _check(L.lsfa_transform_mv_res(_ptr(self._mv), _ptr(self._res), _ci(1 | 2), _ci(H), _ci(W), ctypes.c_double(float(im_scale)), _ci(h1), _ci(w1),
-                                           _ci(int(rcnn_stride)), means, ctypes.c_double(float(pixel_scale)), _ptr(out_mv), _ptr(out_res), _ci(oh), _ci(ow),
-                                           _stream()), "lsfa_transform_mv_res")
+            _check(L.lsfa_mv_field(_ptr(self.acc.accu), W, H, _ptr(self._mv), _stream()), "lsfa_mv_field")
+            _check(L.lsfa_mv_residual(_ptr(bgr_cur), _ptr(bgr_key), _ptr(self.acc.accu), W, H, _ptr(self._res), _stream()), "lsfa_mv_residual")
+            _check(L.lsfa_transform_mv_res(_ptr(self._mv), _ptr(self._res), 1 | 2, H, W, float(im_scale), h1, w1, int(rcnn_stride),
+                                           _means(pixel_means), float(pixel_scale), _ptr(out_mv), _ptr(out_res), oh, ow, _stream()),
+                   "lsfa_transform_mv_res")
         return out_mv, out_res
 
 
@@ -1651,7 +1648,7 @@ def prof_enable(on=True, ops=None):
     mask = 0
     if on:
         mask = -1 if ops is None else sum(1 << OP_NAMES.index(o) for o in ops)
-    _check(lib().lsfa_prof_enable(_ci(mask)), "lsfa_prof_enable")
+    _check(lib().lsfa_prof_enable(mask), "lsfa_prof_enable")
 
 
 def prof_read():
