@@ -576,6 +576,31 @@ int lsfa_luma_u8(const unsigned char* bgr, int width, int height, unsigned char*
 int lsfa_mv_estimate(const unsigned char* luma_cur, const unsigned char* luma_ref, int width, int height,
                      int search, int lambda, int max_sad, int* mvs /* (mbh*mbw, 7) */, int* sad /* may be NULL */,
                      void* stream);
+/* A segment at a time: the inputs of every non-key frame behind a key frame in two launches, from frames alone.
+ * lsfa_mv_estimate_chain: luma holds n_chains * (n_frames + 1) planes (H, W) uint8, plane_stride bytes apart (a multiple of 4 that holds a
+ *   plane; the base 4-byte aligned); plane 0 of a chain is its key frame.  Pair (c, f), f = 1..n_frames, is lsfa_mv_estimate(plane f,
+ *   plane f - 1) of chain c, bit for bit: mvs (n_chains, n_frames, mbh * mbw, 7), sad (n_chains, n_frames, mbh, mbw) or NULL.  One launch
+ *   (the one-workgroup-per-macroblock grid times pairs), no workspace.
+ * lsfa_mv_segment_inputs: mvs as lsfa_mv_estimate_chain wrote them; bgr holds n_chains * (n_frames + 1) packed (H, W, 3) uint8 frames,
+ *   frame_stride bytes apart, frame 0 of a chain its key frame.  out_mv (n_frames, n_chains, 2, out_h, out_w) and out_res (n_frames,
+ *   n_chains, 3, out_h, out_w) float32, frame-major: out_*[f - 1][c] equals lsfa_mv_identity, lsfa_mv_accumulate of chain c's frames 1..f
+ *   (max_block_area 256), lsfa_mv_field, lsfa_mv_residual(cur = frame f, ref = frame 0) and lsfa_transform_mv_res(flags = 1 | 2, ...) bit
+ *   for bit; im_scale .. pixel_scale, out_h, out_w as lsfa_transform_mv_res takes and checks them.  One launch, no workspace, no
+ *   full-resolution map, no atomics: the source pixel of p in frame f is found by walking back, q = p; for k = f .. 1: q' = q + (row[3] -
+ *   row[5], row[4] - row[6]) with row = mvs[c][k - 1][(q.y >> 4) * mbw + (q.x >> 4)], the step not taken where q' lies outside the frame
+ *   (the accumulation's own rule); then mv = p - q, res = cur[p] - key[q], and transform_mv_res_kernel's arithmetic on the (at most 16)
+ *   source pixels an output element reads.
+ *   CONTRACT of mvs: the full-grid rows of lsfa_mv_estimate[_chain] - one row per macroblock in grid order, destination centres at
+ *   16 b + 8, so that the destination blocks partition the frame and the block that contains a pixel IS its last writer.  Other rows
+ *   (a decoder's block lists: use lsfa_mv_accumulate) give the result of the walk as stated, defined and memory-safe, but not the
+ *   accumulation's. */
+int lsfa_mv_estimate_chain(const unsigned char* luma, long long plane_stride, int n_chains, int n_frames, int width, int height,
+                           int search, int lambda, int max_sad, int* mvs /* (n_chains, n_frames, mbh*mbw, 7) */,
+                           int* sad /* (n_chains, n_frames, mbh, mbw) or NULL */, void* stream);
+int lsfa_mv_segment_inputs(const int* mvs, const unsigned char* bgr, long long frame_stride, int n_chains, int n_frames, int width, int height,
+                           double im_scale, int h1, int w1, int rcnn_stride, const double* pixel_means_bgr_host, double pixel_scale,
+                           float* out_mv /* (n_frames, n_chains, 2, oh, ow) */, float* out_res /* (n_frames, n_chains, 3, oh, ow) */,
+                           int out_h, int out_w, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip): the planes a decoder hands over - libav, the VCN decode engines, a raw .yuv dump - straight to

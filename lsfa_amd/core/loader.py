@@ -6,6 +6,12 @@ video, 1 = key frame (every TEST.KEY_FRAME_INTERVAL frames AND the last frame of
 for feat_key_old / feat_key (:138-139); `data_key` persists across videos while the first frame of
 each video overrides `data_key_old` with itself (:119-122).  Frames come from the roidb
 entry's clip generator (lsfa_amd.utils.synthetic) and live on the device.
+
+estimate_mv, or config.TEST.ESTIMATE_MV where it is None (not in the reference; default None = the clip's own `motion_vector` /
+`res_diff`): a dict of
+hip.SegmentMotionEstimator's parameters (search, lam, max_sad).  When a key frame is handed out, the uint8
+frames of it and of the non-key frames behind it are uploaded and the whole segment's inputs are estimated from
+them on the current stream, in three launches; each of those non-key frames then receives its slice.
 """
 import numpy as np
 import torch
@@ -20,8 +26,13 @@ class DataBatch(object):
 
 
 class TestLoader(object):
-    def __init__(self, roidb, config, batch_size=1, shuffle=False, has_rpn=False, device='cuda:0'):
+    def __init__(self, roidb, config, batch_size=1, shuffle=False, has_rpn=False, device='cuda:0', estimate_mv=None):
         assert batch_size == 1 and not shuffle
+        if estimate_mv is None:           # the drivers that build their loader themselves (test_rcnn) are reached through the config
+            estimate_mv = config.TEST.get('ESTIMATE_MV')
+        self.estimate_mv = None if estimate_mv is None else dict(estimate_mv)
+        self._estimators = {}           # (width, height) -> SegmentMotionEstimator
+        self._segment = None            # ((roidb index, key frame), n, mv (n, 1, 2, h, w), res (n, 1, 3, h, w)) of the segment under way
         self.cfg, self.roidb, self.batch_size, self.shuffle, self.has_rpn = config, roidb, batch_size, shuffle, has_rpn
         self.device = device
         self.size = int(np.sum([x['frame_seg_len'] for x in self.roidb]))
@@ -94,8 +105,52 @@ class TestLoader(object):
         data = self._ahead.pop((self.cur_roidb_index, f), None)      # an image upcoming_key_frames already produced: the SAME tensor
         if data is None:
             data = clip.frame(f, self.device)
-        return {'data': data, 'im_info': torch.from_numpy(clip.im_info()).to(self.device),
-                'motion_vector': clip.motion_vector(f, key_f, self.device), 'res_diff': clip.res_diff(f, self.device)}
+        d = {'data': data, 'im_info': torch.from_numpy(clip.im_info()).to(self.device)}
+        if self.estimate_mv is not None and self._is_non_key(entry, f, key_f):
+            d['motion_vector'], d['res_diff'] = self._estimated(entry, f, key_f)
+        else:
+            if self.estimate_mv is not None:
+                self._estimate_segment(entry, f)
+            d['motion_vector'], d['res_diff'] = clip.motion_vector(f, key_f, self.device), clip.res_diff(f, self.device)
+        return d
+
+    @staticmethod
+    def _is_non_key(entry, f, key_f):
+        """get_batch's rule: frame key_f is a key frame and so is the video's last"""
+        return f != key_f and f + 1 != entry['frame_seg_len']
+
+    def _segment_estimator(self, width, height):
+        """the estimator of a frame size, built once: a segment holds at most KEY_FRAME_INTERVAL - 1 non-key frames of one clip"""
+        from lsfa_amd import hip
+        return hip.SegmentMotionEstimator(width, height, frames=max(self.cfg.TEST.KEY_FRAME_INTERVAL - 1, 1), clips=1, device=self.device,
+                                          **self.estimate_mv)
+
+    def _estimate_segment(self, entry, key_f):
+        """Key frame key_f is being handed out: estimate the inputs of the non-key frames behind it - key_f + 1 .. key_f + n with
+        n = KEY_FRAME_INTERVAL - 1, fewer in front of the video's last frame (a key frame) - in one SegmentMotionEstimator.segment call on the
+        current stream.  The result is copied out of the estimator's buffers: a pipeline that groups key frames holds a segment's inputs
+        while the next segment is estimated."""
+        tag = (self.cur_roidb_index, key_f)
+        if self._segment is not None and self._segment[0] == tag:
+            return                       # get_batch runs twice for the very first frame (the constructor's shape probe)
+        self._segment = None
+        n = min(key_f + self.cfg.TEST.KEY_FRAME_INTERVAL - 1, entry['frame_seg_len'] - 2) - key_f
+        if n < 1:
+            return
+        clip = entry['clip']
+        key = (clip.width, clip.height)
+        if key not in self._estimators:
+            self._estimators[key] = self._segment_estimator(clip.width, clip.height)
+        stack = torch.stack([clip.frame_u8(g) for g in range(key_f, key_f + n + 1)]).unsqueeze(0).to(self.device)
+        mv, res = self._estimators[key].segment(stack, float(clip.im_info()[0, 2]), self.cfg.network.PIXEL_MEANS, self.cfg.network.PIXEL_SCALE)
+        self._segment = (tag, n, mv.clone(), res.clone())
+
+    def _estimated(self, entry, f, key_f):
+        seg = self._segment
+        if seg is None or seg[0] != (self.cur_roidb_index, key_f) or not 1 <= f - key_f <= seg[1]:
+            raise RuntimeError("TestLoader: frame %d of video %d is not part of the segment estimated behind key frame %s" %
+                               (f, self.cur_roidb_index, None if seg is None else seg[0]))
+        return seg[2][f - key_f - 1], seg[3][f - key_f - 1]
 
     def upcoming_key_frames(self, n):
         """Call right after a KEY frame was returned: the images of the next `n` key frames of the same video (fewer near its end), for a

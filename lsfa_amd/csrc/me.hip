@@ -150,13 +150,15 @@ __device__ __forceinline__ unsigned long long search_units(const uint32_t* __res
   return best;
 }
 
-__global__ __launch_bounds__(kThreads) void me_search_kernel(const unsigned char* __restrict__ cur, const unsigned char* __restrict__ ref, MeArgs a,
-                                                             int* __restrict__ mvs, int* __restrict__ sad_out) {
+// one workgroup's search: macroblock `blk` of the pair (cur, ref); the row goes to mvs[blk], the SAD to sad_out[blk].  `rot` only picks
+// the wave the units are dealt out from first (it cannot change the result: the minimum is over all units)
+__device__ __forceinline__ void me_search_block(const unsigned char* __restrict__ cur, const unsigned char* __restrict__ ref, const MeArgs& a,
+                                                int* __restrict__ mvs, int* __restrict__ sad_out, int blk, unsigned rot) {
   __shared__ uint4 s_blk[16];                       // the block: 16 rows of 16 bytes, uncovered bytes 0
   __shared__ uint32_t s_win[kMaxWinDwords];         // the window: (16 + 2R) rows of 4 + G dwords, bytes outside the frame 0
   __shared__ unsigned long long s_best[kThreads / 64];
   const int tid = threadIdx.x;
-  const int by = blockIdx.x / a.mbw, bx = blockIdx.x - by * a.mbw;
+  const int by = blk / a.mbw, bx = blk - by * a.mbw;
   const int x0 = 16 * bx, y0 = 16 * by;
   const int bw = min(16, a.W - x0), bh = min(16, a.H - y0);
   const int R = a.R, wsd = 4 + a.G, rows = 16 + 2 * R;
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void me_search_kernel(const unsigned char
     mask[k] = nb >= 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1u);
   }
   // the units are dealt out from a different wave in each workgroup: the last, partly filled round then lands on different SIMDs
-  const int first_unit = (tid + 64 * (int)(blockIdx.x & 3u)) & (kThreads - 1);
+  const int first_unit = (tid + 64 * (int)(rot & 3u)) & (kThreads - 1);
   unsigned long long best;
   if (bw == 16 && bh == 16) best = search_units<Sad4Packed, true>(s_win, c, mask, a, x0, y0, bw, bh, first_unit);
   else if (bw == 16) best = search_units<Sad4Packed, false>(s_win, c, mask, a, x0, y0, bw, bh, first_unit);
@@ -205,11 +207,27 @@ __global__ __launch_bounds__(kThreads) void me_search_kernel(const unsigned char
     const int len = (int)((best >> 14) & 127ull);
     const int sad = (int)(best >> 21) - a.lambda * len;
     if (a.max_sad > 0 && sad > a.max_sad) { dx = 0; dy = 0; }
-    int* row = mvs + (size_t)blockIdx.x * 7;
+    int* row = mvs + (size_t)blk * 7;
     row[0] = -1; row[1] = 16; row[2] = 16;
     row[3] = x0 + 8 + dx; row[4] = y0 + 8 + dy; row[5] = x0 + 8; row[6] = y0 + 8;
-    if (sad_out) sad_out[blockIdx.x] = sad;
+    if (sad_out) sad_out[blk] = sad;
   }
+}
+
+__global__ __launch_bounds__(kThreads) void me_search_kernel(const unsigned char* __restrict__ cur, const unsigned char* __restrict__ ref, MeArgs a,
+                                                             int* __restrict__ mvs, int* __restrict__ sad_out) {
+  me_search_block(cur, ref, a, mvs, sad_out, (int)blockIdx.x, blockIdx.x);
+}
+
+// me_search_chain_kernel: the same search for every pair (frame f, frame f - 1), f = 1..n_frames, of n_chains stacks of n_frames + 1 planes in
+// one grid: workgroup w is macroblock w % blocks of pair w / blocks, and the pair index only selects two base pointers and the pair's slice
+// of the outputs.  The first-unit rotation follows the workgroup's index in the whole grid, as the single-pair kernel's does.
+__global__ __launch_bounds__(kThreads) void me_search_chain_kernel(const unsigned char* __restrict__ luma, long long plane_stride, int n_frames, int blocks,
+                                                                   MeArgs a, int* __restrict__ mvs, int* __restrict__ sad_out) {
+  const int pair = (int)(blockIdx.x / (unsigned)blocks), blk = (int)(blockIdx.x - (unsigned)pair * (unsigned)blocks);
+  const int c = pair / n_frames, f = pair - c * n_frames + 1;
+  const unsigned char* cur = luma + ((size_t)c * (n_frames + 1) + f) * (size_t)plane_stride;
+  me_search_block(cur, cur - plane_stride, a, mvs + (size_t)pair * blocks * 7, sad_out ? sad_out + (size_t)pair * blocks : nullptr, blk, blockIdx.x);
 }
 
 }  // namespace
@@ -228,27 +246,56 @@ extern "C" int lsfa_luma_u8(const unsigned char* bgr, int width, int height, uns
   return LSFA_OK;
 }
 
+namespace {
+
+// the search's arguments, checked: what lsfa_mv_estimate and lsfa_mv_estimate_chain share
+int me_args(const char* who, int width, int height, int search, int lambda, int max_sad, MeArgs* a) {
+  LSFA_REQUIRE(width > 0 && height > 0 && (long)width * height < (1L << 30), "%s: bad frame size %d x %d", who, width, height);
+  LSFA_REQUIRE(search >= 1 && search <= kMaxSearch, "%s: search %d is outside 1..%d", who, search, kMaxSearch);
+  LSFA_REQUIRE(lambda >= 0 && lambda <= kMaxLambda, "%s: lambda %d is outside 0..%d", who, lambda, kMaxLambda);
+  LSFA_REQUIRE(max_sad >= 0, "%s: max_sad %d is negative (0 switches it off)", who, max_sad);
+  a->W = width; a->H = height;
+  a->mbw = ceil_div(width, 16);
+  a->R = search;
+  a->G = ceil_div(2 * search + 1, 4);
+  a->lambda = lambda;
+  a->max_sad = max_sad;
+  a->total = (long)width * height;
+  return LSFA_OK;
+}
+
+}  // namespace
+
 extern "C" int lsfa_mv_estimate(const unsigned char* luma_cur, const unsigned char* luma_ref, int width, int height, int search, int lambda,
                                 int max_sad, int* mvs, int* sad, void* stream) {
   LSFA_REQUIRE(luma_cur && luma_ref && mvs, "lsfa_mv_estimate: NULL argument");
-  LSFA_REQUIRE(width > 0 && height > 0 && (long)width * height < (1L << 30), "lsfa_mv_estimate: bad frame size %d x %d", width, height);
-  LSFA_REQUIRE(search >= 1 && search <= kMaxSearch, "lsfa_mv_estimate: search %d is outside 1..%d", search, kMaxSearch);
-  LSFA_REQUIRE(lambda >= 0 && lambda <= kMaxLambda, "lsfa_mv_estimate: lambda %d is outside 0..%d", lambda, kMaxLambda);
-  LSFA_REQUIRE(max_sad >= 0, "lsfa_mv_estimate: max_sad %d is negative (0 switches it off)", max_sad);
+  MeArgs a;
+  if (const int rc = me_args("lsfa_mv_estimate", width, height, search, lambda, max_sad, &a)) return rc;
   LSFA_REQUIRE(((reinterpret_cast<uintptr_t>(luma_cur) | reinterpret_cast<uintptr_t>(luma_ref)) & 3u) == 0,
                "lsfa_mv_estimate: the luma planes must be 4-byte aligned");
-  MeArgs a;
-  a.W = width; a.H = height;
-  a.mbw = ceil_div(width, 16);
-  a.R = search;
-  a.G = ceil_div(2 * search + 1, 4);
-  a.lambda = lambda;
-  a.max_sad = max_sad;
-  a.total = (long)width * height;
   const int blocks = a.mbw * ceil_div(height, 16);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(LSFA_OP_MV_ESTIMATE, s);
   hipLaunchKernelGGL(me_search_kernel, dim3(blocks), dim3(kThreads), 0, s, luma_cur, luma_ref, a, mvs, sad);
   LSFA_LAUNCH_CHECK("lsfa_mv_estimate");
+  return LSFA_OK;
+}
+
+extern "C" int lsfa_mv_estimate_chain(const unsigned char* luma, long long plane_stride, int n_chains, int n_frames, int width, int height, int search,
+                                      int lambda, int max_sad, int* mvs, int* sad, void* stream) {
+  LSFA_REQUIRE(luma && mvs, "lsfa_mv_estimate_chain: NULL argument");
+  MeArgs a;
+  if (const int rc = me_args("lsfa_mv_estimate_chain", width, height, search, lambda, max_sad, &a)) return rc;
+  LSFA_REQUIRE(n_chains >= 1 && n_frames >= 1, "lsfa_mv_estimate_chain: %d chains of %d frames: both counts must be at least 1", n_chains, n_frames);
+  LSFA_REQUIRE(plane_stride >= a.total && (plane_stride & 3) == 0,
+               "lsfa_mv_estimate_chain: plane stride %lld must hold a %d x %d plane and be a multiple of 4", plane_stride, width, height);
+  LSFA_REQUIRE((reinterpret_cast<uintptr_t>(luma) & 3u) == 0, "lsfa_mv_estimate_chain: the luma planes must be 4-byte aligned");
+  const int blocks = a.mbw * ceil_div(height, 16);
+  const long pairs = (long)n_chains * n_frames;
+  LSFA_REQUIRE(pairs * blocks < (1L << 31), "lsfa_mv_estimate_chain: %ld pairs of %d macroblocks exceed one grid", pairs, blocks);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope prof(LSFA_OP_MV_ESTIMATE, s);
+  hipLaunchKernelGGL(me_search_chain_kernel, dim3((unsigned)(pairs * blocks)), dim3(kThreads), 0, s, luma, plane_stride, n_frames, blocks, a, mvs, sad);
+  LSFA_LAUNCH_CHECK("lsfa_mv_estimate_chain");
   return LSFA_OK;
 }

@@ -1642,6 +1642,192 @@ class MotionEstimator(object):
         return out_mv, out_res
 
 
+def _u8_stack(who, name, t, trailing):
+    """a uint8 CUDA stack (C, F + 1) + trailing whose frames are dense and whose chains lie (F + 1) frames apart -> (C, F, frame stride)"""
+    nd = 2 + len(trailing)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != nd or tuple(t.shape[2:]) != tuple(trailing) or \
+            int(t.shape[0]) < 1 or int(t.shape[1]) < 2:
+        raise LsfaError("%s: %s must be a (C, F + 1, %s) uint8 CUDA stack with C >= 1 and F >= 1, got %s %s" %
+                        (who, name, ", ".join(str(v) for v in trailing), tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
+    C, F1 = int(t.shape[0]), int(t.shape[1])
+    dense = tuple(int(np.prod(trailing[i + 1:])) for i in range(len(trailing)))
+    fs = int(t.stride(1))
+    if tuple(int(s) for s in t.stride()[2:]) != dense or fs < int(np.prod(trailing)) or (C > 1 and int(t.stride(0)) != F1 * fs):
+        raise LsfaError("%s: %s needs dense frames, one stride from frame to frame and chains (F + 1) frames apart; got shape %s strides %s" %
+                        (who, name, tuple(t.shape), tuple(t.stride())))
+    return C, F1 - 1, fs
+
+
+@_on_tensor_device
+def mv_estimate_chain(luma_stack, search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, return_sad=False, out=None, sad_out=None):
+    """lsfa_mv_estimate_chain: a (C, F + 1, H, W) uint8 stack of luma planes on the device, plane 0 of a chain its key frame -> rows
+    (C, F, mbh * mbw, 7) int32, rows[c, f - 1] = mv_estimate(plane f, plane f - 1) of chain c bit for bit; with return_sad also the winners' SAD
+    (C, F, mbh, mbw).  The plane stride is taken from .stride() (a multiple of 4 that holds a plane).  One launch."""
+    who = "mv_estimate_chain"
+    if not isinstance(luma_stack, torch.Tensor) or luma_stack.dim() != 4:
+        raise LsfaError("%s: a (C, F + 1, H, W) uint8 CUDA stack expected, got %s %s" %
+                        (who, tuple(getattr(luma_stack, 'shape', ())), getattr(luma_stack, 'dtype', type(luma_stack))))
+    H, W = int(luma_stack.shape[2]), int(luma_stack.shape[3])
+    C, F, stride = _u8_stack(who, "luma_stack", luma_stack, (H, W))
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    if out is None:
+        out = torch.empty((C, F, mbh * mbw, 7), dtype=torch.int32, device=luma_stack.device)
+    if return_sad and sad_out is None:
+        sad_out = torch.empty((C, F, mbh, mbw), dtype=torch.int32, device=luma_stack.device)
+    for t, shape in ((out, (C, F, mbh * mbw, 7)), (sad_out, (C, F, mbh, mbw))):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != luma_stack.device or not t.is_contiguous()):
+            raise LsfaError("%s: an output buffer is not a contiguous %s int32 tensor on %s" % (who, shape, luma_stack.device))
+    _check(lib().lsfa_mv_estimate_chain(_ptr(luma_stack), stride, C, F, W, H, int(search), int(lam), int(max_sad), _ptr(out), _ptr(sad_out), _stream()),
+           "lsfa_mv_estimate_chain")
+    return (out, sad_out) if return_sad else out
+
+
+@_on_tensor_device
+def mv_segment_inputs(rows, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16, out=None):
+    """lsfa_mv_segment_inputs: rows (C, F, mbh * mbw, 7) int32 as mv_estimate_chain returns them and the (C, F + 1, H, W, 3) uint8 BGR stack
+    they were estimated on (frame 0 of a chain its key frame) -> `motion_vector` (F, C, 2, h, w) and `res_diff` (F, C, 3, h, w) float32,
+    frame-major: [f - 1, c] is what MotionEstimator.network_inputs returns for frame f of chain c, bit for bit.  One launch, no
+    full-resolution map.  The frame stride is taken from .stride().  out: a pair of contiguous float32 tensors of those shapes."""
+    who = "mv_segment_inputs"
+    if not isinstance(bgr_stack, torch.Tensor) or bgr_stack.dim() != 5:
+        raise LsfaError("%s: a (C, F + 1, H, W, 3) uint8 CUDA stack expected, got %s %s" %
+                        (who, tuple(getattr(bgr_stack, 'shape', ())), getattr(bgr_stack, 'dtype', type(bgr_stack))))
+    H, W = int(bgr_stack.shape[2]), int(bgr_stack.shape[3])
+    C, F, stride = _u8_stack(who, "bgr_stack", bgr_stack, (H, W, 3))
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or tuple(rows.shape) != (C, F, mbh * mbw, 7) or rows.device != bgr_stack.device or \
+            not rows.is_contiguous():
+        raise LsfaError("%s: rows must be a contiguous (%d, %d, %d, 7) int32 tensor on %s, got %s %s" %
+                        (who, C, F, mbh * mbw, bgr_stack.device, tuple(getattr(rows, 'shape', ())), getattr(rows, 'dtype', type(rows))))
+    if not float(im_scale) > 0.0 or int(rcnn_stride) < 1:
+        raise LsfaError("%s: im_scale %r must be positive and rcnn_stride %r at least 1" % (who, im_scale, rcnn_stride))
+    rcnn_stride = int(rcnn_stride)
+    h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
+    oh, ow = ph // rcnn_stride, pw // rcnn_stride
+    if out is None:
+        out = (torch.empty((F, C, 2, oh, ow), device=bgr_stack.device, dtype=torch.float32),
+               torch.empty((F, C, 3, oh, ow), device=bgr_stack.device, dtype=torch.float32))
+    out_mv, out_res = out
+    for t, shape in ((out_mv, (F, C, 2, oh, ow)), (out_res, (F, C, 3, oh, ow))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != bgr_stack.device or not t.is_contiguous():
+            raise LsfaError("%s: an output buffer is not a contiguous %s float32 tensor on %s" % (who, shape, bgr_stack.device))
+    _check(lib().lsfa_mv_segment_inputs(_ptr(rows), _ptr(bgr_stack), stride, C, F, W, H, float(im_scale), h1, w1, rcnn_stride, _means(pixel_means),
+                                        float(pixel_scale), _ptr(out_mv), _ptr(out_res), oh, ow, _stream()), "lsfa_mv_segment_inputs")
+    return out_mv, out_res
+
+
+class SegmentMotionEstimator(object):
+    """A key frame and the non-key frames behind it in, the `motion_vector` / `res_diff` of every one of them out - what MotionEstimator builds
+    frame by frame in seven launches each, for a whole segment of `clips` lock-step clips in three: luma of the stack (lsfa_luma_u8; one
+    launch where W * H % 4 == 0, else one per frame), the search of every (frame, previous frame) pair (lsfa_mv_estimate_chain), the inputs
+    (lsfa_mv_segment_inputs).
+
+        sme = SegmentMotionEstimator(width, height, frames=9, clips=1, device=device)
+        mv, res = sme.segment(bgr_stack, im_scale, pixel_means, pixel_scale)      # bgr_stack (C, n + 1, H, W, 3) uint8, frame 0 the key frame
+        mv[f - 1], res[f - 1]                                                      # (C, 2, h, w), (C, 3, h, w): frame f of every clip
+
+    Every buffer is allocated up front for `frames` frames (the outputs at the first call for a scale and a length), nothing is read back
+    and nothing synchronises; all launches sit on the current stream, so a call can be captured in a graph without parallel branches and
+    replayed on new frame contents.  n < frames (the stack's own length, or `n` frames of a longer stack) is the short segment in front of
+    a clip's last frame.  The returned tensors are reused by the next call of the same shape unless `out` supplies others; self.rows
+    (C, n, mbh * mbw, 7) and self.sad (C, n, mbh, mbw) hold the last call's vectors.  segment_yuv takes a decoder's planes through the
+    N-frame conversion (yuv420_to_bgr_u8); luma_from and matrix are MotionEstimator's."""
+
+    def __init__(self, width, height, frames=9, clips=1, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr',
+                 matrix='bt601'):
+        who = "SegmentMotionEstimator"
+        if luma_from not in ('bgr', 'y'):
+            raise LsfaError("%s: luma_from %r is not 'bgr' or 'y'" % (who, luma_from))
+        if matrix not in YUV_MATRICES:
+            raise LsfaError("%s: matrix %r is not one of %s" % (who, matrix, sorted(YUV_MATRICES)))
+        self.luma_from, self.matrix = luma_from, matrix
+        self.width, self.height, self.device = int(width), int(height), torch.device(device)
+        self.frames, self.clips = int(frames), int(clips)
+        self.search, self.lam, self.max_sad = int(search), int(lam), int(max_sad)
+        if not 1 <= self.search <= 32 or self.lam < 0 or self.max_sad < 0:
+            raise LsfaError("%s: search %d (1..32), lam %d (>= 0), max_sad %d (>= 0)" % (who, self.search, self.lam, self.max_sad))
+        if self.frames < 1 or self.clips < 1 or self.width < 1 or self.height < 1:
+            raise LsfaError("%s: frames %d, clips %d and the %d x %d frame must all be at least 1" % (who, self.frames, self.clips, self.width, self.height))
+        H, W, C, F = self.height, self.width, self.clips, self.frames
+        self.mbh, self.mbw = -(-H // 16), -(-W // 16)
+        # flat, so that a shorter segment is a stack of its own in front of the same memory.  The search wants every plane 4-byte aligned: a
+        # frame of W * H % 4 != 0 (no 4:2:0 video has one) gets its planes padded apart and its luma frame by frame
+        self._plane = -(-H * W // 4) * 4
+        if self._plane != H * W and luma_from == 'y':
+            raise LsfaError("%s: luma_from='y' needs W * H %% 4 == 0, got %d x %d" % (who, W, H))
+        self._luma = torch.empty(C * (F + 1) * self._plane, dtype=torch.uint8, device=self.device)
+        self._rows = torch.empty(C * F * self.mbh * self.mbw * 7, dtype=torch.int32, device=self.device)
+        self._sad = torch.empty(C * F * self.mbh * self.mbw, dtype=torch.int32, device=self.device)
+        self._bgr = None                # segment_yuv's converted frames, allocated at its first call
+        self.rows, self.sad = None, None
+        self._out = {}
+
+    def _length(self, have, n, who):
+        n = have if n is None else int(n)
+        if not 1 <= n <= min(have, self.frames):
+            raise LsfaError("SegmentMotionEstimator.%s: n = %d non-key frames asked for; the stack holds %d and the estimator was built for %d" %
+                            (who, n, have, self.frames))
+        return n
+
+    def _run(self, bgr, n, im_scale, pixel_means, pixel_scale, rcnn_stride, out, luma_done):
+        H, W, C = self.height, self.width, self.clips
+        ps = self._plane
+        luma = self._luma.as_strided((C, n + 1, H, W), ((n + 1) * ps, ps, W, 1))
+        self.rows = self._rows[:C * n * self.mbh * self.mbw * 7].view(C, n, self.mbh * self.mbw, 7)
+        self.sad = self._sad[:C * n * self.mbh * self.mbw].view(C, n, self.mbh, self.mbw)
+        if not luma_done and ps == H * W:
+            luma_u8(bgr.view(C * (n + 1) * H, W, 3), out=luma.view(C * (n + 1) * H, W))     # pointwise: a stack is one tall frame
+        elif not luma_done:
+            for c in range(C):
+                for f in range(n + 1):
+                    luma_u8(bgr[c, f], out=luma[c, f])
+        mv_estimate_chain(luma, self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+        if out is None:
+            h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
+            key = (n, ph // rcnn_stride, pw // rcnn_stride)
+            if key not in self._out:
+                self._out[key] = (torch.empty((n, C, 2) + key[1:], device=self.device, dtype=torch.float32),
+                                  torch.empty((n, C, 3) + key[1:], device=self.device, dtype=torch.float32))
+            out = self._out[key]
+        return mv_segment_inputs(self.rows, bgr, im_scale, pixel_means, pixel_scale, rcnn_stride, out=out)
+
+    def segment(self, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, n=None, rcnn_stride=16, out=None):
+        """bgr_stack (C, n + 1, H, W, 3) uint8, contiguous, frame 0 of every clip its key frame -> (mv (n, C, 2, h, w), res (n, C, 3, h, w)).
+        `n` below the stack's length takes its first n + 1 frames."""
+        H, W, C = self.height, self.width, self.clips
+        t = bgr_stack
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 5 or int(t.shape[0]) != C or int(t.shape[1]) < 2 or \
+                tuple(t.shape[2:]) != (H, W, 3) or t.device != self.device or not t.is_contiguous():
+            raise LsfaError("SegmentMotionEstimator.segment: a contiguous (%d, n + 1, %d, %d, 3) uint8 stack on %s expected, got %s %s" %
+                            (C, H, W, self.device, tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
+        have = int(t.shape[1]) - 1
+        n = self._length(have, n, 'segment')
+        if n < have:
+            if C > 1:
+                raise LsfaError("SegmentMotionEstimator.segment: n = %d of a stack of %d frames needs clips = 1 (with more, hand over a stack of "
+                                "n + 1 frames per clip)" % (n, have))
+            t = t[:, :n + 1]
+        return self._run(t, n, im_scale, pixel_means, pixel_scale, int(rcnn_stride), out, False)
+
+    def segment_yuv(self, y, uv=None, u=None, v=None, im_scale=1.0, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16, out=None):
+        """segment on a decoder's planes: y (C * (n + 1), H, W) and uv | u, v as yuv420_to_bgr_u8 takes N frames, clip by clip, a clip's key
+        frame first.  One conversion launch into a BGR stack the estimator owns (self.bgr, (C, n + 1, H, W, 3)); luma_from='y' searches the
+        decoder's Y plane (the conversion's y_packed, no luma launch: three launches in all), 'bgr' lsfa_luma_u8 of the converted frames."""
+        H, W, C = self.height, self.width, self.clips
+        if not isinstance(y, torch.Tensor) or y.dim() != 3 or tuple(y.shape[1:]) != (H, W) or y.device != self.device or int(y.shape[0]) % C or \
+                int(y.shape[0]) < 2 * C:
+            raise LsfaError("SegmentMotionEstimator.segment_yuv: a (%d * (n + 1), %d, %d) uint8 Y stack on %s expected, got %s on %s" %
+                            (C, H, W, self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
+        n = self._length(int(y.shape[0]) // C - 1, None, 'segment_yuv')
+        if self._bgr is None:
+            self._bgr = torch.empty(C * (self.frames + 1) * H * W * 3, dtype=torch.uint8, device=self.device)
+        N = C * (n + 1)
+        self.bgr = self._bgr[:N * H * W * 3].view(C, n + 1, H, W, 3)
+        from_y = self.luma_from == 'y'
+        yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=self.bgr.view(N, H, W, 3), y_packed=self._luma[:N * H * W].view(N, H, W) if from_y else None)
+        return self._run(self.bgr, n, im_scale, pixel_means, pixel_scale, int(rcnn_stride), out, from_y)
+
+
 # ---- live timing -----------------------------------------------------------------------
 def prof_enable(on=True, ops=None):
     """on=True times every op; ops=['warp_bilinear', ...] times only those; on=False stops."""

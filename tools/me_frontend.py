@@ -6,7 +6,17 @@
     one non-key frame                              tools/curframe_only.py's loop body (small net + MV warp + heads + detection post-processing)
 
 The condition to read off: the front end for one frame costs less than the non-key frame.  --kernels-only runs just the front-end
-launches a few times (for `rocprofv3 --kernel-trace --stats -- python tools/me_frontend.py --kernels-only`).  Prints one JSON object."""
+launches a few times (for `rocprofv3 --kernel-trace --stats -- python tools/me_frontend.py --kernels-only`).  Prints one JSON object.
+
+--segment runs the segment leg instead (profiles/r7/me_segment.txt), under a time limit of its own (--time-limit seconds, enforced in
+this process): a key frame + nine frames at R = 16 and 32, one clip,
+
+    per-frame graph        MotionEstimator.key_frame, then next_frame + network_inputs nine times, captured as ONE graph
+    segment graph          SegmentMotionEstimator.segment of the same ten frames: luma of the stack, chain search, inputs
+    each new kernel alone  mv_estimate_chain (against nine mv_estimate launches) and mv_segment_inputs
+
+The two forms are replayed alternately, round by round, in one process; the condition to read off is that the segment form is not
+slower than the per-frame graph beyond the min-to-max spread the same run shows."""
 import argparse
 import json
 import os
@@ -58,6 +68,86 @@ def graphed(fn, iters, rounds=5):
     return dict(min=round(min(us), 2), median=round(float(np.median(us)), 2))
 
 
+def alternating(fns, reps, rounds=9):
+    """{name: microseconds per call, min / median / max over rounds}: every fn captured `reps` times in a graph of its own, the graphs
+    replayed in turn, round by round"""
+    graphs = {}
+    for name, fn in fns:
+        fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(reps):
+                fn()
+        g.replay()
+        graphs[name] = g
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in fns}
+    for _ in range(rounds):
+        for name, _ in fns:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            graphs[name].replay()
+            b.record()
+            torch.cuda.synchronize()
+            us[name].append(a.elapsed_time(b) * 1e3 / reps)
+    return {name: dict(min=round(min(v), 2), median=round(float(np.median(v)), 2), max=round(max(v), 2)) for name, v in us.items()}
+
+
+def segment_leg(reps, time_limit):
+    import signal
+
+    def too_long(signum, frame):
+        raise SystemExit('the segment leg ran into its time limit of %d s' % time_limit)
+
+    signal.signal(signal.SIGALRM, too_long)
+    signal.alarm(time_limit)
+    F = 9
+    clip = SyntheticClip(0, F + 1, H, W)
+    stack = torch.stack([clip.frame_u8(f) for f in range(F + 1)]).unsqueeze(0).to(DEV)
+    out = dict(device=torch.cuda.get_device_name(0), frame='%dx%d' % (W, H), frames=F, clips=1, segments_per_graph=reps)
+    for R in (16, 32):
+        me = hip.MotionEstimator(W, H, DEV, search=R)
+        sme = hip.SegmentMotionEstimator(W, H, frames=F, clips=1, device=DEV, search=R)
+        per_frame_out = []
+
+        def per_frame():
+            del per_frame_out[:]
+            me.key_frame(stack[0, 0])
+            for f in range(1, F + 1):
+                me.next_frame(stack[0, f])
+                per_frame_out.append(me.network_inputs(stack[0, f], stack[0, 0], 1.0, (0.0, 0.0, 0.0), 1.0))
+
+        def segment():
+            return sme.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)
+
+        # the two forms agree on the last frame (every frame: tests/test_me_segment_gpu.py) before anything is timed
+        per_frame()
+        mv, res = segment()
+        torch.cuda.synchronize()
+        assert torch.equal(mv[F - 1], per_frame_out[-1][0]) and torch.equal(res[F - 1], per_frame_out[-1][1])
+        luma = sme._luma[:(F + 1) * H * W].view(1, F + 1, H, W)
+        rows, sad = sme.rows, sme.sad
+        pair_rows, pair_sad = torch.empty_like(rows[0, 0]), torch.empty_like(sad[0, 0])
+
+        def nine_pairs():
+            for f in range(1, F + 1):
+                hip.mv_estimate(luma[0, f], luma[0, f - 1], R, 4, 0, out=pair_rows, sad_out=pair_sad)
+
+        r = alternating([('per_frame_graph', per_frame), ('segment_graph', segment)], reps)
+        r.update(alternating([('nine_mv_estimate', nine_pairs), ('mv_estimate_chain', lambda: hip.mv_estimate_chain(luma, R, 4, 0, out=rows, sad_out=sad)),
+                              ('mv_segment_inputs', lambda: hip.mv_segment_inputs(rows, stack, 1.0, out=(mv, res))),
+                              ('luma_u8_stack', lambda: hip.luma_u8(stack.view((F + 1) * H, W, 3), out=luma.view((F + 1) * H, W)))], reps))
+        a, b = r['per_frame_graph'], r['segment_graph']
+        spread = max(a['max'] - a['min'], b['max'] - b['min'])
+        r['spread_us'] = round(spread, 2)
+        r['segment_not_slower_beyond_spread'] = bool(b['median'] <= a['median'] + spread)
+        r['launches'] = dict(per_frame_graph=2 + 8 * F, segment_graph=3)
+        out['R%d' % R] = r
+    signal.alarm(0)
+    print(json.dumps(out))
+
+
 def non_key_frame(iters):
     from lsfa_amd.config.config import lsfa_test_config
     from lsfa_amd.symbols import params as P
@@ -87,7 +177,12 @@ def main():
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--kernels-only', action='store_true')
     ap.add_argument('--skip-non-key', action='store_true')
+    ap.add_argument('--segment', action='store_true', help='the segment leg: nine frames per-frame against the three-launch segment form')
+    ap.add_argument('--segment-reps', type=int, default=20, help='--segment: segments captured per graph')
+    ap.add_argument('--time-limit', type=int, default=240, help='--segment: seconds after which the leg gives up')
     args = ap.parse_args()
+    if args.segment:
+        return segment_leg(args.segment_reps, args.time_limit)
     clip = SyntheticClip(0, 4, H, W)
     frames = [clip.frame_u8(f).to(DEV) for f in range(3)]
     y = [hip.luma_u8(f) for f in frames]
