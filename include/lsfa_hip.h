@@ -601,6 +601,35 @@ int lsfa_mv_segment_inputs(const int* mvs, const unsigned char* bgr, long long f
                            double im_scale, int h1, int w1, int rcnn_stride, const double* pixel_means_bgr_host, double pixel_scale,
                            float* out_mv /* (n_frames, n_chains, 2, oh, ow) */, float* out_res /* (n_frames, n_chains, 3, oh, ow) */,
                            int out_h, int out_w, void* stream);
+/* Pyramid (coarse-to-fine) search (lsfa_amd/csrc/me_pyramid.hip): vectors of up to R 2^L + r (2^L - 1) <= 137 pixels per axis, a second
+ * mode beside the full search and NOT equal to the full search with a larger range (a coarse level can lock onto the wrong minimum; a
+ * block whose true source is valid can have an ancestor whose shifted rectangle is not).  Defined by its own specification, restated in
+ * numpy as tests/ref_me_pyramid.py, and bit-exact with that:
+ *   P_0 is the plane lsfa_mv_estimate reads; P_{k+1} is ceil(w_k / 2) x ceil(h_k / 2), P_{k+1}[y][x] = (a + b + c + d + 2) >> 2 over P_k
+ *   at (2x, 2y), (2x + 1, 2y), (2x, 2y + 1), (2x + 1, 2y + 1) with coordinates clamped to P_k - each level from the level below, so both
+ *   roundings of P_2 are specified.  The top level L (1 or 2) is lsfa_mv_estimate[_chain](P_L, search = R, lambda, max_sad = 0) on P_L's
+ *   own macroblock grid.  Levels k = L - 1 .. 0 refine: block (bx, by) of P_k has the parent (bx >> 1, by >> 1) on level k + 1, winner
+ *   (pdx, pdy); candidates (2 pdx + ex, 2 pdy + ey), (ex, ey) in [-r, r]^2, plus (0, 0); valid iff the covered rectangle shifted by the
+ *   candidate lies inside P_k; cost = SAD + lambda (|dx| + |dy|) on the absolute vector, the same lambda on every level; winner smallest
+ *   under (cost, |dx| + |dy|, dy, dx); max_sad on level 0 only; rows {-1, 16, 16, 16 bx + 8 + dx, 16 by + 8 + dy, 16 bx + 8, 16 by + 8}
+ *   for every block.  The level-0 rows keep the CONTRACT of lsfa_mv_segment_inputs above.
+ * lsfa_luma_pyramid: luma holds n_planes (1..65535) planes (H, W) uint8, plane_stride bytes apart; level1 receives n_planes planes
+ *   ceil(H / 2) x ceil(W / 2), stride1 bytes apart, and with levels = 2 level2 the planes of P_2, stride2 apart (levels = 1: level2 and
+ *   stride2 are not read).  Output strides are multiples of 4 that hold a plane and the output bases 4-byte aligned (what the searches
+ *   want).  One launch for all planes and both levels; P_2 is formed from the workgroup's P_1 tile.
+ * lsfa_mv_refine_chain: one refinement step on level k for every pair of a segment.  luma holds the n_chains * (n_frames + 1) planes
+ *   (height, width) of level k as lsfa_mv_estimate_chain takes them; a NEGATIVE plane_stride is a stack stored in reverse (luma points at
+ *   plane 0, the plane at the highest address; with n_chains = n_frames = 1 the reference plane followed by the current one behind it: a
+ *   ping-pong pair); |plane_stride| a multiple of 4 that holds a plane.  parent_mvs (n_chains, n_frames, mbh_{k+1} * mbw_{k+1}, 7) are the
+ *   rows of level k + 1 (mb*_{k+1} from ceil(width / 2) x ceil(height / 2)); refine r = 1..3; lambda, max_sad as lsfa_mv_estimate.  mvs
+ *   (n_chains, n_frames, mbh * mbw, 7), sad (n_chains, n_frames, mbh, mbw) or NULL.  One launch, one wave per macroblock, no workspace.
+ *   Parent rows that are not the mode's own: candidates with a component beyond +-255 are dropped like invalid ones (memory-safe, defined). */
+int lsfa_luma_pyramid(const unsigned char* luma, long long plane_stride, int n_planes, int width, int height, int levels,
+                      unsigned char* level1, long long stride1, unsigned char* level2 /* NULL with levels = 1 */, long long stride2,
+                      void* stream);
+int lsfa_mv_refine_chain(const unsigned char* luma, long long plane_stride, int n_chains, int n_frames, int width, int height,
+                         const int* parent_mvs /* (n_chains, n_frames, mbh1*mbw1, 7) */, int refine, int lambda, int max_sad,
+                         int* mvs /* (n_chains, n_frames, mbh*mbw, 7) */, int* sad /* (n_chains, n_frames, mbh, mbw) or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip): the planes a decoder hands over - libav, the VCN decode engines, a raw .yuv dump - straight to

@@ -9,9 +9,9 @@ entry's clip generator (lsfa_amd.utils.synthetic) and live on the device.
 
 estimate_mv, or config.TEST.ESTIMATE_MV where it is None (not in the reference; default None = the clip's own `motion_vector` /
 `res_diff`): a dict of
-hip.SegmentMotionEstimator's parameters (search, lam, max_sad).  When a key frame is handed out, the uint8
-frames of it and of the non-key frames behind it are uploaded and the whole segment's inputs are estimated from
-them on the current stream, in three launches; each of those non-key frames then receives its slice.
+hip.SegmentMotionEstimator's parameters (search, lam, max_sad; levels, refine for the pyramid search).  When a key frame is handed out, the
+uint8 frames of it and of the non-key frames behind it are uploaded and the whole segment's inputs are estimated from
+them on the current stream, in three launches (levels + 4 with the pyramid); each of those non-key frames then receives its slice.
 """
 import numpy as np
 import torch

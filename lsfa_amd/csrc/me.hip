@@ -25,6 +25,7 @@
 // whose integer order IS the total order above, so the argmin is a plain `min`: per lane, then __shfl_xor across the wave, then one LDS
 // step across the four waves.  Invalid candidates are skipped by range arithmetic on (dx, dy), never by clamping addresses.
 #include "common.h"
+#include "me_plane.h"       // plane_byte, plane_dword: shared with the pyramid's refinement (me_pyramid.hip)
 
 using namespace lsfa;
 
@@ -91,24 +92,6 @@ struct MeArgs {
   int W, H, mbw, R, G, lambda, max_sad;
   long total;       // W * H: the planes' size in bytes
 };
-
-// byte (gx, gy) of a plane, 0 outside the frame
-__device__ __forceinline__ uint32_t plane_byte(const unsigned char* __restrict__ p, int W, int H, int gx, int gy) {
-  return (gx >= 0 && gx < W && gy >= 0 && gy < H) ? (uint32_t)p[(size_t)gy * W + gx] : 0u;
-}
-
-// bytes (gx .. gx + 3, gy) of a plane as one little-endian dword, 0 outside the frame: two aligned dwords realigned where all four bytes
-// are inside the frame and the second aligned dword ends inside the plane, byte loads otherwise (frame edges)
-__device__ __forceinline__ uint32_t plane_dword(const unsigned char* __restrict__ p, int W, int H, long total, int gx, int gy) {
-  if (gy >= 0 && gy < H && gx >= 0 && gx + 3 < W) {
-    const long a = (long)gy * W + gx, base = a & ~3L;
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p + base);
-    if ((a & 3L) == 0) return q[0];
-    if (base + 8 <= total) return __builtin_amdgcn_alignbyte(q[1], q[0], (uint32_t)(a & 3L));
-  }
-  return plane_byte(p, W, H, gx, gy) | (plane_byte(p, W, H, gx + 1, gy) << 8) | (plane_byte(p, W, H, gx + 2, gy) << 16) |
-         (plane_byte(p, W, H, gx + 3, gy) << 24);
-}
 
 template <class Sad4, bool kFullHeight>
 __device__ __forceinline__ unsigned long long search_units(const uint32_t* __restrict__ s_win, const uint32_t (&c)[16][4], const uint32_t (&mask)[4],

@@ -5,7 +5,7 @@ score above 0.7 after per-class NMS.
 
     python -m lsfa_amd.demo                         # synthetic 1000x600 clip, random-init weights
     python -m lsfa_amd.demo --frames DIR [--mv DIR] [--prefix P --epoch E] [--out dets.json]
-    python -m lsfa_amd.demo --frames DIR --estimate-mv [--search 16 --mv-lambda 4] [--dump-mv DIR]
+    python -m lsfa_amd.demo --frames DIR --estimate-mv [--search 16 --mv-lambda 4] [--mv-levels L --mv-refine r] [--dump-mv DIR]
 
     python -m lsfa_amd.demo --yuv clip.nv12 --size 1280x720 [--yuv-format nv12|i420] [--yuv-matrix bt601|bt709|jpeg] [--estimate-mv ...]
 
@@ -231,8 +231,12 @@ def parse_args(argv=None):
     ap.add_argument('--yuv-format', default='nv12', choices=('nv12', 'i420'), help='--yuv: semi-planar (interleaved U, V) or planar chroma')
     ap.add_argument('--yuv-matrix', default='bt601', choices=('bt601', 'bt709', 'jpeg'), help='--yuv: the colour matrix of the stream')
     ap.add_argument('--estimate-mv', action='store_true', help='estimate block motion vectors from the frames on the GPU (needs --frames or --yuv)')
-    ap.add_argument('--search', type=int, default=16, help='--estimate-mv: search range in pixels, 1..32 (a parameter, not a tuned value)')
+    ap.add_argument('--search', type=int, default=16,
+                    help='--estimate-mv: search range in pixels, 1..32, with --mv-levels the range on the top level (a parameter, not a tuned value)')
     ap.add_argument('--mv-lambda', type=int, default=4, help='--estimate-mv: cost per pixel of vector length (a parameter, not a tuned value)')
+    ap.add_argument('--mv-levels', type=int, default=0, choices=(0, 1, 2),
+                    help='--estimate-mv: extra pyramid levels; the reach is search * 2^L + refine * (2^L - 1) pixels (0: the full search alone)')
+    ap.add_argument('--mv-refine', type=int, default=2, choices=(1, 2, 3), help='--mv-levels: refinement radius per level (a parameter, not a tuned value)')
     ap.add_argument('--dump-mv', default=None, help='--estimate-mv: write the estimated mv / res as the .npz files --mv reads')
     ap.add_argument('--num', type=int, default=30, help='frames of the synthetic clip')
     ap.add_argument('--interval', type=int, default=10, help='key frame interval (demo.py:68)')
@@ -278,7 +282,7 @@ def main(argv=None):
         cfg = lsfa_test_config()
     cfg.TEST.KEY_FRAME_INTERVAL = args.interval
     dev = 'cuda:0'
-    estimate = dict(search=args.search, lam=args.mv_lambda) if args.estimate_mv else None
+    estimate = dict(search=args.search, lam=args.mv_lambda, levels=args.mv_levels, refine=args.mv_refine) if args.estimate_mv else None
     if args.yuv:
         clip = YuvFileClip(args.yuv, args.yuv_size[0], args.yuv_size[1], cfg, args.yuv_format, args.yuv_matrix, estimate, dev, args.dump_mv)
     else:

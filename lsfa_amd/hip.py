@@ -1479,6 +1479,37 @@ class MotionVectorAccumulator(object):
 # or noisy blocks stay at rest, no intra threshold.  Nothing was fitted to data (there is no encoder output here to fit to).
 ME_SEARCH, ME_LAMBDA, ME_MAX_SAD = 16, 4, 0
 
+# ---- pyramid search (lsfa_amd/csrc/me_pyramid.hip) --------------------------------------------------------------------------------------------
+# levels = 0 is the full search alone.  refine = 2 is a parameter like ME_SEARCH, not a tuned value.
+ME_LEVELS, ME_REFINE = 0, 2
+
+
+def me_reach(levels, search, refine=ME_REFINE):
+    """the longest vector component, in pixels, the search can return: search * 2^levels + refine * (2^levels - 1)"""
+    return int(search) * 2 ** int(levels) + int(refine) * (2 ** int(levels) - 1)
+
+
+def pyramid_shapes(height, width, levels):
+    """[(h_0, w_0), .., (h_levels, w_levels)]: every level ceil(h / 2) x ceil(w / 2) of the one below"""
+    shapes = [(int(height), int(width))]
+    for _ in range(int(levels)):
+        shapes.append((-(-shapes[-1][0] // 2), -(-shapes[-1][1] // 2)))
+    return shapes
+
+
+def _pyramid_params(who, levels, refine):
+    levels, refine = int(levels), int(refine)
+    if not 0 <= levels <= 2:
+        raise LsfaError("%s: levels %d is outside 0..2" % (who, levels))
+    if levels and not 1 <= refine <= 3:
+        raise LsfaError("%s: refine %d is outside 1..3" % (who, refine))
+    return levels, refine
+
+
+def _plane_stack(t, shape, stride0):
+    """a flat uint8 buffer as (N, h, w) planes `stride0` bytes apart"""
+    return t.as_strided(shape, (stride0, shape[2], 1))
+
 
 @_on_tensor_device
 def luma_u8(bgr, out=None):
@@ -1538,9 +1569,16 @@ class MotionEstimator(object):
     lsfa_luma_u8 of the converted frame: the rows are those of feeding the converted frames to key_frame / next_frame.  luma_from='y'
     searches the decoder's own Y plane (the conversion's y_packed output, no luma launch): DIFFERENT numbers - Y is limited-range (16..235)
     and weighs the channels by the stream's matrix, lsfa_luma_u8 is full-range with its own weights - so SADs, the lambda trade-off and
-    therefore some vectors differ.  `matrix` is the conversion's."""
+    therefore some vectors differ.  `matrix` is the conversion's.
 
-    def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr', matrix='bt601'):
+    levels = 1 or 2 switches to the pyramid search (lsfa_amd/csrc/me_pyramid.hip; DESIGN.md "Pyramid search"): `search` is then the range on the
+    top level and self.reach = search * 2^levels + refine * (2^levels - 1) pixels.  The pyramids of both ping-pong planes are kept and only
+    the new frame's is built: next_frame is levels + 2 launches in front of the accumulation (pyramid, top search, one refinement per
+    level) instead of one.  levels = 0 (the default) runs exactly the full search's launches; `refine` is ignored there."""
+
+    def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr', matrix='bt601',
+                 levels=ME_LEVELS, refine=ME_REFINE):
+        self.levels, self.refine = _pyramid_params("MotionEstimator", levels, refine)
         if luma_from not in ('bgr', 'y'):
             raise LsfaError("MotionEstimator: luma_from %r is not 'bgr' or 'y'" % (luma_from,))
         if matrix not in YUV_MATRICES:
@@ -1554,7 +1592,15 @@ class MotionEstimator(object):
         H, W = self.height, self.width
         self.mbh, self.mbw = -(-H // 16), -(-W // 16)
         self.acc = MotionVectorAccumulator(W, H, self.device)
-        self._luma = [torch.empty((H, W), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.reach = me_reach(self.levels, self.search, self.refine)
+        # the two ping-pong planes of every level lie one (4-byte aligned) plane apart in one buffer: the refinement takes a pair as a stack
+        # of two, forwards or in reverse
+        self._shapes = pyramid_shapes(H, W, self.levels)
+        self._pplane = [-(-h * w // 4) * 4 for h, w in self._shapes]
+        self._planes = [_plane_stack(torch.empty(2 * ps, dtype=torch.uint8, device=self.device), (2, h, w), ps)
+                        for ps, (h, w) in zip(self._pplane, self._shapes)]
+        self._luma = [self._planes[0][0], self._planes[0][1]]
+        self._prows = [torch.empty((-(-h // 16) * -(-w // 16), 7), dtype=torch.int32, device=self.device) for h, w in self._shapes[1:]]
         self._ref = 0                   # index of the previous frame's plane
         self.rows = torch.empty((self.mbh * self.mbw, 7), dtype=torch.int32, device=self.device)
         self.sad = torch.empty((self.mbh, self.mbw), dtype=torch.int32, device=self.device)
@@ -1568,8 +1614,32 @@ class MotionEstimator(object):
                             (who, self.height, self.width, self.device, tuple(getattr(bgr, 'shape', ())), getattr(bgr, 'dtype', type(bgr))))
         return bgr
 
+    def _pyramid_of(self, i):
+        """the pyramid of ping-pong plane i alone (one launch; nothing with levels = 0)"""
+        if self.levels:
+            luma_pyramid(self._planes[0][i:i + 1], self.levels, out=[p[i:i + 1] for p in self._planes[1:]])
+
+    def _search(self, cur):
+        """rows / SAD of plane `cur` against plane self._ref: the full search, or with levels > 0 the pyramid of the new plane, the full
+        search on the top level and one refinement per level below it"""
+        ref, L = self._ref, self.levels
+        if L == 0:
+            mv_estimate(self._luma[cur], self._luma[ref], self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+            return
+        self._pyramid_of(cur)
+        rows = [self.rows] + self._prows
+        mv_estimate(self._planes[L][cur], self._planes[L][ref], self.search, self.lam, 0, out=rows[L])
+        with torch.cuda.device(self.device):
+            for k in range(L - 1, -1, -1):
+                h, w = self._shapes[k]
+                # the pair as a stack of two that starts at the reference plane: forwards if the current plane lies behind it, else in reverse
+                _check(lib().lsfa_mv_refine_chain(_ptr(self._planes[k][ref]), (cur - ref) * self._pplane[k], 1, 1, w, h, _ptr(rows[k + 1]), self.refine,
+                                                  self.lam, self.max_sad if k == 0 else 0, _ptr(rows[k]), _ptr(self.sad) if k == 0 else None, _stream()),
+                       "lsfa_mv_refine_chain")
+
     def key_frame(self, bgr):
         luma_u8(self._frame(bgr, 'key_frame'), out=self._luma[self._ref])
+        self._pyramid_of(self._ref)
         self.acc.reset()
 
     def next_frame(self, bgr):
@@ -1577,7 +1647,7 @@ class MotionEstimator(object):
         next call overwrites; self.sad holds the winners' SAD)."""
         cur = 1 - self._ref
         luma_u8(self._frame(bgr, 'next_frame'), out=self._luma[cur])
-        mv_estimate(self._luma[cur], self._luma[self._ref], self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+        self._search(cur)
         self.acc.add_frame(self.rows, max_block_area=256)      # the explicit area: no device-to-host read
         self._ref = cur
         return self.rows
@@ -1607,6 +1677,7 @@ class MotionEstimator(object):
         """key_frame on a decoder's planes: converts into self.bgr_key and returns it"""
         self._yuv_buffers()
         bgr = self._yuv_to(self.bgr_key, self._luma[self._ref], y, uv, u, v, 'key_frame_yuv')
+        self._pyramid_of(self._ref)
         self.acc.reset()
         return bgr
 
@@ -1616,7 +1687,7 @@ class MotionEstimator(object):
         self._yuv_buffers()
         cur, nxt = 1 - self._ref, 1 - self._bgr_i
         bgr = self._yuv_to(self._bgr_pp[nxt], self._luma[cur], y, uv, u, v, 'next_frame_yuv')
-        mv_estimate(self._luma[cur], self._luma[self._ref], self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+        self._search(cur)
         self.acc.add_frame(self.rows, max_block_area=256)
         self._ref, self._bgr_i = cur, nxt
         return bgr
@@ -1683,6 +1754,74 @@ def mv_estimate_chain(luma_stack, search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MA
 
 
 @_on_tensor_device
+def luma_pyramid(luma, levels, out=None):
+    """lsfa_luma_pyramid: luma (N, H, W) uint8 on the device, dense planes any stride apart -> [P_1] or [P_1, P_2], (N, h_k, w_k) uint8 with
+    P_{k+1}[y][x] = (a + b + c + d + 2) >> 2 over the 2 x 2 taps of P_k, coordinates clamped; P_2 from P_1, never from P_0.  The outputs'
+    planes lie a multiple of 4 bytes apart (what the searches want); out: such tensors of the caller's.  One launch."""
+    who = "luma_pyramid"
+    if not isinstance(luma, torch.Tensor) or luma.dtype != torch.uint8 or not luma.is_cuda or luma.dim() != 3 or int(luma.shape[0]) < 1:
+        raise LsfaError("%s: a (N, H, W) uint8 CUDA stack expected, got %s %s" % (who, tuple(getattr(luma, 'shape', ())), getattr(luma, 'dtype', type(luma))))
+    levels = int(levels)
+    if levels not in (1, 2):
+        raise LsfaError("%s: levels %d is outside 1..2" % (who, levels))
+    N, H, W = (int(v) for v in luma.shape)
+    if (int(luma.stride(1)), int(luma.stride(2))) != (W, 1) or (N > 1 and int(luma.stride(0)) < H * W):
+        raise LsfaError("%s: the planes must be dense; got shape %s strides %s" % (who, tuple(luma.shape), tuple(luma.stride())))
+    shapes = pyramid_shapes(H, W, levels)[1:]
+    if out is None:
+        out = []
+        for h, w in shapes:
+            ps = -(-h * w // 4) * 4
+            out.append(_plane_stack(torch.empty(N * ps, dtype=torch.uint8, device=luma.device), (N, h, w), ps))
+    out = list(out)
+    if len(out) != levels:
+        raise LsfaError("%s: out must hold %d tensors, one per level" % (who, levels))
+    strides = []
+    for t, (h, w) in zip(out, shapes):
+        ok = isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) == (N, h, w) and t.device == luma.device and \
+            (int(t.stride(1)), int(t.stride(2))) == (w, 1)
+        s = (int(t.stride(0)) if N > 1 else -(-h * w // 4) * 4) if ok else 0
+        if not ok or s < h * w or s % 4 or t.data_ptr() % 4:
+            raise LsfaError("%s: an output must be a (%d, %d, %d) uint8 tensor on %s with dense, 4-byte aligned planes a multiple of 4 bytes apart" %
+                            (who, N, h, w, luma.device))
+        strides.append(s)
+    _check(lib().lsfa_luma_pyramid(_ptr(luma), int(luma.stride(0)) if N > 1 else H * W, N, W, H, levels, _ptr(out[0]), strides[0],
+                                   _ptr(out[1]) if levels == 2 else None, strides[1] if levels == 2 else 0, _stream()), "lsfa_luma_pyramid")
+    return out
+
+
+@_on_tensor_device
+def mv_refine_chain(luma_stack, parent_rows, refine=ME_REFINE, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, return_sad=False, out=None, sad_out=None):
+    """lsfa_mv_refine_chain: one refinement step of the pyramid search.  luma_stack (C, F + 1, H, W) uint8, the planes of level k as
+    mv_estimate_chain takes them; parent_rows (C, F, mbh1 * mbw1, 7) int32, the rows of level k + 1 (the grid of the ceil(H / 2) x ceil(W / 2)
+    plane) -> rows (C, F, mbh * mbw, 7) of level k; with return_sad also the winners' SAD (C, F, mbh, mbw).  Block (bx, by) tries
+    2 * (its parent (bx >> 1, by >> 1)'s vector) + [-refine, refine]^2 and (0, 0), under the full search's cost, order and validity rule.
+    One launch."""
+    who = "mv_refine_chain"
+    if not isinstance(luma_stack, torch.Tensor) or luma_stack.dim() != 4:
+        raise LsfaError("%s: a (C, F + 1, H, W) uint8 CUDA stack expected, got %s %s" %
+                        (who, tuple(getattr(luma_stack, 'shape', ())), getattr(luma_stack, 'dtype', type(luma_stack))))
+    H, W = int(luma_stack.shape[2]), int(luma_stack.shape[3])
+    C, F, stride = _u8_stack(who, "luma_stack", luma_stack, (H, W))
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    pblocks = -(-(-(-H // 2)) // 16) * -(-(-(-W // 2)) // 16)
+    p = parent_rows
+    if not isinstance(p, torch.Tensor) or p.dtype != torch.int32 or tuple(p.shape) != (C, F, pblocks, 7) or p.device != luma_stack.device or not p.is_contiguous():
+        raise LsfaError("%s: parent_rows must be a contiguous (%d, %d, %d, 7) int32 tensor on %s (the rows of the %d x %d level above), got %s %s" %
+                        (who, C, F, pblocks, luma_stack.device, -(-W // 2), -(-H // 2), tuple(getattr(p, 'shape', ())), getattr(p, 'dtype', type(p))))
+    if out is None:
+        out = torch.empty((C, F, mbh * mbw, 7), dtype=torch.int32, device=luma_stack.device)
+    if return_sad and sad_out is None:
+        sad_out = torch.empty((C, F, mbh, mbw), dtype=torch.int32, device=luma_stack.device)
+    for t, shape in ((out, (C, F, mbh * mbw, 7)), (sad_out, (C, F, mbh, mbw))):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != luma_stack.device or not t.is_contiguous()):
+            raise LsfaError("%s: an output buffer is not a contiguous %s int32 tensor on %s" % (who, shape, luma_stack.device))
+    _check(lib().lsfa_mv_refine_chain(_ptr(luma_stack), stride, C, F, W, H, _ptr(p), int(refine), int(lam), int(max_sad), _ptr(out), _ptr(sad_out),
+                                      _stream()), "lsfa_mv_refine_chain")
+    return (out, sad_out) if return_sad else out
+
+
+@_on_tensor_device
 def mv_segment_inputs(rows, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16, out=None):
     """lsfa_mv_segment_inputs: rows (C, F, mbh * mbw, 7) int32 as mv_estimate_chain returns them and the (C, F + 1, H, W, 3) uint8 BGR stack
     they were estimated on (frame 0 of a chain its key frame) -> `motion_vector` (F, C, 2, h, w) and `res_diff` (F, C, 3, h, w) float32,
@@ -1731,11 +1870,17 @@ class SegmentMotionEstimator(object):
     replayed on new frame contents.  n < frames (the stack's own length, or `n` frames of a longer stack) is the short segment in front of
     a clip's last frame.  The returned tensors are reused by the next call of the same shape unless `out` supplies others; self.rows
     (C, n, mbh * mbw, 7) and self.sad (C, n, mbh, mbw) hold the last call's vectors.  segment_yuv takes a decoder's planes through the
-    N-frame conversion (yuv420_to_bgr_u8); luma_from and matrix are MotionEstimator's."""
+    N-frame conversion (yuv420_to_bgr_u8); luma_from and matrix are MotionEstimator's.
+
+    levels = 1 or 2 switches to the pyramid search (DESIGN.md "Pyramid search"): `search` is the range on the top level, self.reach the longest
+    vector component.  A segment is then levels + 4 launches - luma, lsfa_luma_pyramid of every plane, lsfa_mv_estimate_chain on the top
+    level, one lsfa_mv_refine_chain per level below it, the inputs - with the pyramid planes and the rows of every level allocated up
+    front like everything else.  levels = 0 (the default) runs exactly the three launches above; `refine` is ignored there."""
 
     def __init__(self, width, height, frames=9, clips=1, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr',
-                 matrix='bt601'):
+                 matrix='bt601', levels=ME_LEVELS, refine=ME_REFINE):
         who = "SegmentMotionEstimator"
+        self.levels, self.refine = _pyramid_params(who, levels, refine)
         if luma_from not in ('bgr', 'y'):
             raise LsfaError("%s: luma_from %r is not 'bgr' or 'y'" % (who, luma_from))
         if matrix not in YUV_MATRICES:
@@ -1761,6 +1906,13 @@ class SegmentMotionEstimator(object):
         self._bgr = None                # segment_yuv's converted frames, allocated at its first call
         self.rows, self.sad = None, None
         self._out = {}
+        self.reach = me_reach(self.levels, self.search, self.refine)
+        # the pyramid's planes and the rows of its levels 1 .. levels, flat like the luma planes
+        self._shapes = pyramid_shapes(H, W, self.levels)
+        self._pplane = [-(-h * w // 4) * 4 for h, w in self._shapes]
+        self._pblocks = [-(-h // 16) * -(-w // 16) for h, w in self._shapes]
+        self._pyr = [torch.empty(C * (F + 1) * ps, dtype=torch.uint8, device=self.device) for ps in self._pplane[1:]]
+        self._prows = [torch.empty(C * F * b * 7, dtype=torch.int32, device=self.device) for b in self._pblocks[1:]]
 
     def _length(self, have, n, who):
         n = have if n is None else int(n)
@@ -1781,7 +1933,10 @@ class SegmentMotionEstimator(object):
             for c in range(C):
                 for f in range(n + 1):
                     luma_u8(bgr[c, f], out=luma[c, f])
-        mv_estimate_chain(luma, self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+        if self.levels == 0:
+            mv_estimate_chain(luma, self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+        else:
+            self._pyramid_search(n)
         if out is None:
             h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
             key = (n, ph // rcnn_stride, pw // rcnn_stride)
@@ -1790,6 +1945,26 @@ class SegmentMotionEstimator(object):
                                   torch.empty((n, C, 3) + key[1:], device=self.device, dtype=torch.float32))
             out = self._out[key]
         return mv_segment_inputs(self.rows, bgr, im_scale, pixel_means, pixel_scale, rcnn_stride, out=out)
+
+    def _pyramid_views(self, n):
+        """the buffers of a segment of n non-key frames, level by level (index 0 is the luma stack / self.rows): the planes as
+        (N, h_k, w_k) for the pyramid, as (C, n + 1, h_k, w_k) stacks for the searches, and the rows (C, n, blocks_k, 7)"""
+        C, L, N = self.clips, self.levels, self.clips * (n + 1)
+        flat = [self._luma] + self._pyr
+        planes = [_plane_stack(flat[k], (N,) + self._shapes[k], self._pplane[k]) for k in range(L + 1)]
+        stacks = [flat[k].as_strided((C, n + 1) + self._shapes[k], ((n + 1) * self._pplane[k], self._pplane[k], self._shapes[k][1], 1)) for k in range(L + 1)]
+        rows = [self.rows] + [self._prows[k - 1][:C * n * self._pblocks[k] * 7].view(C, n, self._pblocks[k], 7) for k in range(1, L + 1)]
+        return planes, stacks, rows
+
+    def _pyramid_search(self, n):
+        """levels + 2 launches on the luma stack: the pyramid of every plane, the full search on the top level, one refinement per level
+        below it; self.rows / self.sad receive level 0's"""
+        L = self.levels
+        planes, stacks, rows = self._pyramid_views(n)
+        luma_pyramid(planes[0], L, out=planes[1:])
+        mv_estimate_chain(stacks[L], self.search, self.lam, 0, out=rows[L])
+        for k in range(L - 1, -1, -1):
+            mv_refine_chain(stacks[k], rows[k + 1], self.refine, self.lam, self.max_sad if k == 0 else 0, out=rows[k], sad_out=self.sad if k == 0 else None)
 
     def segment(self, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, n=None, rcnn_stride=16, out=None):
         """bgr_stack (C, n + 1, H, W, 3) uint8, contiguous, frame 0 of every clip its key frame -> (mv (n, C, 2, h, w), res (n, C, 3, h, w)).

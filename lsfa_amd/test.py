@@ -3,7 +3,7 @@
 parse --cfg, build the test symbols, shard videos over the ranks, run pred_eval, gather, report.
 
     python -m lsfa_amd.test [--cfg YAML] [--clips N] [--frames F] [--height H] [--width W] [--prefix P --epoch E]
-    python -m lsfa_amd.test --segment -1 --key-group 2 --estimate-mv [--search R --mv-lambda L]      # frames alone: no motion vectors handed in
+    python -m lsfa_amd.test --segment -1 --key-group 2 --estimate-mv [--search R --mv-lambda L --mv-levels L --mv-refine r]      # frames alone: no motion vectors handed in
     python -m torch.distributed.run --nproc-per-node 8 -m lsfa_amd.test --clips 8
 
 Without a dataset or weights in the image, clips are synthetic (lsfa_amd.utils.synthetic) and the
@@ -45,8 +45,12 @@ def parse_args():
     ap.add_argument('--estimate-mv', action='store_true',
                     help='estimate every segment\'s motion vectors and residuals from the frames themselves (hip.SegmentMotionEstimator, three '
                          'launches per segment) instead of taking the clip\'s')
-    ap.add_argument('--search', type=int, default=16, help='--estimate-mv: search range in pixels, 1..32 (a parameter, not a tuned value)')
+    ap.add_argument('--search', type=int, default=16,
+                    help='--estimate-mv: search range in pixels, 1..32, with --mv-levels the range on the top level (a parameter, not a tuned value)')
     ap.add_argument('--mv-lambda', type=int, default=4, help='--estimate-mv: cost per pixel of vector length (a parameter, not a tuned value)')
+    ap.add_argument('--mv-levels', type=int, default=0, choices=(0, 1, 2),
+                    help='--estimate-mv: extra pyramid levels; the reach is search * 2^L + refine * (2^L - 1) pixels (0: the full search alone)')
+    ap.add_argument('--mv-refine', type=int, default=2, choices=(1, 2, 3), help='--mv-levels: refinement radius per level (a parameter, not a tuned value)')
     ap.add_argument('--out', default=None, help='rank 0 saves the gathered detection rows (n,7) here (.npy)')
     ap.add_argument('--shards-out', default=None, help='rank 0 saves which videos each rank ran (a JSON list per rank, gathered from the ranks themselves)')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'],
@@ -64,7 +68,7 @@ def main():
     if args.interval:
         cfg.TEST.KEY_FRAME_INTERVAL = args.interval
     if args.estimate_mv:                  # read by the loader test_rcnn builds
-        cfg.TEST.ESTIMATE_MV = dict(search=args.search, lam=args.mv_lambda)
+        cfg.TEST.ESTIMATE_MV = dict(search=args.search, lam=args.mv_lambda, levels=args.mv_levels, refine=args.mv_refine)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     # one-GPU boxes: LSFA_BENCH_BACKEND=gloo LSFA_BENCH_ONE_DEVICE=1 puts every rank on cuda:0 and runs the final

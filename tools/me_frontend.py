@@ -16,7 +16,12 @@ this process): a key frame + nine frames at R = 16 and 32, one clip,
     each new kernel alone  mv_estimate_chain (against nine mv_estimate launches) and mv_segment_inputs
 
 The two forms are replayed alternately, round by round, in one process; the condition to read off is that the segment form is not
-slower than the per-frame graph beyond the min-to-max spread the same run shows."""
+slower than the per-frame graph beyond the min-to-max spread the same run shows.
+
+--segment --levels L [--size WxH] runs the pyramid leg instead (profiles/r8/me_pyramid.txt): the segment form with the full search at
+R = 16 and R = 32 and with the pyramid search (L = 1: R = 16; L = 2: R = 8 and R = 16; --refine r, default 2) in the same alternating
+rounds, then each new launch alone: luma_pyramid, the top-level search, every refinement level.  The condition to read off: a pyramid
+configuration whose reach is at least 32 takes no longer per segment than the full search at R = 32 beyond the run's min-to-max spread."""
 import argparse
 import json
 import os
@@ -148,6 +153,44 @@ def segment_leg(reps, time_limit):
     print(json.dumps(out))
 
 
+def pyramid_leg(reps, time_limit, levels, refine):
+    import signal
+
+    def too_long(signum, frame):
+        raise SystemExit('the pyramid leg ran into its time limit of %d s' % time_limit)
+
+    signal.signal(signal.SIGALRM, too_long)
+    signal.alarm(time_limit)
+    F = 9
+    clip = SyntheticClip(0, F + 1, H, W)
+    stack = torch.stack([clip.frame_u8(f) for f in range(F + 1)]).unsqueeze(0).to(DEV)
+    out = dict(device=torch.cuda.get_device_name(0), frame='%dx%d' % (W, H), frames=F, clips=1, segments_per_graph=reps, levels=levels, refine=refine)
+    forms = [('full_R16', hip.SegmentMotionEstimator(W, H, frames=F, device=DEV, search=16)),
+             ('full_R32', hip.SegmentMotionEstimator(W, H, frames=F, device=DEV, search=32))]
+    pyramids = [('pyramid_L%d_R%d_r%d' % (levels, R, refine), hip.SegmentMotionEstimator(W, H, frames=F, device=DEV, search=R, levels=levels, refine=refine))
+                for R in ((16,) if levels == 1 else (8, 16))]
+    for name, sme in forms + pyramids:
+        sme.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)        # the outputs are allocated at the first call
+    torch.cuda.synchronize()
+    r = alternating([(name, (lambda e: lambda: e.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0))(sme)) for name, sme in forms + pyramids], reps)
+    full = r['full_R32']
+    for name, sme in pyramids:
+        p = r[name]
+        spread = max(full['max'] - full['min'], p['max'] - p['min'])
+        p.update(reach=sme.reach, launches=sme.levels + 4, spread_us=round(spread, 2))
+        if sme.reach >= 32:
+            p['not_slower_than_full_R32_beyond_spread'] = bool(p['median'] <= full['median'] + spread)
+        planes, stacks, rows = sme._pyramid_views(F)
+        alone = [('luma_pyramid', lambda planes=planes: hip.luma_pyramid(planes[0], levels, out=planes[1:])),
+                 ('top_search_level%d' % levels, lambda sme=sme, stacks=stacks, rows=rows: hip.mv_estimate_chain(stacks[levels], sme.search, 4, 0, out=rows[levels]))]
+        for k in range(levels - 1, -1, -1):
+            alone.append(('refine_level%d' % k, lambda k=k, stacks=stacks, rows=rows: hip.mv_refine_chain(stacks[k], rows[k + 1], refine, 4, 0, out=rows[k])))
+        p['alone'] = alternating(alone, reps)
+    out.update(r)
+    signal.alarm(0)
+    print(json.dumps(out))
+
+
 def non_key_frame(iters):
     from lsfa_amd.config.config import lsfa_test_config
     from lsfa_amd.symbols import params as P
@@ -173,6 +216,7 @@ def non_key_frame(iters):
 
 
 def main():
+    global W, H
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--kernels-only', action='store_true')
@@ -180,7 +224,16 @@ def main():
     ap.add_argument('--segment', action='store_true', help='the segment leg: nine frames per-frame against the three-launch segment form')
     ap.add_argument('--segment-reps', type=int, default=20, help='--segment: segments captured per graph')
     ap.add_argument('--time-limit', type=int, default=240, help='--segment: seconds after which the leg gives up')
+    ap.add_argument('--levels', type=int, default=0, choices=(0, 1, 2), help='--segment: the pyramid leg with this many extra levels (0: the segment leg)')
+    ap.add_argument('--refine', type=int, default=2, choices=(1, 2, 3), help='--levels: the refinement radius')
+    ap.add_argument('--size', default=None, help='--segment: the frame size as WxH (default 1000x600)')
     args = ap.parse_args()
+    if args.size:
+        if not args.segment:
+            ap.error('--size belongs to --segment')
+        W, H = (int(v) for v in args.size.split('x'))
+    if args.segment and args.levels:
+        return pyramid_leg(args.segment_reps, args.time_limit, args.levels, args.refine)
     if args.segment:
         return segment_leg(args.segment_reps, args.time_limit)
     clip = SyntheticClip(0, 4, H, W)
