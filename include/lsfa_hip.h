@@ -577,10 +577,13 @@ int lsfa_mv_estimate(const unsigned char* luma_cur, const unsigned char* luma_re
                      int search, int lambda, int max_sad, int* mvs /* (mbh*mbw, 7) */, int* sad /* may be NULL */,
                      void* stream);
 /* A segment at a time: the inputs of every non-key frame behind a key frame in two launches, from frames alone.
- * lsfa_mv_estimate_chain: luma holds n_chains * (n_frames + 1) planes (H, W) uint8, plane_stride bytes apart (a multiple of 4 that holds a
- *   plane; the base 4-byte aligned); plane 0 of a chain is its key frame.  Pair (c, f), f = 1..n_frames, is lsfa_mv_estimate(plane f,
- *   plane f - 1) of chain c, bit for bit: mvs (n_chains, n_frames, mbh * mbw, 7), sad (n_chains, n_frames, mbh, mbw) or NULL.  One launch
- *   (the one-workgroup-per-macroblock grid times pairs), no workspace.
+ * lsfa_mv_estimate_chain: luma holds n_chains * (n_frames + 1) planes (H, W) uint8, plane_stride bytes apart; plane 0 of a chain is its key
+ *   frame.  A stack of planes is one thing for this export and lsfa_mv_refine_chain: luma, 4-byte aligned, points at plane 0; |plane_stride|
+ *   is a multiple of 4 that holds a plane and lies below 2^36; a NEGATIVE plane_stride is a stack stored in reverse (plane 0 at the highest
+ *   address; with n_chains = n_frames = 1 the reference plane followed by the current one behind it: a ping-pong pair).  A stride of
+ *   2^36 or more, in either direction, is refused by both.  Pair (c, f), f = 1..n_frames, is
+ *   lsfa_mv_estimate(plane f, plane f - 1) of chain c, bit for bit: mvs (n_chains, n_frames, mbh * mbw, 7), sad (n_chains, n_frames, mbh,
+ *   mbw) or NULL.  One launch (the one-workgroup-per-macroblock grid times pairs), no workspace.
  * lsfa_mv_segment_inputs: mvs as lsfa_mv_estimate_chain wrote them; bgr holds n_chains * (n_frames + 1) packed (H, W, 3) uint8 frames,
  *   frame_stride bytes apart, frame 0 of a chain its key frame.  out_mv (n_frames, n_chains, 2, out_h, out_w) and out_res (n_frames,
  *   n_chains, 3, out_h, out_w) float32, frame-major: out_*[f - 1][c] equals lsfa_mv_identity, lsfa_mv_accumulate of chain c's frames 1..f
@@ -618,9 +621,8 @@ int lsfa_mv_segment_inputs(const int* mvs, const unsigned char* bgr, long long f
  *   stride2 are not read).  Output strides are multiples of 4 that hold a plane and the output bases 4-byte aligned (what the searches
  *   want).  One launch for all planes and both levels; P_2 is formed from the workgroup's P_1 tile.
  * lsfa_mv_refine_chain: one refinement step on level k for every pair of a segment.  luma holds the n_chains * (n_frames + 1) planes
- *   (height, width) of level k as lsfa_mv_estimate_chain takes them; a NEGATIVE plane_stride is a stack stored in reverse (luma points at
- *   plane 0, the plane at the highest address; with n_chains = n_frames = 1 the reference plane followed by the current one behind it: a
- *   ping-pong pair); |plane_stride| a multiple of 4 that holds a plane.  parent_mvs (n_chains, n_frames, mbh_{k+1} * mbw_{k+1}, 7) are the
+ *   (height, width) of level k as lsfa_mv_estimate_chain takes them, forwards or in reverse.  parent_mvs (n_chains, n_frames,
+ *   mbh_{k+1} * mbw_{k+1}, 7) are the
  *   rows of level k + 1 (mb*_{k+1} from ceil(width / 2) x ceil(height / 2)); refine r = 1..3; lambda, max_sad as lsfa_mv_estimate.  mvs
  *   (n_chains, n_frames, mbh * mbw, 7), sad (n_chains, n_frames, mbh, mbw) or NULL.  One launch, one wave per macroblock, no workspace.
  *   Parent rows that are not the mode's own: candidates with a component beyond +-255 are dropped like invalid ones (memory-safe, defined). */

@@ -25,7 +25,7 @@
 // whose integer order IS the total order above, so the argmin is a plain `min`: per lane, then __shfl_xor across the wave, then one LDS
 // step across the four waves.  Invalid candidates are skipped by range arithmetic on (dx, dy), never by clamping addresses.
 #include "common.h"
-#include "me_plane.h"       // plane_byte, plane_dword: shared with the pyramid's refinement (me_pyramid.hip)
+#include "me_common.h"      // shared with the pyramid's refinement (me_pyramid.hip): plane reads, masks, wave min, row store, argument rules
 
 using namespace lsfa;
 
@@ -35,8 +35,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxSearch = 32;
 constexpr int kMaxGroups = (2 * kMaxSearch + 1 + 3) / 4;               // 17
 constexpr int kMaxWinDwords = (16 + 2 * kMaxSearch) * (4 + kMaxGroups);   // 80 rows of 21 dwords
-// cost = SAD + lambda * (|dx| + |dy|) <= 65,280 + 64 lambda must stay below 2^31 for the key (and for int32 arithmetic)
-constexpr int kMaxLambda = (1 << 24);
 
 __global__ __launch_bounds__(kThreads) void luma_u8_kernel(const unsigned char* __restrict__ bgr, int n, unsigned char* __restrict__ luma) {
   // four pixels per thread: 12 source bytes = three aligned dwords in, one dword out (hipMalloc'ed planes are dword aligned; the host
@@ -162,24 +160,15 @@ __device__ __forceinline__ void me_search_block(const unsigned char* __restrict_
     const uint4 v = s_blk[r];
     c[r][0] = v.x; c[r][1] = v.y; c[r][2] = v.z; c[r][3] = v.w;
   }
-  // byte mask of the covered columns per block dword (all ones for a block of full width)
   uint32_t mask[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int nb = min(4, max(0, bw - 4 * k));
-    mask[k] = nb >= 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1u);
-  }
+  covered_masks(bw, mask);
   // the units are dealt out from a different wave in each workgroup: the last, partly filled round then lands on different SIMDs
   const int first_unit = (tid + 64 * (int)(rot & 3u)) & (kThreads - 1);
   unsigned long long best;
   if (bw == 16 && bh == 16) best = search_units<Sad4Packed, true>(s_win, c, mask, a, x0, y0, bw, bh, first_unit);
   else if (bw == 16) best = search_units<Sad4Packed, false>(s_win, c, mask, a, x0, y0, bw, bh, first_unit);
   else best = search_units<Sad4Masked, false>(s_win, c, mask, a, x0, y0, bw, bh, first_unit);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(best, o, 64);
-    best = other < best ? other : best;
-  }
+  wave_min(best);
   if ((tid & 63) == 0) s_best[tid >> 6] = best;
   __syncthreads();
   if (tid == 0) {
@@ -190,9 +179,7 @@ __device__ __forceinline__ void me_search_block(const unsigned char* __restrict_
     const int len = (int)((best >> 14) & 127ull);
     const int sad = (int)(best >> 21) - a.lambda * len;
     if (a.max_sad > 0 && sad > a.max_sad) { dx = 0; dy = 0; }
-    int* row = mvs + (size_t)blk * 7;
-    row[0] = -1; row[1] = 16; row[2] = 16;
-    row[3] = x0 + 8 + dx; row[4] = y0 + 8 + dy; row[5] = x0 + 8; row[6] = y0 + 8;
+    store_row(mvs + (size_t)blk * 7, x0, y0, dx, dy);
     if (sad_out) sad_out[blk] = sad;
   }
 }
@@ -203,14 +190,15 @@ __global__ __launch_bounds__(kThreads) void me_search_kernel(const unsigned char
 }
 
 // me_search_chain_kernel: the same search for every pair (frame f, frame f - 1), f = 1..n_frames, of n_chains stacks of n_frames + 1 planes in
-// one grid: workgroup w is macroblock w % blocks of pair w / blocks, and the pair index only selects two base pointers and the pair's slice
-// of the outputs.  The first-unit rotation follows the workgroup's index in the whole grid, as the single-pair kernel's does.
+// one grid: workgroup w is macroblock w % blocks of pair w / blocks, and the pair index only selects two base pointers (pair_planes: the
+// stride is signed, a stack may be stored in reverse) and the pair's slice of the outputs.  The first-unit rotation follows the
+// workgroup's index in the whole grid, as the single-pair kernel's does.
 __global__ __launch_bounds__(kThreads) void me_search_chain_kernel(const unsigned char* __restrict__ luma, long long plane_stride, int n_frames, int blocks,
                                                                    MeArgs a, int* __restrict__ mvs, int* __restrict__ sad_out) {
   const int pair = (int)(blockIdx.x / (unsigned)blocks), blk = (int)(blockIdx.x - (unsigned)pair * (unsigned)blocks);
-  const int c = pair / n_frames, f = pair - c * n_frames + 1;
-  const unsigned char* cur = luma + ((size_t)c * (n_frames + 1) + f) * (size_t)plane_stride;
-  me_search_block(cur, cur - plane_stride, a, mvs + (size_t)pair * blocks * 7, sad_out ? sad_out + (size_t)pair * blocks : nullptr, blk, blockIdx.x);
+  const unsigned char *cur, *ref;
+  pair_planes(luma, plane_stride, n_frames, pair, cur, ref);
+  me_search_block(cur, ref, a, mvs + (size_t)pair * blocks * 7, sad_out ? sad_out + (size_t)pair * blocks : nullptr, blk, blockIdx.x);
 }
 
 }  // namespace
@@ -231,12 +219,9 @@ extern "C" int lsfa_luma_u8(const unsigned char* bgr, int width, int height, uns
 
 namespace {
 
-// the search's arguments, checked: what lsfa_mv_estimate and lsfa_mv_estimate_chain share
+// the search's own arguments behind a frame me_frame_args has checked: what lsfa_mv_estimate and lsfa_mv_estimate_chain launch with
 int me_args(const char* who, int width, int height, int search, int lambda, int max_sad, MeArgs* a) {
-  LSFA_REQUIRE(width > 0 && height > 0 && (long)width * height < (1L << 30), "%s: bad frame size %d x %d", who, width, height);
   LSFA_REQUIRE(search >= 1 && search <= kMaxSearch, "%s: search %d is outside 1..%d", who, search, kMaxSearch);
-  LSFA_REQUIRE(lambda >= 0 && lambda <= kMaxLambda, "%s: lambda %d is outside 0..%d", who, lambda, kMaxLambda);
-  LSFA_REQUIRE(max_sad >= 0, "%s: max_sad %d is negative (0 switches it off)", who, max_sad);
   a->W = width; a->H = height;
   a->mbw = ceil_div(width, 16);
   a->R = search;
@@ -251,34 +236,32 @@ int me_args(const char* who, int width, int height, int search, int lambda, int 
 
 extern "C" int lsfa_mv_estimate(const unsigned char* luma_cur, const unsigned char* luma_ref, int width, int height, int search, int lambda,
                                 int max_sad, int* mvs, int* sad, void* stream) {
-  LSFA_REQUIRE(luma_cur && luma_ref && mvs, "lsfa_mv_estimate: NULL argument");
+  const char* who = "lsfa_mv_estimate";
+  LSFA_REQUIRE(luma_cur && luma_ref && mvs, "%s: NULL argument", who);
   MeArgs a;
-  if (const int rc = me_args("lsfa_mv_estimate", width, height, search, lambda, max_sad, &a)) return rc;
-  LSFA_REQUIRE(((reinterpret_cast<uintptr_t>(luma_cur) | reinterpret_cast<uintptr_t>(luma_ref)) & 3u) == 0,
-               "lsfa_mv_estimate: the luma planes must be 4-byte aligned");
+  if (const int rc = me_frame_args(who, width, height, lambda, max_sad)) return rc;
+  if (const int rc = me_args(who, width, height, search, lambda, max_sad, &a)) return rc;
+  LSFA_REQUIRE(((reinterpret_cast<uintptr_t>(luma_cur) | reinterpret_cast<uintptr_t>(luma_ref)) & 3u) == 0, "%s: the luma planes must be 4-byte aligned", who);
   const int blocks = a.mbw * ceil_div(height, 16);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(LSFA_OP_MV_ESTIMATE, s);
   hipLaunchKernelGGL(me_search_kernel, dim3(blocks), dim3(kThreads), 0, s, luma_cur, luma_ref, a, mvs, sad);
-  LSFA_LAUNCH_CHECK("lsfa_mv_estimate");
+  LSFA_LAUNCH_CHECK(who);
   return LSFA_OK;
 }
 
 extern "C" int lsfa_mv_estimate_chain(const unsigned char* luma, long long plane_stride, int n_chains, int n_frames, int width, int height, int search,
                                       int lambda, int max_sad, int* mvs, int* sad, void* stream) {
-  LSFA_REQUIRE(luma && mvs, "lsfa_mv_estimate_chain: NULL argument");
+  const char* who = "lsfa_mv_estimate_chain";
+  LSFA_REQUIRE(luma && mvs, "%s: NULL argument", who);
   MeArgs a;
-  if (const int rc = me_args("lsfa_mv_estimate_chain", width, height, search, lambda, max_sad, &a)) return rc;
-  LSFA_REQUIRE(n_chains >= 1 && n_frames >= 1, "lsfa_mv_estimate_chain: %d chains of %d frames: both counts must be at least 1", n_chains, n_frames);
-  LSFA_REQUIRE(plane_stride >= a.total && (plane_stride & 3) == 0,
-               "lsfa_mv_estimate_chain: plane stride %lld must hold a %d x %d plane and be a multiple of 4", plane_stride, width, height);
-  LSFA_REQUIRE((reinterpret_cast<uintptr_t>(luma) & 3u) == 0, "lsfa_mv_estimate_chain: the luma planes must be 4-byte aligned");
-  const int blocks = a.mbw * ceil_div(height, 16);
-  const long pairs = (long)n_chains * n_frames;
-  LSFA_REQUIRE(pairs * blocks < (1L << 31), "lsfa_mv_estimate_chain: %ld pairs of %d macroblocks exceed one grid", pairs, blocks);
+  int blocks;
+  long pairs;
+  if (const int rc = me_stack_args(who, luma, plane_stride, n_chains, n_frames, width, height, lambda, max_sad, &blocks, &pairs)) return rc;
+  if (const int rc = me_args(who, width, height, search, lambda, max_sad, &a)) return rc;
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(LSFA_OP_MV_ESTIMATE, s);
   hipLaunchKernelGGL(me_search_chain_kernel, dim3((unsigned)(pairs * blocks)), dim3(kThreads), 0, s, luma, plane_stride, n_frames, blocks, a, mvs, sad);
-  LSFA_LAUNCH_CHECK("lsfa_mv_estimate_chain");
+  LSFA_LAUNCH_CHECK(who);
   return LSFA_OK;
 }

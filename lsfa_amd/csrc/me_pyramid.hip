@@ -29,7 +29,7 @@
 // that - only a parent row that is not the mode's own can ask for one - is dropped like an invalid one.  The argmin is a `min` over the
 // wave (__shfl_xor); lane 0 writes the row.
 #include "common.h"
-#include "me_plane.h"
+#include "me_common.h"
 
 using namespace lsfa;
 
@@ -38,7 +38,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxRefine = 3;
-constexpr int kMaxLambda = (1 << 24);                    // the full search's bound; cost <= 65,280 + 510 * 2^24 < 2^34 sits in the key's top 37 bits
 constexpr int kWinStride = 7;                            // dwords from one staged row to the next: six staged, odd against bank conflicts
 constexpr int kWinRows = 16 + 2 * kMaxRefine;            // 22
 constexpr int kVecLimit = 255;                           // the key's nine-bit vector fields
@@ -136,9 +135,8 @@ __global__ __launch_bounds__(kThreads) void refine_chain_kernel(const unsigned c
   const bool live = g < a.waves;
   if (!live) g = a.waves - 1;       // a wave past the end does the last block again and stores nothing: every wave reaches the barrier
   const int pair = (int)(g / a.blocks), blk = (int)(g - (long)pair * a.blocks);
-  const int c = pair / a.n_frames, f = pair - c * a.n_frames + 1;
-  const unsigned char* cur = luma + ((long long)c * (a.n_frames + 1) + f) * a.stride;
-  const unsigned char* ref = cur - a.stride;
+  const unsigned char *cur, *ref;
+  pair_planes(luma, a.stride, a.n_frames, pair, cur, ref);
   const int by = blk / a.mbw, bx = blk - by * a.mbw;
   const int x0 = 16 * bx, y0 = 16 * by;
   const int bw = min(16, a.W - x0), bh = min(16, a.H - y0);
@@ -177,13 +175,8 @@ __global__ __launch_bounds__(kThreads) void refine_chain_kernel(const unsigned c
   valid = valid && x0 + dx >= 0 && x0 + bw - 1 + dx <= a.W - 1 && y0 + dy >= 0 && y0 + bh - 1 + dy <= a.H - 1 && dx >= -kVecLimit && dx <= kVecLimit &&
           dy >= -kVecLimit && dy <= kVecLimit;
 
-  // byte mask of the covered columns per block dword (all ones for a block of full width)
   uint32_t mask[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int nb = min(4, max(0, bw - 4 * k));
-    mask[k] = nb >= 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1u);
-  }
+  covered_masks(bw, mask);
   uint32_t acc0 = 0u, acc1 = 0u;       // two dependency chains
 #pragma unroll
   for (int rr = 0; rr < 16; ++rr) {
@@ -203,20 +196,14 @@ __global__ __launch_bounds__(kThreads) void refine_chain_kernel(const unsigned c
     const unsigned long long cost = (unsigned long long)(acc0 + acc1) + (unsigned long long)a.lambda * len;
     best = (cost << 27) | (len << 18) | ((unsigned long long)(dy + 256) << 9) | (unsigned long long)(dx + 256);
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(best, o, 64);
-    best = other < best ? other : best;
-  }
+  wave_min(best);
   if (lane == 0 && live) {
     // (0, 0) is always valid, so a key exists
     int bdx = (int)(best & 511ull) - 256, bdy = (int)((best >> 9) & 511ull) - 256;
     const long long len = (long long)((best >> 18) & 511ull);
     const int sad = (int)((long long)(best >> 27) - (long long)a.lambda * len);
     if (a.max_sad > 0 && sad > a.max_sad) { bdx = 0; bdy = 0; }
-    int* row = mvs + (size_t)g * 7;
-    row[0] = -1; row[1] = 16; row[2] = 16;
-    row[3] = x0 + 8 + bdx; row[4] = y0 + 8 + bdy; row[5] = x0 + 8; row[6] = y0 + 8;
+    store_row(mvs + (size_t)g * 7, x0, y0, bdx, bdy);
     if (sad_out) sad_out[g] = sad;
   }
 }
@@ -256,31 +243,23 @@ extern "C" int lsfa_mv_refine_chain(const unsigned char* luma, long long plane_s
                                     const int* parent_mvs, int refine, int lambda, int max_sad, int* mvs, int* sad, void* stream) {
   const char* who = "lsfa_mv_refine_chain";
   LSFA_REQUIRE(luma && parent_mvs && mvs, "%s: NULL argument", who);
-  LSFA_REQUIRE(width > 0 && height > 0 && (long)width * height < (1L << 30), "%s: bad frame size %d x %d", who, width, height);
   LSFA_REQUIRE(refine >= 1 && refine <= kMaxRefine, "%s: refine %d is outside 1..%d", who, refine, kMaxRefine);
-  LSFA_REQUIRE(lambda >= 0 && lambda <= kMaxLambda, "%s: lambda %d is outside 0..%d", who, lambda, kMaxLambda);
-  LSFA_REQUIRE(max_sad >= 0, "%s: max_sad %d is negative (0 switches it off)", who, max_sad);
-  LSFA_REQUIRE(n_chains >= 1 && n_frames >= 1, "%s: %d chains of %d frames: both counts must be at least 1", who, n_chains, n_frames);
   RefineArgs a;
+  long pairs;
+  if (const int rc = me_stack_args(who, luma, plane_stride, n_chains, n_frames, width, height, lambda, max_sad, &a.blocks, &pairs)) return rc;
+  // the kernel's own index arithmetic: a wave's pair index times the parent grid's blocks
+  LSFA_REQUIRE(pairs < (1L << 24), "%s: %ld pairs of %d macroblocks exceed one grid", who, pairs, a.blocks);
   a.total = (long)width * height;
-  // stated without |plane_stride| (the negation of LLONG_MIN overflows); below 2^36 the kernel's plane offsets stay inside 64 bits
-  LSFA_REQUIRE((plane_stride >= a.total || plane_stride <= -(long long)a.total) && (plane_stride & 3) == 0 && plane_stride > -(1LL << 36) &&
-                   plane_stride < (1LL << 36),
-               "%s: plane stride %lld must hold a %d x %d plane, be a multiple of 4 and lie below 2^36", who, plane_stride, width, height);
-  LSFA_REQUIRE((reinterpret_cast<uintptr_t>(luma) & 3u) == 0, "%s: the luma planes must be 4-byte aligned", who);
   a.W = width; a.H = height;
   a.mbw = ceil_div(width, 16);
-  a.blocks = a.mbw * ceil_div(height, 16);
   a.pmbw = ceil_div(ceil_div(width, 2), 16);
   a.pblocks = a.pmbw * ceil_div(ceil_div(height, 2), 16);
   a.r = refine; a.lambda = lambda; a.max_sad = max_sad; a.n_frames = n_frames;
   a.stride = plane_stride;
-  a.waves = (long)n_chains * n_frames * a.blocks;
-  LSFA_REQUIRE((long)n_chains * n_frames < (1L << 24) && a.waves < (1L << 31), "%s: %ld pairs of %d macroblocks exceed one grid", who,
-               (long)n_chains * n_frames, a.blocks);
+  a.waves = pairs * a.blocks;
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(LSFA_OP_MV_ESTIMATE, s);
   hipLaunchKernelGGL(refine_chain_kernel, dim3((unsigned)((a.waves + kWaves - 1) / kWaves)), dim3(kThreads), 0, s, luma, parent_mvs, a, mvs, sad);
-  LSFA_LAUNCH_CHECK("lsfa_mv_refine_chain");
+  LSFA_LAUNCH_CHECK(who);
   return LSFA_OK;
 }

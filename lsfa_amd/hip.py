@@ -133,6 +133,17 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _tensor(who, what, t, dtype, shape, device=None):
+    """t, if it is a contiguous `dtype` tensor of `shape` (a string stands for an axis of any size) on `device` (None: any CUDA device);
+    else an LsfaError that names what arrived"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != len(shape) or not (t.is_cuda if device is None else t.device == device) or \
+            any(not isinstance(w, str) and int(v) != w for v, w in zip(t.shape, shape)) or not t.is_contiguous():
+        raise LsfaError("%s: %s must be a contiguous (%s) %s tensor on %s, got %s %s on %s" %
+                        (who, what, ", ".join(str(w) for w in shape), dtype, device or "a CUDA device", tuple(getattr(t, 'shape', ())),
+                         getattr(t, 'dtype', type(t)), getattr(t, 'device', None)))
+    return t
+
+
 def _on_tensor_device(fn):
     """Run an op with the device of its first tensor argument current, so that `_stream()` (the CURRENT
     stream of the CURRENT device) and the C side's per-device state belong to the tensors' device even
@@ -713,10 +724,10 @@ def copy_many(pairs):
 
 
 @_on_tensor_device
-def transform_mv_res(motion_vector, res_diff, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16, negate_mv=False):
+def transform_mv_res(motion_vector, res_diff, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16, negate_mv=False, out=None):
     """lsfa_transform_mv_res: (H, W, 2) motion vectors + (H, W, 3) residual on the device (int32 or float32) -> `motion_vector` (1, 2, h, w),
     `res_diff` (1, 3, h, w) float32 (transform_mv_res, lib/utils/image.py:202-228), one launch.  negate_mv: get_image's
-    `motion_vector = - motion_vector` (:54) applied to the source values."""
+    `motion_vector = - motion_vector` (:54) applied to the source values.  out: a pair of contiguous float32 tensors of those shapes."""
     mv, res = motion_vector, res_diff
     if mv.dtype != res.dtype or mv.dtype not in (torch.int32, torch.float32):
         raise LsfaError("transform_mv_res: int32 or float32 maps expected, got %s / %s" % (mv.dtype, res.dtype))
@@ -725,8 +736,10 @@ def transform_mv_res(motion_vector, res_diff, im_scale, pixel_means=(0.0, 0.0, 0
     H, W = int(mv.shape[0]), int(mv.shape[1])
     h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
     oh, ow = ph // rcnn_stride, pw // rcnn_stride
-    out_mv = torch.empty((1, 2, oh, ow), device=mv.device, dtype=torch.float32)
-    out_res = torch.empty((1, 3, oh, ow), device=mv.device, dtype=torch.float32)
+    if out is None:
+        out = (torch.empty((1, 2, oh, ow), device=mv.device, dtype=torch.float32), torch.empty((1, 3, oh, ow), device=mv.device, dtype=torch.float32))
+    out_mv = _tensor("transform_mv_res", "output buffer out[0]", out[0], torch.float32, (1, 2, oh, ow), mv.device)
+    out_res = _tensor("transform_mv_res", "output buffer out[1]", out[1], torch.float32, (1, 3, oh, ow), mv.device)
     _check(lib().lsfa_transform_mv_res(_ptr(mv), _ptr(res), int(mv.dtype == torch.int32) | (2 if negate_mv else 0), H, W, float(im_scale), h1, w1,
                                        int(rcnn_stride), _means(pixel_means), float(pixel_scale), _ptr(out_mv), _ptr(out_res), oh, ow, _stream()),
            "lsfa_transform_mv_res")
@@ -1417,7 +1430,8 @@ class MotionVectorAccumulator(object):
         acc.add_frame(mvs)          # one P-frame's blocks, (n,7) int32 {source,w,h,src_x,src_y,dst_x,dst_y}
         acc.motion_vectors()        # (H,W,2) int32, what load(..., representation=MV, accumulate=True) returns
         acc.residual(bgr_cur, bgr_ref)   # (H,W,3) int32
-    """
+
+    motion_vectors and residual write into `out`, a contiguous int32 tensor of that shape on the device, where one is given."""
 
     def __init__(self, width, height, device='cuda:0'):
         self.width, self.height, self.device = int(width), int(height), torch.device(device)
@@ -1451,18 +1465,25 @@ class MotionVectorAccumulator(object):
                                             _stream()), "lsfa_mv_accumulate")
         self._cur = 1 - self._cur
 
-    def motion_vectors(self):
-        mv = torch.empty((self.height, self.width, 2), dtype=torch.int32, device=self.device)
+    def _map(self, who, channels, out):
+        """the (H, W, channels) int32 map a method returns: the caller's `out`, checked, or a new one"""
+        shape = (self.height, self.width, channels)
+        if out is None:
+            return torch.empty(shape, dtype=torch.int32, device=self.device)
+        return _tensor(who, "output buffer out", out, torch.int32, shape, self.device)
+
+    def motion_vectors(self, out=None):
+        mv = self._map("MotionVectorAccumulator.motion_vectors", 2, out)
         with torch.cuda.device(self.device):
             _check(lib().lsfa_mv_field(_ptr(self.accu), self.width, self.height, _ptr(mv), _stream()), "lsfa_mv_field")
         return mv
 
-    def residual(self, bgr_cur, bgr_ref):
+    def residual(self, bgr_cur, bgr_ref, out=None):
         for t in (bgr_cur, bgr_ref):
             if t.dtype != torch.uint8 or tuple(t.shape) != (self.height, self.width, 3):
                 raise LsfaError("frames must be (H, W, 3) uint8")
         bgr_cur, bgr_ref = bgr_cur.to(self.device).contiguous(), bgr_ref.to(self.device).contiguous()
-        res = torch.empty((self.height, self.width, 3), dtype=torch.int32, device=self.device)
+        res = self._map("MotionVectorAccumulator.residual", 3, out)
         with torch.cuda.device(self.device):
             _check(lib().lsfa_mv_residual(_ptr(bgr_cur), _ptr(bgr_ref), _ptr(self.accu), self.width, self.height, _ptr(res), _stream()),
                    "lsfa_mv_residual")
@@ -1497,30 +1518,33 @@ def pyramid_shapes(height, width, levels):
     return shapes
 
 
-def _pyramid_params(who, levels, refine):
-    levels, refine = int(levels), int(refine)
-    if not 0 <= levels <= 2:
-        raise LsfaError("%s: levels %d is outside 0..2" % (who, levels))
-    if levels and not 1 <= refine <= 3:
-        raise LsfaError("%s: refine %d is outside 1..3" % (who, refine))
-    return levels, refine
-
-
 def _plane_stack(t, shape, stride0):
     """a flat uint8 buffer as (N, h, w) planes `stride0` bytes apart"""
     return t.as_strided(shape, (stride0, shape[2], 1))
 
 
+def _search_outputs(who, lead, H, W, device, out, sad_out, return_sad):
+    """the rows `lead` + (mbh * mbw, 7) and the SAD `lead` + (mbh, mbw) of a search on (H, W) planes: allocated where the caller gave none
+    (the SAD only if asked for), the caller's checked -> (out, sad_out or None)"""
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    if out is None:
+        out = torch.empty(lead + (mbh * mbw, 7), dtype=torch.int32, device=device)
+    if return_sad and sad_out is None:
+        sad_out = torch.empty(lead + (mbh, mbw), dtype=torch.int32, device=device)
+    _tensor(who, "output buffer out", out, torch.int32, lead + (mbh * mbw, 7), device)
+    if sad_out is not None:
+        _tensor(who, "output buffer sad_out", sad_out, torch.int32, lead + (mbh, mbw), device)
+    return out, sad_out
+
+
 @_on_tensor_device
 def luma_u8(bgr, out=None):
     """lsfa_luma_u8: (H, W, 3) uint8 BGR frame on the device -> (H, W) uint8 luma, Y = (29 B + 150 G + 77 R + 128) >> 8."""
-    if not isinstance(bgr, torch.Tensor) or bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3 or not bgr.is_cuda or not bgr.is_contiguous():
-        raise LsfaError("luma_u8: a contiguous (H, W, 3) uint8 CUDA tensor expected, got %s %s" % (tuple(getattr(bgr, 'shape', ())), getattr(bgr, 'dtype', type(bgr))))
+    _tensor("luma_u8", "bgr", bgr, torch.uint8, ("H", "W", 3))
     H, W = int(bgr.shape[0]), int(bgr.shape[1])
     if out is None:
         out = torch.empty((H, W), dtype=torch.uint8, device=bgr.device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or out.device != bgr.device or not out.is_contiguous():
-        raise LsfaError("luma_u8: out must be a contiguous (%d, %d) uint8 tensor on %s" % (H, W, bgr.device))
+    _tensor("luma_u8", "out", out, torch.uint8, (H, W), bgr.device)
     _check(lib().lsfa_luma_u8(_ptr(bgr), W, H, _ptr(out), _stream()), "lsfa_luma_u8")
     return out
 
@@ -1531,202 +1555,30 @@ def mv_estimate(luma_cur, luma_ref, search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_
     16 x 16 macroblock (zero vectors included), as MotionVectorAccumulator.add_frame takes them; with return_sad also the winners' SAD
     (mbh, mbw) int32.  Full search over [-search, search]^2, cost = SAD + lam (|dx| + |dy|), ties by (|dx| + |dy|, dy, dx); max_sad > 0 zeroes
     the vector of a block whose best SAD exceeds it.  Defined by its own specification (include/lsfa_hip.h), not by an encoder's search."""
-    for t in (luma_cur, luma_ref):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or not t.is_cuda or not t.is_contiguous():
-            raise LsfaError("mv_estimate: contiguous (H, W) uint8 CUDA planes expected, got %s %s" % (tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
-    if luma_cur.shape != luma_ref.shape or luma_cur.device != luma_ref.device:
-        raise LsfaError("mv_estimate: the planes differ: %s on %s / %s on %s" % (tuple(luma_cur.shape), luma_cur.device, tuple(luma_ref.shape), luma_ref.device))
+    _tensor("mv_estimate", "luma_cur", luma_cur, torch.uint8, ("H", "W"))
     H, W = int(luma_cur.shape[0]), int(luma_cur.shape[1])
-    mbh, mbw = -(-H // 16), -(-W // 16)
-    if out is None:
-        out = torch.empty((mbh * mbw, 7), dtype=torch.int32, device=luma_cur.device)
-    if return_sad and sad_out is None:
-        sad_out = torch.empty((mbh, mbw), dtype=torch.int32, device=luma_cur.device)
-    for t, shape in ((out, (mbh * mbw, 7)), (sad_out, (mbh, mbw))):
-        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != luma_cur.device or not t.is_contiguous()):
-            raise LsfaError("mv_estimate: an output buffer is not a contiguous %s int32 tensor on %s" % (shape, luma_cur.device))
+    _tensor("mv_estimate", "luma_ref (a plane like luma_cur)", luma_ref, torch.uint8, (H, W), luma_cur.device)
+    out, sad_out = _search_outputs("mv_estimate", (), H, W, luma_cur.device, out, sad_out, return_sad)
     _check(lib().lsfa_mv_estimate(_ptr(luma_cur), _ptr(luma_ref), W, H, int(search), int(lam), int(max_sad), _ptr(out), _ptr(sad_out), _stream()),
            "lsfa_mv_estimate")
     return (out, sad_out) if return_sad else out
 
 
-class MotionEstimator(object):
-    """Decoded uint8 frames in, the network's `motion_vector` / `res_diff` out: block motion estimation (lsfa_luma_u8 + lsfa_mv_estimate) in
-    front of a MotionVectorAccumulator, for clips without compressed-stream side data.
-
-        me = MotionEstimator(width, height, device)
-        me.key_frame(bgr0)                   # the GOP's I-frame: identity accumulation, bgr0 becomes the reference
-        me.next_frame(bgr1)                  # a P-frame: vectors against the PREVIOUS frame (an IPPP chain), accumulated
-        mv, res = me.network_inputs(bgr1, bgr0, im_scale, pixel_means, pixel_scale)
-
-    Every buffer is allocated up front (the outputs of network_inputs at its first call for a scale), nothing is read back and nothing
-    synchronises, so the three calls can be captured in a graph on one stream and replayed on new frame contents written into the same
-    tensors.  The tensors network_inputs returns are reused by the next call.
-
-    Frames that arrive as a decoder's YUV 4:2:0 planes (see yuv420_to_bgr_u8) go through key_frame_yuv / next_frame_yuv, which convert into
-    BGR buffers the estimator owns (self.bgr_key; self.bgr_cur, a ping-pong pair - allocated at the first such call, nothing after it) and
-    return that buffer: `me.network_inputs(me.bgr_cur, me.bgr_key, ...)` works unchanged.  luma_from='bgr' (the default) searches
-    lsfa_luma_u8 of the converted frame: the rows are those of feeding the converted frames to key_frame / next_frame.  luma_from='y'
-    searches the decoder's own Y plane (the conversion's y_packed output, no luma launch): DIFFERENT numbers - Y is limited-range (16..235)
-    and weighs the channels by the stream's matrix, lsfa_luma_u8 is full-range with its own weights - so SADs, the lambda trade-off and
-    therefore some vectors differ.  `matrix` is the conversion's.
-
-    levels = 1 or 2 switches to the pyramid search (lsfa_amd/csrc/me_pyramid.hip; DESIGN.md "Pyramid search"): `search` is then the range on the
-    top level and self.reach = search * 2^levels + refine * (2^levels - 1) pixels.  The pyramids of both ping-pong planes are kept and only
-    the new frame's is built: next_frame is levels + 2 launches in front of the accumulation (pyramid, top search, one refinement per
-    level) instead of one.  levels = 0 (the default) runs exactly the full search's launches; `refine` is ignored there."""
-
-    def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr', matrix='bt601',
-                 levels=ME_LEVELS, refine=ME_REFINE):
-        self.levels, self.refine = _pyramid_params("MotionEstimator", levels, refine)
-        if luma_from not in ('bgr', 'y'):
-            raise LsfaError("MotionEstimator: luma_from %r is not 'bgr' or 'y'" % (luma_from,))
-        if matrix not in YUV_MATRICES:
-            raise LsfaError("MotionEstimator: matrix %r is not one of %s" % (matrix, sorted(YUV_MATRICES)))
-        self.luma_from, self.matrix = luma_from, matrix
-        self.bgr_key, self._bgr_pp, self._bgr_i = None, None, 0
-        self.width, self.height, self.device = int(width), int(height), torch.device(device)
-        self.search, self.lam, self.max_sad = int(search), int(lam), int(max_sad)
-        if not 1 <= self.search <= 32 or self.lam < 0 or self.max_sad < 0:
-            raise LsfaError("MotionEstimator: search %d (1..32), lam %d (>= 0), max_sad %d (>= 0)" % (self.search, self.lam, self.max_sad))
-        H, W = self.height, self.width
-        self.mbh, self.mbw = -(-H // 16), -(-W // 16)
-        self.acc = MotionVectorAccumulator(W, H, self.device)
-        self.reach = me_reach(self.levels, self.search, self.refine)
-        # the two ping-pong planes of every level lie one (4-byte aligned) plane apart in one buffer: the refinement takes a pair as a stack
-        # of two, forwards or in reverse
-        self._shapes = pyramid_shapes(H, W, self.levels)
-        self._pplane = [-(-h * w // 4) * 4 for h, w in self._shapes]
-        self._planes = [_plane_stack(torch.empty(2 * ps, dtype=torch.uint8, device=self.device), (2, h, w), ps)
-                        for ps, (h, w) in zip(self._pplane, self._shapes)]
-        self._luma = [self._planes[0][0], self._planes[0][1]]
-        self._prows = [torch.empty((-(-h // 16) * -(-w // 16), 7), dtype=torch.int32, device=self.device) for h, w in self._shapes[1:]]
-        self._ref = 0                   # index of the previous frame's plane
-        self.rows = torch.empty((self.mbh * self.mbw, 7), dtype=torch.int32, device=self.device)
-        self.sad = torch.empty((self.mbh, self.mbw), dtype=torch.int32, device=self.device)
-        self._mv = torch.empty((H, W, 2), dtype=torch.int32, device=self.device)
-        self._res = torch.empty((H, W, 3), dtype=torch.int32, device=self.device)
-        self._out = {}
-
-    def _frame(self, bgr, who):
-        if not isinstance(bgr, torch.Tensor) or bgr.dtype != torch.uint8 or tuple(bgr.shape) != (self.height, self.width, 3) or bgr.device != self.device or not bgr.is_contiguous():
-            raise LsfaError("MotionEstimator.%s: a contiguous (%d, %d, 3) uint8 frame on %s expected, got %s %s" %
-                            (who, self.height, self.width, self.device, tuple(getattr(bgr, 'shape', ())), getattr(bgr, 'dtype', type(bgr))))
-        return bgr
-
-    def _pyramid_of(self, i):
-        """the pyramid of ping-pong plane i alone (one launch; nothing with levels = 0)"""
-        if self.levels:
-            luma_pyramid(self._planes[0][i:i + 1], self.levels, out=[p[i:i + 1] for p in self._planes[1:]])
-
-    def _search(self, cur):
-        """rows / SAD of plane `cur` against plane self._ref: the full search, or with levels > 0 the pyramid of the new plane, the full
-        search on the top level and one refinement per level below it"""
-        ref, L = self._ref, self.levels
-        if L == 0:
-            mv_estimate(self._luma[cur], self._luma[ref], self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
-            return
-        self._pyramid_of(cur)
-        rows = [self.rows] + self._prows
-        mv_estimate(self._planes[L][cur], self._planes[L][ref], self.search, self.lam, 0, out=rows[L])
-        with torch.cuda.device(self.device):
-            for k in range(L - 1, -1, -1):
-                h, w = self._shapes[k]
-                # the pair as a stack of two that starts at the reference plane: forwards if the current plane lies behind it, else in reverse
-                _check(lib().lsfa_mv_refine_chain(_ptr(self._planes[k][ref]), (cur - ref) * self._pplane[k], 1, 1, w, h, _ptr(rows[k + 1]), self.refine,
-                                                  self.lam, self.max_sad if k == 0 else 0, _ptr(rows[k]), _ptr(self.sad) if k == 0 else None, _stream()),
-                       "lsfa_mv_refine_chain")
-
-    def key_frame(self, bgr):
-        luma_u8(self._frame(bgr, 'key_frame'), out=self._luma[self._ref])
-        self._pyramid_of(self._ref)
-        self.acc.reset()
-
-    def next_frame(self, bgr):
-        """Estimates the frame's vectors against the previous frame and accumulates them; returns the (mbh * mbw, 7) rows (a buffer the
-        next call overwrites; self.sad holds the winners' SAD)."""
-        cur = 1 - self._ref
-        luma_u8(self._frame(bgr, 'next_frame'), out=self._luma[cur])
-        self._search(cur)
-        self.acc.add_frame(self.rows, max_block_area=256)      # the explicit area: no device-to-host read
-        self._ref = cur
-        return self.rows
-
-    @property
-    def bgr_cur(self):
-        """the BGR frame the last next_frame_yuv converted (None before the first)"""
-        return None if self._bgr_pp is None else self._bgr_pp[self._bgr_i]
-
-    def _yuv_buffers(self):
-        if self.bgr_key is None:          # the first *_yuv call: the only allocation
-            self.bgr_key = torch.empty((self.height, self.width, 3), dtype=torch.uint8, device=self.device)
-            self._bgr_pp = [torch.empty_like(self.bgr_key) for _ in range(2)]
-
-    def _yuv_to(self, bgr, luma, y, uv, u, v, who):
-        if not isinstance(y, torch.Tensor) or tuple(y.shape) != (self.height, self.width) or y.device != self.device:
-            raise LsfaError("MotionEstimator.%s: a (%d, %d) uint8 Y plane on %s expected, got %s on %s" %
-                            (who, self.height, self.width, self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
-        if self.luma_from == 'y':
-            yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=bgr, y_packed=luma)
-        else:
-            yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=bgr)
-            luma_u8(bgr, out=luma)
-        return bgr
-
-    def key_frame_yuv(self, y, uv=None, u=None, v=None):
-        """key_frame on a decoder's planes: converts into self.bgr_key and returns it"""
-        self._yuv_buffers()
-        bgr = self._yuv_to(self.bgr_key, self._luma[self._ref], y, uv, u, v, 'key_frame_yuv')
-        self._pyramid_of(self._ref)
-        self.acc.reset()
-        return bgr
-
-    def next_frame_yuv(self, y, uv=None, u=None, v=None):
-        """next_frame on a decoder's planes: converts into the other buffer of the ping-pong pair, which becomes self.bgr_cur, and returns it
-        (the rows are in self.rows, the winners' SAD in self.sad)"""
-        self._yuv_buffers()
-        cur, nxt = 1 - self._ref, 1 - self._bgr_i
-        bgr = self._yuv_to(self._bgr_pp[nxt], self._luma[cur], y, uv, u, v, 'next_frame_yuv')
-        self._search(cur)
-        self.acc.add_frame(self.rows, max_block_area=256)
-        self._ref, self._bgr_i = cur, nxt
-        return bgr
-
-    def network_inputs(self, bgr_cur, bgr_key, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16):
-        """`motion_vector` (1, 2, h, w) and `res_diff` (1, 3, h, w) of the current frame against the key frame, as
-        MotionVectorAccumulator.network_inputs builds them (lsfa_mv_field, lsfa_mv_residual, lsfa_transform_mv_res), into buffers of its own."""
-        bgr_cur, bgr_key = self._frame(bgr_cur, 'network_inputs'), self._frame(bgr_key, 'network_inputs')
-        H, W = self.height, self.width
-        h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
-        oh, ow = ph // rcnn_stride, pw // rcnn_stride
-        if (oh, ow) not in self._out:
-            self._out[(oh, ow)] = (torch.empty((1, 2, oh, ow), device=self.device, dtype=torch.float32),
-                                   torch.empty((1, 3, oh, ow), device=self.device, dtype=torch.float32))
-        out_mv, out_res = self._out[(oh, ow)]
-        L = lib()
-        with torch.cuda.device(self.device):
-            _check(L.lsfa_mv_field(_ptr(self.acc.accu), W, H, _ptr(self._mv), _stream()), "lsfa_mv_field")
-            _check(L.lsfa_mv_residual(_ptr(bgr_cur), _ptr(bgr_key), _ptr(self.acc.accu), W, H, _ptr(self._res), _stream()), "lsfa_mv_residual")
-            _check(L.lsfa_transform_mv_res(_ptr(self._mv), _ptr(self._res), 1 | 2, H, W, float(im_scale), h1, w1, int(rcnn_stride),
-                                           _means(pixel_means), float(pixel_scale), _ptr(out_mv), _ptr(out_res), oh, ow, _stream()),
-                   "lsfa_transform_mv_res")
-        return out_mv, out_res
-
-
 def _u8_stack(who, name, t, trailing):
-    """a uint8 CUDA stack (C, F + 1) + trailing whose frames are dense and whose chains lie (F + 1) frames apart -> (C, F, frame stride)"""
+    """a uint8 CUDA stack (C, F + 1) + trailing (a string stands for an axis of any size) whose frames are dense and whose chains lie (F + 1)
+    frames apart -> (C, F, frame stride, the frame's shape)"""
     nd = 2 + len(trailing)
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != nd or tuple(t.shape[2:]) != tuple(trailing) or \
-            int(t.shape[0]) < 1 or int(t.shape[1]) < 2:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != nd or int(t.shape[0]) < 1 or int(t.shape[1]) < 2 or \
+            any(not isinstance(w, str) and int(v) != w for v, w in zip(t.shape[2:], trailing)):
         raise LsfaError("%s: %s must be a (C, F + 1, %s) uint8 CUDA stack with C >= 1 and F >= 1, got %s %s" %
                         (who, name, ", ".join(str(v) for v in trailing), tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
-    C, F1 = int(t.shape[0]), int(t.shape[1])
-    dense = tuple(int(np.prod(trailing[i + 1:])) for i in range(len(trailing)))
+    C, F1, frame = int(t.shape[0]), int(t.shape[1]), tuple(int(v) for v in t.shape[2:])
+    dense = tuple(int(np.prod(frame[i + 1:])) for i in range(len(frame)))
     fs = int(t.stride(1))
-    if tuple(int(s) for s in t.stride()[2:]) != dense or fs < int(np.prod(trailing)) or (C > 1 and int(t.stride(0)) != F1 * fs):
+    if tuple(int(s) for s in t.stride()[2:]) != dense or fs < int(np.prod(frame)) or (C > 1 and int(t.stride(0)) != F1 * fs):
         raise LsfaError("%s: %s needs dense frames, one stride from frame to frame and chains (F + 1) frames apart; got shape %s strides %s" %
                         (who, name, tuple(t.shape), tuple(t.stride())))
-    return C, F1 - 1, fs
+    return C, F1 - 1, fs, frame
 
 
 @_on_tensor_device
@@ -1734,20 +1586,8 @@ def mv_estimate_chain(luma_stack, search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MA
     """lsfa_mv_estimate_chain: a (C, F + 1, H, W) uint8 stack of luma planes on the device, plane 0 of a chain its key frame -> rows
     (C, F, mbh * mbw, 7) int32, rows[c, f - 1] = mv_estimate(plane f, plane f - 1) of chain c bit for bit; with return_sad also the winners' SAD
     (C, F, mbh, mbw).  The plane stride is taken from .stride() (a multiple of 4 that holds a plane).  One launch."""
-    who = "mv_estimate_chain"
-    if not isinstance(luma_stack, torch.Tensor) or luma_stack.dim() != 4:
-        raise LsfaError("%s: a (C, F + 1, H, W) uint8 CUDA stack expected, got %s %s" %
-                        (who, tuple(getattr(luma_stack, 'shape', ())), getattr(luma_stack, 'dtype', type(luma_stack))))
-    H, W = int(luma_stack.shape[2]), int(luma_stack.shape[3])
-    C, F, stride = _u8_stack(who, "luma_stack", luma_stack, (H, W))
-    mbh, mbw = -(-H // 16), -(-W // 16)
-    if out is None:
-        out = torch.empty((C, F, mbh * mbw, 7), dtype=torch.int32, device=luma_stack.device)
-    if return_sad and sad_out is None:
-        sad_out = torch.empty((C, F, mbh, mbw), dtype=torch.int32, device=luma_stack.device)
-    for t, shape in ((out, (C, F, mbh * mbw, 7)), (sad_out, (C, F, mbh, mbw))):
-        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != luma_stack.device or not t.is_contiguous()):
-            raise LsfaError("%s: an output buffer is not a contiguous %s int32 tensor on %s" % (who, shape, luma_stack.device))
+    C, F, stride, (H, W) = _u8_stack("mv_estimate_chain", "luma_stack", luma_stack, ("H", "W"))
+    out, sad_out = _search_outputs("mv_estimate_chain", (C, F), H, W, luma_stack.device, out, sad_out, return_sad)
     _check(lib().lsfa_mv_estimate_chain(_ptr(luma_stack), stride, C, F, W, H, int(search), int(lam), int(max_sad), _ptr(out), _ptr(sad_out), _stream()),
            "lsfa_mv_estimate_chain")
     return (out, sad_out) if return_sad else out
@@ -1798,26 +1638,13 @@ def mv_refine_chain(luma_stack, parent_rows, refine=ME_REFINE, lam=ME_LAMBDA, ma
     2 * (its parent (bx >> 1, by >> 1)'s vector) + [-refine, refine]^2 and (0, 0), under the full search's cost, order and validity rule.
     One launch."""
     who = "mv_refine_chain"
-    if not isinstance(luma_stack, torch.Tensor) or luma_stack.dim() != 4:
-        raise LsfaError("%s: a (C, F + 1, H, W) uint8 CUDA stack expected, got %s %s" %
-                        (who, tuple(getattr(luma_stack, 'shape', ())), getattr(luma_stack, 'dtype', type(luma_stack))))
-    H, W = int(luma_stack.shape[2]), int(luma_stack.shape[3])
-    C, F, stride = _u8_stack(who, "luma_stack", luma_stack, (H, W))
-    mbh, mbw = -(-H // 16), -(-W // 16)
-    pblocks = -(-(-(-H // 2)) // 16) * -(-(-(-W // 2)) // 16)
-    p = parent_rows
-    if not isinstance(p, torch.Tensor) or p.dtype != torch.int32 or tuple(p.shape) != (C, F, pblocks, 7) or p.device != luma_stack.device or not p.is_contiguous():
-        raise LsfaError("%s: parent_rows must be a contiguous (%d, %d, %d, 7) int32 tensor on %s (the rows of the %d x %d level above), got %s %s" %
-                        (who, C, F, pblocks, luma_stack.device, -(-W // 2), -(-H // 2), tuple(getattr(p, 'shape', ())), getattr(p, 'dtype', type(p))))
-    if out is None:
-        out = torch.empty((C, F, mbh * mbw, 7), dtype=torch.int32, device=luma_stack.device)
-    if return_sad and sad_out is None:
-        sad_out = torch.empty((C, F, mbh, mbw), dtype=torch.int32, device=luma_stack.device)
-    for t, shape in ((out, (C, F, mbh * mbw, 7)), (sad_out, (C, F, mbh, mbw))):
-        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != luma_stack.device or not t.is_contiguous()):
-            raise LsfaError("%s: an output buffer is not a contiguous %s int32 tensor on %s" % (who, shape, luma_stack.device))
-    _check(lib().lsfa_mv_refine_chain(_ptr(luma_stack), stride, C, F, W, H, _ptr(p), int(refine), int(lam), int(max_sad), _ptr(out), _ptr(sad_out),
-                                      _stream()), "lsfa_mv_refine_chain")
+    C, F, stride, (H, W) = _u8_stack(who, "luma_stack", luma_stack, ("H", "W"))
+    h1, w1 = pyramid_shapes(H, W, 1)[1]
+    _tensor(who, "parent_rows (the rows of the %d x %d level above)" % (w1, h1), parent_rows, torch.int32, (C, F, -(-h1 // 16) * -(-w1 // 16), 7),
+            luma_stack.device)
+    out, sad_out = _search_outputs(who, (C, F), H, W, luma_stack.device, out, sad_out, return_sad)
+    _check(lib().lsfa_mv_refine_chain(_ptr(luma_stack), stride, C, F, W, H, _ptr(parent_rows), int(refine), int(lam), int(max_sad), _ptr(out),
+                                      _ptr(sad_out), _stream()), "lsfa_mv_refine_chain")
     return (out, sad_out) if return_sad else out
 
 
@@ -1828,16 +1655,8 @@ def mv_segment_inputs(rows, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pi
     frame-major: [f - 1, c] is what MotionEstimator.network_inputs returns for frame f of chain c, bit for bit.  One launch, no
     full-resolution map.  The frame stride is taken from .stride().  out: a pair of contiguous float32 tensors of those shapes."""
     who = "mv_segment_inputs"
-    if not isinstance(bgr_stack, torch.Tensor) or bgr_stack.dim() != 5:
-        raise LsfaError("%s: a (C, F + 1, H, W, 3) uint8 CUDA stack expected, got %s %s" %
-                        (who, tuple(getattr(bgr_stack, 'shape', ())), getattr(bgr_stack, 'dtype', type(bgr_stack))))
-    H, W = int(bgr_stack.shape[2]), int(bgr_stack.shape[3])
-    C, F, stride = _u8_stack(who, "bgr_stack", bgr_stack, (H, W, 3))
-    mbh, mbw = -(-H // 16), -(-W // 16)
-    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or tuple(rows.shape) != (C, F, mbh * mbw, 7) or rows.device != bgr_stack.device or \
-            not rows.is_contiguous():
-        raise LsfaError("%s: rows must be a contiguous (%d, %d, %d, 7) int32 tensor on %s, got %s %s" %
-                        (who, C, F, mbh * mbw, bgr_stack.device, tuple(getattr(rows, 'shape', ())), getattr(rows, 'dtype', type(rows))))
+    C, F, stride, (H, W, _) = _u8_stack(who, "bgr_stack", bgr_stack, ("H", "W", 3))
+    _tensor(who, "rows", rows, torch.int32, (C, F, -(-H // 16) * -(-W // 16), 7), bgr_stack.device)
     if not float(im_scale) > 0.0 or int(rcnn_stride) < 1:
         raise LsfaError("%s: im_scale %r must be positive and rcnn_stride %r at least 1" % (who, im_scale, rcnn_stride))
     rcnn_stride = int(rcnn_stride)
@@ -1846,13 +1665,197 @@ def mv_segment_inputs(rows, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pi
     if out is None:
         out = (torch.empty((F, C, 2, oh, ow), device=bgr_stack.device, dtype=torch.float32),
                torch.empty((F, C, 3, oh, ow), device=bgr_stack.device, dtype=torch.float32))
-    out_mv, out_res = out
-    for t, shape in ((out_mv, (F, C, 2, oh, ow)), (out_res, (F, C, 3, oh, ow))):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != bgr_stack.device or not t.is_contiguous():
-            raise LsfaError("%s: an output buffer is not a contiguous %s float32 tensor on %s" % (who, shape, bgr_stack.device))
+    out_mv = _tensor(who, "output buffer out[0]", out[0], torch.float32, (F, C, 2, oh, ow), bgr_stack.device)
+    out_res = _tensor(who, "output buffer out[1]", out[1], torch.float32, (F, C, 3, oh, ow), bgr_stack.device)
     _check(lib().lsfa_mv_segment_inputs(_ptr(rows), _ptr(bgr_stack), stride, C, F, W, H, float(im_scale), h1, w1, rcnn_stride, _means(pixel_means),
                                         float(pixel_scale), _ptr(out_mv), _ptr(out_res), oh, ow, _stream()), "lsfa_mv_segment_inputs")
     return out_mv, out_res
+
+
+class _MotionSearch(object):
+    """What MotionEstimator and SegmentMotionEstimator share: the checked parameters, the geometry of every level, the planes and rows of
+    every level for `planes` luma planes and `pairs` pairs - flat, so that any run of planes is a stack of its own in front of the same
+    memory - and the coarse-to-fine sequence on a stack of them."""
+
+    def __init__(self, who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes, pairs):
+        self.levels, self.refine = int(levels), int(refine)
+        if not 0 <= self.levels <= 2:
+            raise LsfaError("%s: levels %d is outside 0..2" % (who, self.levels))
+        if self.levels and not 1 <= self.refine <= 3:
+            raise LsfaError("%s: refine %d is outside 1..3" % (who, self.refine))
+        if luma_from not in ('bgr', 'y'):
+            raise LsfaError("%s: luma_from %r is not 'bgr' or 'y'" % (who, luma_from))
+        if matrix not in YUV_MATRICES:
+            raise LsfaError("%s: matrix %r is not one of %s" % (who, matrix, sorted(YUV_MATRICES)))
+        self.luma_from, self.matrix = luma_from, matrix
+        self.width, self.height, self.device = int(width), int(height), torch.device(device)
+        self.search, self.lam, self.max_sad = int(search), int(lam), int(max_sad)
+        if not 1 <= self.search <= 32 or self.lam < 0 or self.max_sad < 0:
+            raise LsfaError("%s: search %d (1..32), lam %d (>= 0), max_sad %d (>= 0)" % (who, self.search, self.lam, self.max_sad))
+        self.reach = me_reach(self.levels, self.search, self.refine)
+        self.mbh, self.mbw = -(-self.height // 16), -(-self.width // 16)
+        # per level: the plane's shape, its size padded to the 4 bytes the searches want from plane to plane, its macroblocks
+        self.shapes = pyramid_shapes(self.height, self.width, self.levels)
+        self.plane = [-(-h * w // 4) * 4 for h, w in self.shapes]
+        self.blocks = [-(-h // 16) * -(-w // 16) for h, w in self.shapes]
+        self.flat = [torch.empty(planes * ps, dtype=torch.uint8, device=self.device) for ps in self.plane]
+        self.rows = [torch.empty(pairs * b * 7, dtype=torch.int32, device=self.device) for b in self.blocks]
+        self.sad = torch.empty(pairs * self.blocks[0], dtype=torch.int32, device=self.device)
+
+    def planes(self, k, first, count):
+        """planes first .. first + count - 1 of level k as (count, h_k, w_k)"""
+        return _plane_stack(self.flat[k][first * self.plane[k]:], (count,) + self.shapes[k], self.plane[k])
+
+    def pyramid(self, first, count):
+        """the upper levels of planes first .. first + count - 1 (one launch; nothing with levels = 0)"""
+        if self.levels:
+            luma_pyramid(self.planes(0, first, count), self.levels, out=[self.planes(k, first, count) for k in range(1, self.levels + 1)])
+
+    def run(self, chains, frames, first=0, step=1, built=0):
+        """Rows and SAD of every pair of `chains` stacks of frames + 1 planes, into the front of self.rows[0] / self.sad (self.rows[k]: level
+        k's).  The stack is addressed on every level as the exports address one - plane 0 at plane `first` of the flat buffer, the others
+        `step` planes on, -1 for a stack stored in reverse - and the pyramid of its first `built` planes exists already.  levels + 2
+        launches: the pyramid of the other planes, the full search on the top level, one refinement per level below it; with levels = 0
+        the full search alone.  max_sad and the SAD belong to level 0."""
+        L, N = self.levels, chains * (frames + 1)
+        self.pyramid(first + step * (built if step > 0 else N - 1), N - built)
+        with torch.cuda.device(self.device):
+            for k in range(L, -1, -1):
+                luma, stride, (h, w) = _ptr(self.flat[k][first * self.plane[k]:]), step * self.plane[k], self.shapes[k]
+                max_sad, sad = (0, None) if k else (self.max_sad, _ptr(self.sad))
+                if k == L:
+                    _check(lib().lsfa_mv_estimate_chain(luma, stride, chains, frames, w, h, self.search, self.lam, max_sad, _ptr(self.rows[k]), sad,
+                                                        _stream()), "lsfa_mv_estimate_chain")
+                else:
+                    _check(lib().lsfa_mv_refine_chain(luma, stride, chains, frames, w, h, _ptr(self.rows[k + 1]), self.refine, self.lam, max_sad,
+                                                      _ptr(self.rows[k]), sad, _stream()), "lsfa_mv_refine_chain")
+
+
+class MotionEstimator(object):
+    """Decoded uint8 frames in, the network's `motion_vector` / `res_diff` out: block motion estimation (lsfa_luma_u8 + lsfa_mv_estimate) in
+    front of a MotionVectorAccumulator, for clips without compressed-stream side data.
+
+        me = MotionEstimator(width, height, device)
+        me.key_frame(bgr0)                   # the GOP's I-frame: identity accumulation, bgr0 becomes the reference
+        me.next_frame(bgr1)                  # a P-frame: vectors against the PREVIOUS frame (an IPPP chain), accumulated
+        mv, res = me.network_inputs(bgr1, bgr0, im_scale, pixel_means, pixel_scale)
+
+    Every buffer is allocated up front (the outputs of network_inputs at its first call for a scale), nothing is read back and nothing
+    synchronises, so the three calls can be captured in a graph on one stream and replayed on new frame contents written into the same
+    tensors.  The tensors network_inputs returns are reused by the next call.
+
+    Frames that arrive as a decoder's YUV 4:2:0 planes (see yuv420_to_bgr_u8) go through key_frame_yuv / next_frame_yuv, which convert into
+    BGR buffers the estimator owns (self.bgr_key; self.bgr_cur, a ping-pong pair - allocated at the first such call, nothing after it) and
+    return that buffer: `me.network_inputs(me.bgr_cur, me.bgr_key, ...)` works unchanged.  luma_from='bgr' (the default) searches
+    lsfa_luma_u8 of the converted frame: the rows are those of feeding the converted frames to key_frame / next_frame.  luma_from='y'
+    searches the decoder's own Y plane (the conversion's y_packed output, no luma launch): DIFFERENT numbers - Y is limited-range (16..235)
+    and weighs the channels by the stream's matrix, lsfa_luma_u8 is full-range with its own weights - so SADs, the lambda trade-off and
+    therefore some vectors differ.  `matrix` is the conversion's.
+
+    levels = 1 or 2 switches to the pyramid search (lsfa_amd/csrc/me_pyramid.hip; DESIGN.md "Pyramid search"): `search` is then the range on the
+    top level and self.reach = search * 2^levels + refine * (2^levels - 1) pixels.  The pyramids of both ping-pong planes are kept and only
+    the new frame's is built: next_frame is levels + 2 launches in front of the accumulation (pyramid, top search, one refinement per
+    level) instead of one.  levels = 0 (the default) runs exactly the full search's launches; `refine` is ignored there.
+
+    The pyramid search is SegmentMotionEstimator's on one chain of one pair: the two ping-pong planes of every level lie one plane apart in
+    one buffer, a stack of two that starts at the reference plane - forwards if the current plane lies behind it, else stored in reverse."""
+
+    def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr', matrix='bt601',
+                 levels=ME_LEVELS, refine=ME_REFINE):
+        s = self._search = _MotionSearch("MotionEstimator", width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes=2, pairs=1)
+        self.width, self.height, self.device = s.width, s.height, s.device
+        self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
+        self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
+        self.bgr_key, self._bgr_pp, self._bgr_i = None, None, 0
+        H, W = self.height, self.width
+        self.acc = MotionVectorAccumulator(W, H, self.device)
+        self._luma = s.planes(0, 0, 2)
+        self._ref = 0                   # index of the previous frame's plane
+        self.rows, self.sad = s.rows[0].view(self.mbh * self.mbw, 7), s.sad.view(self.mbh, self.mbw)
+        self._mv = torch.empty((H, W, 2), dtype=torch.int32, device=self.device)
+        self._res = torch.empty((H, W, 3), dtype=torch.int32, device=self.device)
+        self._out = {}
+
+    def _frame(self, bgr, who):
+        return _tensor("MotionEstimator." + who, "the frame", bgr, torch.uint8, (self.height, self.width, 3), self.device)
+
+    def _key(self):
+        """the reference plane holds a key frame: its pyramid, and the accumulation starts over"""
+        self._search.pyramid(self._ref, 1)
+        self.acc.reset()
+
+    def _next(self, cur):
+        """plane `cur` holds the next frame: its rows against the reference plane's, accumulated; it becomes the reference"""
+        if self.levels == 0:
+            # the pair kernel, not run(1, 1, ...): through the chain kernel the per-frame graph of nine frames was 3.3 us (1000 x 600) to
+            # 12.4 us (1920 x 1080) slower, beyond the parent's run-to-run spread of 0.4 .. 2.4 us (profiles/r9/me_frontend_refactor.txt)
+            mv_estimate(self._luma[cur], self._luma[self._ref], self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+        else:
+            self._search.run(1, 1, self._ref, cur - self._ref, built=1)
+        self.acc.add_frame(self.rows, max_block_area=256)      # the explicit area: no device-to-host read
+        self._ref = cur
+
+    def key_frame(self, bgr):
+        luma_u8(self._frame(bgr, 'key_frame'), out=self._luma[self._ref])
+        self._key()
+
+    def next_frame(self, bgr):
+        """Estimates the frame's vectors against the previous frame and accumulates them; returns the (mbh * mbw, 7) rows (a buffer the
+        next call overwrites; self.sad holds the winners' SAD)."""
+        cur = 1 - self._ref
+        luma_u8(self._frame(bgr, 'next_frame'), out=self._luma[cur])
+        self._next(cur)
+        return self.rows
+
+    @property
+    def bgr_cur(self):
+        """the BGR frame the last next_frame_yuv converted (None before the first)"""
+        return None if self._bgr_pp is None else self._bgr_pp[self._bgr_i]
+
+    def _yuv_buffers(self):
+        if self.bgr_key is None:          # the first *_yuv call: the only allocation
+            self.bgr_key = torch.empty((self.height, self.width, 3), dtype=torch.uint8, device=self.device)
+            self._bgr_pp = [torch.empty_like(self.bgr_key) for _ in range(2)]
+
+    def _yuv_to(self, bgr, luma, y, uv, u, v, who):
+        if not isinstance(y, torch.Tensor) or tuple(y.shape) != (self.height, self.width) or y.device != self.device:
+            raise LsfaError("MotionEstimator.%s: a (%d, %d) uint8 Y plane on %s expected, got %s on %s" %
+                            (who, self.height, self.width, self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
+        if self.luma_from == 'y':
+            yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=bgr, y_packed=luma)
+        else:
+            yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=bgr)
+            luma_u8(bgr, out=luma)
+        return bgr
+
+    def key_frame_yuv(self, y, uv=None, u=None, v=None):
+        """key_frame on a decoder's planes: converts into self.bgr_key and returns it"""
+        self._yuv_buffers()
+        bgr = self._yuv_to(self.bgr_key, self._luma[self._ref], y, uv, u, v, 'key_frame_yuv')
+        self._key()
+        return bgr
+
+    def next_frame_yuv(self, y, uv=None, u=None, v=None):
+        """next_frame on a decoder's planes: converts into the other buffer of the ping-pong pair, which becomes self.bgr_cur, and returns it
+        (the rows are in self.rows, the winners' SAD in self.sad)"""
+        self._yuv_buffers()
+        cur, nxt = 1 - self._ref, 1 - self._bgr_i
+        bgr = self._yuv_to(self._bgr_pp[nxt], self._luma[cur], y, uv, u, v, 'next_frame_yuv')
+        self._next(cur)
+        self._bgr_i = nxt
+        return bgr
+
+    def network_inputs(self, bgr_cur, bgr_key, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16):
+        """`motion_vector` (1, 2, h, w) and `res_diff` (1, 3, h, w) of the current frame against the key frame: MotionVectorAccumulator's
+        network_inputs (lsfa_mv_field, lsfa_mv_residual, lsfa_transform_mv_res) into buffers of its own."""
+        bgr_cur, bgr_key = self._frame(bgr_cur, 'network_inputs'), self._frame(bgr_key, 'network_inputs')
+        _, _, ph, pw = _resized(self.height, self.width, im_scale, rcnn_stride)
+        oh, ow = ph // rcnn_stride, pw // rcnn_stride
+        if (oh, ow) not in self._out:
+            self._out[(oh, ow)] = (torch.empty((1, 2, oh, ow), device=self.device, dtype=torch.float32),
+                                   torch.empty((1, 3, oh, ow), device=self.device, dtype=torch.float32))
+        return transform_mv_res(self.acc.motion_vectors(out=self._mv), self.acc.residual(bgr_cur, bgr_key, out=self._res), im_scale, pixel_means,
+                                pixel_scale, rcnn_stride, negate_mv=True, out=self._out[(oh, ow)])
 
 
 class SegmentMotionEstimator(object):
@@ -1880,39 +1883,22 @@ class SegmentMotionEstimator(object):
     def __init__(self, width, height, frames=9, clips=1, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr',
                  matrix='bt601', levels=ME_LEVELS, refine=ME_REFINE):
         who = "SegmentMotionEstimator"
-        self.levels, self.refine = _pyramid_params(who, levels, refine)
-        if luma_from not in ('bgr', 'y'):
-            raise LsfaError("%s: luma_from %r is not 'bgr' or 'y'" % (who, luma_from))
-        if matrix not in YUV_MATRICES:
-            raise LsfaError("%s: matrix %r is not one of %s" % (who, matrix, sorted(YUV_MATRICES)))
-        self.luma_from, self.matrix = luma_from, matrix
-        self.width, self.height, self.device = int(width), int(height), torch.device(device)
         self.frames, self.clips = int(frames), int(clips)
-        self.search, self.lam, self.max_sad = int(search), int(lam), int(max_sad)
-        if not 1 <= self.search <= 32 or self.lam < 0 or self.max_sad < 0:
-            raise LsfaError("%s: search %d (1..32), lam %d (>= 0), max_sad %d (>= 0)" % (who, self.search, self.lam, self.max_sad))
-        if self.frames < 1 or self.clips < 1 or self.width < 1 or self.height < 1:
-            raise LsfaError("%s: frames %d, clips %d and the %d x %d frame must all be at least 1" % (who, self.frames, self.clips, self.width, self.height))
-        H, W, C, F = self.height, self.width, self.clips, self.frames
-        self.mbh, self.mbw = -(-H // 16), -(-W // 16)
-        # flat, so that a shorter segment is a stack of its own in front of the same memory.  The search wants every plane 4-byte aligned: a
-        # frame of W * H % 4 != 0 (no 4:2:0 video has one) gets its planes padded apart and its luma frame by frame
-        self._plane = -(-H * W // 4) * 4
-        if self._plane != H * W and luma_from == 'y':
-            raise LsfaError("%s: luma_from='y' needs W * H %% 4 == 0, got %d x %d" % (who, W, H))
-        self._luma = torch.empty(C * (F + 1) * self._plane, dtype=torch.uint8, device=self.device)
-        self._rows = torch.empty(C * F * self.mbh * self.mbw * 7, dtype=torch.int32, device=self.device)
-        self._sad = torch.empty(C * F * self.mbh * self.mbw, dtype=torch.int32, device=self.device)
+        if self.frames < 1 or self.clips < 1 or int(width) < 1 or int(height) < 1:
+            raise LsfaError("%s: frames %d, clips %d and the %d x %d frame must all be at least 1" % (who, self.frames, self.clips, int(width), int(height)))
+        s = self._search = _MotionSearch(who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine,
+                                         planes=self.clips * (self.frames + 1), pairs=self.clips * self.frames)
+        self.width, self.height, self.device = s.width, s.height, s.device
+        self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
+        self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
+        # the search wants every plane 4-byte aligned: a frame of W * H % 4 != 0 (no 4:2:0 video has one) gets its planes padded apart and
+        # its luma frame by frame
+        if s.plane[0] != self.height * self.width and luma_from == 'y':
+            raise LsfaError("%s: luma_from='y' needs W * H %% 4 == 0, got %d x %d" % (who, self.width, self.height))
+        self._luma = s.flat[0]
         self._bgr = None                # segment_yuv's converted frames, allocated at its first call
         self.rows, self.sad = None, None
         self._out = {}
-        self.reach = me_reach(self.levels, self.search, self.refine)
-        # the pyramid's planes and the rows of its levels 1 .. levels, flat like the luma planes
-        self._shapes = pyramid_shapes(H, W, self.levels)
-        self._pplane = [-(-h * w // 4) * 4 for h, w in self._shapes]
-        self._pblocks = [-(-h // 16) * -(-w // 16) for h, w in self._shapes]
-        self._pyr = [torch.empty(C * (F + 1) * ps, dtype=torch.uint8, device=self.device) for ps in self._pplane[1:]]
-        self._prows = [torch.empty(C * F * b * 7, dtype=torch.int32, device=self.device) for b in self._pblocks[1:]]
 
     def _length(self, have, n, who):
         n = have if n is None else int(n)
@@ -1922,21 +1908,17 @@ class SegmentMotionEstimator(object):
         return n
 
     def _run(self, bgr, n, im_scale, pixel_means, pixel_scale, rcnn_stride, out, luma_done):
-        H, W, C = self.height, self.width, self.clips
-        ps = self._plane
-        luma = self._luma.as_strided((C, n + 1, H, W), ((n + 1) * ps, ps, W, 1))
-        self.rows = self._rows[:C * n * self.mbh * self.mbw * 7].view(C, n, self.mbh * self.mbw, 7)
-        self.sad = self._sad[:C * n * self.mbh * self.mbw].view(C, n, self.mbh, self.mbw)
-        if not luma_done and ps == H * W:
-            luma_u8(bgr.view(C * (n + 1) * H, W, 3), out=luma.view(C * (n + 1) * H, W))     # pointwise: a stack is one tall frame
+        H, W, C, s = self.height, self.width, self.clips, self._search
+        N, blocks = C * (n + 1), self.mbh * self.mbw
+        self.rows = s.rows[0][:C * n * blocks * 7].view(C, n, blocks, 7)
+        self.sad = s.sad[:C * n * blocks].view(C, n, self.mbh, self.mbw)
+        luma = s.planes(0, 0, N)
+        if not luma_done and s.plane[0] == H * W:
+            luma_u8(bgr.view(N * H, W, 3), out=luma.view(N * H, W))     # pointwise: a stack is one tall frame
         elif not luma_done:
-            for c in range(C):
-                for f in range(n + 1):
-                    luma_u8(bgr[c, f], out=luma[c, f])
-        if self.levels == 0:
-            mv_estimate_chain(luma, self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
-        else:
-            self._pyramid_search(n)
+            for i, frame in enumerate(bgr.view(N, H, W, 3)):
+                luma_u8(frame, out=luma[i])
+        s.run(C, n)
         if out is None:
             h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
             key = (n, ph // rcnn_stride, pw // rcnn_stride)
@@ -1946,35 +1928,15 @@ class SegmentMotionEstimator(object):
             out = self._out[key]
         return mv_segment_inputs(self.rows, bgr, im_scale, pixel_means, pixel_scale, rcnn_stride, out=out)
 
-    def _pyramid_views(self, n):
-        """the buffers of a segment of n non-key frames, level by level (index 0 is the luma stack / self.rows): the planes as
-        (N, h_k, w_k) for the pyramid, as (C, n + 1, h_k, w_k) stacks for the searches, and the rows (C, n, blocks_k, 7)"""
-        C, L, N = self.clips, self.levels, self.clips * (n + 1)
-        flat = [self._luma] + self._pyr
-        planes = [_plane_stack(flat[k], (N,) + self._shapes[k], self._pplane[k]) for k in range(L + 1)]
-        stacks = [flat[k].as_strided((C, n + 1) + self._shapes[k], ((n + 1) * self._pplane[k], self._pplane[k], self._shapes[k][1], 1)) for k in range(L + 1)]
-        rows = [self.rows] + [self._prows[k - 1][:C * n * self._pblocks[k] * 7].view(C, n, self._pblocks[k], 7) for k in range(1, L + 1)]
-        return planes, stacks, rows
-
-    def _pyramid_search(self, n):
-        """levels + 2 launches on the luma stack: the pyramid of every plane, the full search on the top level, one refinement per level
-        below it; self.rows / self.sad receive level 0's"""
-        L = self.levels
-        planes, stacks, rows = self._pyramid_views(n)
-        luma_pyramid(planes[0], L, out=planes[1:])
-        mv_estimate_chain(stacks[L], self.search, self.lam, 0, out=rows[L])
-        for k in range(L - 1, -1, -1):
-            mv_refine_chain(stacks[k], rows[k + 1], self.refine, self.lam, self.max_sad if k == 0 else 0, out=rows[k], sad_out=self.sad if k == 0 else None)
-
     def segment(self, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, n=None, rcnn_stride=16, out=None):
         """bgr_stack (C, n + 1, H, W, 3) uint8, contiguous, frame 0 of every clip its key frame -> (mv (n, C, 2, h, w), res (n, C, 3, h, w)).
         `n` below the stack's length takes its first n + 1 frames."""
-        H, W, C = self.height, self.width, self.clips
-        t = bgr_stack
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 5 or int(t.shape[0]) != C or int(t.shape[1]) < 2 or \
-                tuple(t.shape[2:]) != (H, W, 3) or t.device != self.device or not t.is_contiguous():
-            raise LsfaError("SegmentMotionEstimator.segment: a contiguous (%d, n + 1, %d, %d, 3) uint8 stack on %s expected, got %s %s" %
-                            (C, H, W, self.device, tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t))))
+        C = self.clips
+        who = "SegmentMotionEstimator.segment"
+        t = _tensor(who, "bgr_stack (a uint8 stack, frame 0 of every clip its key frame)", bgr_stack, torch.uint8, (C, "n + 1", self.height, self.width, 3),
+                    self.device)
+        if int(t.shape[1]) < 2:
+            raise LsfaError("%s: the uint8 stack holds %d frame(s) per clip; a key frame and at least one frame behind it expected" % (who, int(t.shape[1])))
         have = int(t.shape[1]) - 1
         n = self._length(have, n, 'segment')
         if n < have:

@@ -9,6 +9,7 @@ import torch
 
 import oracle
 import ref_me
+from me_util import t
 from oracle import np_ref
 
 pytestmark = pytest.mark.gpu
@@ -17,10 +18,6 @@ DEV = "cuda:0"
 SIZES = [(1000, 600), (96, 64), (37, 23), (250, 130)]        # (width, height)
 SMALL = SIZES[1:]
 MEANS = (102.9801, 115.9465, 122.7717)
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def plane_pair(kind, width, height, seed):

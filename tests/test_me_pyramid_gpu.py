@@ -2,12 +2,16 @@
 TestLoader(estimate_mv=dict(levels=...)) on the GPU: the two kernels against tests/ref_me_pyramid.py bit for bit, the segment's inputs against
 the per-frame accumulation of the same rows, the known answer beyond the full search's reach, graph capture, the YUV path and the error
 paths.  tests/test_me_pyramid_cpu.py pins the reference itself."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import me_util
 import ref_me
 import ref_me_pyramid as rp
+from me_util import plane_stack, t
 
 pytestmark = pytest.mark.gpu
 
@@ -15,27 +19,7 @@ DEV = "cuda:0"
 MEANS = (102.9801, 115.9465, 122.7717)
 PIXEL_SCALE = 0.5
 
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def clip(n, width, height, seed, m=(7, -5), sigma=3.0):
-    return ref_me.translated_clip(n, width, height, m, seed=seed, sigma=sigma)
-
-
-def plane_stack(planes, chains, stride=None):
-    """chains: lists of indices into `planes` -> a (C, F + 1, H, W) uint8 view on the device whose planes lie `stride` bytes apart (default:
-    the plane's size rounded up to a multiple of 4), the bytes between them 0xA5"""
-    H, W = planes[0].shape
-    stride = stride or -(-H * W // 4) * 4
-    C, F1 = len(chains), len(chains[0])
-    buf = torch.full((C * F1 * stride,), 0xA5, dtype=torch.uint8, device=DEV)
-    view = buf.as_strided((C, F1, H, W), (F1 * stride, stride, W, 1))
-    for c, chain in enumerate(chains):
-        for f, i in enumerate(chain):
-            view[c, f].copy_(t(planes[i]))
-    return view
+clip = functools.partial(me_util.clip, m=(7, -5))          # this file's clips move further than the segment tests': (7, -5) unless a test says otherwise
 
 
 # ---- lsfa_luma_pyramid -----------------------------------------------------------------------------------------------------------------------------

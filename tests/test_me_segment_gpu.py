@@ -12,6 +12,7 @@ import torch
 import oracle
 import ref_me
 import ref_me_segment
+from me_util import clip, plane_stack, t
 from oracle import np_ref
 
 pytestmark = pytest.mark.gpu
@@ -22,28 +23,6 @@ PARAMS = [(4, 0, 0), (16, 4, 0), (32, 4, 20000)]              # (search, lambda,
 SCALES = [1.0, 1.25, 0.6, 0.5]                                # h1 / w1 are no multiples of 16: the padded region is read
 MEANS = (102.9801, 115.9465, 122.7717)
 PIXEL_SCALE = 0.5
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def clip(n, width, height, seed, m=(3, -2), sigma=3.0):
-    return ref_me.translated_clip(n, width, height, m, seed=seed, sigma=sigma)
-
-
-def plane_stack(planes, chains, stride=None):
-    """chains: a list of lists of indices into `planes` -> a (C, F + 1, H, W) uint8 view on the device whose planes lie `stride` bytes apart
-    (default: the plane's size rounded up to a multiple of 4, which the search requires)"""
-    H, W = planes[0].shape
-    stride = stride or -(-H * W // 4) * 4
-    C, F1 = len(chains), len(chains[0])
-    buf = torch.full((C * F1 * stride,), 0xA5, dtype=torch.uint8, device=DEV)
-    view = buf.as_strided((C, F1, H, W), (F1 * stride, stride, W, 1))
-    for c, chain in enumerate(chains):
-        for f, i in enumerate(chain):
-            view[c, f].copy_(t(planes[i]))
-    return view
 
 
 _PAIRS = {}
@@ -98,6 +77,40 @@ def test_chain_search_with_a_plane_stride_beyond_the_plane(hip):
         for f in range(1, 4):
             np.testing.assert_array_equal(rows[c, f - 1].cpu().numpy(), ref[c + f - 1][0])
             np.testing.assert_array_equal(sad[c, f - 1].cpu().numpy(), ref[c + f - 1][1])
+
+
+@pytest.mark.parametrize("size,C,F,gap", [((40, 24), 1, 1, 0), ((250, 130), 2, 2, 0), ((37, 23), 1, 2, 12)])
+def test_chain_search_on_a_stack_stored_in_reverse(hip, size, C, F, gap):
+    """lsfa_mv_estimate_chain with a negative plane stride: plane 0 of the stack is the LAST plane in memory, every other one a padded
+    plane size in front of the one before it, so that the chain offset c * (F + 1) is walked backwards too.  Rows and SAD of every pair ==
+    hip.mv_estimate of that pair == ref_me.estimate.  40 x 24: one whole block and blocks cut by the right and the bottom edge.  37 x 23:
+    W * H % 4 != 0 and the planes a further 12 bytes apart, so the stride exceeds the plane (0xA5 between the planes)."""
+    width, height = size
+    planes = [ref_me.luma(f) for f in clip(C + F, width, height, seed=width)]
+    chains = [list(range(c, c + F + 1)) for c in range(C)]
+    in_stack_order = [i for chain in chains for i in chain]
+    N, stride = C * (F + 1), -(-height * width // 4) * 4 + gap
+    memory = plane_stack(planes, [in_stack_order[::-1]], stride=stride)[0]  # memory plane m holds stack plane N - 1 - m
+    assert memory.stride(0) == stride
+    dev = [t(p) for p in planes]
+    mbh, mbw = -(-height // 16), -(-width // 16)
+    zeroed = 0
+    for max_sad in (0, 900):
+        rows = torch.full((C, F, mbh * mbw, 7), -7, dtype=torch.int32, device=DEV)
+        sad = torch.full((C, F, mbh, mbw), -7, dtype=torch.int32, device=DEV)
+        rc = hip.lib().lsfa_mv_estimate_chain(memory[N - 1].data_ptr(), -stride, C, F, width, height, 4, 4, max_sad, rows.data_ptr(), sad.data_ptr(), None)
+        assert rc == 0, hip.lib().lsfa_last_error()
+        torch.cuda.synchronize()
+        for c in range(C):
+            for f in range(1, F + 1):
+                cur, ref = chains[c][f], chains[c][f - 1]
+                pair_rows, pair_sad = hip.mv_estimate(dev[cur], dev[ref], 4, 4, max_sad, return_sad=True)
+                assert torch.equal(rows[c, f - 1], pair_rows) and torch.equal(sad[c, f - 1], pair_sad), (max_sad, c, f)
+                want_rows, want_sad = ref_me.estimate(planes[cur], planes[ref], 4, 4, max_sad)
+                np.testing.assert_array_equal(rows[c, f - 1].cpu().numpy(), want_rows, err_msg="rows max_sad %d pair (%d, %d)" % (max_sad, c, f))
+                np.testing.assert_array_equal(sad[c, f - 1].cpu().numpy(), want_sad, err_msg="SAD max_sad %d pair (%d, %d)" % (max_sad, c, f))
+                zeroed += int((want_sad > max_sad).sum()) if max_sad else 0
+    assert zeroed > 0           # the threshold bites somewhere
 
 
 def test_chain_search_full_size_equals_the_pair_kernel(hip):

@@ -180,7 +180,10 @@ def pyramid_leg(reps, time_limit, levels, refine):
         p.update(reach=sme.reach, launches=sme.levels + 4, spread_us=round(spread, 2))
         if sme.reach >= 32:
             p['not_slower_than_full_R32_beyond_spread'] = bool(p['median'] <= full['median'] + spread)
-        planes, stacks, rows = sme._pyramid_views(F)
+        s = sme._search          # the buffers of the segment, level by level: the planes, the same as (1, F + 1, h_k, w_k) stacks, the rows
+        planes = [s.planes(k, 0, F + 1) for k in range(levels + 1)]
+        stacks = [p.unsqueeze(0) for p in planes]
+        rows = [s.rows[k][:F * s.blocks[k] * 7].view(1, F, s.blocks[k], 7) for k in range(levels + 1)]
         alone = [('luma_pyramid', lambda planes=planes: hip.luma_pyramid(planes[0], levels, out=planes[1:])),
                  ('top_search_level%d' % levels, lambda sme=sme, stacks=stacks, rows=rows: hip.mv_estimate_chain(stacks[levels], sme.search, 4, 0, out=rows[levels]))]
         for k in range(levels - 1, -1, -1):

@@ -1,7 +1,9 @@
-// Host-side sanitiser check of the argument checking of lsfa_luma_pyramid and lsfa_mv_refine_chain: every refusal happens before any launch,
-// so this runs without a GPU.  Build and run (address + undefined-behaviour sanitisers on the host code only):
+// Host-side sanitiser check of the argument checking of lsfa_luma_pyramid, lsfa_mv_refine_chain, lsfa_mv_estimate and lsfa_mv_estimate_chain
+// (the rules the searches share, me_common.h, through every export that uses them): every refusal happens before any launch, so this runs
+// without a GPU.  Build and run (address + undefined-behaviour sanitisers on the host code only):
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I include -I lsfa_amd/csrc \
-//         tools/san_me_pyramid_args.cpp lsfa_amd/csrc/me_pyramid.hip lsfa_amd/csrc/runtime.hip -o san_me_pyramid_args && ./san_me_pyramid_args
+//         tools/san_me_pyramid_args.cpp lsfa_amd/csrc/me_pyramid.hip lsfa_amd/csrc/me.hip lsfa_amd/csrc/runtime.hip -o san_me_pyramid_args && \
+//         ./san_me_pyramid_args
 // Pointers are never dereferenced by a refused call; they only need the right alignment.
 #include <stdint.h>
 #include <stdio.h>
@@ -63,6 +65,39 @@ int main(void) {
   refused(lsfa_mv_refine_chain(p, S, 1 << 14, 1 << 14, W, H, rows, 2, 4, 0, rows, nullptr, nullptr), "exceed one grid", "refine 2^28 pairs");
   refused(lsfa_mv_refine_chain(p, S, 46341, 46341, W, H, rows, 2, 4, 0, rows, nullptr, nullptr), "exceed one grid", "refine pairs beyond int");
   refused(lsfa_mv_refine_chain(p, 1LL << 32, 1 << 10, 1 << 10, 30000, 30000, rows, 2, 4, 0, rows, nullptr, nullptr), "exceed one grid", "refine 2^20 pairs of 3.5 M blocks");
+  // lsfa_mv_estimate
+  refused(lsfa_mv_estimate(nullptr, p, W, H, 16, 4, 0, rows, nullptr, nullptr), "NULL", "estimate cur NULL");
+  refused(lsfa_mv_estimate(p, nullptr, W, H, 16, 4, 0, rows, nullptr, nullptr), "NULL", "estimate ref NULL");
+  refused(lsfa_mv_estimate(p, p, W, H, 16, 4, 0, nullptr, nullptr, nullptr), "NULL", "estimate mvs NULL");
+  refused(lsfa_mv_estimate(p, p, 0, H, 16, 4, 0, rows, nullptr, nullptr), "bad frame size", "estimate width 0");
+  refused(lsfa_mv_estimate(p, p, W, -1, 16, 4, 0, rows, nullptr, nullptr), "bad frame size", "estimate height -1");
+  refused(lsfa_mv_estimate(p, p, 1 << 16, 1 << 16, 16, 4, 0, rows, nullptr, nullptr), "bad frame size", "estimate 2^32 pixels");
+  refused(lsfa_mv_estimate(p, p, W, H, 0, 4, 0, rows, nullptr, nullptr), "search 0", "estimate search 0");
+  refused(lsfa_mv_estimate(p, p, W, H, 33, 4, 0, rows, nullptr, nullptr), "search 33", "estimate search 33");
+  refused(lsfa_mv_estimate(p, p, W, H, 16, -1, 0, rows, nullptr, nullptr), "lambda -1", "estimate lambda -1");
+  refused(lsfa_mv_estimate(p, p, W, H, 16, (1 << 24) + 1, 0, rows, nullptr, nullptr), "lambda", "estimate lambda 2^24 + 1");
+  refused(lsfa_mv_estimate(p, p, W, H, 16, 4, -1, rows, nullptr, nullptr), "max_sad -1", "estimate max_sad -1");
+  refused(lsfa_mv_estimate(p + 1, p, W, H, 16, 4, 0, rows, nullptr, nullptr), "4-byte aligned", "estimate cur misaligned");
+  refused(lsfa_mv_estimate(p, p + 2, W, H, 16, 4, 0, rows, nullptr, nullptr), "4-byte aligned", "estimate ref misaligned");
+  // lsfa_mv_estimate_chain
+  refused(lsfa_mv_estimate_chain(nullptr, S, 1, 2, W, H, 16, 4, 0, rows, nullptr, nullptr), "NULL", "chain luma NULL");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 2, W, H, 16, 4, 0, nullptr, nullptr, nullptr), "NULL", "chain mvs NULL");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 2, 0, H, 16, 4, 0, rows, nullptr, nullptr), "bad frame size", "chain width 0");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 2, W, -1, 16, 4, 0, rows, nullptr, nullptr), "bad frame size", "chain height -1");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 2, W, H, 0, 4, 0, rows, nullptr, nullptr), "search 0", "chain search 0");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 2, W, H, 33, 4, 0, rows, nullptr, nullptr), "search 33", "chain search 33");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 2, W, H, 16, -1, 0, rows, nullptr, nullptr), "lambda -1", "chain lambda -1");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 2, W, H, 16, (1 << 24) + 1, 0, rows, nullptr, nullptr), "lambda", "chain lambda 2^24 + 1");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 2, W, H, 16, 4, -1, rows, nullptr, nullptr), "max_sad -1", "chain max_sad -1");
+  refused(lsfa_mv_estimate_chain(p, S, 0, 2, W, H, 16, 4, 0, rows, nullptr, nullptr), "at least 1", "chain 0 chains");
+  refused(lsfa_mv_estimate_chain(p, S, 1, 0, W, H, 16, 4, 0, rows, nullptr, nullptr), "at least 1", "chain 0 frames");
+  refused(lsfa_mv_estimate_chain(p, S - 4, 1, 2, W, H, 16, 4, 0, rows, nullptr, nullptr), "plane stride", "chain short stride");
+  refused(lsfa_mv_estimate_chain(p, S + 2, 1, 2, W, H, 16, 4, 0, rows, nullptr, nullptr), "multiple of 4", "chain stride + 2");
+  refused(lsfa_mv_estimate_chain(p, -S + 4, 1, 1, W, H, 16, 4, 0, rows, nullptr, nullptr), "plane stride", "chain short negative stride");
+  refused(lsfa_mv_estimate_chain(p, INT64_MIN, 1, 1, W, H, 16, 4, 0, rows, nullptr, nullptr), "plane stride", "chain stride INT64_MIN");
+  refused(lsfa_mv_estimate_chain(p + 1, S, 1, 2, W, H, 16, 4, 0, rows, nullptr, nullptr), "4-byte aligned", "chain luma misaligned");
+  refused(lsfa_mv_estimate_chain(p, S, 1 << 16, 1 << 12, W, H, 16, 4, 0, rows, nullptr, nullptr), "exceed one grid", "chain 2^28 pairs");
+  refused(lsfa_mv_estimate_chain(p, S, 46341, 46341, W, H, 16, 4, 0, rows, nullptr, nullptr), "exceed one grid", "chain pairs beyond int");
   printf("%d of %d refusals as declared\n", checks - failures, checks);
   return failures ? 1 : 0;
 }
