@@ -387,6 +387,23 @@ int lsfa_conv_weights(const float* w, int Cout, int kh, int kw, int Cin, int pie
 int lsfa_conv_weights_pc(const float* w, int Cout, int kh, int kw, int Cin, const int* w_exp_pc, void* wfrag, void* stream);
 size_t lsfa_conv_workspace_bytes(const lsfa_conv_desc* d);
 int lsfa_conv_fwd(const lsfa_conv_desc* d, void* ws, size_t ws_bytes, void* stream);
+/* r8: a pre-activation unit's conv3 + shortcut add and the NEXT unit's conv1 in one launch (dff_rfcn/symbols/resnet.py:70-101: conv3 :93-95,
+ * `sum = conv3 + shortcut` :101, then the next unit's bn1 :78, relu1 :79, conv1 :80 with bn2 folded in and relu2 :82), for the stages whose sum
+ * is too large to stay in cache between two launches: it is written once and not read back.
+ *   x (N,H,W,Cm) channels-last = c2, amax_in its 256 maxima;  y (N,H,W,C) = conv3(x) + residual (residual may BE y), C = 4 Cm;
+ *   z (N,H,W,Cn) = max(conv1(max(y * scale2[c] + shift2[c], 0)) + bias, 0)   (scale2 / shift2: C floats, bias: Cn floats or NULL).
+ * w3frag / w1frag: lsfa_conv_weights_pc fragments of the (C,1,1,Cm) and (Cn,1,1,C) weights, w3_scale / w1_scale their 2^-w_exp[co].
+ * conv3's arithmetic is lsfa_conv_fwd's (same products, same order: y is bit-identical to the two-launch form).  conv1's operand is cut
+ * with one power-of-two scale per 32-pixel x 128-channel block of the activated sum (the block's own maximum into [2^13, 2^14)) instead of
+ * one per map, and accumulated per block.  amax_out_sum: 256 slots that receive the maximum of the activated sum (what a strided shortcut
+ * that reads y through in_scale / in_shift needs as its amax_in); amax_out_z: those of z.  Either may be NULL.
+ * LSFA_ENOTSUP for: pieces3 / pieces1 other than 2 (two fp16 pieces), C != 4 Cm, Cm or Cn outside {64, 128}, views (ldx != Cm, ldy != C,
+ * ldz != Cn), y_nchw != 0, stride != 1.  No workspace, no allocation, no synchronisation. */
+int lsfa_conv_pair_fwd(const float* x, int ldx, int N, int H, int W, int Cm, const float* amax_in, const void* w3frag,
+                       const float* w3_scale, int pieces3, int C, const float* residual, float* y, int ldy, const float* scale2,
+                       const float* shift2, const void* w1frag, const float* w1_scale, int pieces1, int Cn, const float* bias,
+                       float* z, int ldz, int stride, int y_nchw, unsigned* amax_out_sum, unsigned* amax_out_z, unsigned* status,
+                       void* stream);
 /* 256 partial maxima of |x| (n floats, n % 4 == 0, 16-byte aligned): an `amax_in` for maps no convolution of this library produced */
 int lsfa_amax_partial(const float* x, long long n, float* out256, void* stream);
 /* Reads and clears the status word the convolutions raise (synchronises `stream`): LSFA_OK, or LSFA_EOVERFLOW with lsfa_last_error()

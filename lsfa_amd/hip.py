@@ -1295,6 +1295,58 @@ def conv_split(x, sw, bias=None, stride=1, pad=0, dil=1, relu=False, out=None, r
     return out if out2 is None else (out, out2)
 
 
+def _pair_kernel_name(cm, cn):
+    return "conv_pair_kernel<%d, %d>" % (cm // 32, cn // 32)
+
+
+@_on_tensor_device
+def conv_pair(x, sw3, residual, scale2, shift2, sw1, bias=None, out=None, out_z=None, amax_in=None, amax_out_sum=None, amax_out_z=None,
+              status=None, stride=1, nchw=False):
+    """lsfa_conv_pair_fwd: a ResNet unit's conv3 + shortcut add and the next unit's conv1 (+ bias + ReLU) in one launch.
+    x (N, H, W, Cm) contiguous fp32 (c2); sw3 (C = 4 Cm outputs) and sw1 (C -> Cn) two-piece SplitWeights with per-channel scales;
+    residual (N, H, W, C), may BE `out`.  -> (y, z): y = conv3(x) + residual (bit-identical to conv_split's), z = max(conv1(max(y * scale2 +
+    shift2, 0)) + bias, 0); the activated map is never stored.  amax_out_sum receives its maximum, amax_out_z that of z.  Channel counts
+    outside Cm, Cn in {64, 128}, other piece counts, non-contiguous operands, NCHW or a stride raise LsfaError (LSFA_ENOTSUP)."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise LsfaError("conv_pair: x must be a (N, H, W, Cm) float32 tensor")
+    N, H, W, Cm = x.shape
+    C, Cn = sw3.cout, sw1.cout
+    if (sw3.kh, sw3.kw, sw1.kh, sw1.kw) != (1, 1, 1, 1) or sw3.cin != Cm or sw1.cin != C:
+        raise LsfaError("conv_pair: two 1x1 convolutions Cm=%d -> C -> Cn, not %dx%d %d -> %d and %dx%d %d -> %d"
+                        % (Cm, sw3.kh, sw3.kw, sw3.cin, C, sw1.kh, sw1.kw, sw1.cin, Cn))
+    if getattr(sw3, 'w_scale', None) is None or getattr(sw1, 'w_scale', None) is None:
+        if sw3.pieces == 2 and sw1.pieces == 2:
+            raise LsfaError("conv_pair: the weights must carry per-channel scales (SplitWeight(per_channel_scale=True))")
+    if amax_in is None:
+        amax_in = amax_partial(_f32c(x, "x"))
+    if out is None:
+        out = torch.empty((N, H, W, C), device=x.device, dtype=torch.float32)
+    if out_z is None:
+        out_z = torch.empty((N, H, W, Cn), device=x.device, dtype=torch.float32)
+    for name, t, c in (("out", out, C), ("residual", residual, C), ("out_z", out_z, Cn)):
+        if t is None or t.numel() != N * H * W * c or t.dtype != torch.float32:
+            raise LsfaError("conv_pair: %s must be a float32 tensor of %d elements" % (name, N * H * W * c))
+    # a view is described to the library by its pixel pitch (which then refuses it): dense operands have pitch = channel count
+    ldx = x.stride(2) if x.stride(3) == 1 else 0
+    ldy = out.stride(-2) if out.stride(-1) == 1 and out.dim() == 4 else C
+    ldz = out_z.stride(-2) if out_z.stride(-1) == 1 and out_z.dim() == 4 else Cn
+    if not (residual.is_contiguous() and scale2.is_contiguous() and shift2.is_contiguous()):
+        raise LsfaError("conv_pair: residual, scale2 and shift2 must be contiguous")
+    if _conv_flops["count"] and sw3.pieces == 2 and sw1.pieces == 2:
+        P = N * H * W
+        f = 2.0 * P * (Cm * C + C * Cn)
+        _conv_flops["flops"] += f
+        _conv_flops["launches"] += 1
+        _conv_flops["flops_three_products"] += f
+        # each operand once: c2, the residual, the sum, z and both weight blocks (two fp16 pieces per weight)
+        _count_conv_launch(_pair_kernel_name(Cm, Cn), f, 4.0 * P * (Cm + 2 * C + Cn) + 4.0 * (Cm * C + C * Cn))
+    _check(lib().lsfa_conv_pair_fwd(x.data_ptr(), ldx, N, H, W, Cm, _ptr(amax_in), _ptr(sw3.frag), _ptr(getattr(sw3, 'w_scale', None)), sw3.pieces, C,
+                                    _ptr(residual), out.data_ptr(), ldy, _ptr(scale2), _ptr(shift2), _ptr(sw1.frag),
+                                    _ptr(getattr(sw1, 'w_scale', None)), sw1.pieces, Cn, _ptr(bias), out_z.data_ptr(), ldz, int(stride), int(nchw),
+                                    _ptr(amax_out_sum), _ptr(amax_out_z), _ptr(status), _stream()), "lsfa_conv_pair_fwd")
+    return out, out_z
+
+
 @_on_tensor_device
 def conv_split_view(x, sw, bias, out, stride=1, pad=(0, 0), dil=1, act=0, cin=None, c0=0, grid=None, place=None, amax_in=None,
                     amax_out=None, status=None, cin0=0):

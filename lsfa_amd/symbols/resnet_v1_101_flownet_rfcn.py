@@ -293,6 +293,8 @@ class Executor(object):
         self.pieces = (_FP32_PIECES if pieces is None else int(pieces)) if dtype == torch.float32 else 1
         self.flow_pieces = self.pieces       # FlowNet too: a Concat map's scale is the maximum over its producers (they share its amax slots)
         self.taps = None              # set to {} to record stage outputs (parity tests)
+        self.stage_taps = None        # set to {} to record every ResNet stage's sum (tests/test_resnet_pair_gpu.py); apart from `taps`, whose
+                                      # entries the frame graphs keep and compare frame by frame
         self.status = hip.new_status(self.device)
         # conv1 applies its unit's bn1 + relu1 where it cuts its operand (see _resnet); 0: every conv3 stores the activated map (r3's form, for A/B runs)
         self.input_activation_at_cut = _os.environ.get('LSFA_INPUT_ACT_AT_CUT', '1') == '1'
@@ -300,6 +302,13 @@ class Executor(object):
         # second output costs little and conv1's extra arithmetic shows (tools/lab: 3088 vs 3160 us for one image, 10706 vs 11080 for six).
         # The choice never changes a bit of the result (tests/test_hip_ops.py::test_conv_input_activation_at_the_cut).
         self.input_activation_min_bytes = int(float(_os.environ.get('LSFA_INPUT_ACT_MIN_MB', '48')) * (1 << 20))
+        # a unit's conv3 and the NEXT unit's conv1 as one launch (hip.conv_pair: the sum is written once and not read back), where both are
+        # two-piece 1x1s on 64 | 128 channels: 0 = never (two launches, for A/B runs), 1 = the boundaries behind stage-1 units, 2 = stages 1 and 2.
+        # Stage 1 is the default: the twelve-image backbone pass goes 18.64 -> 18.27 ms and the small net's nine-frame pass 1.71 -> 1.52 with it;
+        # stage 2's instantiation (Cm = Cn = 128: one workgroup per CU) gives the backbone pass back what stage 1 won (profiles/r8/conv_pair_passes.txt)
+        self.pair_1x1 = int(_os.environ.get('LSFA_PAIR_1X1', '1'))
+        if self.pair_1x1 not in (0, 1, 2):
+            raise ValueError("LSFA_PAIR_1X1 must be 0, 1 or 2")
         cfg = self.cfg
         arg = {k: np.asarray(v, dtype=np.float32) for k, v in arg_params.items()}
         aux = {k: np.asarray(v, dtype=np.float32) for k, v in aux_params.items()}
@@ -448,6 +457,12 @@ class Executor(object):
             amax_in = hip.amax_partial(x)
         return hip.conv_split(x, sw, bias, stride, pad, dil, act=act, amax_in=amax_in, amax_out=amax_out, status=self.status, **kw)
 
+    @staticmethod
+    def _pairable(w3, w1):
+        """what lsfa_conv_pair_fwd takes: two fp16 pieces with per-channel scales, 1x1, Cm -> 4 Cm -> Cn with Cm, Cn in {64, 128}"""
+        return w3.pieces == 2 and w1.pieces == 2 and getattr(w3, 'w_scale', None) is not None and getattr(w1, 'w_scale', None) is not None and \
+            (w3.kh, w3.kw, w1.kh, w1.kw) == (1, 1, 1, 1) and w3.cin in (64, 128) and w3.cout == 4 * w3.cin and w1.cin == w3.cout and w1.cout in (64, 128)
+
     def _resnet(self, x, net, stages, section):
         """Pre-activation ResNet (resnet.py:138-240) on channels-last activations, every contraction on lsfa_conv_fwd.
         x (N, 3, H, W) NCHW -> (map (N, h, w, C) channels-last, its amax slots): relu(bn1(.)) of the last unit's output when the
@@ -468,6 +483,7 @@ class Executor(object):
         x4, a = hip.maxpool3x3s2_nhwc(y, scale2=units[0]['bn1'][0], shift2=units[0]['bn1'][1], amax_out=am_a)
         dilate = 1
         pre = None                 # (scale, shift) of this unit's bn1 when its input `a` is still the raw sum (applied where conv1 cuts it)
+        carry = None               # (c1, its amax slots) of this unit when the previous unit's launch computed it (hip.conv_pair)
         for ui, u in enumerate(units):
             first = u['unit'] == 1
             # stage 4 keeps stride 1 and doubles the dilation from its 2nd unit on (resnet.py:33-34, :72-76, :223-230)
@@ -475,8 +491,10 @@ class Executor(object):
             ud = dilate
             if first and u['stage'] == 4:
                 dilate = dilate * 2
-            am_c1, am_c2, am_n = S.new(), S.new(), S.new()
-            if pre is None:
+            am_c1, am_c2, am_n = (carry[1] if carry is not None else S.new()), S.new(), S.new()
+            if carry is not None:  # conv1 + folded bn2 + relu2 came out of the previous unit's conv3 launch
+                c1, carry = carry[0], None
+            elif pre is None:
                 c1 = self._conv(a, u['w1'], u['b1'], act=1, amax_in=am_a, amax_out=am_c1)     # conv1 + folded bn2 + relu2
             else:                  # ... on max(sum * bn1 scale + bn1 shift, 0), which only this convolution reads: never stored
                 c1 = self._conv(a, u['w1'], u['b1'], act=1, amax_in=am_a, amax_out=am_c1, in_scale=pre[0], in_shift=pre[1])
@@ -504,7 +522,15 @@ class Executor(object):
             lone = self.input_activation_at_cut and ui + 1 < len(units) and u['w1'].pieces != 3 and \
                 sc.numel() * 4 >= self.input_activation_min_bytes
             pre = None
-            if nxt is not None and lone:
+            nu = units[ui + 1] if ui + 1 < len(units) else None
+            if nu is not None and u['stage'] <= self.pair_1x1 and self._pairable(u['w3'], nu['w1']):
+                # conv3 + shortcut add in place, then the next unit's bn1 + relu1 + conv1 on the tile the workgroup still holds, whatever `lone`
+                # says: the activated map is never stored, and a strided shortcut reads the sum through bn1 + relu1 itself (am_n is its scale)
+                am_z = S.new()
+                x4, z = hip.conv_pair(c2, u['w3'], sc, nxt[0], nxt[1], nu['w1'], nu['b1'], out=sc, amax_in=am_c2, amax_out_sum=am_n,
+                                      amax_out_z=am_z, status=self.status)
+                a, pre, carry = x4, nxt, (z, am_z)
+            elif nxt is not None and lone:
                 if u['w3'].pieces == 2:      # max(relu1) is the next conv1's fp16 scale; the one-piece (bf16) mode has no scale
                     x4 = self._conv(c2, u['w3'], None, amax_in=am_c2, amax_out=am_n, out=sc, residual=sc, scale2=nxt[0], shift2=nxt[1])
                 else:
@@ -516,6 +542,8 @@ class Executor(object):
             else:
                 x4, a = self._conv(c2, u['w3'], None, amax_in=am_c2, amax_out=am_n, out=sc, residual=sc), None
             am_a = am_n
+            if self.stage_taps is not None and (nu is None or nu['stage'] != u['stage']):      # the stage's sum (later units write other maps)
+                self.stage_taps['%s_stage%d' % (section, u['stage'])] = x4
         return (a if a is not None else x4), am_a
 
     def _backbone(self, data):
