@@ -7,7 +7,7 @@
 //      pieces (16 KM registers) stay live for the whole tile.
 //   2. per 128-channel block j of the sum (KM blocks): acc3[4] = pieces x W3[j] (conv3's products in conv3's order: bit-identical to
 //      conv_ring_kernel<4, 2, 2, false, false, 4>), the row epilogue (out-scale, through LDS to float4 rows, + residual, store), then
-//      a = max(sum * scale2 + shift2, 0) (two roundings, affine_relu4's), which goes back into the wave's staging area in the A-stage layout.
+//      a = max(sum * scale2 + shift2, 0) (two roundings, as affine_relu4), which goes back into the wave's staging area in the A-stage layout.
 //   3. the wave's own 32 x 128 block of `a` gets its own power-of-two scale s_j (its maximum into [2^13, 2^14); the map-wide maximum
 //      cannot be known inside the launch, and a block's maximum is no larger: no value loses bits it keeps under the map scale, and
 //      nothing overflows), is cut with it and multiplied by W1[4j .. 4j+3] into acc1[KN]; then sum1 += acc1 * (2^-s_j * w_scale[co]):
@@ -75,13 +75,10 @@ __device__ __forceinline__ void pair_mma(const uint4* B, const Cut& p, f32x16 (&
   }
 }
 
-// a chunk of the wave's A image (256 uint4: 32 pixels x 8 swizzled slots) -> the lane's pieces, as ring_cut
+// a chunk of the wave's A image (256 uint4: 32 pixels x 8 swizzled slots) -> the lane's pieces
 __device__ __forceinline__ Cut pair_cut(const uint4* A, const int (&frag)[4], float s) {
   const uint4 r0 = A[frag[0]], r1 = A[frag[1]], r2 = A[frag[2]], r3 = A[frag[3]];
-  Cut n;
-  n.s0 = cut8<2>(as_f4(r0), as_f4(r1), s);
-  n.s1 = cut8<2>(as_f4(r2), as_f4(r3), s);
-  return n;
+  return cut_rows<2, false>(r0, r1, r2, r3, s, nullptr, 0, 0);
 }
 
 // every copy this wave has issued has landed and its LDS accesses are done, then the workgroup meets.  The wait is the BUILTIN (gfx9's
@@ -112,16 +109,16 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
   uint4* Sw = &S[wave][0];
   float* Tf = reinterpret_cast<float*>(Sw);
 
-  // the map scale of c2 (scale_finish's arithmetic)
+  // the map scale of c2: the rule of scale_finish / amax_exponent_asm, written out (see there)
   const uint32_t* am = reinterpret_cast<const uint32_t*>(a.amax);
   uint32_t mi = max(max(am[lane] & 0x7FFFFFFFu, am[lane + 64] & 0x7FFFFFFFu), max(am[lane + 128] & 0x7FFFFFFFu, am[lane + 192] & 0x7FFFFFFFu));
-  // c2: DMA i of chunk c moves pixels 8i .. 8i+7 of the wave's rows, lane -> pixel 8i + (lane >> 3), slot lane & 7 (ring_issue_a's swizzle)
+  // c2: DMA i of chunk c moves pixels 8i .. 8i+7 of the wave's rows, lane -> pixel 8i + (lane >> 3), slot lane & 7
 #pragma unroll
   for (int c = 0; c < KM; ++c)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int pix = m0 + 8 * i + (lane >> 3);
-      const int piece = (lane & 7) ^ ((4 * i + (lane >> 4)) & 7);
+      const int piece = LSFA_DMA_SRC_PIECE(i, lane);
       const float* src = pix < P ? a.x + (pix * Cm + c * kChunk + 4 * piece) : g_zero_block;
       __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(src), Sw + c * 256 + i * 64, 16, 0, 0);
     }
@@ -134,11 +131,7 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
   const float a_scale = ldexpf(1.f, s_in), inv_in = ldexpf(1.f, -s_in);
 
   int frag[4];
-  {
-    const int r = lane & 31, h = lane >> 5, sw = (r >> 1) & 7;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) frag[k] = r * 8 + ((4 * h + k) ^ sw);
-  }
+  LSFA_FRAG_SLOTS(lane, frag)
   // the row path's lane -> (row 8k + lane / 8, channels 4 (lane % 8) ..); in the staging area a row's eight float4 sit in swizzled slots
   const int c4 = (lane & 7) * 4;
   int base[4], rowf[4];
@@ -150,7 +143,7 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
     base[k] = ok[k] ? p : 0;                                     // row 0 for a pixel past the end: a valid address, not used
     rowf[k] = row * 32 + (((lane & 7) ^ ((row >> 1) & 7)) << 2);
   }
-  // where accumulator register r of a column tile goes: pixel row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), channel lane & 31, the channel's piece
+  // where accumulator register r of a column tile goes: pixel row acc_row(r, lane) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), channel lane & 31, the channel's piece
   // in the row's swizzled slot.  The row's swizzle (row >> 1) & 7 is ((r & 3) >> 1) | (lane >> 5) << 1 | ((r >> 2) & 1) << 2: the lane's part sits
   // in accl, the register's part is one XOR with a constant (PAIR_ACCF)
   const int accl = 128 * (lane >> 5) + (((((lane & 31) >> 2) ^ ((lane >> 5) << 1)) << 2) | (lane & 3));
@@ -190,7 +183,7 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
         }
         pair_mma<kGroupTiles>(((i & 1) ? R1 : R0) + lane, pc[kGroups == 1 ? q >> 1 : q], acc3, kGroups == 1 ? q & 1 : 0);
       }
-      // conv3's epilogue, as the ring kernel's row path: (0 + acc) * out-scale through LDS, + residual, store; then the next unit's bn1 + relu1
+      // conv3's epilogue, tile_rows_out's arithmetic on the staging area's swizzled rows: (0 + acc) * out-scale through LDS, + residual, store; then the next unit's bn1 + relu1
 #pragma unroll
       for (int tq = 0; tq < kGroupTiles; ++tq)
 #pragma unroll
@@ -260,11 +253,7 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
       }
     }
   }
-  {
-    uint32_t m = __float_as_uint(mx_sum);
-    if ((__float_as_uint(nf_sum) & 0x7F800000u) == 0x7F800000u) m = 0x7FC00000u;       // a non-finite value went through this lane
-    publish_amax(m, a.amax_sum, a.status, blockIdx.x * 4 + wave);
-  }
+  publish_amax(amax_word(mx_sum, nf_sum), a.amax_sum, a.status, blockIdx.x * 4 + wave);
   // z = max(sum1 + bias, 0) through the row path (the staging area is the wave's own: no barrier)
 #pragma unroll
   for (int t = 0; t < KN; ++t)
@@ -286,9 +275,7 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
       *reinterpret_cast<float4*>(a.z + (unsigned)(base[k] * Cn + t * 32 + c4)) = o;
       mx = fmaxf(fmaxf(mx, fmaxf(o.x, o.y)), fmaxf(o.z, o.w));
     }
-  uint32_t m = __float_as_uint(mx);
-  if ((__float_as_uint(nf) & 0x7F800000u) == 0x7F800000u) m = 0x7FC00000u;
-  publish_amax(m, a.amax_z, a.status, blockIdx.x * 4 + wave);
+  publish_amax(amax_word(mx, nf), a.amax_z, a.status, blockIdx.x * 4 + wave);
 }
 
 #undef PAIR_ACCF

@@ -101,6 +101,35 @@ __device__ __forceinline__ void ring_issue_b(uint4 (*R)[(Ring<NT, PC, ST, WV>::k
   for (int i = I0; i < I1; ++i) __builtin_amdgcn_global_load_lds(wsrc + i * 64, b_dst + i * 64, 16, 0, LSFA_RING_B_AUX);
 }
 
+// One chunk's copies into stage S, and the walk one further.  Two ring forms (PIPE):
+//   pipelined  stage v % ST holds B(v) beside A(v + 1): the walk stands at A(v + 1), the weights are the block BEFORE it (bprev); the last
+//              v-chunk's A half is not `live` (filled from the block of zeros)
+//   r4         stage c % ST holds A(c) and B(c): the walk's own block (bidx), always live
+template <int NT, int PC, int ST, int WV, int S, bool PIPE>
+__device__ __forceinline__ void ring_issue_chunk(uint4 (*R)[(Ring<NT, PC, ST, WV>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
+                                                 const Geom& g, Walk& wk, bool live) {
+  ring_issue_a<NT, PC, ST, WV, S>(R, x, g, wk, PIPE ? live : true);
+  ring_issue_b<NT, PC, ST, WV, S, 0, Ring<NT, PC, ST, WV>::kDmaB>(R, wblock, g, PIPE ? wk.bprev : wk.bidx);
+  wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
+}
+
+// the prologue's chunks: S = 0 .. ST - 2 (pipelined: v-chunk S, behind v-chunk -1 = A(0) alone in stage ST - 1).  GUARD: only the chunks
+// there are; the uniform step issues every one (past the end: into a stage nobody reads), so that every wait is the same count
+template <int NT, int PC, int ST, int WV, int S, bool PIPE, bool GUARD>
+__device__ __forceinline__ void ring_prologue(uint4 (*R)[(Ring<NT, PC, ST, WV>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
+                                              const Geom& g, Walk& wk, int n) {
+  if (!GUARD || S < n) ring_issue_chunk<NT, PC, ST, WV, S, PIPE>(R, x, wblock, g, wk, S + 1 < n);
+}
+
+// a step's counted wait: the chunks beyond the current one that this wave has already issued (`ahead`, 0 .. ST - 2, kDma copies each)
+// may stay in flight
+template <int ST, int kDma>
+__device__ __forceinline__ void wait_chunks_ahead(int ahead) {
+  if (ST >= 4 && ahead >= 2) wait_vmcnt<(ST >= 4 ? 2 : 0) * kDma>();
+  else if (ST >= 3 && ahead == 1) wait_vmcnt<(ST >= 3 ? 1 : 0) * kDma>();
+  else wait_vmcnt<0>();
+}
+
 // ---- r5: the cut of chunk v + 1 runs UNDER the matrix instructions of chunk v ---------------------------------------------------------
 // r4's step was [barrier, read A, cut (64-112 vector instructions, ~300-450 cycles), then 8 groups of (2 B reads, wait, 3 MFMAs)]: the
 // matrix pipe idled during the cut and at the head of every group (an LDS round trip for 96 cycles of work): 17-35 % duty by PMC.  An MFMA
@@ -112,6 +141,18 @@ __device__ __forceinline__ void ring_issue_b(uint4 (*R)[(Ring<NT, PC, ST, WV>::k
 // before the loop; the last v-chunk's A half is filled from the block of zeros, so that every v-chunk is the same number of DMAs.  Same cut,
 // same MFMAs in the same order per accumulator as r4: bit-identical results.  One barrier more per workgroup (n + 1).
 struct Cut { PiecesN s0, s1; };
+
+// the lane's four raw rows of a chunk (A[frag[0 .. 3]] of the wave's A image) -> its pieces.  AF: through the input's bn + ReLU (the table T,
+// chunk gch), then cut with scale 1.  The LDS reads stay with the caller: where they sit among the B reads is part of a step's schedule.
+template <int PC, bool AF>
+__device__ __forceinline__ Cut cut_rows(const uint4& r0, const uint4& r1, const uint4& r2, const uint4& r3, float a_scale, const float* T, int gch, int lane) {
+  float4 c0 = as_f4(r0), c1 = as_f4(r1), c2 = as_f4(r2), c3 = as_f4(r3);
+  if (AF) affine_chunk(T, gch, lane, c0, c1, c2, c3);
+  Cut n;
+  n.s0 = cut8<PC>(c0, c1, AF ? 1.f : a_scale);
+  n.s1 = cut8<PC>(c2, c3, AF ? 1.f : a_scale);
+  return n;
+}
 
 // the vector instructions of one cut, for the interleave's arithmetic (fp16 pair: 2 mul, cvt_pk, 2 cvt back, 2 sub, cvt_pk; AF: mul, add, max per value)
 template <int PC, bool AF> struct CutCost { static constexpr int kValu = (PC == 2 ? 64 : PC == 3 ? 96 : 16) + (AF ? 48 : 0); };
@@ -155,11 +196,7 @@ __device__ __forceinline__ Cut ring_mma_cut(const uint4 (*R)[(Ring<NT, PC, ST, W
   for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int q = 0; q < PC; ++q) bf[t * 2 + 1][q] = B[((t * 2 + 1) * PC + q) * 64];
-  float4 c0 = as_f4(r0), c1 = as_f4(r1), c2 = as_f4(r2), c3 = as_f4(r3);
-  if (AF) affine_chunk(T, min(gch_next, g.chunks_per_tap - 1), g.lane, c0, c1, c2, c3);
-  Cut n;
-  n.s0 = cut8<PC>(c0, c1, AF ? 1.f : a_scale);
-  n.s1 = cut8<PC>(c2, c3, AF ? 1.f : a_scale);
+  const Cut n = cut_rows<PC, AF>(r0, r1, r2, r3, a_scale, T, min(gch_next, g.chunks_per_tap - 1), g.lane);
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = mma_pc<PC>(p.s0, bf[t * 2][0], bf[t * 2][PC > 1 ? 1 : 0], bf[t * 2][PC > 2 ? 2 : 0], acc[t]);
 #pragma unroll
@@ -173,12 +210,7 @@ template <int NT, int PC, int ST, int WV, int S, bool AF>
 __device__ __forceinline__ Cut ring_cut(const uint4 (*R)[(Ring<NT, PC, ST, WV>::kStageN)], const Geom& g, float a_scale, int gch, const float* T) {
   const uint4* A = &R[S][g.wave * 256];
   const uint4 r0 = A[g.frag[0]], r1 = A[g.frag[1]], r2 = A[g.frag[2]], r3 = A[g.frag[3]];
-  float4 c0 = as_f4(r0), c1 = as_f4(r1), c2 = as_f4(r2), c3 = as_f4(r3);
-  if (AF) affine_chunk(T, min(gch, g.chunks_per_tap - 1), g.lane, c0, c1, c2, c3);
-  Cut n;
-  n.s0 = cut8<PC>(c0, c1, AF ? 1.f : a_scale);
-  n.s1 = cut8<PC>(c2, c3, AF ? 1.f : a_scale);
-  return n;
+  return cut_rows<PC, AF>(r0, r1, r2, r3, a_scale, T, min(gch, g.chunks_per_tap - 1), g.lane);
 }
 
 // (A pipelined step for the four-wave mixed-role kernels - the wave issuing its share of v-chunk v + ST - 1 between its MFMAs, a second body
@@ -203,35 +235,21 @@ __device__ __forceinline__ void ring_step_uniform(uint4 (*R)[(Ring<NT, PC, ST, W
   p = ring_mma_cut<NT, PC, ST, WV, S, AF, RG::kDma>(R, g, p, acc, a_scale, g.chunk0 + v + 1, T);
 }
 
-template <int NT, int PC, int ST, int WV, int S>
-__device__ __forceinline__ void ring_prologue_uniform(uint4 (*R)[(Ring<NT, PC, ST, WV>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
-                                                      const Geom& g, Walk& wk, int n) {
-  ring_issue_a<NT, PC, ST, WV, S>(R, x, g, wk, S + 1 < n);
-  ring_issue_b<NT, PC, ST, WV, S, 0, Ring<NT, PC, ST, WV>::kDmaB>(R, wblock, g, wk.bprev);      // B(S): the walk stands at A(S + 1)
-  wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
-}
-
 // ---- split roles (SP): waves 4-7 of a 512-thread workgroup issue the copies, waves 0-3 cut and multiply ------------------------------
 // Measured (rocprofv3 kernel trace, r4): a chunk costs a mixed-role wave ~1.3 us whatever the ring depth - its 6-8 LDS-DMA
 // instructions (~100 cycles of issue each), ~100 VALU instructions of cutting, 16 LDS reads and 12-24 MFMAs are ONE in-order
 // instruction stream, and the matrix pipe idles while the wave sits in a DMA issue.  With the copies issued by a partner wave on
 // the same SIMD the consumer's stream is LDS reads + cut + MFMAs only and the two streams overlap.  Same LDS image, same barrier
 // per chunk (all eight waves), same arithmetic: bit-identical results to the mixed-role form.
-template <int NT, int PC, int ST, int WV, int S>
+// a loader wave's step for chunk (v-chunk) v of n, stage S: wait for it, meet, refill the stage chunk v - 1 left
+template <int NT, int PC, int ST, int WV, int S, bool PIPE>
 __device__ __forceinline__ void ring_load_step(uint4 (*R)[(Ring<NT, PC, ST, WV>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
                                                const Geom& g, Walk& wk, int v, int n) {
   typedef Ring<NT, PC, ST, WV> RG;
   constexpr int SN = (S + ST - 1) % ST;
-  const int ahead = min(n - 1 - v, ST - 2);
-  if (ST >= 4 && ahead >= 2) wait_vmcnt<(ST >= 4 ? 2 : 0) * RG::kDma>();
-  else if (ST >= 3 && ahead == 1) wait_vmcnt<(ST >= 3 ? 1 : 0) * RG::kDma>();
-  else wait_vmcnt<0>();
+  wait_chunks_ahead<ST, RG::kDma>(min(n - 1 - v, ST - 2));
   __builtin_amdgcn_s_barrier();
-  if (v + ST - 1 < n) {
-    ring_issue_a<NT, PC, ST, WV, SN>(R, x, g, wk, v + ST < n);
-    ring_issue_b<NT, PC, ST, WV, SN, 0, RG::kDmaB>(R, wblock, g, wk.bprev);      // B(v + ST - 1): the walk stands at A(v + ST)
-    wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
-  }
+  if (v + ST - 1 < n) ring_issue_chunk<NT, PC, ST, WV, SN, PIPE>(R, x, wblock, g, wk, v + ST < n);      // pipelined: B(v + ST - 1), the walk stands at A(v + ST)
 }
 
 template <int NT, int PC, int ST, int WV, int S, bool AF>
@@ -242,18 +260,8 @@ __device__ __forceinline__ void ring_consume_step(uint4 (*R)[(Ring<NT, PC, ST, W
   p = ring_mma_cut<NT, PC, ST, WV, S, AF>(R, g, p, acc, a_scale, g.chunk0 + v + 1, T);
 }
 
-// the prologue's v-chunks: -1 (A(0) alone, into stage ST - 1), then 0 .. ST - 2 (B(v) and A(v + 1))
-template <int NT, int PC, int ST, int WV, int S>
-__device__ __forceinline__ void ring_prologue(uint4 (*R)[(Ring<NT, PC, ST, WV>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
-                                              const Geom& g, Walk& wk, int n) {
-  if (S < n) {
-    ring_issue_a<NT, PC, ST, WV, S>(R, x, g, wk, S + 1 < n);
-    ring_issue_b<NT, PC, ST, WV, S, 0, Ring<NT, PC, ST, WV>::kDmaB>(R, wblock, g, wk.bprev);      // B(S): the walk stands at A(S + 1)
-    wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
-  }
-}
-
-// everything of v-chunk -1 has landed once at most the DMAs of the v-chunks issued behind it are outstanding
+// everything of v-chunk -1 has landed once at most the DMAs of the v-chunks issued behind it are outstanding (its own ladder: up to
+// ST - 1 v-chunks sit behind v-chunk -1, one rung more than wait_chunks_ahead's ST - 2 ahead of a step)
 template <int NT, int PC, int ST, int WV>
 __device__ __forceinline__ void ring_wait_first(int n) {
   typedef Ring<NT, PC, ST, WV> RG;
@@ -270,26 +278,25 @@ __device__ __forceinline__ void ring_wait_first(int n) {
 // repetitions of one layer: stage 2's conv2 84.7 vs 100.4 us, conv3 129.5 vs 150.6; res4 conv3 (mixed roles, two stages) 52.4 vs 58.3
 // on 256-pixel tiles - and the pipelined step needs 160 (NT = 2) / 230 (NT = 4) registers.  Here stage c % ST holds A(c) and B(c);
 // a step is [wait, barrier, read A, cut, multiply].
-// chunk c of n, its data in stage S = c % ST
-template <int NT, int PC, int ST, int S, bool AF>
+// chunk c of n, its data in stage S = c % ST.  COPIES: the wave also issues its share of chunk c + ST - 1 (mixed roles); without them
+// it is a consumer wave's step (split roles: the loader waves' step is ring_load_step with PIPE = false)
+template <int NT, int PC, int ST, int S, bool AF, bool COPIES>
 __device__ __forceinline__ void ring_step_r4(uint4 (*R)[(Ring<NT, PC, ST, 4>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
                                           const Geom& g, Walk& wk, int c, int n, f32x16 (&acc)[NT], float a_scale, const float* T) {
   typedef Ring<NT, PC, ST, 4> RG;
   constexpr int kDmaB = RG::kDmaB;
   constexpr int SN = (S + ST - 1) % ST;                 // the stage chunk c - 1 lived in: free once everybody is past the barrier
-  // how many chunks beyond c this wave has already issued (they may stay in flight)
-  const int ahead = min(n - 1 - c, ST - 2);
-  if (ST >= 4 && ahead >= 2) wait_vmcnt<(ST >= 4 ? 2 : 0) * RG::kDma>();
-  else if (ST >= 3 && ahead == 1) wait_vmcnt<(ST >= 3 ? 1 : 0) * RG::kDma>();
-  else wait_vmcnt<0>();
+  if (COPIES) wait_chunks_ahead<ST, RG::kDma>(min(n - 1 - c, ST - 2));
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  const bool more = c + ST - 1 < n;
+  const bool more = COPIES && c + ST - 1 < n;
   const int gch_next = wk.bidx;
   if (more) ring_issue_a<NT, PC, ST, 4, SN>(R, x, g, wk, true);
   const uint4* A = &R[S][g.wave * 256];
   const uint4* B = &R[S][Ring<NT, PC, ST, 4>::kStageA + g.lane];
   const uint4 r0 = A[g.frag[0]], r1 = A[g.frag[1]], r2 = A[g.frag[2]], r3 = A[g.frag[3]];
+  // cut_rows, written out: with the pieces passed through a Cut (or through references) the twelve <2, 1, *, *, *, 4> kernels come out
+  // with other register numbers and their conversions in another order (profiles/r10/conv_kernel_refactor_isa.txt)
   float4 c0 = as_f4(r0), c1 = as_f4(r1), c2 = as_f4(r2), c3 = as_f4(r3);
   if (AF) affine_chunk(T, g.chunk0 + c, g.lane, c0, c1, c2, c3);
   const PiecesN s0 = cut8<PC>(c0, c1, AF ? 1.f : a_scale), s1 = cut8<PC>(c2, c3, AF ? 1.f : a_scale);
@@ -310,57 +317,6 @@ __device__ __forceinline__ void ring_step_r4(uint4 (*R)[(Ring<NT, PC, ST, 4>::kS
     }
   }
   if (more) wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
-}
-
-// ---- split roles (SP): waves 4-7 of a 512-thread workgroup issue the copies, waves 0-3 cut and multiply ------------------------------
-// Measured (rocprofv3 kernel trace, r4): a chunk costs a mixed-role wave ~1.3 us whatever the ring depth - its 6-8 LDS-DMA
-// instructions (~100 cycles of issue each), ~100 VALU instructions of cutting, 16 LDS reads and 12-24 MFMAs are ONE in-order
-// instruction stream, and the matrix pipe idles while the wave sits in a DMA issue.  With the copies issued by a partner wave on
-// the same SIMD the consumer's stream is LDS reads + cut + MFMAs only and the two streams overlap.  Same LDS image, same barrier
-// per chunk (all eight waves), same arithmetic: bit-identical results to the mixed-role form.
-template <int NT, int PC, int ST, int S>
-__device__ __forceinline__ void ring_load_step_r4(uint4 (*R)[(Ring<NT, PC, ST, 4>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
-                                               const Geom& g, Walk& wk, int c, int n) {
-  typedef Ring<NT, PC, ST, 4> RG;
-  constexpr int SN = (S + ST - 1) % ST;
-  const int ahead = min(n - 1 - c, ST - 2);
-  if (ST >= 4 && ahead >= 2) wait_vmcnt<(ST >= 4 ? 2 : 0) * RG::kDma>();
-  else if (ST >= 3 && ahead == 1) wait_vmcnt<(ST >= 3 ? 1 : 0) * RG::kDma>();
-  else wait_vmcnt<0>();
-  __builtin_amdgcn_s_barrier();
-  if (c + ST - 1 < n) {
-    ring_issue_a<NT, PC, ST, 4, SN>(R, x, g, wk, true);
-    ring_issue_b<NT, PC, ST, 4, SN, 0, RG::kDmaB>(R, wblock, g, wk.bidx);
-    wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
-  }
-}
-
-template <int NT, int PC, int ST, int S, bool AF>
-__device__ __forceinline__ void ring_consume_step_r4(uint4 (*R)[(Ring<NT, PC, ST, 4>::kStageN)], const Geom& g, f32x16 (&acc)[NT], float a_scale, int c,
-                                                  const float* T) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  const uint4* A = &R[S][g.wave * 256];
-  const uint4* B = &R[S][Ring<NT, PC, ST, 4>::kStageA + g.lane];
-  const uint4 r0 = A[g.frag[0]], r1 = A[g.frag[1]], r2 = A[g.frag[2]], r3 = A[g.frag[3]];
-  float4 c0 = as_f4(r0), c1 = as_f4(r1), c2 = as_f4(r2), c3 = as_f4(r3);
-  if (AF) affine_chunk(T, g.chunk0 + c, g.lane, c0, c1, c2, c3);
-  const PiecesN s0 = cut8<PC>(c0, c1, AF ? 1.f : a_scale), s1 = cut8<PC>(c2, c3, AF ? 1.f : a_scale);
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    acc[t] = mma_pc<PC>(s0, B + ((t * 2 + 0) * PC) * 64, acc[t]);
-    acc[t] = mma_pc<PC>(s1, B + ((t * 2 + 1) * PC) * 64, acc[t]);
-  }
-}
-
-template <int NT, int PC, int ST, int S>
-__device__ __forceinline__ void ring_prologue_r4(uint4 (*R)[(Ring<NT, PC, ST, 4>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
-                                              const Geom& g, Walk& wk, int n) {
-  if (S < n) {
-    ring_issue_a<NT, PC, ST, 4, S>(R, x, g, wk, true);
-    ring_issue_b<NT, PC, ST, 4, S, 0, Ring<NT, PC, ST, 4>::kDmaB>(R, wblock, g, wk.bidx);
-    wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
-  }
 }
 
 // grid (8 * ceil(tiles / 8)); block 256 (SP: 512).  tiles = ceil(P / 128) * (Cout / (32 * NT)) * slices (* phases)
@@ -432,12 +388,12 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
   g.wstride = (size_t)col_tiles * RG::kColTile;
   const uint4* wblock = a.wfrag + (size_t)(NT * tile.y) * RG::kColTile;
   const int m0 = tile.x * kPix + g.wave * kWavePix;
-  // DMA role: instruction i moves pixels 8i .. 8i+7 of the wave's tile, lane -> pixel 8i + (lane >> 3), slot lane & 7
+  // DMA role: instruction i moves pixels 8i .. 8i+7 of the wave's tile, lane -> pixel 8i + (lane >> 3), slot lane & 7 (LSFA_DMA_SRC_PIECE)
   if (!SP || loader) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int pix = m0 + 8 * i + (g.lane >> 3);
-    const int piece = (g.lane & 7) ^ ((4 * i + (g.lane >> 4)) & 7);      // slot -> source piece: the bank swizzle
+    const int piece = LSFA_DMA_SRC_PIECE(i, g.lane);
     g.iy0[i] = g.ix0[i] = -(1 << 24);
     g.off0[i] = 0;
     if (pix < P) {
@@ -448,11 +404,7 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
     }
   }
   }
-  {
-    const int r = g.lane & 31, h = g.lane >> 5, sw = (r >> 1) & 7;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) g.frag[j] = r * 8 + ((4 * h + j) ^ sw);
-  }
+  LSFA_FRAG_SLOTS(g.lane, g.frag)
   f32x16 acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -466,28 +418,32 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
   for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int i = 0; i < 16; ++i) sum[t][i] = 0.f;
+  // The loop is unrolled over the stages (every LDS address of a step is a compile-time offset), so each prologue and each step is a ladder
+  // over S, and every loop ends in the same flush.  Both stay written out at each place: through one helper - the ladder taking the step
+  // as a generic lambda, the flush as a function of (sum, acc), per tile or with its counter - 63 resp. 25-31 of the 66 kernels compile to
+  // other code (profiles/r10/conv_kernel_refactor_isa.txt).
   if constexpr (!kPipelined) {
     if (SP) {
       if (loader) {
         // prologue: chunks 0 .. ST-2 into stages 0 .. ST-2, then one step per chunk: wait for chunk c, meet, refill the stage chunk c - 1 left
-        ring_prologue_r4<NT, PC, ST, 0>(R, a.x, wblock, g, wk, nchunks);
-        if (ST > 2) ring_prologue_r4<NT, PC, ST, (ST > 2 ? 1 : 0)>(R, a.x, wblock, g, wk, nchunks);
-        if (ST > 3) ring_prologue_r4<NT, PC, ST, (ST > 3 ? 2 : 0)>(R, a.x, wblock, g, wk, nchunks);
+        ring_prologue<NT, PC, ST, 4, 0, false, true>(R, a.x, wblock, g, wk, nchunks);
+        if (ST > 2) ring_prologue<NT, PC, ST, 4, (ST > 2 ? 1 : 0), false, true>(R, a.x, wblock, g, wk, nchunks);
+        if (ST > 3) ring_prologue<NT, PC, ST, 4, (ST > 3 ? 2 : 0), false, true>(R, a.x, wblock, g, wk, nchunks);
         for (int c = 0; c < nchunks; c += ST) {
-          ring_load_step_r4<NT, PC, ST, 0>(R, a.x, wblock, g, wk, c, nchunks);
-          if (c + 1 < nchunks) ring_load_step_r4<NT, PC, ST, 1>(R, a.x, wblock, g, wk, c + 1, nchunks);
-          if (ST > 2 && c + 2 < nchunks) ring_load_step_r4<NT, PC, ST, (ST > 2 ? 2 : 0)>(R, a.x, wblock, g, wk, c + 2, nchunks);
-          if (ST > 3 && c + 3 < nchunks) ring_load_step_r4<NT, PC, ST, (ST > 3 ? 3 : 0)>(R, a.x, wblock, g, wk, c + 3, nchunks);
+          ring_load_step<NT, PC, ST, 4, 0, false>(R, a.x, wblock, g, wk, c, nchunks);
+          if (c + 1 < nchunks) ring_load_step<NT, PC, ST, 4, 1, false>(R, a.x, wblock, g, wk, c + 1, nchunks);
+          if (ST > 2 && c + 2 < nchunks) ring_load_step<NT, PC, ST, 4, (ST > 2 ? 2 : 0), false>(R, a.x, wblock, g, wk, c + 2, nchunks);
+          if (ST > 3 && c + 3 < nchunks) ring_load_step<NT, PC, ST, 4, (ST > 3 ? 3 : 0), false>(R, a.x, wblock, g, wk, c + 3, nchunks);
         }
         return;                 // the epilogue is the consumers'
       }
       LSFA_SCALES_READY(0)
       int since = 0;
       for (int c = 0; c < nchunks; c += ST) {
-        ring_consume_step_r4<NT, PC, ST, 0, AF>(R, g, acc, a_scale, c, T);
-        if (c + 1 < nchunks) ring_consume_step_r4<NT, PC, ST, 1, AF>(R, g, acc, a_scale, c + 1, T);
-        if (ST > 2 && c + 2 < nchunks) ring_consume_step_r4<NT, PC, ST, (ST > 2 ? 2 : 0), AF>(R, g, acc, a_scale, c + 2, T);
-        if (ST > 3 && c + 3 < nchunks) ring_consume_step_r4<NT, PC, ST, (ST > 3 ? 3 : 0), AF>(R, g, acc, a_scale, c + 3, T);
+        ring_step_r4<NT, PC, ST, 0, AF, false>(R, a.x, wblock, g, wk, c, nchunks, acc, a_scale, T);
+        if (c + 1 < nchunks) ring_step_r4<NT, PC, ST, 1, AF, false>(R, a.x, wblock, g, wk, c + 1, nchunks, acc, a_scale, T);
+        if (ST > 2 && c + 2 < nchunks) ring_step_r4<NT, PC, ST, (ST > 2 ? 2 : 0), AF, false>(R, a.x, wblock, g, wk, c + 2, nchunks, acc, a_scale, T);
+        if (ST > 3 && c + 3 < nchunks) ring_step_r4<NT, PC, ST, (ST > 3 ? 3 : 0), AF, false>(R, a.x, wblock, g, wk, c + 3, nchunks, acc, a_scale, T);
         since += ST;
         if (since >= kFlush) {
           since = 0;
@@ -499,16 +455,16 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
       }
     } else {
       // prologue: chunks 0 .. ST-2 into stages 0 .. ST-2
-      ring_prologue_r4<NT, PC, ST, 0>(R, a.x, wblock, g, wk, nchunks);
-      if (ST > 2) ring_prologue_r4<NT, PC, ST, (ST > 2 ? 1 : 0)>(R, a.x, wblock, g, wk, nchunks);
-      if (ST > 3) ring_prologue_r4<NT, PC, ST, (ST > 3 ? 2 : 0)>(R, a.x, wblock, g, wk, nchunks);
+      ring_prologue<NT, PC, ST, 4, 0, false, true>(R, a.x, wblock, g, wk, nchunks);
+      if (ST > 2) ring_prologue<NT, PC, ST, 4, (ST > 2 ? 1 : 0), false, true>(R, a.x, wblock, g, wk, nchunks);
+      if (ST > 3) ring_prologue<NT, PC, ST, 4, (ST > 3 ? 2 : 0), false, true>(R, a.x, wblock, g, wk, nchunks);
       LSFA_SCALES_READY(0)      // (behind the prologue's copies: their count depends on nchunks, so everything is waited for - chunk 0 is needed next anyway)
       int since = 0;
       for (int c = 0; c < nchunks; c += ST) {
-        ring_step_r4<NT, PC, ST, 0, AF>(R, a.x, wblock, g, wk, c, nchunks, acc, a_scale, T);
-        if (c + 1 < nchunks) ring_step_r4<NT, PC, ST, 1, AF>(R, a.x, wblock, g, wk, c + 1, nchunks, acc, a_scale, T);
-        if (ST > 2 && c + 2 < nchunks) ring_step_r4<NT, PC, ST, (ST > 2 ? 2 : 0), AF>(R, a.x, wblock, g, wk, c + 2, nchunks, acc, a_scale, T);
-        if (ST > 3 && c + 3 < nchunks) ring_step_r4<NT, PC, ST, (ST > 3 ? 3 : 0), AF>(R, a.x, wblock, g, wk, c + 3, nchunks, acc, a_scale, T);
+        ring_step_r4<NT, PC, ST, 0, AF, true>(R, a.x, wblock, g, wk, c, nchunks, acc, a_scale, T);
+        if (c + 1 < nchunks) ring_step_r4<NT, PC, ST, 1, AF, true>(R, a.x, wblock, g, wk, c + 1, nchunks, acc, a_scale, T);
+        if (ST > 2 && c + 2 < nchunks) ring_step_r4<NT, PC, ST, (ST > 2 ? 2 : 0), AF, true>(R, a.x, wblock, g, wk, c + 2, nchunks, acc, a_scale, T);
+        if (ST > 3 && c + 3 < nchunks) ring_step_r4<NT, PC, ST, (ST > 3 ? 3 : 0), AF, true>(R, a.x, wblock, g, wk, c + 3, nchunks, acc, a_scale, T);
         since += ST;
         if (since >= kFlush) {
           since = 0;
@@ -525,25 +481,25 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
     // refill the stage v-chunk v - 1 left
     ring_issue_a<NT, PC, ST, WV, ST - 1>(R, a.x, g, wk, true);
     wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
-    ring_prologue<NT, PC, ST, WV, 0>(R, a.x, wblock, g, wk, nchunks);
-    if (ST > 2) ring_prologue<NT, PC, ST, WV, (ST > 2 ? 1 : 0)>(R, a.x, wblock, g, wk, nchunks);
-    if (ST > 3) ring_prologue<NT, PC, ST, WV, (ST > 3 ? 2 : 0)>(R, a.x, wblock, g, wk, nchunks);
+    ring_prologue<NT, PC, ST, WV, 0, true, true>(R, a.x, wblock, g, wk, nchunks);
+    if (ST > 2) ring_prologue<NT, PC, ST, WV, (ST > 2 ? 1 : 0), true, true>(R, a.x, wblock, g, wk, nchunks);
+    if (ST > 3) ring_prologue<NT, PC, ST, WV, (ST > 3 ? 2 : 0), true, true>(R, a.x, wblock, g, wk, nchunks);
     ring_wait_first<NT, PC, ST, WV>(nchunks);
     __builtin_amdgcn_s_barrier();
     for (int c = 0; c < nchunks; c += ST) {
-      ring_load_step<NT, PC, ST, WV, 0>(R, a.x, wblock, g, wk, c, nchunks);
-      if (c + 1 < nchunks) ring_load_step<NT, PC, ST, WV, 1>(R, a.x, wblock, g, wk, c + 1, nchunks);
-      if (ST > 2 && c + 2 < nchunks) ring_load_step<NT, PC, ST, WV, (ST > 2 ? 2 : 0)>(R, a.x, wblock, g, wk, c + 2, nchunks);
-      if (ST > 3 && c + 3 < nchunks) ring_load_step<NT, PC, ST, WV, (ST > 3 ? 3 : 0)>(R, a.x, wblock, g, wk, c + 3, nchunks);
+      ring_load_step<NT, PC, ST, WV, 0, true>(R, a.x, wblock, g, wk, c, nchunks);
+      if (c + 1 < nchunks) ring_load_step<NT, PC, ST, WV, 1, true>(R, a.x, wblock, g, wk, c + 1, nchunks);
+      if (ST > 2 && c + 2 < nchunks) ring_load_step<NT, PC, ST, WV, (ST > 2 ? 2 : 0), true>(R, a.x, wblock, g, wk, c + 2, nchunks);
+      if (ST > 3 && c + 3 < nchunks) ring_load_step<NT, PC, ST, WV, (ST > 3 ? 3 : 0), true>(R, a.x, wblock, g, wk, c + 3, nchunks);
     }
     return;                 // the epilogue is the consumers'
   }
   if (kUniform) {
     ring_issue_a<NT, PC, ST, WV, ST - 1>(R, a.x, g, wk, true);
     wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
-    ring_prologue_uniform<NT, PC, ST, WV, 0>(R, a.x, wblock, g, wk, nchunks);
-    if (ST > 2) ring_prologue_uniform<NT, PC, ST, WV, (ST > 2 ? 1 : 0)>(R, a.x, wblock, g, wk, nchunks);
-    if (ST > 3) ring_prologue_uniform<NT, PC, ST, WV, (ST > 3 ? 2 : 0)>(R, a.x, wblock, g, wk, nchunks);
+    ring_prologue<NT, PC, ST, WV, 0, true, false>(R, a.x, wblock, g, wk, nchunks);
+    if (ST > 2) ring_prologue<NT, PC, ST, WV, (ST > 2 ? 1 : 0), true, false>(R, a.x, wblock, g, wk, nchunks);
+    if (ST > 3) ring_prologue<NT, PC, ST, WV, (ST > 3 ? 2 : 0), true, false>(R, a.x, wblock, g, wk, nchunks);
     wait_vmcnt<(ST - 1) * RG::kDma>();
     LSFA_SCALES_READY((ST - 1) * RG::kDma)      // (older than every copy: landed with A(0))
   } else {
@@ -582,7 +538,7 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[t][i] = (sum[t][i] + acc[t][i]) * out_scale[t];    // 1 unless PC == 2 (a power of two: exact)
 
-  // C/D layout of 32x32: column = lane & 31 (channel), row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (pixel)
+  // C/D layout of 32x32: column = lane & 31 (channel), row = acc_row(reg, lane) (pixel)
   const int lane = g.lane;
   // Channels-last outputs leave through LDS: in the accumulator layout a lane holds ONE channel of 16 pixels, i.e. 4-byte accesses
   // (16 per tile and output, plus 16 residual loads: the epilogue of a conv3 - residual, sum, next bn1 / relu1 - was 7 of its 27 us).
@@ -602,7 +558,7 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) T[t * 1024 + ((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = acc[t][r];
+      for (int r = 0; r < 16; ++r) T[t * 1024 + acc_row(r, lane) * 32 + (lane & 31)] = acc[t][r];
     const uint32_t m = tile_rows_out<NT>(a, T, m0, P, tile.y * (32 * NT), part, lane, in);
     if (!part) publish_amax(m, a.amax_out, a.status, blockIdx.x * WV + g.wave);
     return;
@@ -615,7 +571,7 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Tc[(t * 32 + (lane & 31)) * kColPitch + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)] = acc[t][r];
+      for (int r = 0; r < 16; ++r) Tc[acc_row(r, lane, (t * 32 + (lane & 31)) * kColPitch)] = acc[t][r];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the wave reads back what its own lanes wrote
     const uint32_t m = tile_cols_out_nchw<NT>(a, Tc, m0, P, tile.y * (32 * NT), lane);
     publish_amax(m, a.amax_out, a.status, blockIdx.x * WV + g.wave);
@@ -626,7 +582,7 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
   ro.valid = 0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    prow[r] = m0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    prow[r] = acc_row(r, lane, m0);
     if (prow[r] < P) ro.valid |= 1u << r;
   }
   if (a.part) {      // a K slice whose ring is too small for the row path (128 x 128 one-piece tiles at two stages): partial sums, no epilogue

@@ -10,14 +10,21 @@
 // Each partial product of two 16-bit values is exact in fp32, so the only differences to an fp32 FMA chain are the dropped terms and
 // the summation order; against a float64 convolution forms 3 and 2 are as close as an fp32 FMA chain (tests/test_hip_ops.py).
 //
-// What is in this file (the 128-pixel ring kernel, the main kernel of the family, lives in conv_ring_kernel.h):
+// What is in this file (the 128-pixel ring kernel, the main kernel of the family, lives in conv_ring_kernel.h; conv3 + the next conv1 in
+// one launch in conv_pair_kernel.h).  Every kernel of the family takes its arithmetic and its geometry from here:
 //   Args                    the argument block every kernel of the family takes (filled by conv.hip from lsfa_conv_desc)
-//   cut8 / mma_pc           cutting 8 fp32 values into pieces and the 1 / 3 / 6 matrix instructions of one k-step
-//   amax plumbing           amax_exponent_asm (the scale from 256 partial maxima), publish_amax (an epilogue's maximum into the slots the
-//                           next layer reads), the status word
+//   cut8 / mma_pc           cutting 8 fp32 values into PiecesN and the 1 / 3 / 6 matrix instructions of one k-step, on the primitives
+//                           cut3, cut2h_pair, lead, pack_hi, as_bf, as_h, mma
+//   the fp16 form's scale   scale_loads_issue / _wait / scale_finish (the ring kernel: the 256 amax slots and the weight scales in one round
+//                           trip -> the map's power-of-two scale and the accumulator columns' factors), amax_exponent_asm + column_scales
+//                           (the direct kernel: the same rule, read where it is wanted)
+//   amax plumbing           amax_word (an epilogue lane's maximum, a non-finite value kept visible), publish_amax (a wave's maximum into
+//                           the slots the next layer reads), the status word
 //   epilogues               tile_store_max (fragment-shaped stores: NCHW, views), tile_rows_out (channels-last rows through LDS as
 //                           float4), with bias / residual / activation / second output (the next unit's bn1 + relu1)
 //   split_reduce_*          the pass that adds a K-sliced launch's partial sums in slice order and applies the epilogue
+//   geometry                Geom, LSFA_FRAG_SLOTS (a lane's fragment pieces in a wave's A image), LSFA_DMA_SRC_PIECE (the bank swizzle of the
+//                           LDS-DMA copies that fill it), acc_row (accumulator register -> pixel row), Walk, xcd_tile
 //   conv_split_direct_*     small weights on a small map: a wave per 32 x 64 tile, operands straight into registers
 // Weights (B) are cut and laid out ONCE at bind time in fragment order (lsfa_conv_weights / pack_weights_kernel):
 // [tap][chunk][32-col tile][k-step][piece][lane][8 x 16 bit], so a fragment is 1 KB contiguous.  One chunk = 32 input channels of one tap.
@@ -54,7 +61,7 @@ struct Args {
   // ph_wstride uint4 behind the previous phase's (everything a phase needs follows from (py, px): a table in the argument
   // struct would be indexed dynamically, which makes hipcc keep the struct in scratch)
   int nphase; long part_stride; long ph_wstride;
-  // r3, fp16 two-piece form (conv_split_wide_kernel<NT, 2>): `amax` = kAmaxSlots partial maxima of |x| (lsfa_amax_partial), from which
+  // r3, fp16 two-piece form (PC == 2): `amax` = kAmaxSlots partial maxima of |x| (lsfa_amax_partial), from which
   // every wave derives the power-of-two scale that puts x into fp16's range; the weights were packed as w * 2^w_exp
   const float* amax; int w_exp;
   // r5: per-OUTPUT-channel weight scales: wscale[co] = 2^-w_exp[co] (the weights were packed as w[co] * 2^w_exp[co], lsfa_conv_weights_pc), or
@@ -111,25 +118,12 @@ __device__ __forceinline__ uint32_t lead(float v) { return __float_as_uint(v) & 
 // two bf16 (upper halves of b's and a's bit patterns) -> one dword, a in the low half
 __device__ __forceinline__ uint32_t pack_hi(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
 
-struct Pieces { uint4 p1, p2, p3; };     // 8 values x 3 pieces, packed bf16
-
 __device__ __forceinline__ void cut3(float v, uint32_t& h, uint32_t& m, uint32_t& l) {
   h = lead(v);
   const float r1 = v - __uint_as_float(h);       // exact
   m = lead(r1);
   const float r2 = r1 - __uint_as_float(m);      // exact, at most 8 significant bits
   l = __float_as_uint(r2);
-}
-
-__device__ __forceinline__ Pieces split8(const float4& a, const float4& b) {
-  uint32_t h[8], m[8], l[8];
-  cut3(a.x, h[0], m[0], l[0]); cut3(a.y, h[1], m[1], l[1]); cut3(a.z, h[2], m[2], l[2]); cut3(a.w, h[3], m[3], l[3]);
-  cut3(b.x, h[4], m[4], l[4]); cut3(b.y, h[5], m[5], l[5]); cut3(b.z, h[6], m[6], l[6]); cut3(b.w, h[7], m[7], l[7]);
-  Pieces r;
-  r.p1 = make_uint4(pack_hi(h[0], h[1]), pack_hi(h[2], h[3]), pack_hi(h[4], h[5]), pack_hi(h[6], h[7]));
-  r.p2 = make_uint4(pack_hi(m[0], m[1]), pack_hi(m[2], m[3]), pack_hi(m[4], m[5]), pack_hi(m[6], m[7]));
-  r.p3 = make_uint4(pack_hi(l[0], l[1]), pack_hi(l[2], l[3]), pack_hi(l[4], l[5]), pack_hi(l[6], l[7]));
-  return r;
 }
 
 __device__ __forceinline__ bf16x8 as_bf(const uint4& u) {
@@ -142,18 +136,7 @@ __device__ __forceinline__ f32x16 mma(const uint4& a, const uint4& b, const f32x
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a), as_bf(b), c, 0, 0, 0);
 }
 
-// acc += (a1 + a2 + a3) * (b1 + b2 + b3) without the three smallest terms, smallest kept terms first
-__device__ __forceinline__ f32x16 mma6(const Pieces& a, const uint4& b1, const uint4& b2, const uint4& b3, f32x16 acc) {
-  acc = mma(a.p3, b1, acc);
-  acc = mma(a.p1, b3, acc);
-  acc = mma(a.p2, b2, acc);
-  acc = mma(a.p2, b1, acc);
-  acc = mma(a.p1, b2, acc);
-  acc = mma(a.p1, b1, acc);
-  return acc;
-}
-
-// ---- r3 (opt-in): fp16 in TWO pieces, three matrix instructions per k-step ----------------------------------------------------------
+// ---- r3: fp16 in TWO pieces, three matrix instructions per k-step ----------------------------------------------------------
 // hi = fp16(x s), lo = fp16(x s - hi), s a power of two that puts max|x| into [2^13, 2^14): x s = hi + lo to 2^-24 relative (like fp32
 // itself; below 2^-3 of the scaled range lo goes subnormal and the absolute error is 2^-25 of that range), and
 // x y = hi hi + hi lo + lo hi + (lo lo <= 2^-24 |x y|, dropped).  Same accumulator, smallest terms first.  Against float64 this is as
@@ -161,8 +144,6 @@ __device__ __forceinline__ f32x16 mma6(const Pieces& a, const uint4& b1, const u
 // large convolutions are bound by.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr int kAmaxSlots = 256;
-
-struct PiecesH { uint4 hi, lo; };
 
 // two values at a time: gfx950's v_cvt_pk_f16_f32 rounds (to nearest even) and packs both in one instruction; the way back is
 // one v_cvt_f32_f16 per half.  8 VALU instructions per pair where the scalar conversions + shifts + ors took 12.
@@ -182,26 +163,10 @@ __device__ __forceinline__ void cut2h_pair(float v0, float v1, float s, uint32_t
   l = __builtin_bit_cast(uint32_t, ll);
 }
 
-__device__ __forceinline__ PiecesH split8h(const float4& a, const float4& b, float s) {
-  PiecesH r;
-  cut2h_pair(a.x, a.y, s, r.hi.x, r.lo.x);
-  cut2h_pair(a.z, a.w, s, r.hi.y, r.lo.y);
-  cut2h_pair(b.x, b.y, s, r.hi.z, r.lo.z);
-  cut2h_pair(b.z, b.w, s, r.hi.w, r.lo.w);
-  return r;
-}
-
 __device__ __forceinline__ f16x8 as_h(const uint4& u) {
   union { uint4 u; f16x8 v; } c;
   c.u = u;
   return c.v;
-}
-
-__device__ __forceinline__ f32x16 mma3h(const PiecesH& a, const uint4& bhi, const uint4& blo, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(a.lo), as_h(bhi), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(a.hi), as_h(blo), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(a.hi), as_h(bhi), acc, 0, 0, 0);
-  return acc;
 }
 
 // ---- epilogue shared by the kernels below -----------------------------------------------------------------------
@@ -231,6 +196,7 @@ __device__ __forceinline__ void tile_store_part(float* part, int Cout, const int
 // ---- r4: operand pieces generic in PC (pieces per fp32 operand) -----------------------------------------------------------------------
 //   3 = three bf16 pieces, six products;  2 = two fp16 pieces + a power-of-two scale per map, three products;
 //   1 = one bf16 piece (round to nearest even), one product: the bf16 mode of BASELINE configs[2]
+// p[0 .. PC - 1], leading piece first: 3 = bf16 p1, p2, p3 (8 values each, packed);  2 = fp16 hi, lo;  1 = the bf16 value
 struct PiecesN { uint4 p[3]; };
 
 __device__ __forceinline__ uint32_t bf16_rne_pair(float a, float b) {
@@ -241,6 +207,8 @@ __device__ __forceinline__ uint32_t bf16_rne_pair(float a, float b) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// 8 values (a, b) -> their PC pieces.  3: cut3 per value, exact, no scale.  2: cut2h_pair under the power-of-two scale s, two values at a
+// time.  1: round to nearest even.
 template <int PC>
 __device__ __forceinline__ PiecesN cut8(const float4& a, const float4& b, float s) {
   PiecesN r;
@@ -250,11 +218,17 @@ __device__ __forceinline__ PiecesN cut8(const float4& a, const float4& b, float 
   return r;
 #endif
   if (PC == 3) {
-    const Pieces p = split8(a, b);
-    r.p[0] = p.p1; r.p[1] = p.p2; r.p[2] = p.p3;
+    uint32_t h[8], m[8], l[8];
+    cut3(a.x, h[0], m[0], l[0]); cut3(a.y, h[1], m[1], l[1]); cut3(a.z, h[2], m[2], l[2]); cut3(a.w, h[3], m[3], l[3]);
+    cut3(b.x, h[4], m[4], l[4]); cut3(b.y, h[5], m[5], l[5]); cut3(b.z, h[6], m[6], l[6]); cut3(b.w, h[7], m[7], l[7]);
+    r.p[0] = make_uint4(pack_hi(h[0], h[1]), pack_hi(h[2], h[3]), pack_hi(h[4], h[5]), pack_hi(h[6], h[7]));
+    r.p[1] = make_uint4(pack_hi(m[0], m[1]), pack_hi(m[2], m[3]), pack_hi(m[4], m[5]), pack_hi(m[6], m[7]));
+    r.p[2] = make_uint4(pack_hi(l[0], l[1]), pack_hi(l[2], l[3]), pack_hi(l[4], l[5]), pack_hi(l[6], l[7]));
   } else if (PC == 2) {
-    const PiecesH p = split8h(a, b, s);
-    r.p[0] = p.hi; r.p[1] = p.lo;
+    cut2h_pair(a.x, a.y, s, r.p[0].x, r.p[1].x);
+    cut2h_pair(a.z, a.w, s, r.p[0].y, r.p[1].y);
+    cut2h_pair(b.x, b.y, s, r.p[0].z, r.p[1].z);
+    cut2h_pair(b.z, b.w, s, r.p[0].w, r.p[1].w);
   } else {
     r.p[0] = make_uint4(bf16_rne_pair(a.x, a.y), bf16_rne_pair(a.z, a.w), bf16_rne_pair(b.x, b.y), bf16_rne_pair(b.z, b.w));
   }
@@ -265,15 +239,22 @@ __device__ __forceinline__ float4 as_f4(const uint4& r) {
   return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
 }
 
-// acc += A * B for one k-step; b0, b1, b2 = the (up to) PC fragments of (column tile, step) in piece order
+// acc += A * B for one k-step; b0, b1, b2 = the (up to) PC fragments of (column tile, step) in piece order.  Same accumulator, smallest
+// kept terms first:  3: (a1 + a2 + a3) * (b1 + b2 + b3) without the three smallest terms (a2 b3, a3 b2, a3 b3 < 2^-23 |a b|), six products;
+// 2: (hi + lo) * (hi' + lo') without lo lo' (<= 2^-24 |a b|), three products.
 template <int PC>
 __device__ __forceinline__ f32x16 mma_pc(const PiecesN& a, const uint4& b0, const uint4& b1, const uint4& b2, f32x16 acc) {
   if (PC == 3) {
-    Pieces p; p.p1 = a.p[0]; p.p2 = a.p[1]; p.p3 = a.p[2];
-    return mma6(p, b0, b1, b2, acc);
+    acc = mma(a.p[2], b0, acc);
+    acc = mma(a.p[0], b2, acc);
+    acc = mma(a.p[1], b1, acc);
+    acc = mma(a.p[1], b0, acc);
+    acc = mma(a.p[0], b1, acc);
+    return mma(a.p[0], b0, acc);
   } else if (PC == 2) {
-    PiecesH p; p.hi = a.p[0]; p.lo = a.p[1];
-    return mma3h(p, b0, b1, acc);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(a.p[1]), as_h(b0), acc, 0, 0, 0);      // lo * hi'
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(a.p[0]), as_h(b1), acc, 0, 0, 0);      // hi * lo'
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(a.p[0]), as_h(b0), acc, 0, 0, 0);     // hi * hi'
   }
   return mma(a.p[0], b0, acc);
 }
@@ -381,7 +362,9 @@ __device__ __forceinline__ float scale_finish(const Args& a, const ScaleRegs& r,
 
 // the fp16 form's scale from the kAmaxSlots partial maxima (floats or bit patterns of |x|: the same thing for non-negative values),
 // read by inline assembly with its own wait so that no compiler-visible vector load is pending when a DMA ring starts.
-// -> floor(log2(max)), 0 for an all-zero map; an inf / NaN maximum raises bit 1 of *status
+// -> floor(log2(max)), 0 for an all-zero map; an inf / NaN maximum raises bit 1 of *status.  (The rule of scale_finish, which has the loads
+// behind it, and of the pair kernel: as ONE function called from the three, all 28 two-piece ring kernels and the 4 pair kernels compile
+// to other code - profiles/r10/conv_kernel_refactor_isa.txt - so it stays written out; change the three together.)
 __device__ __forceinline__ int amax_exponent_asm(const float* amax, int lane, unsigned* status) {
   static_assert(kAmaxSlots == 256, "four slots per lane");
   const float* p = amax + lane;
@@ -416,6 +399,15 @@ __device__ __forceinline__ void publish_amax(uint32_t m, unsigned* amax_out, uns
 __device__ __forceinline__ uint32_t amax_bits(float pre, float post) {
   const uint32_t b = __float_as_uint(pre) & 0x7FFFFFFFu;
   return b >= 0x7F800000u ? b : (__float_as_uint(post) & 0x7FFFFFFFu);
+}
+
+// an epilogue lane's word for publish_amax: mx = the maximum of |what the next layer multiplies| as a float maximum (one instruction per
+// value; a NaN drops out of it), nf = the SUM of the pre-activation magnitudes, which is non-finite exactly when one of them is (ReLU
+// would hide a NaN or a -inf): one add per value
+__device__ __forceinline__ uint32_t amax_word(float mx, float nf) {
+  uint32_t m = __float_as_uint(mx);
+  if ((__float_as_uint(nf) & 0x7F800000u) == 0x7F800000u) m = 0x7FC00000u;       // a non-finite value went through this lane
+  return m;
 }
 
 // tile_store that also returns the maximum of what it wrote (of y2 when there is a second output: that is what the next layer multiplies)
@@ -457,7 +449,7 @@ __device__ __forceinline__ uint32_t tile_store_max(const Args& a, const RowOut& 
 // are read back as float4 along the channels - lane -> (row 8k + lane / 8, channels 4 (lane % 8) ..): whole 128-byte rows per
 // 8 lanes, 16 bytes per lane, a quarter of the memory instructions.  Same values, same arithmetic per element as tile_store.
 // m0 = first pixel of the 32 rows, ch0 = first channel of tile 0; part != NULL: a K slice's partial sums instead of the epilogue.
-// -> the wave's contribution to amax_out (bit pattern; 0x7FC00000 if a non-finite value went through this lane)
+// -> the wave's contribution to amax_out (amax_word)
 // Every load of the epilogue is issued before its first store: the residual is usually the output itself (a ResNet unit adds in place),
 // so the compiler must assume that a store may change what a later load reads and would run the 4 x NT (load, add, store) steps one
 // memory latency after the other - 16 round trips for a 128 x 128 tile, most of a conv3's time (res4 conv3 at six images: 74 us for a
@@ -495,9 +487,7 @@ __device__ __forceinline__ void tile_rows_in(const Args& a, int m0, int P, int c
 template <int NT>
 __device__ __forceinline__ uint32_t tile_rows_out(const Args& a, const float* T, int m0, int P, int ch0, float* part, int lane, const RowsIn<NT>& in) {
   const int c4 = (lane & 7) * 4;
-  // the maximum as a float maximum of |.| (one instruction per value; a NaN drops out of it) and, beside it, the SUM of the
-  // pre-activation magnitudes, which is non-finite exactly when one of them is (ReLU would hide a NaN or a -inf): one add per value
-  float mx = 0.f, nf = 0.f;
+  float mx = 0.f, nf = 0.f;                      // -> amax_word
   const int act = a.act;                         // wave-uniform: the branches below are scalar
   const bool has_y2 = a.scale2 != nullptr, store_y2 = a.y2 != nullptr, has_res = a.res != nullptr, has_bias = a.bias != nullptr;
   if (part) {
@@ -538,9 +528,7 @@ __device__ __forceinline__ uint32_t tile_rows_out(const Args& a, const float* T,
       }
     }
   }
-  uint32_t m = __float_as_uint(mx);
-  if ((__float_as_uint(nf) & 0x7F800000u) == 0x7F800000u) m = 0x7FC00000u;       // a non-finite value went through this lane
-  return m;
+  return amax_word(mx, nf);
 }
 
 // can a channels-last output take the float4 row path (alignment of the operands it touches)
@@ -592,9 +580,7 @@ __device__ __forceinline__ uint32_t tile_cols_out_nchw(const Args& a, const floa
       }
     }
   }
-  uint32_t m = __float_as_uint(mx);
-  if ((__float_as_uint(nf) & 0x7F800000u) == 0x7F800000u) m = 0x7FC00000u;       // a non-finite value went through this lane
-  return m;
+  return amax_word(mx, nf);
 }
 
 __device__ __forceinline__ bool rows_path_ok(const Args& a) {
@@ -726,8 +712,25 @@ struct Geom {       // per lane / per wave constants of the loop
   int wave, lane;
 };
 
-// the 7 LDS-DMA instructions of one chunk into stage ST (compile-time LDS offsets).  x / wblock (this workgroup's
-// 12 KB of chunk 0) are __restrict__ parameters on purpose (see the header comment).
+// A wave's A image of one chunk in LDS: 32 pixels (rows) x 8 slots of 16 bytes; a row's eight 4-channel pieces sit in slot
+// piece ^ ((row >> 1) & 7) (the bank swizzle, applied on the SOURCE side of the copies).
+//   LSFA_DMA_SRC_PIECE  LDS-DMA instruction i of a chunk moves pixels 8i .. 8i+7 of the wave's rows, lane -> pixel 8i + (lane >> 3), slot
+//                       lane & 7: the source piece that belongs into that slot
+//   LSFA_FRAG_SLOTS     frag[0 .. 3] = the uint4 index of the lane's four fragment pieces (fragment role: row = lane & 31, k half =
+//                       lane >> 5: channels 16 h + 4 k ..)
+// Macros, not functions: the compiler simplifies a function's integer arithmetic before it inlines it, without what the caller knows
+// (lane < 64, i a constant), and the kernels' set-up code then comes out as other instructions (profiles/r10/conv_kernel_refactor_isa.txt).
+#define LSFA_DMA_SRC_PIECE(i, lane) (((lane) & 7) ^ ((4 * (i) + ((lane) >> 4)) & 7))
+#define LSFA_FRAG_SLOTS(lane, frag)                                                  \
+  {                                                                                  \
+    const int r_ = (lane) & 31, h_ = (lane) >> 5, sw_ = (r_ >> 1) & 7;               \
+    _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_) (frag)[k_] = r_ * 8 + ((4 * h_ + k_) ^ sw_); \
+  }
+// C/D layout of the 32x32 matrix instructions: accumulator register r of a lane is column lane & 31 (channel) and this row (pixel).
+// `base` is what the row is added to (a first pixel, an offset): it comes first in the sum, as the call sites had it written out -
+// another association of the same additions changes the kernels' code
+__device__ __forceinline__ int acc_row(int r, int lane, int base = 0) { return base + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+
 // which (tap row, tap column, channel chunk) a chunk index is, walked incrementally (an integer division per chunk
 // cost ~50 scalar instructions in the loop)
 // r6: two orders.  k_order 0 walks a tap's channel chunks before the next tap (weights are packed that way: block (tap, chunk) at index
@@ -923,7 +926,7 @@ __device__ __forceinline__ void direct_tile(const Args& a, int bx, int by, int n
     float* T = red_dyn;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      const int row = acc_row(r, lane);
       T[row * 32 + (lane & 31)] = acc0[r];
       T[1024 + row * 32 + (lane & 31)] = acc1[r];
     }
@@ -937,7 +940,7 @@ __device__ __forceinline__ void direct_tile(const Args& a, int bx, int by, int n
   ro.valid = 0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int p = m0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int p = acc_row(r, lane, m0);
     ro.base[r] = 0;
     if (p < P) { ro.valid |= 1u << r; ro.base[r] = out_pixel_base(a, p); }
   }

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Does the float64-anchored parity criterion notice a degraded convolution?  ("the same test FAILS if mma3h drops a
-# second product".)  Builds a copy of the library whose fp16 two-piece product drops the hi*lo term as well (hi*hi + lo*hi only:
+# Does the float64-anchored parity criterion notice a degraded convolution?  ("the same test FAILS if the fp16 two-piece
+# product drops a second product".)  Builds a copy of the library whose fp16 two-piece product drops the hi*lo term as well (hi*hi + lo*hi only:
 # weights effectively rounded to 11 bits), runs tests/test_parity_fullres_gpu.py against it through LSFA_HIP_LIBRARY and expects
 # the test to FAIL; then runs it against the real library and expects it to pass.  Lab only: the product header is not touched.
 set -u
@@ -11,9 +11,9 @@ python - $B/csrc/conv_split_kernel.h <<'PY'
 import sys
 p = sys.argv[1]
 s = open(p).read()
-old = "  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(a.hi), as_h(blo), acc, 0, 0, 0);\n"
+old = "    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(a.p[0]), as_h(b1), acc, 0, 0, 0);      // hi * lo'\n"
 assert s.count(old) == 1
-open(p, 'w').write(s.replace(old, "  /* dropped for the lab check: hi * lo */\n"))
+open(p, 'w').write(s.replace(old, "    /* dropped for the lab check: hi * lo */\n"))
 PY
 OBJS=""
 for f in $B/csrc/*.hip; do
