@@ -649,6 +649,24 @@ int lsfa_luma_pyramid(const unsigned char* luma, long long plane_stride, int n_p
 int lsfa_mv_refine_chain(const unsigned char* luma, long long plane_stride, int n_chains, int n_frames, int width, int height,
                          const int* parent_mvs /* (n_chains, n_frames, mbh1*mbw1, 7) */, int refine, int lambda, int max_sad,
                          int* mvs /* (n_chains, n_frames, mbh*mbw, 7) */, int* sad /* (n_chains, n_frames, mbh, mbw) or NULL */, void* stream);
+/* Scene cuts from the searches' own SADs (lsfa_amd/csrc/me_cut.hip): a third, opt-in mode of the front end.  The textbook encoder rule -
+ * a macroblock's inter cost against its intra cost - NOT ffmpeg's scene detection; like the two searches it replaces nothing of the
+ * reference (ImageNet-VID snippets have no cuts; the reference's key frames are every TEST.KEY_FRAME_INTERVAL-th) and is comparable with
+ * nothing in it.  Defined by its own specification (DESIGN.md "Scene cuts", restated in numpy as tests/ref_me_cut.py) and bit-exact with
+ * that.  For pair (c, f), f = 1..n_frames (plane f against plane f - 1 of chain c) and macroblock b of the level-0 grid, n_b its covered
+ * pixels (256, fewer for a block cut by the right or bottom edge):
+ *   inter_b = sad[c][f - 1][b] as a search wrote it (the full search's or the pyramid's level-0 winner; max_sad does not change it);
+ *   m_b = (sum p + n_b / 2) / n_b, integer division, over the covered pixels of the CURRENT plane f;  intra_b = sum |p - m_b|;
+ *   b is unmatched iff inter_b > intra_b + bias * n_b, bias 0..255 grey levels per pixel (two frames of one flat, noisy area differ by
+ *   about sqrt(2) times the noise, a block from its own mean by the noise only: without a bias every flat block would vote "cut");
+ *   unmatched[c][f - 1] = the number of unmatched blocks.  The frame decision is the caller's: a cut iff unmatched * 100 > percent * mbh * mbw.
+ * lsfa_mv_cut_score: luma is the stack lsfa_mv_estimate_chain takes, addressed and refused as there (a negative plane_stride is a stack
+ *   stored in reverse; plane 0 of a chain is read by no pair's intra cost).  intra (n_chains, n_frames, mbh, mbw) and unmatched (n_chains,
+ *   n_frames) int32 are both written in full.  Two launches (sixteen lanes per macroblock; one workgroup per pair), no workspace, no memset, no
+ *   atomics, nothing read back. */
+int lsfa_mv_cut_score(const unsigned char* luma, long long plane_stride, int n_chains, int n_frames, int width, int height,
+                      const int* sad /* (n_chains, n_frames, mbh, mbw) */, int bias, int* intra /* (n_chains, n_frames, mbh, mbw) */,
+                      int* unmatched /* (n_chains, n_frames) */, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip): the planes a decoder hands over - libav, the VCN decode engines, a raw .yuv dump - straight to

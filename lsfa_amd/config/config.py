@@ -94,7 +94,7 @@ def default_config():
     t.KEY_FRAME_INTERVAL = 12
     t.max_per_image = 300
     t.test_epoch = 0
-    # not in the reference: None, or hip.SegmentMotionEstimator's parameters (search, lam, max_sad, levels, refine) with which TestLoader estimates every
+    # not in the reference: None, or hip.SegmentMotionEstimator's parameters (search, lam, max_sad, levels, refine, cut) with which TestLoader estimates every
     # segment's motion vectors and residuals from the frames themselves (its estimate_mv argument, when given, wins)
     t.ESTIMATE_MV = None
     c.TEST = t

@@ -12,9 +12,33 @@ estimate_mv, or config.TEST.ESTIMATE_MV where it is None (not in the reference; 
 hip.SegmentMotionEstimator's parameters (search, lam, max_sad; levels, refine for the pyramid search).  When a key frame is handed out, the
 uint8 frames of it and of the non-key frames behind it are uploaded and the whole segment's inputs are estimated from
 them on the current stream, in three launches (levels + 4 with the pyramid); each of those non-key frames then receives its slice.
+
+estimate_mv=dict(..., cut=dict(bias=..., percent=...)) (not in the reference either: its dataset has no cuts) places a key frame where the
+search says a new scene starts (hip.SegmentMotionEstimator(cut=...), DESIGN.md "Scene cuts"): the key frames of a video are key_plan() of
+its cut frames.  A cut frame is handed out with flag 1 like any key frame and the segment behind it is estimated from it; the pairs a
+segment estimated beyond its first cut are discarded.  Finding a segment's cut costs one readback (4 bytes per frame), and
+upcoming_key_frames estimates the coming segments ahead, as far as it has to, to announce the key frames that will really come.
 """
 import numpy as np
 import torch
+
+
+def next_key_frame(key_f, length, interval, cuts):
+    """The key frame behind key frame key_f of a video of `length` frames: the smallest of key_f + interval, the video's last frame and
+    the first cut frame in key_f + 1 .. min(key_f + interval - 1, length - 2).  `cuts`: the frames f whose pair (f, f - 1) is a cut."""
+    last = min(key_f + interval, length - 1)
+    return min([f for f in cuts if key_f < f < last] + [last])
+
+
+def key_plan(length, interval, cuts):
+    """Every key frame of a video, in order: a pure function of (length, interval, set of cut frames) - cut flags belong to consecutive
+    pairs, so they do not depend on where the segments start.  It is what TestLoader's flags follow (next() and get_batch() move the key
+    frame on by the same three rules, a segment's first cut taken from its estimate) and what upcoming_key_frames announces, one
+    next_key_frame at a time."""
+    keys = [0]
+    while keys[-1] < length - 1:
+        keys.append(next_key_frame(keys[-1], length, interval, cuts))
+    return keys
 
 
 class DataBatch(object):
@@ -32,7 +56,10 @@ class TestLoader(object):
             estimate_mv = config.TEST.get('ESTIMATE_MV')
         self.estimate_mv = None if estimate_mv is None else dict(estimate_mv)
         self._estimators = {}           # (width, height) -> SegmentMotionEstimator
-        self._segment = None            # ((roidb index, key frame), n, mv (n, 1, 2, h, w), res (n, 1, 3, h, w)) of the segment under way
+        self.cut = self.estimate_mv is not None and self.estimate_mv.get('cut') is not None
+        # ((roidb index, key frame), n, mv (n, 1, 2, h, w), res (n, 1, 3, h, w), cut frame or None) of the segment under way
+        self._segment = None
+        self._segments = {}             # `cut`: (roidb index, key frame) -> such a tuple (None: nothing to estimate), the segments estimated ahead
         self.cfg, self.roidb, self.batch_size, self.shuffle, self.has_rpn = config, roidb, batch_size, shuffle, has_rpn
         self.device = device
         self.size = int(np.sum([x['frame_seg_len'] for x in self.roidb]))
@@ -92,7 +119,7 @@ class TestLoader(object):
                 self.cur_roidb_index += 1
                 self.cur_frameid = 0
                 self.key_frameid = 0
-            elif self.cur_frameid - self.key_frameid == self.cfg.TEST.KEY_FRAME_INTERVAL:
+            elif self.cur_frameid - self.key_frameid == self.cfg.TEST.KEY_FRAME_INTERVAL or self._cut_at(self.key_frameid) == self.cur_frameid:
                 self.key_frameid = self.cur_frameid
             return self.im_info, self.key_frame_flag, DataBatch(data=self.data, label=self.label, pad=0,
                                                                 index=self.cur // self.batch_size,
@@ -125,25 +152,52 @@ class TestLoader(object):
         return hip.SegmentMotionEstimator(width, height, frames=max(self.cfg.TEST.KEY_FRAME_INTERVAL - 1, 1), clips=1, device=self.device,
                                           **self.estimate_mv)
 
-    def _estimate_segment(self, entry, key_f):
-        """Key frame key_f is being handed out: estimate the inputs of the non-key frames behind it - key_f + 1 .. key_f + n with
-        n = KEY_FRAME_INTERVAL - 1, fewer in front of the video's last frame (a key frame) - in one SegmentMotionEstimator.segment call on the
-        current stream.  The result is copied out of the estimator's buffers: a pipeline that groups key frames holds a segment's inputs
-        while the next segment is estimated."""
-        tag = (self.cur_roidb_index, key_f)
-        if self._segment is not None and self._segment[0] == tag:
-            return                       # get_batch runs twice for the very first frame (the constructor's shape probe)
-        self._segment = None
+    def _compute_segment(self, index, entry, key_f):
+        """One SegmentMotionEstimator.segment call on the current stream for key frame key_f of video `index` and the non-key frames behind
+        it - key_f + 1 .. key_f + n with n = KEY_FRAME_INTERVAL - 1, fewer in front of the video's last frame (a key frame) -> ((index,
+        key_f), n, mv (n, 1, 2, h, w), res (n, 1, 3, h, w), cut frame or None), or None where no frame follows the key frame.  The result
+        is copied out of the estimator's buffers: a pipeline that groups key frames holds a segment's inputs while the next segment is
+        estimated.  With `cut` the segment ends in front of its first cut frame (one readback) and the pairs from there on are dropped."""
         n = min(key_f + self.cfg.TEST.KEY_FRAME_INTERVAL - 1, entry['frame_seg_len'] - 2) - key_f
         if n < 1:
-            return
+            return None
         clip = entry['clip']
         key = (clip.width, clip.height)
         if key not in self._estimators:
             self._estimators[key] = self._segment_estimator(clip.width, clip.height)
         stack = torch.stack([clip.frame_u8(g) for g in range(key_f, key_f + n + 1)]).unsqueeze(0).to(self.device)
         mv, res = self._estimators[key].segment(stack, float(clip.im_info()[0, 2]), self.cfg.network.PIXEL_MEANS, self.cfg.network.PIXEL_SCALE)
-        self._segment = (tag, n, mv.clone(), res.clone())
+        cut_f = None
+        if self.cut:
+            first = self._estimators[key].first_cuts()[0]
+            if first is not None:        # frame key_f + first starts a new scene: it becomes a key frame
+                cut_f, n = key_f + first, first - 1
+        return ((index, key_f), n, mv[:n].clone(), res[:n].clone(), cut_f)
+
+    def _estimate_segment(self, entry, key_f):
+        """Key frame key_f is being handed out: the segment behind it becomes the one under way - estimated now, or taken from what
+        upcoming_key_frames estimated ahead (`cut` only)."""
+        tag = (self.cur_roidb_index, key_f)
+        if self._segment is not None and self._segment[0] == tag:
+            return                       # get_batch runs twice for the very first frame (the constructor's shape probe)
+        self._segment = None
+        for old in [t for t in self._segments if t < tag]:       # the iteration has passed them
+            del self._segments[old]
+        self._segment = self._segments.pop(tag) if tag in self._segments else self._compute_segment(self.cur_roidb_index, entry, key_f)
+
+    def _segment_ahead(self, entry, key_f):
+        """`cut`: the segment behind a coming key frame of the current video, estimated once and kept until the iteration reaches it"""
+        tag = (self.cur_roidb_index, key_f)
+        if self._segment is not None and self._segment[0] == tag:
+            return self._segment
+        if tag not in self._segments:
+            self._segments[tag] = self._compute_segment(self.cur_roidb_index, entry, key_f)
+        return self._segments[tag]
+
+    def _cut_at(self, key_f):
+        """the cut frame that ends the segment under way behind key frame key_f of the current video, or None"""
+        seg = self._segment
+        return seg[4] if self.cut and seg is not None and seg[0] == (self.cur_roidb_index, key_f) else None
 
     def _estimated(self, entry, f, key_f):
         seg = self._segment
@@ -155,7 +209,8 @@ class TestLoader(object):
     def upcoming_key_frames(self, n):
         """Call right after a KEY frame was returned: the images of the next `n` key frames of the same video (fewer near its end), for a
         caller that computes the image-only part of several key frames at once (FramePipeline.key_frame(upcoming=...)).  Key frames are
-        every KEY_FRAME_INTERVAL-th frame and, by the rule of get_batch above (:106-109), the video's last frame.  The tensors are kept and
+        every KEY_FRAME_INTERVAL-th frame and, by the rule of get_batch above (:106-109), the video's last frame; with `cut` also the cut
+        frames (next_key_frame), for which the segments behind the coming key frames are estimated here and kept.  The tensors are kept and
         handed out again when the iteration reaches those frames."""
         if self.cur_frameid == 0:             # the frame just returned was its video's last: nothing ahead in this video
             return []
@@ -163,7 +218,9 @@ class TestLoader(object):
         K, L = self.cfg.TEST.KEY_FRAME_INTERVAL, entry['frame_seg_len']
         out, prev = [], self.cur_frameid - 1       # the (key) frame just returned; key_frameid may already point past it (interval 1)
         while len(out) < n and prev < L - 1:
-            f = min(prev + K, L - 1)          # the next multiple of the interval, or the video's last frame if that comes first
+            seg = self._segment_ahead(entry, prev) if self.cut else None
+            # the next multiple of the interval, or the video's last frame if that comes first - or, with `cut`, the segment's cut frame
+            f = next_key_frame(prev, L, K, () if seg is None or seg[4] is None else (seg[4],))
             key = (self.cur_roidb_index, f)
             if key not in self._ahead:
                 self._ahead[key] = entry['clip'].frame(f, self.device)

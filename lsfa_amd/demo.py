@@ -6,6 +6,7 @@ score above 0.7 after per-class NMS.
     python -m lsfa_amd.demo                         # synthetic 1000x600 clip, random-init weights
     python -m lsfa_amd.demo --frames DIR [--mv DIR] [--prefix P --epoch E] [--out dets.json]
     python -m lsfa_amd.demo --frames DIR --estimate-mv [--search 16 --mv-lambda 4] [--mv-levels L --mv-refine r] [--dump-mv DIR]
+    python -m lsfa_amd.demo --frames DIR --estimate-mv --scene-cut [PERCENT] [--cut-bias B]     # a key frame wherever a new scene starts
 
     python -m lsfa_amd.demo --yuv clip.nv12 --size 1280x720 [--yuv-format nv12|i420] [--yuv-matrix bt601|bt709|jpeg] [--estimate-mv ...]
 
@@ -48,7 +49,7 @@ from lsfa_amd.utils.synthetic import SyntheticClip
 class FrameDirClip(object):
     """Frames of one clip from a directory, preprocessed like the reference's demo (:73-82).  estimate: None, or a dict of
     hip.MotionEstimator's parameters (search, lam, max_sad) - motion vectors and residuals are then estimated from the frames on
-    `device`; dump_mv: a directory that receives them as the .npz files `mv_dir` is read from."""
+    `device`; with cut=dict(...) among them mv_res returns None for a frame the estimator finds to start a new scene; dump_mv: a directory that receives them as the .npz files `mv_dir` is read from."""
 
     def __init__(self, frame_dir, mv_dir, cfg, estimate=None, device='cuda:0', dump_mv=None):
         from PIL import Image
@@ -101,6 +102,8 @@ class FrameDirClip(object):
         for f in range(self._me_last + 1, i + 1):             # the P-frame chain: every frame against the one before it
             me.next_frame(self._frame_u8(f))
         self._me_last = i
+        if self.estimate.get('cut') is not None and me.is_cut():
+            return None                                       # frame i starts a new scene: the caller makes it a key frame
         cfg = self.cfg
         cur, key = self._frame_u8(i), self._frame_u8(key_i)
         if self.dump_mv is not None:
@@ -193,6 +196,8 @@ class YuvFileClip(object):
         for f in range(self._me_last + 1, i + 1):             # the P-frame chain: every frame against the one before it
             me.next_frame_yuv(**self.planes(f))
         self._me_last = i
+        if self.estimate.get('cut') is not None and me.is_cut():
+            return None                                       # frame i starts a new scene: the caller makes it a key frame
         cfg = self.cfg
         cur, key = me.bgr_cur, me.bgr_key
         if self.dump_mv is not None:
@@ -237,6 +242,11 @@ def parse_args(argv=None):
     ap.add_argument('--mv-levels', type=int, default=0, choices=(0, 1, 2),
                     help='--estimate-mv: extra pyramid levels; the reach is search * 2^L + refine * (2^L - 1) pixels (0: the full search alone)')
     ap.add_argument('--mv-refine', type=int, default=2, choices=(1, 2, 3), help='--mv-levels: refinement radius per level (a parameter, not a tuned value)')
+    ap.add_argument('--scene-cut', type=int, nargs='?', const=50, default=None, metavar='PERCENT',
+                    help='--estimate-mv: a frame more than PERCENT (1..100, default 50) of whose macroblocks the previous frame does not predict '
+                         'becomes a key frame (DESIGN.md "Scene cuts"; a parameter, not a tuned value)')
+    ap.add_argument('--cut-bias', type=int, default=4,
+                    help='--scene-cut: grey levels per pixel a block\'s search residual may exceed its intra cost by, 0..255 (a parameter, not a tuned value)')
     ap.add_argument('--dump-mv', default=None, help='--estimate-mv: write the estimated mv / res as the .npz files --mv reads')
     ap.add_argument('--num', type=int, default=30, help='frames of the synthetic clip')
     ap.add_argument('--interval', type=int, default=10, help='key frame interval (demo.py:68)')
@@ -270,6 +280,8 @@ def parse_args(argv=None):
         ap.error('--estimate-mv needs --frames or --yuv and excludes --mv')
     if args.dump_mv and not args.estimate_mv:
         ap.error('--dump-mv needs --estimate-mv')
+    if args.scene_cut is not None and (not args.estimate_mv or not 1 <= args.scene_cut <= 100 or not 0 <= args.cut_bias <= 255):
+        ap.error('--scene-cut PERCENT (1..100) needs --estimate-mv; --cut-bias is 0..255')
     return args
 
 
@@ -283,6 +295,8 @@ def main(argv=None):
     cfg.TEST.KEY_FRAME_INTERVAL = args.interval
     dev = 'cuda:0'
     estimate = dict(search=args.search, lam=args.mv_lambda, levels=args.mv_levels, refine=args.mv_refine) if args.estimate_mv else None
+    if args.scene_cut is not None:
+        estimate['cut'] = dict(bias=args.cut_bias, percent=args.scene_cut)
     if args.yuv:
         clip = YuvFileClip(args.yuv, args.yuv_size[0], args.yuv_size[1], cfg, args.yuv_format, args.yuv_matrix, estimate, dev, args.dump_mv)
     else:
@@ -301,9 +315,14 @@ def main(argv=None):
     classes = None       # class names live in the dataset (imdb.classes); ids are reported without one
 
     results, total, count = [], 0.0, 0
+    key_idx = 0          # the running key frame: every `interval` frames behind the last one - or, with --scene-cut, where a scene starts
     for idx in range(clip.num_frames):
         data = clip.frame(idx).to(dev)
-        mv, res = (None, None) if idx % args.interval == 0 else [t.to(dev) for t in clip.mv_res(idx, idx - idx % args.interval)]
+        is_key = idx == 0 or idx - key_idx == args.interval
+        mv_res = None if is_key else clip.mv_res(idx, key_idx)
+        if mv_res is None:       # --scene-cut: the estimator's next_frame* found a cut; the clip starts its chain over at this frame (key_frame*)
+            is_key, key_idx = True, idx
+        mv, res = (None, None) if is_key else [t.to(dev) for t in mv_res]
         torch.cuda.synchronize()
         t0 = time.time()
         if idx == 0:
@@ -313,7 +332,7 @@ def main(argv=None):
             fg.capture()                                   # the reference's "warm up" (:104-116)
             print('warmup done')
         else:
-            dets, counts, _ = fg.key_frame(data) if idx % args.interval == 0 else fg.cur_frame(data, mv, res)
+            dets, counts, _ = fg.key_frame(data) if is_key else fg.cur_frame(data, mv, res)
             dets_h, counts_h = dets.cpu().numpy(), counts.cpu().numpy()    # .cpu() is the per-frame sync
             total += time.time() - t0
             count += 1
@@ -323,7 +342,7 @@ def main(argv=None):
             for x1, y1, x2, y2, s in dets_h[j, :counts_h[j]]:
                 frame_dets.append({'class': classes[j] if classes else j, 'score': float(s),
                                    'box': [float(x1), float(y1), float(x2), float(y2)]})
-        results.append({'frame': clip.names[idx], 'key': idx % args.interval == 0, 'dets': frame_dets})
+        results.append({'frame': clip.names[idx], 'key': is_key, 'dets': frame_dets})
     print('done: {} frames, {} detections above {:.2f}'.format(len(results), sum(len(r['dets']) for r in results),
                                                                 args.score))
     if args.out:

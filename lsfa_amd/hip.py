@@ -1556,6 +1556,12 @@ ME_SEARCH, ME_LAMBDA, ME_MAX_SAD = 16, 4, 0
 # levels = 0 is the full search alone.  refine = 2 is a parameter like ME_SEARCH, not a tuned value.
 ME_LEVELS, ME_REFINE = 0, 2
 
+# ---- scene cuts (lsfa_amd/csrc/me_cut.hip) -----------------------------------------------------------------------------------------------------
+# Parameters like the searches', not tuned values: a block is unmatched beyond 4 grey levels per pixel over its intra cost (two frames of one
+# flat, noisy area differ by about sqrt(2) times the noise, a block from its own mean by the noise only); a frame most of whose blocks are
+# unmatched is a cut.
+ME_CUT_BIAS, ME_CUT_PERCENT = 4, 50
+
 
 def me_reach(levels, search, refine=ME_REFINE):
     """the longest vector component, in pixels, the search can return: search * 2^levels + refine * (2^levels - 1)"""
@@ -1701,6 +1707,46 @@ def mv_refine_chain(luma_stack, parent_rows, refine=ME_REFINE, lam=ME_LAMBDA, ma
 
 
 @_on_tensor_device
+def mv_cut_score(luma_stack, sad, bias=ME_CUT_BIAS, out=None):
+    """lsfa_mv_cut_score: luma_stack (C, F + 1, H, W) uint8 as mv_estimate_chain takes it and the winners' SAD (C, F, mbh, mbw) int32 a search
+    wrote for it (the full search's, or the pyramid's level 0) -> (intra (C, F, mbh, mbw), unmatched (C, F)) int32: per macroblock of plane
+    f = 1..F the sum of |p - mean| over its covered pixels, per pair the number of blocks with sad > intra + bias * covered pixels (bias
+    0..255).  Pair (c, f) is a cut iff unmatched * 100 > percent * mbh * mbw (hip.cut_flags).  Two launches, nothing read back.  out: a pair
+    of contiguous int32 tensors of those shapes.  Defined by its own specification (include/lsfa_hip.h; tests/ref_me_cut.py): the textbook
+    inter-against-intra rule, not an encoder's scene detection."""
+    who = "mv_cut_score"
+    C, F, stride, (H, W) = _u8_stack(who, "luma_stack", luma_stack, ("H", "W"))
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    _tensor(who, "sad (the winners' SAD of a search on this stack)", sad, torch.int32, (C, F, mbh, mbw), luma_stack.device)
+    if not 0 <= int(bias) <= 255:
+        raise LsfaError("%s: bias %r is outside 0..255" % (who, bias))
+    if out is None:
+        out = (torch.empty((C, F, mbh, mbw), dtype=torch.int32, device=luma_stack.device),
+               torch.empty((C, F), dtype=torch.int32, device=luma_stack.device))
+    intra = _tensor(who, "output buffer out[0]", out[0], torch.int32, (C, F, mbh, mbw), luma_stack.device)
+    unmatched = _tensor(who, "output buffer out[1]", out[1], torch.int32, (C, F), luma_stack.device)
+    _check(lib().lsfa_mv_cut_score(_ptr(luma_stack), stride, C, F, W, H, _ptr(sad), int(bias), _ptr(intra), _ptr(unmatched), _stream()),
+           "lsfa_mv_cut_score")
+    return intra, unmatched
+
+
+def cut_flags(unmatched, blocks, percent=ME_CUT_PERCENT):
+    """the frame decision on HOST counts (a list, an array or a CPU tensor): unmatched * 100 > percent * blocks, elementwise, in integers"""
+    return np.asarray(unmatched, dtype=np.int64) * 100 > int(percent) * int(blocks)
+
+
+def _cut_params(who, cut):
+    """cut=None | dict(bias=..., percent=...) -> None | (bias, percent), checked"""
+    if cut is None:
+        return None
+    extra = set(cut) - {'bias', 'percent'}
+    bias, percent = int(cut.get('bias', ME_CUT_BIAS)), int(cut.get('percent', ME_CUT_PERCENT))
+    if extra or not 0 <= bias <= 255 or not 1 <= percent <= 100:
+        raise LsfaError("%s: cut takes bias (0..255) and percent (1..100), got %r" % (who, dict(cut)))
+    return bias, percent
+
+
+@_on_tensor_device
 def mv_segment_inputs(rows, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16, out=None):
     """lsfa_mv_segment_inputs: rows (C, F, mbh * mbw, 7) int32 as mv_estimate_chain returns them and the (C, F + 1, H, W, 3) uint8 BGR stack
     they were estimated on (frame 0 of a chain its key frame) -> `motion_vector` (F, C, 2, h, w) and `res_diff` (F, C, 3, h, w) float32,
@@ -1729,7 +1775,8 @@ class _MotionSearch(object):
     every level for `planes` luma planes and `pairs` pairs - flat, so that any run of planes is a stack of its own in front of the same
     memory - and the coarse-to-fine sequence on a stack of them."""
 
-    def __init__(self, who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes, pairs):
+    def __init__(self, who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes, pairs, cut=None):
+        self.cut = _cut_params(who, cut)
         self.levels, self.refine = int(levels), int(refine)
         if not 0 <= self.levels <= 2:
             raise LsfaError("%s: levels %d is outside 0..2" % (who, self.levels))
@@ -1753,6 +1800,9 @@ class _MotionSearch(object):
         self.flat = [torch.empty(planes * ps, dtype=torch.uint8, device=self.device) for ps in self.plane]
         self.rows = [torch.empty(pairs * b * 7, dtype=torch.int32, device=self.device) for b in self.blocks]
         self.sad = torch.empty(pairs * self.blocks[0], dtype=torch.int32, device=self.device)
+        # scene cuts (cut=dict(bias, percent)): every block's intra cost and every pair's count of unmatched blocks
+        self.intra = torch.empty(pairs * self.blocks[0], dtype=torch.int32, device=self.device) if self.cut else None
+        self.unmatched = torch.empty(pairs, dtype=torch.int32, device=self.device) if self.cut else None
 
     def planes(self, k, first, count):
         """planes first .. first + count - 1 of level k as (count, h_k, w_k)"""
@@ -1768,7 +1818,8 @@ class _MotionSearch(object):
         k's).  The stack is addressed on every level as the exports address one - plane 0 at plane `first` of the flat buffer, the others
         `step` planes on, -1 for a stack stored in reverse - and the pyramid of its first `built` planes exists already.  levels + 2
         launches: the pyramid of the other planes, the full search on the top level, one refinement per level below it; with levels = 0
-        the full search alone.  max_sad and the SAD belong to level 0."""
+        the full search alone.  max_sad and the SAD belong to level 0.  With `cut` set, lsfa_mv_cut_score's two launches follow level 0:
+        the front of self.intra / self.unmatched."""
         L, N = self.levels, chains * (frames + 1)
         self.pyramid(first + step * (built if step > 0 else N - 1), N - built)
         with torch.cuda.device(self.device):
@@ -1781,6 +1832,21 @@ class _MotionSearch(object):
                 else:
                     _check(lib().lsfa_mv_refine_chain(luma, stride, chains, frames, w, h, _ptr(self.rows[k + 1]), self.refine, self.lam, max_sad,
                                                       _ptr(self.rows[k]), sad, _stream()), "lsfa_mv_refine_chain")
+        self.cut_score(chains, frames, first, step)
+
+    def cut_score(self, chains, frames, first=0, step=1):
+        """lsfa_mv_cut_score on the stack run() was given, behind its level-0 SAD (nothing without `cut`)"""
+        if self.cut:
+            with torch.cuda.device(self.device):
+                _check(lib().lsfa_mv_cut_score(_ptr(self.flat[0][first * self.plane[0]:]), step * self.plane[0], chains, frames, self.width,
+                                               self.height, _ptr(self.sad), self.cut[0], _ptr(self.intra), _ptr(self.unmatched), _stream()),
+                       "lsfa_mv_cut_score")
+
+    def read_cuts(self, count):
+        """the one readback: synchronises the current stream and returns the first `count` pairs' cut flags as a numpy bool array"""
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+        return cut_flags(self.unmatched[:count].cpu().numpy(), self.blocks[0], self.cut[1])
 
 
 class MotionEstimator(object):
@@ -1810,11 +1876,18 @@ class MotionEstimator(object):
     level) instead of one.  levels = 0 (the default) runs exactly the full search's launches; `refine` is ignored there.
 
     The pyramid search is SegmentMotionEstimator's on one chain of one pair: the two ping-pong planes of every level lie one plane apart in
-    one buffer, a stack of two that starts at the reference plane - forwards if the current plane lies behind it, else stored in reverse."""
+    one buffer, a stack of two that starts at the reference plane - forwards if the current plane lies behind it, else stored in reverse.
+
+    cut=dict(bias=..., percent=...) (either may be left out; default None: every launch and every bit as without it) adds scene-cut
+    detection (lsfa_mv_cut_score, two launches behind the search; DESIGN.md "Scene cuts"): after next_frame / next_frame_yuv, self.unmatched
+    is the (1,) int32 device count of blocks the previous frame does not predict, and is_cut() - the one readback, a synchronisation -
+    says whether the frame starts a new scene: the caller then hands the same frame to key_frame / key_frame_yuv."""
 
     def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr', matrix='bt601',
-                 levels=ME_LEVELS, refine=ME_REFINE):
-        s = self._search = _MotionSearch("MotionEstimator", width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes=2, pairs=1)
+                 levels=ME_LEVELS, refine=ME_REFINE, cut=None):
+        s = self._search = _MotionSearch("MotionEstimator", width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes=2, pairs=1,
+                                         cut=cut)
+        self.cut, self.unmatched = s.cut, s.unmatched
         self.width, self.height, self.device = s.width, s.height, s.device
         self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
         self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
@@ -1842,6 +1915,7 @@ class MotionEstimator(object):
             # the pair kernel, not run(1, 1, ...): through the chain kernel the per-frame graph of nine frames was 3.3 us (1000 x 600) to
             # 12.4 us (1920 x 1080) slower, beyond the parent's run-to-run spread of 0.4 .. 2.4 us (profiles/r9/me_frontend_refactor.txt)
             mv_estimate(self._luma[cur], self._luma[self._ref], self.search, self.lam, self.max_sad, out=self.rows, sad_out=self.sad)
+            self._search.cut_score(1, 1, self._ref, cur - self._ref)
         else:
             self._search.run(1, 1, self._ref, cur - self._ref, built=1)
         self.acc.add_frame(self.rows, max_block_area=256)      # the explicit area: no device-to-host read
@@ -1858,6 +1932,13 @@ class MotionEstimator(object):
         luma_u8(self._frame(bgr, 'next_frame'), out=self._luma[cur])
         self._next(cur)
         return self.rows
+
+    def is_cut(self):
+        """Does the frame the last next_frame / next_frame_yuv took start a new scene?  Synchronises the current stream and reads
+        self.unmatched (4 bytes): the one readback of the mode."""
+        if not self.cut:
+            raise LsfaError("MotionEstimator.is_cut: the estimator was built without cut=")
+        return bool(self._search.read_cuts(1)[0])
 
     @property
     def bgr_cur(self):
@@ -1930,16 +2011,24 @@ class SegmentMotionEstimator(object):
     levels = 1 or 2 switches to the pyramid search (DESIGN.md "Pyramid search"): `search` is the range on the top level, self.reach the longest
     vector component.  A segment is then levels + 4 launches - luma, lsfa_luma_pyramid of every plane, lsfa_mv_estimate_chain on the top
     level, one lsfa_mv_refine_chain per level below it, the inputs - with the pyramid planes and the rows of every level allocated up
-    front like everything else.  levels = 0 (the default) runs exactly the three launches above; `refine` is ignored there."""
+    front like everything else.  levels = 0 (the default) runs exactly the three launches above; `refine` is ignored there.
+
+    cut=dict(bias=..., percent=...) (either may be left out; default None: every launch, every tensor and every bit as without it) adds
+    scene-cut detection (DESIGN.md "Scene cuts"): lsfa_mv_cut_score's two launches between the level-0 search and the inputs, on the same
+    stream, into buffers allocated up front.  segment / segment_yuv return what they return without it; self.unmatched is the (C, n)
+    device view of the last call's counts of unmatched blocks, self.intra (C, n, mbh, mbw) the blocks' intra costs, and first_cuts() - the
+    one readback, a synchronisation - gives per clip the first frame that starts a new scene.  The inputs of the frames from a cut on
+    were estimated across it: the caller discards them and makes the cut frame a key frame."""
 
     def __init__(self, width, height, frames=9, clips=1, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr',
-                 matrix='bt601', levels=ME_LEVELS, refine=ME_REFINE):
+                 matrix='bt601', levels=ME_LEVELS, refine=ME_REFINE, cut=None):
         who = "SegmentMotionEstimator"
         self.frames, self.clips = int(frames), int(clips)
         if self.frames < 1 or self.clips < 1 or int(width) < 1 or int(height) < 1:
             raise LsfaError("%s: frames %d, clips %d and the %d x %d frame must all be at least 1" % (who, self.frames, self.clips, int(width), int(height)))
         s = self._search = _MotionSearch(who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine,
-                                         planes=self.clips * (self.frames + 1), pairs=self.clips * self.frames)
+                                         planes=self.clips * (self.frames + 1), pairs=self.clips * self.frames, cut=cut)
+        self.cut, self.intra, self.unmatched = s.cut, None, None
         self.width, self.height, self.device = s.width, s.height, s.device
         self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
         self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
@@ -1964,6 +2053,8 @@ class SegmentMotionEstimator(object):
         N, blocks = C * (n + 1), self.mbh * self.mbw
         self.rows = s.rows[0][:C * n * blocks * 7].view(C, n, blocks, 7)
         self.sad = s.sad[:C * n * blocks].view(C, n, self.mbh, self.mbw)
+        if self.cut:
+            self.intra, self.unmatched = s.intra[:C * n * blocks].view(C, n, self.mbh, self.mbw), s.unmatched[:C * n].view(C, n)
         luma = s.planes(0, 0, N)
         if not luma_done and s.plane[0] == H * W:
             luma_u8(bgr.view(N * H, W, 3), out=luma.view(N * H, W))     # pointwise: a stack is one tall frame
@@ -1979,6 +2070,18 @@ class SegmentMotionEstimator(object):
                                   torch.empty((n, C, 3) + key[1:], device=self.device, dtype=torch.float32))
             out = self._out[key]
         return mv_segment_inputs(self.rows, bgr, im_scale, pixel_means, pixel_scale, rcnn_stride, out=out)
+
+    def first_cuts(self, n=None):
+        """Per clip the first frame f = 1..n (default: the last call's length) of the last segment whose pair (f, f - 1) is a cut, or None.
+        Synchronises the current stream and reads self.unmatched (4 * C * n bytes) once: the one readback of the mode."""
+        if not self.cut or self.unmatched is None:
+            raise LsfaError("SegmentMotionEstimator.first_cuts: needs cut= and a segment() / segment_yuv() call before it")
+        C, have = int(self.unmatched.shape[0]), int(self.unmatched.shape[1])
+        n = have if n is None else int(n)
+        if not 1 <= n <= have:
+            raise LsfaError("SegmentMotionEstimator.first_cuts: n = %d; the last segment holds %d frames" % (n, have))
+        flags = self._search.read_cuts(C * have).reshape(C, have)[:, :n]
+        return [int(np.argmax(row)) + 1 if row.any() else None for row in flags]
 
     def segment(self, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, n=None, rcnn_stride=16, out=None):
         """bgr_stack (C, n + 1, H, W, 3) uint8, contiguous, frame 0 of every clip its key frame -> (mv (n, C, 2, h, w), res (n, C, 3, h, w)).

@@ -4,6 +4,7 @@ parse --cfg, build the test symbols, shard videos over the ranks, run pred_eval,
 
     python -m lsfa_amd.test [--cfg YAML] [--clips N] [--frames F] [--height H] [--width W] [--prefix P --epoch E]
     python -m lsfa_amd.test --segment -1 --key-group 2 --estimate-mv [--search R --mv-lambda L --mv-levels L --mv-refine r]      # frames alone: no motion vectors handed in
+    python -m lsfa_amd.test --estimate-mv --scene-cut [PERCENT] [--cut-bias B] [--synthetic-cuts 7,15]      # key frames where a new scene starts
     python -m torch.distributed.run --nproc-per-node 8 -m lsfa_amd.test --clips 8
 
 Without a dataset or weights in the image, clips are synthetic (lsfa_amd.utils.synthetic) and the
@@ -51,11 +52,24 @@ def parse_args():
     ap.add_argument('--mv-levels', type=int, default=0, choices=(0, 1, 2),
                     help='--estimate-mv: extra pyramid levels; the reach is search * 2^L + refine * (2^L - 1) pixels (0: the full search alone)')
     ap.add_argument('--mv-refine', type=int, default=2, choices=(1, 2, 3), help='--mv-levels: refinement radius per level (a parameter, not a tuned value)')
+    ap.add_argument('--scene-cut', type=int, nargs='?', const=50, default=None, metavar='PERCENT',
+                    help='--estimate-mv: a frame more than PERCENT (1..100, default 50) of whose macroblocks the previous frame does not predict '
+                         'becomes a key frame (DESIGN.md "Scene cuts"; a parameter, not a tuned value)')
+    ap.add_argument('--cut-bias', type=int, default=4,
+                    help='--scene-cut: grey levels per pixel a block\'s search residual may exceed its intra cost by, 0..255 (a parameter, not a tuned value)')
+    ap.add_argument('--synthetic-cuts', default='', help='frames at which every synthetic clip starts a new scene, e.g. 7,15 (default: none)')
     ap.add_argument('--out', default=None, help='rank 0 saves the gathered detection rows (n,7) here (.npy)')
     ap.add_argument('--shards-out', default=None, help='rank 0 saves which videos each rank ran (a JSON list per rank, gathered from the ranks themselves)')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'],
                     help='f32: every fp32 product from two fp16 pieces (fp32 accuracy); bf16: one bf16 product per fp32 product (BASELINE configs[2])')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.scene_cut is not None and (not args.estimate_mv or not 1 <= args.scene_cut <= 100 or not 0 <= args.cut_bias <= 255):
+        ap.error('--scene-cut PERCENT (1..100) needs --estimate-mv; --cut-bias is 0..255')
+    try:
+        args.synthetic_cuts = tuple(int(v) for v in args.synthetic_cuts.split(',') if v.strip())
+    except ValueError:
+        ap.error('--synthetic-cuts takes frame numbers separated by commas, got %r' % (args.synthetic_cuts,))
+    return args
 
 
 def main():
@@ -69,6 +83,8 @@ def main():
         cfg.TEST.KEY_FRAME_INTERVAL = args.interval
     if args.estimate_mv:                  # read by the loader test_rcnn builds
         cfg.TEST.ESTIMATE_MV = dict(search=args.search, lam=args.mv_lambda, levels=args.mv_levels, refine=args.mv_refine)
+        if args.scene_cut is not None:
+            cfg.TEST.ESTIMATE_MV['cut'] = dict(bias=args.cut_bias, percent=args.scene_cut)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     # one-GPU boxes: LSFA_BENCH_BACKEND=gloo LSFA_BENCH_ONE_DEVICE=1 puts every rank on cuda:0 and runs the final
@@ -87,7 +103,7 @@ def main():
             dist.init_process_group(backend)
     logging.basicConfig(level=logging.INFO, format='%(asctime)s %(message)s')
     logger = logging.getLogger('lsfa')
-    roidb = synthetic_roidb(args.clips, args.frames, args.height, args.width, cfg.TEST.KEY_FRAME_INTERVAL)
+    roidb = synthetic_roidb(args.clips, args.frames, args.height, args.width, cfg.TEST.KEY_FRAME_INTERVAL, cuts=args.synthetic_cuts)
     if args.prefix:
         arg_params, aux_params = load_param(args.prefix, args.epoch, process=True)
         net = resnet_v1_101_flownet_rfcn(cfg)

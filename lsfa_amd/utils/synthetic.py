@@ -5,26 +5,42 @@ produce (lib/rpn/rpn.py:33-52, lib/utils/image.py:202-263), without ffmpeg or a 
 A clip is a smooth random field plus three moving rectangles, translated by a per-clip
 global motion; `motion_vector` is what the compressed stream would carry after
 accumulation back to the key frame (image.py:53-54: negated, in stride-16 cells).
+
+cuts=(f1, f2, ..) (not in the reference's data: ImageNet-VID snippets have none) starts a new scene at each listed frame: field,
+rectangles and motion are redrawn from a seed of the scene's own.  The default () keeps every frame bit for bit.
 """
 import numpy as np
 import torch
 
 
 class SyntheticClip(object):
-    def __init__(self, clip_id, num_frames, height=600, width=1000, key_frame_interval=10, seed=0):
+    def __init__(self, clip_id, num_frames, height=600, width=1000, key_frame_interval=10, seed=0, cuts=()):
         self.clip_id, self.num_frames = clip_id, num_frames
         self.height, self.width = height, width
         self.key_frame_interval = key_frame_interval
-        rs = np.random.RandomState(seed * 100003 + clip_id * 1000)
-        self.motion = rs.uniform(-4, 4, 2)                       # px / frame, (dx, dy)
-        self.freq = rs.uniform(0.002, 0.02, (8, 2))
-        self.phase = rs.uniform(0, 2 * np.pi, (8, 3))
-        self.amp = rs.uniform(10, 30, (8, 3))
-        self.rects = [dict(x=rs.uniform(100, width - 300), y=rs.uniform(50, height - 250), w=rs.uniform(80, 260),
-                           h=rs.uniform(60, 200), v=rs.uniform(-6, 6, 2), color=rs.uniform(0, 255, 3))
-                      for _ in range(3)]
+        self.cuts = tuple(sorted(set(int(f) for f in cuts)))
+        if self.cuts and not (1 <= self.cuts[0] and self.cuts[-1] < num_frames and len(self.cuts) < 1000):
+            raise ValueError("SyntheticClip: cuts %r must lie in 1..%d" % (self.cuts, num_frames - 1))
+        # scene 0 is the clip's own; scene i starts at cuts[i - 1] and has the i-th seed behind the clip's (clips lie 1000 seeds apart)
+        self._scenes = [self._scene(np.random.RandomState(seed * 100003 + clip_id * 1000 + i)) for i in range(len(self.cuts) + 1)]
+        self._select(0)
         self.fh, self.fw = int(np.ceil(height / 16.0)), int(np.ceil(width / 16.0))
         self.frame_seg_len = num_frames
+
+    def _scene(self, rs):
+        width, height = self.width, self.height
+        motion = rs.uniform(-4, 4, 2)                            # px / frame, (dx, dy)
+        freq = rs.uniform(0.002, 0.02, (8, 2))
+        phase = rs.uniform(0, 2 * np.pi, (8, 3))
+        amp = rs.uniform(10, 30, (8, 3))
+        rects = [dict(x=rs.uniform(100, width - 300), y=rs.uniform(50, height - 250), w=rs.uniform(80, 260),
+                      h=rs.uniform(60, 200), v=rs.uniform(-6, 6, 2), color=rs.uniform(0, 255, 3))
+                 for _ in range(3)]
+        return motion, freq, phase, amp, rects
+
+    def _select(self, f):
+        """the scene frame f belongs to becomes self.motion, .freq, .phase, .amp, .rects"""
+        self.motion, self.freq, self.phase, self.amp, self.rects = self._scenes[sum(1 for c in self.cuts if c <= f)]
 
     def im_info(self):
         return np.array([[self.height, self.width, 1.0]], dtype=np.float32)
@@ -32,6 +48,7 @@ class SyntheticClip(object):
     def frame(self, f, device='cpu'):
         """`data`: float32 RGB (1,3,H,W), PIXEL_MEANS = 0 (config.py:171-176 for resnet-101)."""
         g = torch.Generator(device='cpu').manual_seed(1000 * self.clip_id + f)
+        self._select(f)
         ys = torch.arange(self.height, dtype=torch.float32, device=device).view(-1, 1)
         xs = torch.arange(self.width, dtype=torch.float32, device=device).view(1, -1)
         sx, sy = float(self.motion[0] * f), float(self.motion[1] * f)
@@ -59,6 +76,7 @@ class SyntheticClip(object):
     def motion_vector(self, f, key_f, device='cpu'):
         """(1,2,fh,fw): -(displacement accumulated since the key frame)/16 + N(0,0.05)."""
         g = torch.Generator(device='cpu').manual_seed(7000 + 1000 * self.clip_id + f)
+        self._select(f)
         d = (f - key_f) / 16.0
         mv = torch.empty((1, 2, self.fh, self.fw), dtype=torch.float32)
         mv[:, 0] = -float(self.motion[0]) * d
@@ -71,12 +89,12 @@ class SyntheticClip(object):
         return (4.0 * torch.randn((1, 3, self.fh, self.fw), generator=g)).to(device)
 
 
-def synthetic_roidb(num_clips, frames_per_clip, height=600, width=1000, key_frame_interval=10, seed=0):
+def synthetic_roidb(num_clips, frames_per_clip, height=600, width=1000, key_frame_interval=10, seed=0, cuts=()):
     """roidb entries shaped like ImageNetVID.gt_roidb()'s (lib/dataset/imagenet_vid.py) as far as
-    the test path reads them: frame_seg_len, frame_id, pattern + a clip generator."""
+    the test path reads them: frame_seg_len, frame_id, pattern + a clip generator.  cuts: SyntheticClip's, the same frames in every clip."""
     roidb, fid = [], 0
     for c in range(num_clips):
-        clip = SyntheticClip(c, frames_per_clip, height, width, key_frame_interval, seed)
+        clip = SyntheticClip(c, frames_per_clip, height, width, key_frame_interval, seed, cuts)
         roidb.append({'clip': clip, 'frame_seg_len': frames_per_clip, 'frame_id': fid,
                       'pattern': 'synthetic/%04d/%%06d' % c, 'height': height, 'width': width})
         fid += frames_per_clip

@@ -21,7 +21,13 @@ slower than the per-frame graph beyond the min-to-max spread the same run shows.
 --segment --levels L [--size WxH] runs the pyramid leg instead (profiles/r8/me_pyramid.txt): the segment form with the full search at
 R = 16 and R = 32 and with the pyramid search (L = 1: R = 16; L = 2: R = 8 and R = 16; --refine r, default 2) in the same alternating
 rounds, then each new launch alone: luma_pyramid, the top-level search, every refinement level.  The condition to read off: a pyramid
-configuration whose reach is at least 32 takes no longer per segment than the full search at R = 32 beyond the run's min-to-max spread."""
+configuration whose reach is at least 32 takes no longer per segment than the full search at R = 32 beyond the run's min-to-max spread.
+
+--segment --cut [--size WxH] runs the scene-cut leg instead (profiles/r10/me_cut.txt): the segment form without and with cut= (DESIGN.md
+"Scene cuts") at L = 0 / R = 16 and L = 2 / R = 8 in the same alternating rounds, then lsfa_mv_cut_score alone (both its launches) next to
+the luma launch of the same stack.  With --kernels-only the cut form is run a few times without timing (for a kernel trace that splits the
+two launches).  Nothing is gated: the figures to read off are the difference of the medians against the spreads, and the cut launches
+against the luma launch."""
 import argparse
 import json
 import os
@@ -194,6 +200,45 @@ def pyramid_leg(reps, time_limit, levels, refine):
     print(json.dumps(out))
 
 
+def cut_leg(reps, time_limit, kernels_only):
+    import signal
+
+    def too_long(signum, frame):
+        raise SystemExit('the scene-cut leg ran into its time limit of %d s' % time_limit)
+
+    signal.signal(signal.SIGALRM, too_long)
+    signal.alarm(time_limit)
+    F = 9
+    clip = SyntheticClip(0, F + 1, H, W)
+    stack = torch.stack([clip.frame_u8(f) for f in range(F + 1)]).unsqueeze(0).to(DEV)
+    out = dict(device=torch.cuda.get_device_name(0), frame='%dx%d' % (W, H), frames=F, clips=1, segments_per_graph=reps)
+    for levels, R in ((0, 16), (2, 8)):
+        plain = hip.SegmentMotionEstimator(W, H, frames=F, device=DEV, search=R, levels=levels)
+        cut = hip.SegmentMotionEstimator(W, H, frames=F, device=DEV, search=R, levels=levels, cut=dict())
+        want = [x.clone() for x in plain.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)]
+        got = cut.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)
+        torch.cuda.synchronize()
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(cut.rows, plain.rows)
+        if kernels_only:
+            for _ in range(20):
+                cut.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)
+            torch.cuda.synchronize()
+            continue
+        r = alternating([('segment', lambda: plain.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)),
+                         ('segment_cut', lambda: cut.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0))], reps)
+        a, b = r['segment'], r['segment_cut']
+        r['cut_costs_us'] = round(b['median'] - a['median'], 2)
+        r['spread_us'] = round(max(a['max'] - a['min'], b['max'] - b['min']), 2)
+        r['launches'] = dict(segment=levels + (4 if levels else 3), segment_cut=levels + (4 if levels else 3) + 2)
+        r['unmatched'] = cut.unmatched.cpu().tolist()
+        luma = cut._search.planes(0, 0, F + 1).unsqueeze(0)
+        r['alone'] = alternating([('mv_cut_score', lambda: hip.mv_cut_score(luma, cut.sad, out=(cut.intra, cut.unmatched))),
+                                  ('luma_u8_stack', lambda: hip.luma_u8(stack.view((F + 1) * H, W, 3), out=luma.view((F + 1) * H, W)))], reps)
+        out['L%d_R%d' % (levels, R)] = r
+    signal.alarm(0)
+    print(json.dumps(out))
+
+
 def non_key_frame(iters):
     from lsfa_amd.config.config import lsfa_test_config
     from lsfa_amd.symbols import params as P
@@ -229,12 +274,17 @@ def main():
     ap.add_argument('--time-limit', type=int, default=240, help='--segment: seconds after which the leg gives up')
     ap.add_argument('--levels', type=int, default=0, choices=(0, 1, 2), help='--segment: the pyramid leg with this many extra levels (0: the segment leg)')
     ap.add_argument('--refine', type=int, default=2, choices=(1, 2, 3), help='--levels: the refinement radius')
+    ap.add_argument('--cut', action='store_true', help='--segment: the scene-cut leg (the segment form without and with cut=)')
     ap.add_argument('--size', default=None, help='--segment: the frame size as WxH (default 1000x600)')
     args = ap.parse_args()
     if args.size:
         if not args.segment:
             ap.error('--size belongs to --segment')
         W, H = (int(v) for v in args.size.split('x'))
+    if args.cut:
+        if not args.segment:
+            ap.error('--cut belongs to --segment')
+        return cut_leg(args.segment_reps, args.time_limit, args.kernels_only)
     if args.segment and args.levels:
         return pyramid_leg(args.segment_reps, args.time_limit, args.levels, args.refine)
     if args.segment:
