@@ -16,7 +16,14 @@ needs only that frame's image, while the tail of a frame (Proposal's single-work
 select/sort/NMS, the R-FCN head, the detection NMS) keeps one or a few CUs busy.  Each captured
 graph therefore forks a second stream that computes the small-net feature of the NEXT frame while
 the current frame's tail runs, and the next replay consumes it.
+
+What the classes below share is stated once: `_Parts` warms up, captures, replays and closes a set of named launch
+sequences (FrameGraphs: key / cur; KeyLane: front / flow / agg / tail; KeyBank: front / flow) and says which capture stream
+each is captured on; `_taps_into` points an executor's tap dict at a caller's for the duration of a call (parity tests);
+`_FrameSlot` is the static inputs and detection outputs of one frame position, and where its scale is set (FrameGraphs and
+KeyLane are frame slots).  FramePipeline decides what runs on which stream and what waits for what.
 """
+import contextlib
 import os
 import sys
 
@@ -76,7 +83,97 @@ def _post_all(out, full, cfg, h, w, scale, thresh):
                               max_per_image=cfg.TEST.max_per_image, class_agnostic=cfg.CLASS_AGNOSTIC)
 
 
-class FrameGraphs(object):
+class _Parts(object):
+    """Named launch sequences ("parts") that are warmed up, captured into one hipGraph each and replayed - or, with use_graphs off,
+    simply called.  A part is a callable plus the label of the capture stream it is captured on: parts that replay on one stream (one
+    after the other) may share a capture stream, parts that replay side by side must not."""
+
+    def __init__(self, device, use_graphs, **parts):
+        """parts: name = (callable, capture-stream label)."""
+        self.device, self.use_graphs, self.parts = device, use_graphs, parts
+        self.graphs, self.streams = {}, {}
+
+    def _stream(self, label):
+        # Warm up and capture on streams of our own.  torch keeps one BLAS workspace per (handle, stream) and captured GEMMs bake its
+        # address in; with torch's default (shared) capture stream - or with two pool streams that are the same hipStream_t
+        # (streams.new_stream) - graphs replayed concurrently on different streams (FramePipeline) would share, and corrupt, split-K scratch.
+        if label not in self.streams:
+            self.streams[label] = streams.new_stream(self.device)
+        return self.streams[label]
+
+    def capture(self, warm, names):
+        """Run the parts named in `warm`, in that order, on the first capture stream (MIOpen find, workspaces, lazy attributes), then
+        capture the parts in `names`, in that order, each on the stream of its label (made when first needed)."""
+        if not (self.use_graphs and names):
+            return
+        s, main = self._stream(self.parts[names[0]][1]), torch.cuda.current_stream(self.device)
+        s.wait_stream(main)
+        with torch.cuda.stream(s):
+            for name in warm:
+                self.parts[name][0]()
+        main.wait_stream(s)
+        torch.cuda.synchronize(self.device)
+        for name in names:
+            fn, label = self.parts[name]
+            st = self._stream(label)
+            self.graphs[name] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graphs[name], stream=st):
+                fn()
+
+    def run(self, name):
+        """Replay the part (call it, without graphs).  A KeyError after close(): a closed helper has nothing to run."""
+        if self.use_graphs:
+            self.graphs[name].replay()
+        else:
+            self.parts[name][0]()
+
+    def close(self):
+        """Drop the captured graphs (and with them their private memory pools) and the parts, then hand back the capture streams.  The
+        device must be idle with respect to them (call after a synchronize / FramePipeline.join + sync)."""
+        self.graphs, self.parts = {}, {}
+        for st in self.streams.values():
+            streams.release(st)
+        self.streams = {}
+
+
+@contextlib.contextmanager
+def _taps_into(executor, taps):
+    """Point `executor.taps` at the dict `taps` for the duration (parity tests read the stage outputs there); None: leave it alone."""
+    if taps is None:
+        yield
+        return
+    saved, executor.taps = executor.taps, taps
+    try:
+        yield
+    finally:
+        executor.taps = saved
+
+
+class _FrameSlot(object):
+    """The static inputs and detection outputs of one frame position - what a captured graph reads a frame from and leaves its
+    detections in - with the scale and threshold the post-processing uses."""
+
+    def __init__(self, cfg, height, width, device, thresh, batch):
+        self.cfg, self.device = cfg, torch.device(device)
+        self.h, self.w, self.thresh, self.scale = height, width, thresh, 1.0
+        self.batch = B = int(batch)        # clips advancing in lock-step, one image of each per frame (BASELINE configs[2])
+        fh, fw = -(-height // 16), -(-width // 16)
+        z = lambda *s: torch.zeros(s, device=self.device, dtype=torch.float32)
+        self.data = z(B, 3, height, width)
+        self.data_key_old = z(B, 3, height, width)
+        self.feat_old = z(B, cfg.network.DFF_FEAT_DIM, fh, fw)
+        self.im_info = torch.tensor([[height, width, 1.0]] * B, device=self.device, dtype=torch.float32)
+        self._post_full, self.post_bufs = _alloc_post(B, cfg.dataset.NUM_CLASSES, cfg.TEST.RPN_POST_NMS_TOP_N, self.device)
+
+    def set_scale(self, im_scale):
+        self.scale = float(im_scale)
+        self.im_info[:, 2] = self.scale
+
+    def _post(self, out):
+        _post_all(out, self._post_full, self.cfg, self.h, self.w, self.scale, self.thresh)
+
+
+class FrameGraphs(_FrameSlot):
     def __init__(self, key_exec, cur_exec, cfg, height, width, device, thresh=1e-4, use_graphs=True, prefetch=True,
                  feat_shared=None, taps=False, batch=1, frames_by_table=False):
         """feat_shared: a caller-owned (1, DFF_FEAT_DIM, h, w) buffer the non-key graph reads the key feature
@@ -84,7 +181,7 @@ class FrameGraphs(object):
         taps=True (parity tests): the stage outputs of the last key / non-key frame stay readable in
         `key_taps` / `cur_taps` (+ the network outputs in `key_out` / `cur_out`); under hipGraph replay they
         are the graphs' static buffers, so read or clone them on the frame's stream before the next replay."""
-        self.key, self.cur, self.cfg = key_exec, cur_exec, cfg
+        self.key, self.cur = key_exec, cur_exec
         self.feat_shared = feat_shared
         # r6: a lane whose non-key frames run on channels-last maps takes the key feature channels-last (feat_shared_cl: the pipeline's hand-over
         # IS the transposing copy - set_key_feature - instead of a plain copy followed by a transposition in every pass)
@@ -92,30 +189,20 @@ class FrameGraphs(object):
         if feat_shared is not None and not prefetch and cur_exec is not None and cur_exec.cur_channels_last(cfg.network.DFF_FEAT_DIM):
             self.feat_shared_cl = torch.zeros((feat_shared.shape[0], feat_shared.shape[2], feat_shared.shape[3], feat_shared.shape[1]),
                                               device=feat_shared.device, dtype=torch.float32)
+        _FrameSlot.__init__(self, cfg, height, width, device, thresh, batch)
         self.want_taps = taps
         self.key_taps = self.cur_taps = self.key_out = self.cur_out = None
         self._small_valid = False      # small_cur holds the small-net feature of the frame cur_frame is about to get
-        self.device = torch.device(device)
         self.use_graphs = use_graphs
-        self.h, self.w = height, width
-        self.thresh = thresh
-        self.batch = B = int(batch)        # clips advancing in lock-step, one image of each per frame (BASELINE configs[2])
+        B, dev = self.batch, self.device
         fh, fw = -(-height // 16), -(-width // 16)
         dim = cfg.network.DFF_FEAT_DIM
-        dev = self.device
         z = lambda *s: torch.zeros(s, device=dev, dtype=torch.float32)
-        # static inputs
-        self.data = z(B, 3, height, width)
         # frames_by_table (a FramePipeline's segment lanes): cur_segment reads the frames where the caller left them - no staging copy
         self._use_tbl = bool(frames_by_table) and not prefetch
         self.data_tbl = hip.ImageTable(B, 3, height, width, dev).set([self.data[i] for i in range(B)]) if self._use_tbl else None
-        self.data_key_old = z(B, 3, height, width)
-        self.feat_old = z(B, dim, fh, fw)
         self.mv = z(B, 2, fh, fw)
         self.res = z(B, 3, fh, fw)
-        self.im_info = torch.tensor([[height, width, 1.0]] * B, device=dev, dtype=torch.float32)
-        R, ncls = cfg.TEST.RPN_POST_NMS_TOP_N, cfg.dataset.NUM_CLASSES
-        self._post_full, self.post_bufs = _alloc_post(B, ncls, R, dev)
         self.prefetch = prefetch and cfg.network.add_small_net
         self.data_next = z(B, 3, height, width)        # image of the frame after the current one
         # small-net feature (the image-only part of the fuse: small_net_channels wide) of the current / next non-key frame
@@ -123,9 +210,14 @@ class FrameGraphs(object):
         self.small_cur = z(B, sdim, fh, fw)
         self.small_next = z(B, sdim, fh, fw)
         self.side = streams.new_stream(dev) if self.prefetch else None
-        self.feat = None            # the key graph's output feature (static address once captured)
-        self.key_graph = self.cur_graph = None
-        self.scale = 1.0
+        self.feat = None            # the key part's output feature (static address once captured)
+        # both parts replay on the caller's stream, one after the other: one capture stream
+        self.parts = _Parts(dev, use_graphs, key=(self._key_seq, 'frame'), cur=(self._cur_seq, 'frame'))
+
+    @property
+    def last_taps(self):
+        """(taps, out) of the last non-key frame - what a FramePipeline's lane of this kind delivers."""
+        return self.cur_taps, self.cur_out
 
     def set_key_feature(self, feat):
         """A lane's copy of the key feature its next frames are served from (on the current stream): channels-last when the lane's frames run
@@ -136,9 +228,6 @@ class FrameGraphs(object):
             _stage_inputs([(self.feat_shared, feat)])
 
     # ---- the two launch sequences -------------------------------------------------------
-    def _post(self, out):
-        _post_all(out, self._post_full, self.cfg, self.h, self.w, self.scale, self.thresh)
-
     def _fork_small_next(self):
         """side stream: small-net feature of the next frame (reads data_next, writes small_next)."""
         main = torch.cuda.current_stream(self.device)
@@ -154,25 +243,19 @@ class FrameGraphs(object):
     def _key_seq(self):
         if self.prefetch:
             self._fork_small_next()
-        saved = self.key.taps
-        if self.want_taps:
-            self.key.taps = self.key_taps = {}
-        try:
+        self.key_taps = {} if self.want_taps else None
+        with _taps_into(self.key, self.key_taps):
             out = self.key.forward(data=self.data, im_info=self.im_info, data_key_old=self.data_key_old,
                                    feat_key_old=self.feat_old)
-        finally:
-            self.key.taps = saved
         self.key_out = out if self.want_taps else None
         self._post(out)
         if self.prefetch:
             self._join_small_next()
-        return out['choose_feat_output']
+        self.feat = out['choose_feat_output']
 
     def _cur_seq(self):
-        saved = self.cur.taps
-        if self.want_taps:
-            self.cur.taps = self.cur_taps = {}
-        try:
+        self.cur_taps = {} if self.want_taps else None
+        with _taps_into(self.cur, self.cur_taps):
             if self.prefetch:
                 self._fork_small_next()
                 out = self.cur.forward(data=self.data, im_info=self.im_info, feat_key=self.feat, motion_vector=self.mv,
@@ -180,8 +263,6 @@ class FrameGraphs(object):
             else:
                 out = self.cur.forward(data=self.data_tbl if self._use_tbl else self.data, im_info=self.im_info, feat_key=self.feat,
                                        motion_vector=self.mv, res_diff=self.res, feat_key_cl=self.feat_shared_cl)
-        finally:
-            self.cur.taps = saved
         self.cur_out = out if self.want_taps else None
         self._post(out)
         if self.prefetch:
@@ -210,7 +291,7 @@ class FrameGraphs(object):
         return self.post_bufs
 
     def capture(self, warmup=3, key=True, cur=True):
-        """Warm up (MIOpen find, workspaces, lazy attributes) on a side stream, then capture."""
+        """Warm up (key x warmup, then cur x warmup) and capture the two parts; without graphs only the key feature gets its buffer."""
         if self.feat_shared is not None:
             key = False
             self.feat = self.feat_shared
@@ -218,43 +299,18 @@ class FrameGraphs(object):
             if self.feat_shared is None:
                 self.feat = self._first_feat.clone()
             return
-        # Warm up and capture on a stream of our own.  torch keeps one BLAS workspace per (handle, stream) and
-        # captured GEMMs bake its address in; with torch's default (shared) capture stream — or with two pool
-        # streams that are the same hipStream_t (streams.new_stream) — graphs replayed concurrently on different
-        # streams (FramePipeline) would share, and corrupt, split-K scratch.
-        s = self._capture_stream = streams.new_stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            if key:
-                for _ in range(warmup):
-                    f = self._key_seq()
-                self.feat = f
-            if cur:
-                for _ in range(warmup):
-                    self._cur_seq()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        if key:
-            self.key_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.key_graph, stream=self._capture_stream):
-                self.feat = self._key_seq()
-        if cur:
-            self.cur_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.cur_graph, stream=self._capture_stream):
-                self._cur_seq()
+        names = [name for name, wanted in (('key', key), ('cur', cur)) if wanted]
+        self.parts.capture([name for name in names for _ in range(warmup)], names)
         if self.feat_shared is None:
             self.feat.copy_(self._first_feat)
         self._small_valid = False      # the warm-up replays left their own small-net feature in small_cur
 
     def close(self):
-        """Drop the captured graphs (and with them their private memory pools), then destroy the streams this object
-        created.  The device must be idle with respect to them (call after a synchronize / FramePipeline.join + sync)."""
-        self.key_graph = self.cur_graph = None
-        for name in ('side', '_capture_stream'):
-            st = getattr(self, name, None)
-            if st is not None:
-                streams.release(st)
-                setattr(self, name, None)
+        """Drop the captured graphs, then hand back the streams this object created (see _Parts.close for when that is allowed)."""
+        self.parts.close()
+        if self.side is not None:
+            streams.release(self.side)
+            self.side = None
 
     # ---- per-frame entry points ---------------------------------------------------------
     def key_frame(self, data, next_data=None):
@@ -264,10 +320,7 @@ class FrameGraphs(object):
         self.data.copy_(data)
         if self.prefetch:
             self.data_next.copy_(next_data if next_data is not None else data)
-        if self.use_graphs:
-            self.key_graph.replay()
-        else:
-            self.feat = self._key_seq()
+        self.parts.run('key')
         self._small_valid = self.prefetch and next_data is not None
         # becomes the "old key" state of the next key frame
         self.feat_old.copy_(self.feat)
@@ -285,13 +338,9 @@ class FrameGraphs(object):
                 self.small_cur.copy_(self.cur.small_net_feature(data))
             jobs.append((self.data_next, next_data if next_data is not None else data))
         _stage_inputs(jobs)
-        if self.use_graphs:
-            self.cur_graph.replay()
-        else:
-            self._cur_seq()
+        self.parts.run('cur')
         self._small_valid = self.prefetch and next_data is not None
         return self.post_bufs
-
 
     def cur_segment(self, frames):
         """The non-key frames of one segment in ONE pass, batch axis = frames x clips, frame-major (this instance was built with batch =
@@ -311,10 +360,7 @@ class FrameGraphs(object):
             self.data_tbl.set([data[b] for data, _, _ in frames for b in range(B)])
         elif self._use_tbl:      # frames the table cannot take went through the dense buffer: point the table at it
             self.data_tbl.set([self.data[i] for i in range(self.batch)])
-        if self.use_graphs:
-            self.cur_graph.replay()
-        else:
-            self._cur_seq()
+        self.parts.run('cur')
         return self._post_full
 
 
@@ -336,8 +382,9 @@ class KeyBank(object):
         self.data_tbl = hip.ImageTable(n, 3, height, width, device).set([self.data[i] for i in range(n)]) if self.by_table else None
         self.data_old_tbl = hip.ImageTable(n, 3, height, width, device).set([self.data_old[i] for i in range(n)]) if self.by_table else None
         self.conv_feat = self.flow_out = None
-        self.front_graph = self.flow_graph = None
         self.want_taps = taps
+        # FlowNet replays on another stream, beside the backbone: a capture stream each (BLAS workspace, see _Parts)
+        self.parts = _Parts(device, use_graphs, front=(self.front, 'key'), flow=(self.flow, 'flow'))
         E = torch.cuda.Event
         self.ev_front, self.ev_flow, self.ev_free = E(), E(), E()      # backbone done / FlowNet done / every slice copied out
 
@@ -362,140 +409,105 @@ class KeyBank(object):
                       [(self.data_old[i * nb:(i + 1) * nb], olds[i]) for i in range(self.G)])
 
     def capture(self, warmup=2):
-        if not self.use_graphs:
-            return
-        s = self._capture_stream = streams.new_stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.front()
-                self.flow()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        self.front_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.front_graph, stream=self._capture_stream):
-            self.front()
-        self._capture_stream_flow = streams.new_stream(self.device)
-        self.flow_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.flow_graph, stream=self._capture_stream_flow):
-            self.flow()
+        self.parts.capture(['front', 'flow'] * warmup, ['front', 'flow'])
 
     def close(self):
-        self.front_graph = self.flow_graph = None
-        for name in ('_capture_stream', '_capture_stream_flow'):
-            st = getattr(self, name, None)
-            if st is not None:
-                streams.release(st)
-                setattr(self, name, None)
-
-    def run_front(self):
-        self.front_graph.replay() if self.use_graphs else self.front()
-
-    def run_flow(self):
-        self.flow_graph.replay() if self.use_graphs else self.flow()
+        self.parts.close()
 
 
-class KeyLane(object):
+class KeyLane(_FrameSlot):
     """Static buffers and the captured parts of a key frame: `front` (backbone) and `flow` (FlowNet) need
     only images; `agg` (flow warp of the previous key feature x scale map, aggregation) produces the
     frame's feature; `tail` (RPN, Proposal, R-FCN head, detection post-processing) consumes it."""
 
     def __init__(self, key_exec, cfg, height, width, device, thresh, use_graphs, taps=False, batch=1):
-        self.key, self.cfg, self.device, self.use_graphs = key_exec, cfg, device, use_graphs
-        B = int(batch)
+        _FrameSlot.__init__(self, cfg, height, width, device, thresh, batch)
+        self.key, self.use_graphs = key_exec, use_graphs
         self.want_taps = taps
         self.taps = {}         # taps=True: stage outputs of this buffer set's last frame (static under replay)
         self.out = None
-        self.h, self.w, self.thresh, self.scale = height, width, thresh, 1.0
-        fh, fw = -(-height // 16), -(-width // 16)
-        z = lambda *s: torch.zeros(s, device=device, dtype=torch.float32)
-        self.data = z(B, 3, height, width)
-        self.data_key_old = z(B, 3, height, width)
-        self.feat_old = z(B, cfg.network.DFF_FEAT_DIM, fh, fw)
-        self.im_info = torch.tensor([[height, width, 1.0]] * B, device=device, dtype=torch.float32)
-        R, ncls = cfg.TEST.RPN_POST_NMS_TOP_N, cfg.dataset.NUM_CLASSES
-        self._post_full, self.post_bufs = _alloc_post(B, ncls, R, device)
-        self.conv_feat = self.flow_out = None
-        self.flow_graph = None
-        self.feat = None
-        self.front_graph = self.agg_graph = self.tail_graph = None
+        self.conv_feat = self.flow_out = self.feat = None
+        # FlowNet replays on another stream, beside the backbone: its own capture stream (BLAS workspace, see _Parts); the tail replays
+        # where FlowNet does (after it, same stream), so it may share that capture stream, as `agg` shares the backbone's
+        self.parts = _Parts(device, use_graphs, front=(self.front, 'key'), flow=(self.flow, 'flow'), agg=(self.agg, 'key'),
+                            tail=(self.tail, 'flow'))
         self.ev_front, self.ev_flow = torch.cuda.Event(), torch.cuda.Event()
 
-    def _tapped(self, fn):
-        """Run one part with the executor's tap dict pointed at this lane's (parity tests only)."""
-        if not self.want_taps:
-            return fn()
-        saved = self.key.taps
-        self.key.taps = self.taps
-        try:
-            return fn()
-        finally:
-            self.key.taps = saved
+    @property
+    def last_taps(self):
+        """(taps, out) of this buffer set's last key frame."""
+        return self.taps, self.out
+
+    def _tapped(self):
+        """The executor's tap dict pointed at this lane's while one part runs (parity tests only)."""
+        return _taps_into(self.key, self.taps if self.want_taps else None)
 
     def front(self):
-        self.conv_feat = self._tapped(lambda: self.key.key_backbone(self.data))
+        with self._tapped():
+            self.conv_feat = self.key.key_backbone(self.data)
 
     def flow(self):
         self.flow_out = self.key.key_flow(self.data, self.data_key_old)
 
     def agg(self):
-        self.feat = self._tapped(lambda: self.key.key_aggregate(self.conv_feat, self.flow_out[0], self.flow_out[1],
-                                                                self.feat_old))
+        with self._tapped():
+            self.feat = self.key.key_aggregate(self.conv_feat, self.flow_out[0], self.flow_out[1], self.feat_old)
 
     def tail(self):
-        cfg = self.cfg
-        out = self._tapped(lambda: self.key.key_heads(self.feat, self.im_info))
+        with self._tapped():
+            out = self.key.key_heads(self.feat, self.im_info)
         self.out = out if self.want_taps else None
-        _post_all(out, self._post_full, cfg, self.h, self.w, self.scale, self.thresh)
+        self._post(out)
 
     def capture(self, warmup=3):
-        if not self.use_graphs:
-            return
-        s = self._capture_stream = streams.new_stream(self.device)     # see FrameGraphs.capture
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.front()
-                self.flow()
-                self.agg()
-                self.tail()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        self.front_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.front_graph, stream=self._capture_stream):
-            self.front()
-        # FlowNet replays on another stream, beside the backbone: its own capture stream (BLAS workspace)
-        self._capture_stream_flow = streams.new_stream(self.device)
-        self.flow_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.flow_graph, stream=self._capture_stream_flow):
-            self.flow()
-        self.agg_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.agg_graph, stream=self._capture_stream):
-            self.agg()
-        # the tail replays where FlowNet does (after it, same stream), so it may share that capture stream
-        self.tail_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.tail_graph, stream=self._capture_stream_flow):
-            self.tail()
+        names = ['front', 'flow', 'agg', 'tail']
+        self.parts.capture(names * warmup, names)
 
     def close(self):
-        self.front_graph = self.flow_graph = self.agg_graph = self.tail_graph = None
-        for name in ('_capture_stream', '_capture_stream_flow'):
-            st = getattr(self, name, None)
-            if st is not None:
-                streams.release(st)
-                setattr(self, name, None)
+        self.parts.close()
 
-    def run_front(self):
-        self.front_graph.replay() if self.use_graphs else self.front()
 
-    def run_flow(self):
-        self.flow_graph.replay() if self.use_graphs else self.flow()
+def _pick_streams(layout, flow_stream, lanes, device):
+    """The work streams of a FramePipeline under `layout` (None: $LSFA_STREAM_LAYOUT or 'probe'; see FramePipeline.__init__):
+    -> (key stream, FlowNet stream or None, lane streams, every stream made here - the pipeline owns them -, the `layout_used` string)."""
+    want = 1 + (1 if flow_stream else 0) + lanes
+    layout = layout or os.environ.get('LSFA_STREAM_LAYOUT', 'probe')
+    if layout == 'probe':
+        chosen, aliased = streams.concurrent_streams(want, device)
+    elif layout == 'plain':
+        # LSFA_STREAM_PRIO (experiments): which of the streams are created with the device's greatest priority
+        prio = os.environ.get('LSFA_STREAM_PRIO', '')
+        roles = ['key'] + (['flow'] if flow_stream else []) + ['lanes'] * lanes
+        chosen, aliased = [streams.new_stream(device, high_priority=(r in prio.split(','))) for r in roles], []
+    elif layout == 'one-queue':
+        chosen, aliased = [streams.new_stream(device)], [(streams.new_stream(device), 0) for _ in range(want)]
+    else:
+        raise ValueError("FramePipeline: layout must be 'probe', 'plain' or 'one-queue', got %r" % (layout,))
+    s_key, rest = chosen[0], chosen[1:]
+    s_flow = rest.pop(0) if (flow_stream and rest) else None
+    flow_q = chosen.index(s_flow) if s_flow is not None else -1
+    # lanes without a hardware queue of their own: first the spare streams on the FlowNet stream's queue, last those on the key stream's
+    spare = [st for st, q in aliased if q == flow_q] + [st for st, q in aliased if q not in (flow_q, 0)] + \
+            [st for st, q in aliased if q == 0]
+    s_lane = [rest.pop(0) if rest else spare.pop(0) if spare else streams.new_stream(device) for _ in range(lanes)]
+    owned = list(chosen) + [st for st, _ in aliased]
+    owned += [st for st in s_lane if st not in owned]
+    used = '%s: %d concurrent stream(s) of %d wanted, FlowNet stream %s, lanes %s' % (
+        layout, len(chosen), want, 'own' if s_flow is not None else 'none (key stream)', ['own' if st in chosen else 'spare' for st in s_lane])
+    return s_key, s_flow, s_lane, owned, used
 
-    def run_agg(self):
-        self.agg_graph.replay() if self.use_graphs else self.agg()
 
-    def run_tail(self):
-        self.tail_graph.replay() if self.use_graphs else self.tail()
+def _ramp_steps(ramp, key_group):
+    """The sizes of the first passes of key fronts after the pipeline ran empty (True = (1, 2); a tuple = those sizes; $LSFA_RAMP = "2" /
+    "1,2" / "" overrides it: lab), clamped to 1 .. key_group; () = full groups from the start.
+    While the pipeline is empty (the first key frames of a clip, or after flush() / join()) nothing overlaps a pass of key_group fronts
+    and every lane waits for it: with a ramp the first pass after that is one front, the second a group of two, then full groups - the
+    first detections arrive after 3 ms instead of 10.  Off by default since the end of r4: small passes cost 1.4-1.8x per frame what a
+    pass of six does, and over a 20-interval region the ramp lost 4-6 % (3063 vs 3261 frames/s)."""
+    steps = (1, 2) if ramp is True else tuple(int(v) for v in ramp) if ramp else ()
+    if os.environ.get('LSFA_RAMP') is not None:
+        steps = tuple(int(v) for v in os.environ['LSFA_RAMP'].split(',') if v.strip())
+    return tuple(min(max(v, 1), key_group) for v in steps) if key_group > 2 else ()
 
 
 class FramePipeline(object):
@@ -584,49 +596,16 @@ class FramePipeline(object):
         self._bank_turn = 0
         self._bank_ready = []                        # [(bank, slot, image tensor)]: fronts of upcoming key frames already computed (the tensor is HELD: its
                                                      # storage cannot be freed and handed to another image at the same address while its front waits)
-        # ramp (True = (1, 2)): while the pipeline is empty (the first key frames of a clip, or after flush() / join()) nothing overlaps a
-        # pass of key_group fronts and every lane waits for it: with a ramp the first pass after that is one front, the second a group of
-        # two, then full groups - the first detections arrive after 3 ms instead of 10.  Off by default since the end of r4: small passes
-        # cost 1.4-1.8x per frame what a pass of six does, and over a 20-interval region the ramp lost 4-6 % (3063 vs 3261 frames/s).
-        # (ramp may also be the tuple of those first pass sizes; $LSFA_RAMP = "2" / "1,2" / "" overrides it: lab)
-        steps = (1, 2) if ramp is True else tuple(int(v) for v in ramp) if ramp else ()
-        if os.environ.get('LSFA_RAMP') is not None:
-            steps = tuple(int(v) for v in os.environ['LSFA_RAMP'].split(',') if v.strip())
-        self.ramp_steps = tuple(min(max(v, 1), self.key_group) for v in steps) if self.key_group > 2 else ()
-        self.ramp = bool(self.ramp_steps)
+        self.ramp_steps = _ramp_steps(ramp, self.key_group)       # the first pass sizes after the pipeline ran empty; () = off
         self._ramp_step = 0
         self.group_sizes = []                        # the sizes of the passes issued so far (diagnostics / tests)
         self._next_seg = 0
-        want = 1 + (1 if flow_stream else 0) + lanes
-        layout = layout or os.environ.get('LSFA_STREAM_LAYOUT', 'probe')
-        if layout == 'probe':
-            chosen, aliased = streams.concurrent_streams(want, dev)
-        elif layout == 'plain':
-            # LSFA_STREAM_PRIO (experiments): which of the streams are created with the device's greatest priority
-            prio = os.environ.get('LSFA_STREAM_PRIO', '')
-            roles = ['key'] + (['flow'] if flow_stream else []) + ['lanes'] * lanes
-            chosen, aliased = [streams.new_stream(dev, high_priority=(r in prio.split(','))) for r in roles], []
-        elif layout == 'one-queue':
-            chosen, aliased = [streams.new_stream(dev)], [(streams.new_stream(dev), 0) for _ in range(want)]
-        else:
-            raise ValueError("FramePipeline: layout must be 'probe', 'plain' or 'one-queue', got %r" % (layout,))
-        self.hw_queues = len(chosen)
-        self._owned_streams = list(chosen) + [st for st, _ in aliased]
-        self.s_key = chosen[0]
-        rest = chosen[1:]
-        self.s_flow = rest.pop(0) if (flow_stream and rest) else None
-        flow_q = chosen.index(self.s_flow) if self.s_flow is not None else -1
-        spare = [st for st, q in aliased if q == flow_q] + [st for st, q in aliased if q not in (flow_q, 0)] + \
-                [st for st, q in aliased if q == 0]
-        self.s_lane = [rest.pop(0) if rest else (spare.pop(0) if spare else streams.new_stream(dev))
-                       for _ in range(lanes)]
-        self.layout_used = '%s: %d concurrent stream(s) of %d wanted, FlowNet stream %s, lanes %s' % (
-            layout, len(chosen), want, 'own' if self.s_flow is not None else 'none (key stream)',
-            ['own' if st in chosen else 'spare' for st in self.s_lane])
+        self.s_key, self.s_flow, self.s_lane, self._owned_streams, self.layout_used = _pick_streams(layout, flow_stream, lanes, dev)
         if os.environ.get('LSFA_LOG_LAYOUT') == '1':
             sys.stderr.write('[lsfa] FramePipeline %dx%d streams: %s\n' % (height, width, self.layout_used))
         E = torch.cuda.Event
-        self.ev_in, self.ev_flow, self.ev_tail, self.ev_handover = E(), E(), E(), E()
+        # ev_in: a pass's images are in place (the FlowNet stream waits for it); ev_handover: so is the per-frame lanes' copy of the key feature
+        self.ev_in, self.ev_handover = E(), E()
         # A key frame's feature leaves its key lane right after `agg`: into one of key_group + 2 pool buffers, which is what the next key
         # frame's aggregation, the non-key lanes' copies and the caller's `feat` read.  The key lane (two alternate) is then only held by
         # its own tail; with the lanes copying out of the key lane itself the aggregations of a group advanced at the pace of the
@@ -645,7 +624,6 @@ class FramePipeline(object):
         # _handed[b]: events of the copies taken from key buffer b's current feature (key frame k + 2 overwrites it after them)
         self._seg_key, self._seg_buf, self._cur_key, self._lane_key = 0, None, 0, [-1] * len(self.seg_lanes)
         self._handed = [[] for _ in self._feat_pool]
-        self._seg_needs_handover = False
         self._held = []                              # non-key frames recorded but not yet queued
 
     # the state the serial FrameGraphs exposes under the same names
@@ -663,9 +641,8 @@ class FramePipeline(object):
 
     def set_scale(self, im_scale):
         self.scale = float(im_scale)
-        for g in self.klanes + self.lanes + self.seg_lanes:
-            g.scale = float(im_scale)
-            g.im_info[:, 2] = float(im_scale)
+        for slot in self.klanes + self.lanes + self.seg_lanes:
+            slot.set_scale(im_scale)
 
     def _all_streams(self):
         return [self.s_key] + self.s_lane + ([self.s_flow] if self.s_flow is not None else [])
@@ -678,8 +655,7 @@ class FramePipeline(object):
         torch.cuda.synchronize(self.device)
         for g in self.klanes + self.lanes + self.seg_lanes + [b for bs in self.banks.values() for b in bs]:
             g.close()
-        extra = [st for st in self.s_lane if st not in self._owned_streams]
-        for st in self._owned_streams + extra:
+        for st in self._owned_streams:
             streams.release(st)
         self._owned_streams = []
         self.captured = False
@@ -718,14 +694,10 @@ class FramePipeline(object):
         self._bank_ready = []
         self._ramp_step = 0
         lane, cfg = self.klanes[0], self.cfg
-        saved = self.key_exec.taps
-        if lane.want_taps:
-            self.key_exec.taps = self.first_taps = {}
-        try:
+        self.first_taps = {} if lane.want_taps else None
+        with _taps_into(self.key_exec, self.first_taps):
             conv_feat, _, _ = self.key_exec.key_front(data, None)
             out = self.key_exec.key_back(conv_feat, None, None, None, lane.im_info)
-        finally:
-            self.key_exec.taps = saved
         self.first_out = out if lane.want_taps else None
         if not hasattr(self, '_first_post'):
             self._first_full, self._first_post = _alloc_post(self.batch, cfg.dataset.NUM_CLASSES, cfg.TEST.RPN_POST_NMS_TOP_N,
@@ -746,9 +718,9 @@ class FramePipeline(object):
         self._set_lanes_feature(self._feat_latest)
         for s in self._all_streams():
             s.wait_stream(main)
-        for e in [self.ev_handover, self.ev_tail] + self.ev_feat + self.ev_lane + self.ev_tail_of:
+        for e in [self.ev_handover] + self.ev_feat + self.ev_lane + self.ev_tail_of:
             e.record(main)
-        self._seg_feat, self._seg_event, self._seg_needs_handover = self._feat_latest, None, False
+        self._seg_feat, self._seg_event = self._feat_latest, None
         self._seg_key += 1
         self._seg_buf, self._cur_key, self._lane_key, self._handed = None, self._seg_key, [-1] * len(self.seg_lanes), [[] for _ in self._feat_pool]
 
@@ -776,7 +748,6 @@ class FramePipeline(object):
         front for this frame, the fronts (backbone, FlowNet) of this frame and those G - 1 are computed in one pass (KeyBank) and the
         next G - 1 key_frame calls - which must hand over exactly those tensors - take theirs from the bank.  With fewer than G - 1
         images (the end of a clip) the group is that much smaller; without any the frame's front is computed alone, as with key_group = 1."""
-        bank, slot, group = None, -1, None
         # checked before ANYTHING is queued or counted: the call leaves no trace.  The front belongs to the tensor handed over in `upcoming` (held by
         # the bank) or to a view of the same storage at the same offset and shape.
         if self._bank_ready and not (self._bank_ready[0][2] is data or (self._bank_ready[0][2].data_ptr() == data.data_ptr()
@@ -785,58 +756,89 @@ class FramePipeline(object):
                              "order, or drop_fronts())")
         if not self.lookahead:
             self._issue_segment()
+        bank, slot, group = self._choose_group(data, upcoming)
+        b = self._nkey % 2                       # the key lane (two alternate) ...
+        j = self._nkey % len(self._feat_pool)    # ... and the pool buffer of this frame
+        self._nkey += 1
+        lane = self.klanes[b]
+        if slot < 0 or group is not None:
+            self._image_pass(lane, b, bank, group, data, ready)
+        self._own_part(lane, b, j, bank, slot, deliver, ready)
+        if self.lookahead:
+            self._issue_segment()                # the frames BEFORE this key frame, served from the previous feature
+        self._feat_latest, self._prev_key_data = self._feat_pool[j], data
+        self._seg_feat, self._seg_event, self._seg_buf = self._feat_pool[j], self.ev_feat[j], j
+        self._seg_key += 1
+        return lane.post_bufs
+
+    def _choose_group(self, data, upcoming):
+        """Host only, nothing queued: where this key frame's front comes from -> (bank, slot, group).  A front computed ahead: (its bank, its
+        slot, None).  Else a new pass is due, of `data` and as many of `upcoming` as the ramp, key_group and the bank sizes allow: (the
+        bank, 0, the pass's images), the other fronts announced in `_bank_ready`; or (None, -1, None): this frame's front alone."""
         if self._bank_ready:
             bank, slot, _ = self._bank_ready.pop(0)
-        b = self._nkey % 2
-        self._nkey += 1
-        lane, s = self.klanes[b], self.s_key
-        if bank is None:
-            cap = self.ramp_steps[self._ramp_step] if self._ramp_step < len(self.ramp_steps) else self.key_group
-            self._ramp_step += 1
-            g = min(cap, 1 + len(upcoming or ())) if self.banks else 1
-            g = max([n for n in self.banks if n <= g] or [1])         # (key_group > 6: not every size has a bank)
-            self.group_sizes.append(g)
-            del self.group_sizes[:-64]
-            if g >= 2:
-                self._bank_turn += 1
-                bank, group, slot = self.banks[g][self._bank_turn % len(self.banks[g])], [data] + list(upcoming[:g - 1]), 0
-                self._bank_ready = [(bank, i, group[i]) for i in range(1, g)]
-        # ---- the image-only part, when this call starts one: a pass of the bank (or this frame's front alone) on the key stream, FlowNet
-        #      beside it; nothing here waits for aggregations or tails, so passes run back to back
-        src = bank if slot >= 0 else lane
-        if slot < 0 or group is not None:
-            with torch.cuda.stream(s):
-                if ready is not None:
-                    s.wait_event(ready)
-                if slot < 0:
-                    # the key lane's own front: its static buffers are free once its previous frame (k - 2) is through tail and `deliver`
-                    s.wait_event(self.ev_tail_of[b])
-                    for t in (data, self._prev_key_data):
-                        t.record_stream(s)               # the caller may drop its reference right after this call
-                    _stage_inputs([(lane.data, data), (lane.data_key_old, self._prev_key_data)])
-                else:
-                    s.wait_event(bank.ev_free)           # the bank's previous group has taken all its slices
-                    # frame i of the group against its predecessor (the previous key frame for i = 0)
-                    olds = [self._prev_key_data] + group[:-1]
-                    for t in group + olds[:1]:
-                        t.record_stream(s)
-                    bank.set_images(group, olds)
-                if self.s_flow is not None:
-                    self.ev_in.record(s)
-                    with torch.cuda.stream(self.s_flow):
-                        self.s_flow.wait_event(self.ev_in)
-                        src.run_flow()
-                        src.ev_flow.record(self.s_flow)
-                    src.run_front()
-                    src.ev_front.record(s)
-                else:
-                    src.run_front()
-                    src.run_flow()
-                    src.ev_front.record(s)
-                    src.ev_flow.record(s)
-        # ---- this key frame's own part: its slice of the bank, aggregation, the feature into the pool - on the FlowNet / tail stream when
-        #      there is one (in order behind the FlowNet pass and the previous key frames' tails), so that the key stream is free for the next pass
-        sa = self.s_flow if self.s_flow is not None else s
+            return bank, slot, None
+        cap = self.ramp_steps[self._ramp_step] if self._ramp_step < len(self.ramp_steps) else self.key_group
+        self._ramp_step += 1
+        g = min(cap, 1 + len(upcoming or ())) if self.banks else 1
+        g = max([n for n in self.banks if n <= g] or [1])         # (key_group > 6: not every size has a bank)
+        self.group_sizes.append(g)
+        del self.group_sizes[:-64]
+        if g < 2:
+            return None, -1, None
+        self._bank_turn += 1
+        bank, group = self.banks[g][self._bank_turn % len(self.banks[g])], [data] + list(upcoming[:g - 1])
+        self._bank_ready = [(bank, i, group[i]) for i in range(1, g)]
+        return bank, 0, group
+
+    def _image_pass(self, lane, b, bank, group, data, ready):
+        """The image-only part, when a key_frame call starts one: a pass of the bank over `group` (or, bank None, the key lane's own front)
+        on the key stream, FlowNet beside it on its stream.  Nothing here waits for aggregations or tails, so passes run back to back.
+        Waits on the key stream: `ready` (the caller's inputs are complete); `ev_tail_of[b]` (own front: the lane's static buffers are free
+        once its previous frame, k - 2, is through tail and `deliver`) or `bank.ev_free` (the bank's previous group has taken all its
+        slices).  Records `ev_in` (the images are in place: the FlowNet stream waits for it) and the source's `ev_front` / `ev_flow`
+        (backbone maps / flow and scale map exist: _own_part waits for them before it reads either)."""
+        s, src = self.s_key, lane if bank is None else bank
+        with torch.cuda.stream(s):
+            if ready is not None:
+                s.wait_event(ready)
+            if bank is None:
+                s.wait_event(self.ev_tail_of[b])
+                for t in (data, self._prev_key_data):
+                    t.record_stream(s)               # the caller may drop its reference right after this call
+                _stage_inputs([(lane.data, data), (lane.data_key_old, self._prev_key_data)])
+            else:
+                s.wait_event(bank.ev_free)
+                # frame i of the group against its predecessor (the previous key frame for i = 0)
+                olds = [self._prev_key_data] + group[:-1]
+                for t in group + olds[:1]:
+                    t.record_stream(s)
+                bank.set_images(group, olds)
+            if self.s_flow is not None:
+                self.ev_in.record(s)
+                with torch.cuda.stream(self.s_flow):
+                    self.s_flow.wait_event(self.ev_in)
+                    src.parts.run('flow')
+                    src.ev_flow.record(self.s_flow)
+                src.parts.run('front')
+                src.ev_front.record(s)
+            else:
+                src.parts.run('front')
+                src.parts.run('flow')
+                src.ev_front.record(s)
+                src.ev_flow.record(s)
+
+    def _own_part(self, lane, b, j, bank, slot, deliver, ready):
+        """This key frame's own part: its slice of the bank into the key lane, `agg`, the feature into pool buffer j, `tail`, `deliver` - on the
+        FlowNet / tail stream when there is one (in order behind the FlowNet pass and the previous key frames' tails), so that the key
+        stream is free for the next pass.
+        Waits: `ready`; the source's `ev_front` and `ev_flow` (the maps `agg` reads exist); `ev_tail_of[b]` (this lane's previous frame,
+        k - 2, is through its tail and its `deliver`: the heads are done reading its feature, and whoever reads the lane's taps there -
+        tests - is done with the static buffers that the slice copies and `agg` overwrite); `_handed[j]` (the copies the non-key lanes took
+        from pool buffer j's previous occupant, key frame k - len(pool), are done).
+        Records: `bank.ev_free` after the group's last slice (the next pass may overwrite the bank); `ev_feat[j]` (the feature is in the
+        pool: the segment's lanes wait for it); `ev_tail_of[b]` (tail and `deliver` are queued: the lane's next frame may follow)."""
+        sa, src = self.s_flow if self.s_flow is not None else self.s_key, lane if slot < 0 else bank
         with torch.cuda.stream(sa):
             if ready is not None:
                 sa.wait_event(ready)
@@ -846,8 +848,6 @@ class FramePipeline(object):
                 # eager mode: the maps were allocated on the streams that produced them and are read here
                 for t in (src.conv_feat,) + tuple(src.flow_out):
                     t.record_stream(sa)
-            # this key lane's previous frame (k - 2) is through its tail and its `deliver`: the heads are done reading its feature, and whoever
-            # reads the lane's taps there (tests) is done with the static buffers that the copies from the bank / `agg` overwrite
             sa.wait_event(self.ev_tail_of[b])
             if slot >= 0:
                 # this frame's slice of the bank -> what the key lane's `agg` reads (static buffers under replay)
@@ -866,27 +866,17 @@ class FramePipeline(object):
                     lane.taps['backbone_feat'] = lane.conv_feat
             else:
                 _stage_inputs([(lane.feat_old, self._feat_latest)])   # the previous key frame's feature
-            lane.run_agg()
-            # out of the key lane: pool buffer j, once the copies taken from its previous occupant (key frame k - len(pool)) are done
-            j = (self._nkey - 1) % len(self._feat_pool)
+            lane.parts.run('agg')
             for e in self._handed[j]:
                 sa.wait_event(e)
             self._handed[j] = []
-            pooled = self._feat_pool[j]
-            _stage_inputs([(pooled, lane.feat)])
+            _stage_inputs([(self._feat_pool[j], lane.feat)])
             self.ev_feat[j].record(sa)
-            lane.run_tail()                      # heads + detections
+            lane.parts.run('tail')               # heads + detections
             if deliver is not None:
                 self.delivering = lane           # whose buffers `deliver` sees (tests read its taps)
                 deliver(lane.post_bufs)
-            self.ev_tail.record(sa)
             self.ev_tail_of[b].record(sa)
-        if self.lookahead:
-            self._issue_segment()                # the frames BEFORE this key frame, served from the previous feature
-        self._feat_latest, self._prev_key_data = pooled, data
-        self._seg_feat, self._seg_event, self._seg_needs_handover, self._seg_buf = pooled, self.ev_feat[j], True, j
-        self._seg_key += 1
-        return lane.post_bufs
 
     def cur_frame(self, data, motion_vector, res_diff, deliver=None, ready=None):
         """flag 2.  Recorded; queued on the next lane when the segment is issued (see the class
@@ -960,7 +950,6 @@ class FramePipeline(object):
                 self.ev_handover.record(s)
                 self._copied_out(s)
             self._cur_key = self._seg_key
-            self._seg_needs_handover = False
         for data, motion_vector, res_diff, deliver, ready in self._held:
             i = self._next
             self._next = (i + 1) % len(self.lanes)

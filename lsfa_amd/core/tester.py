@@ -246,8 +246,8 @@ def pred_eval_pipelined(gpu_id, key_predictor, cur_predictor, test_data, imdb, c
                 if flag == 0:
                     taps, out = dict(fp.first_taps), fp.first_out
                 else:
-                    taps = dict(lane.taps if hasattr(lane, 'front') else lane.cur_taps)
-                    out = lane.out if hasattr(lane, 'front') else lane.cur_out
+                    taps, out = lane.last_taps
+                    taps = dict(taps)
                 taps.update({k: v for k, v in (out or {}).items() if isinstance(v, torch.Tensor)})
                 names = sorted(k for k, v in taps.items() if isinstance(v, torch.Tensor) and v.is_floating_point())
                 vals = torch.stack([torch.stack([taps[k].double().abs().sum(), taps[k].double().sum()]) for k in names])

@@ -362,9 +362,7 @@ class Executor(object):
             self._flownet_prepare({k: _t(v, dev, f32) for k, v in arg.items()
                                    if k.startswith(('flow_conv1', 'conv', 'Convolution', 'deconv', 'upsample_flow')) and 'stage' not in k
                                    and not k.startswith('conv0')})
-            if sym.kind == 'batch':
-                pass
-            elif cfg.network.add_Nq_net:
+            if sym.kind == 'key' and cfg.network.add_Nq_net:
                 # Nq_net (:94-109): 3x3 1024 -> 256 + ReLU, 1x1 256 -> 16 + ReLU, 1x1 16 -> 1; the 16 / 1 output channels are padded to
                 # the kernels' 64-channel tiles with zero weights
                 w2, b2 = _pad_rows(W('Nq_conv2_weight'), W('Nq_conv2_bias'), 64)
@@ -372,7 +370,7 @@ class Executor(object):
                 self.nq = [(hip.SplitWeight(W('Nq_conv1_weight'), pieces=self.pieces), W('Nq_conv1_bias')),
                            (hip.SplitWeight(w2, real_cout=16, pieces=self.pieces), b2),
                            (hip.SplitWeight(w3, real_cout=1, real_cin=16, pieces=self.pieces), b3)]
-            elif cfg.network.add_Fgfa_net:
+            elif sym.kind == 'key' and cfg.network.add_Fgfa_net:
                 self.em = [(hip.SplitWeight(W('em_conv%d_weight' % i), pieces=self.pieces), W('em_conv%d_bias' % i)) for i in (1, 2, 3)]
         else:
             self.rnet_w = _t(arg['rnet_conv0_weight'].reshape(1024, 3), dev, f32)

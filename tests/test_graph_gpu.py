@@ -973,3 +973,69 @@ def test_frames_run_without_a_library_convolution(world, monkeypatch, dtype):
     assert bool(torch.isfinite(out10['choose_feat_output']).all())
     key.check_status()
     cur.check_status()
+
+
+def test_captured_parts_helper_alone():
+    """graphs._Parts on its own, two trivial parts (each adds a constant into its own 16-element tensor) on two capture-stream labels: the
+    warm-up runs each part exactly as often as the sequence names it (counted in the callable, and seen in the tensors: a capture runs
+    nothing); a replay leaves what a plain call leaves; close() hands both capture streams back, and a closed helper raises, never replays."""
+    from lsfa_amd.core import streams
+    from lsfa_amd.core.graphs import _Parts
+    dev = torch.device(DEV)
+    bufs = {'a': torch.zeros(16, device=dev), 'b': torch.zeros(16, device=dev)}
+    step = {'a': 1.0, 'b': 2.5}
+    calls = {}
+
+    def part(name):
+        def fn():
+            calls[name] = calls.get(name, 0) + 1
+            bufs[name].add_(step[name])
+        return fn
+
+    left = {}
+    for use_graphs in (True, False):
+        for t in bufs.values():
+            t.zero_()
+        calls.clear()
+        parts = _Parts(dev, use_graphs, a=(part('a'), 'one'), b=(part('b'), 'two'))
+        parts.capture(['a', 'b', 'a', 'b'], ['a', 'b'])
+        torch.cuda.synchronize()
+        if use_graphs:
+            assert calls == {'a': 3, 'b': 3}                    # twice each to warm up, once each under capture
+            for name, t in bufs.items():
+                assert t.tolist() == [2 * step[name]] * 16      # the capture itself ran nothing
+            handles = [st.cuda_stream for st in parts.streams.values()]
+            assert len(set(handles)) == 2 and all(h in streams._OWNED for h in handles)
+        else:
+            assert calls == {} and not parts.streams            # nothing to warm up or capture without graphs
+        for t in bufs.values():
+            t.zero_()
+        calls.clear()
+        parts.run('a')
+        parts.run('b')
+        torch.cuda.synchronize()
+        assert calls == ({} if use_graphs else {'a': 1, 'b': 1})
+        left[use_graphs] = {name: t.tolist() for name, t in bufs.items()}
+        parts.close()
+        if use_graphs:
+            assert not any(h in streams._OWNED for h in handles)
+        with pytest.raises(KeyError):
+            parts.run('a')
+    assert left[True] == left[False] == {name: [step[name]] * 16 for name in bufs}
+
+
+def test_set_scale_reaches_every_frame_slot(world):
+    """FramePipeline.set_scale goes through each frame slot's own set_scale: every key lane, per-frame lane and segment lane ends with the
+    scale in `scale` and in column 2 of `im_info`, height and width untouched (construction is enough: nothing is captured)."""
+    from lsfa_amd.core.graphs import FramePipeline
+    fp = FramePipeline(world['key'], world['cur'], world['cfg'], H, W, DEV, segment=2, key_group=2, lanes=2)
+    slots = fp.klanes + fp.lanes + fp.seg_lanes
+    assert (len(fp.klanes), len(fp.lanes), len(fp.seg_lanes)) == (2, 2, 2)
+    fp.set_scale(1.5)
+    assert fp.scale == 1.5
+    for slot in slots:
+        assert slot.scale == 1.5
+        info = slot.im_info.cpu()
+        assert info.shape[0] == slot.batch and info[:, 2].tolist() == [1.5] * slot.batch
+        assert info[:, 0].tolist() == [float(H)] * slot.batch and info[:, 1].tolist() == [float(W)] * slot.batch
+    fp.close()

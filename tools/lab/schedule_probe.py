@@ -31,10 +31,18 @@ def timed(label, fn):
     return wrapped
 
 
-graphs.KeyBank.run_front = timed('pass of fronts', graphs.KeyBank.run_front)
-graphs.KeyBank.run_flow = timed('FlowNet pass', graphs.KeyBank.run_flow)
-graphs.KeyLane.run_agg = timed('  aggregation', graphs.KeyLane.run_agg)
-graphs.KeyLane.run_tail = timed('  key tail', graphs.KeyLane.run_tail)
+# the parts of a key frame run through the captured-parts helper (graphs._Parts.run): label them by the object whose method the part is
+PARTS = {(graphs.KeyBank, 'front'): 'pass of fronts', (graphs.KeyBank, 'flow'): 'FlowNet pass',
+         (graphs.KeyLane, 'agg'): '  aggregation', (graphs.KeyLane, 'tail'): '  key tail'}
+_run = graphs._Parts.run
+
+
+def run_part(self, name):
+    label = PARTS.get((type(self.parts[name][0].__self__), name))
+    return timed(label, _run)(self, name) if label else _run(self, name)
+
+
+graphs._Parts.run = run_part
 graphs.FrameGraphs.cur_segment = timed('    segment pass', graphs.FrameGraphs.cur_segment)
 
 

@@ -31,7 +31,7 @@ def run(fp, pipelined):
             outs[f] = (bufs[0].clone(), bufs[1].clone())
         return deliver
     fp.first_frame(frames[0])
-    if not (fp.captured if pipelined else fp.key_graph is not None):
+    if not (fp.captured if pipelined else bool(fp.parts.graphs)):
         fp.capture()
     for f, kf in sched:
         if pipelined:
@@ -47,8 +47,10 @@ def run(fp, pipelined):
 def compare(name, a, b):
     bad = []
     for f, kf in sched:
-        n = int((a[f][0] != b[f][0]).sum())
-        if n or (a[f][1] != b[f][1]).any():
+        (da, ca), (db, cb) = a[f], b[f]
+        # a class's rows past its count are whatever an earlier frame left in the buffer: not part of the result
+        n = sum(int((da[j, :ca[j]] != db[j, :ca[j]]).sum()) for j in range(1, len(ca)))
+        if n or (ca != cb).any():
             bad.append((f, 'key' if f == kf else 'cur', n))
     print(name, 'mismatching frames:', bad if bad else 'none', flush=True)
 

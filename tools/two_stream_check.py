@@ -37,7 +37,7 @@ def run(n_streams, frames_total, which='cur'):
     for i in range(frames_total):
         k = i % n_streams
         with torch.cuda.stream(streams[k]):
-            (fgs[k].cur_graph if which == 'cur' else fgs[k].key_graph).replay()
+            fgs[k].parts.graphs[which].replay()
     torch.cuda.synchronize()
     return (time.time() - t0) / frames_total * 1e3
 
@@ -51,7 +51,7 @@ for ns in range(1, nstreams + 1):
         for i in range(10):
             k = i % ns
             with torch.cuda.stream(streams[k]):
-                (fgs[k].key_graph if i == 0 else fgs[k].cur_graph).replay()
+                fgs[k].parts.graphs['key' if i == 0 else 'cur'].replay()
     for _ in range(3): step()
     torch.cuda.synchronize(); t0 = time.time()
     for _ in range(20): step()
