@@ -615,10 +615,21 @@ def conv_by_kernel():
     return {k: {"calls": v[0], "gflop": round(v[1] / 1e9, 3), "mbytes": round(v[2] / 1e6, 3)} for k, v in _conv_flops["by_kernel"].items()}
 
 
-def _count_conv_launch(name, flops, nbytes):
-    if _conv_flops["count"]:
-        _conv_flops["bytes"] += nbytes
-        e = _conv_flops["by_kernel"].setdefault(name, [0, 0.0, 0.0])
+def _count_launch(name, flops, nbytes=0.0, pieces=3):
+    """THE counting entry: every wrapper calls it once per launch, and only while _conv_flops["count"] is set (so that a launch that is not
+    counted computes none of its arguments - the plan query behind a kernel's name least of all).  The launch's algorithmic FLOPs go into
+    the total and its piece form's share; with the kernel's name also its bytes and its by_kernel row (None: lsfa_conv_nhwc_fused_fwd,
+    which the roofline does not list)."""
+    c = _conv_flops
+    c["flops"] += flops
+    c["launches"] += 1
+    if pieces == 2:
+        c["flops_three_products"] += flops
+    elif pieces == 1:
+        c["flops_one_product"] += flops
+    if name is not None:
+        c["bytes"] += nbytes
+        e = c["by_kernel"].setdefault(name, [0, 0.0, 0.0])
         e[0] += 1
         e[1] += flops
         e[2] += nbytes
@@ -649,15 +660,21 @@ def conv_flops_one_product():
     return _conv_flops["flops_one_product"]
 
 
-def _count_conv(N, Ho, Wo, Cout, Cin, kh, kw, pieces=3, launches=1):
-    if _conv_flops["count"]:
-        f = 2.0 * N * Ho * Wo * Cout * Cin * kh * kw
-        _conv_flops["flops"] += f
-        _conv_flops["launches"] += launches
-        if pieces == 2:
-            _conv_flops["flops_three_products"] += f
-        elif pieces == 1:
-            _conv_flops["flops_one_product"] += f
+def round_up(c, m):
+    """c rounded up to a multiple of m: channel counts to the kernels' granularities (32 input channels, 64 output channels)"""
+    return -(-c // m) * m
+
+
+def conv_out_hw(H, W, kh, kw, stride=1, pad=(0, 0), dil=1):
+    """(Ho, Wo): the output grid of a convolution of an H x W map; pad = (pad_h, pad_w)"""
+    return tuple((n + 2 * p - dil * (k - 1) - 1) // stride + 1 for n, p, k in ((H, pad[0], kh), (W, pad[1], kw)))
+
+
+def _check_outputs(who, numel, **tensors):
+    """the tensors a convolution writes into or adds (None = not given): contiguous float32 of the output's size"""
+    for name, t in tensors.items():
+        if t is not None and (t.numel() != numel or not t.is_contiguous() or t.dtype != torch.float32):
+            raise LsfaError("%s: %s must be a contiguous float32 tensor of %d elements" % (who, name, numel))
 
 
 def conv_weight_kc(weight):
@@ -677,13 +694,12 @@ def conv_nhwc(x, w_kc, bias, kh, kw, stride=1, pad=0, dil=1, relu=False, out=Non
     Cout = w_kc.shape[0]
     if tuple(w_kc.shape) != (Cout, kh * kw, Cin):
         raise LsfaError("conv_nhwc: weight %s does not match (Cout, %d, %d)" % (tuple(w_kc.shape), kh * kw, Cin))
-    Ho, Wo = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1, (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    Ho, Wo = conv_out_hw(H, W, kh, kw, stride, (pad, pad), dil)
     if out is None:
         out = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    for name, t in (("out", out), ("residual", residual), ("out2", out2)):
-        if t is not None and (t.numel() != N * Ho * Wo * Cout or not t.is_contiguous() or t.dtype != torch.float32):
-            raise LsfaError("conv_nhwc: %s must be a contiguous float32 tensor of %d elements" % (name, N * Ho * Wo * Cout))
-    _count_conv(N, Ho, Wo, Cout, Cin, kh, kw)
+    _check_outputs("conv_nhwc", N * Ho * Wo * Cout, out=out, residual=residual, out2=out2)
+    if _conv_flops["count"]:
+        _count_launch(None, 2.0 * N * Ho * Wo * Cout * Cin * kh * kw)
     need = lib().lsfa_conv_nhwc_workspace_bytes(N, H, W, Cout, kh, kw, stride, pad, dil)
     ws = torch.empty(need, dtype=torch.uint8, device=x.device)
     _check(lib().lsfa_conv_nhwc_fused_fwd(_ptr(x), N, H, W, Cin, _ptr(w_kc), _ptr(bias), Cout, kh, kw, stride, pad, dil, int(relu), _ptr(residual),
@@ -1036,7 +1052,8 @@ def nchw_to_nhwc(x, c0=0, c=None, out=None, amax_out=None):
         raise LsfaError("nchw_to_nhwc: out must be a contiguous float32 %s tensor" % ((N, H, W, c),))
     if 'nhwc' in LAB_SKIP and out.data_ptr() in _lab_filled:
         return out
-    _lab_filled.add(out.data_ptr())
+    if LAB_SKIP:
+        _lab_filled.add(out.data_ptr())
     _check(lib().lsfa_nchw_to_nhwc(_ptr(x), N, C, H * W, c0, c, _ptr(out), _ptr(amax_out), _stream()), "lsfa_nchw_to_nhwc")
     return out
 
@@ -1090,49 +1107,55 @@ DEFAULT_PIECES = 3
 AMAX_SLOTS = 256
 
 
+def _fp16_exponent(amax):
+    """THE exponent rule of the fp16 two-piece form: amax (a float64 tensor of maxima: one per tensor or one per output channel) -> int32
+    exponents e with amax * 2^e in [2^13, 2^14); 0 for a zero or non-finite maximum (an all-zero padding channel), clamped to +-100"""
+    ok = torch.isfinite(amax) & (amax > 0)
+    e = torch.where(ok, 13 - torch.floor(torch.log2(torch.where(ok, amax, torch.ones_like(amax)))), torch.zeros_like(amax))
+    return e.clamp(-100, 100).to(torch.int32)
+
+
 class SplitWeight(object):
     """A convolution weight cut into `pieces` pieces per value and laid out in MFMA fragment order (lsfa_conv_weights); made once per
-    layer at bind time.  pieces = 2: the values are scaled by 2^w_exp so that the largest lands in [2^13, 2^14)."""
+    layer at bind time.  pieces = 2: the values are scaled by 2^w_exp so that the largest lands in [2^13, 2^14).
+    Every instance carries pieces, cout, cin, kh, kw, real_cout, real_cin, w_exp (0 unless one exponent scales the whole tensor), w_scale
+    (None unless each output channel has its own), frag (None only for pieces == 0) and w_kc (None unless pieces == 0)."""
 
-    def __init__(self, weight, real_cout=None, real_cin=None, into=None, pieces=None, per_channel_scale=True):
+    def __init__(self, weight, real_cout=None, real_cin=None, into=None, pieces=None, per_channel_scale=True, w_exp=None):
         """weight: (Cout, Cin, kh, kw) float32 CUDA tensor (the framework's layout).  real_cout / real_cin: the layer's own
-        channel counts when `weight` was zero-padded to the kernel's tile sizes (algorithmic FLOPs are counted on those)."""
+        channel counts when `weight` was zero-padded to the kernel's tile sizes (algorithmic FLOPs are counted on those).
+        into: the fragments' storage (a slice of a shared allocation); w_exp: the two-piece form's exponent when the caller knows it (one
+        shared by several weights: deconv_phase_weights) - then the tensor is not measured and carries no per-channel scale."""
         w_kc = _f32c(conv_weight_kc(weight), "weight")
         self.pieces = int(DEFAULT_PIECES if pieces is None else pieces)
         self.cout, self.cin, self.kh, self.kw = [int(v) for v in weight.shape]
         self.real_cout, self.real_cin = int(real_cout or self.cout), int(real_cin or self.cin)
+        self.w_exp, self.w_scale, self.frag, self.w_kc = 0, None, None, None
         if self.pieces == 0:
             # r5, the exact-fp32 evaluation (a REFERENCE mode for tests and one bench line, LSFA_CONV_PIECES=0): the weight stays fp32 in the
             # (Cout, taps, Cin) layout lsfa_conv_nhwc_fused_fwd reads; conv_split / conv_split_view dispatch on pieces == 0 (_conv_exact)
             if self.cin % 32 or self.cout % 64:
                 raise LsfaError("SplitWeight: Cin=%d must be a multiple of 32, Cout=%d of 64" % (self.cin, self.cout))
-            self.w_exp, self.frag, self.w_kc = 0, None, w_kc
+            self.w_kc = w_kc
             return
         need = lib().lsfa_conv_weight_bytes(self.cout, self.kh, self.kw, self.cin, self.pieces)
         if need == 0:
             raise LsfaError("SplitWeight: Cin=%d must be a multiple of 32, Cout=%d of 64, pieces=%d one of 1, 2, 3" % (self.cin, self.cout, self.pieces))
-        self.w_exp, self.w_scale = 0, None
         self.frag = torch.empty(need, dtype=torch.uint8, device=weight.device) if into is None else into
         if self.frag.numel() != need or not self.frag.is_contiguous():
             raise LsfaError("SplitWeight: `into` must be a contiguous uint8 tensor of %d bytes" % need)
-        if self.pieces == 2 and per_channel_scale:
+        if self.pieces == 2 and per_channel_scale and w_exp is None:
             # r5: one power of two per OUTPUT channel, from the channel's own maximum (a BatchNorm folded into trained weights spreads the
             # channels over many octaves: with one scale per tensor the small channels' lo pieces go subnormal).  An all-zero (padding)
             # channel gets exponent 0.
-            amax_c = weight.detach().abs().reshape(self.cout, -1).amax(1).double()
-            ok = torch.isfinite(amax_c) & (amax_c > 0)
-            e = torch.where(ok, 13 - torch.floor(torch.log2(torch.where(ok, amax_c, torch.ones_like(amax_c)))), torch.zeros_like(amax_c))
-            e = e.clamp(-100, 100).to(torch.int32).contiguous()
-            self.w_exp_pc = e
+            e = _fp16_exponent(weight.detach().abs().reshape(self.cout, -1).amax(1).double()).contiguous()
             self.w_scale = torch.ldexp(torch.ones(self.cout, dtype=torch.float32, device=weight.device), -e).contiguous()
             with torch.cuda.device(weight.device):
                 _check(lib().lsfa_conv_weights_pc(_ptr(w_kc), self.cout, self.kh, self.kw, self.cin, _ptr(e), _ptr(self.frag), _stream()),
                        "lsfa_conv_weights_pc")
             return
-        if self.pieces == 2:
-            amax = float(weight.abs().max().item())              # bind time: a host synchronisation is fine here
-            self.w_exp = 0 if not (amax > 0 and math.isfinite(amax)) else 13 - int(math.floor(math.log2(amax)))
-            self.w_exp = max(-100, min(100, self.w_exp))
+        if self.pieces == 2:      # one exponent for the tensor: the caller's, or from its maximum (bind time: a host synchronisation is fine here)
+            self.w_exp = int(_fp16_exponent(weight.detach().abs().max().double()).item() if w_exp is None else w_exp)
         with torch.cuda.device(weight.device):
             _check(lib().lsfa_conv_weights(_ptr(w_kc), self.cout, self.kh, self.kw, self.cin, self.pieces, self.w_exp, _ptr(self.frag), _stream()),
                    "lsfa_conv_weights")
@@ -1197,59 +1220,56 @@ def _conv_desc(x, sw, N, H, W, y_ptr, x_offset=0, lda=0, cin=None, ldy=0, bias=N
     d.Ho, d.Wo = grid
     d.out_H, d.out_W, d.out_sy, d.out_sx = view
     d.prof_tag, d.x_nchw = prof_tag, int(x_nchw)
-    d.in_scale, d.in_shift, d.w_scale = _ptr(in_scale), _ptr(in_shift), _ptr(getattr(sw, 'w_scale', None))
+    d.in_scale, d.in_shift, d.w_scale = _ptr(in_scale), _ptr(in_shift), _ptr(sw.w_scale)
     return d
 
 
 def _conv_launch(who, x, sw, N, H, W, y_ptr, **desc):
-    """lsfa_conv_fwd on the descriptor _conv_desc(x, sw, N, H, W, y_ptr, **desc) with its workspace, counted for bench.py's roofline"""
+    """lsfa_conv_fwd on the descriptor _conv_desc(x, sw, N, H, W, y_ptr, **desc) with its workspace.  Everything that goes through
+    lsfa_conv_fwd is counted for bench.py's roofline HERE: FLOPs on the layer's own channel counts; bytes: every operand once, on the
+    channels the launch reads and writes."""
     if sw.pieces == 2 and desc.get("amax_in") is None:
-        raise LsfaError("%s: a two-piece (fp16) weight needs amax_in" % who)
+        desc["amax_in"] = amax_partial(x)      # no producer left the map's maximum: measured here (the whole map bounds the channels a view reads)
     d = _conv_desc(x, sw, N, H, W, y_ptr, **desc)
     need = lib().lsfa_conv_workspace_bytes(ctypes.byref(d))
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
     if _conv_flops["count"]:
-        Ho = d.Ho if d.Ho > 0 else (H + 2 * d.pad_h - d.dil * (sw.kh - 1) - 1) // d.stride + 1
-        Wo = d.Wo if d.Wo > 0 else (W + 2 * d.pad_w - d.dil * (sw.kw - 1) - 1) // d.stride + 1
+        Ho, Wo = (d.Ho, d.Wo) if d.Ho > 0 else conv_out_hw(H, W, sw.kh, sw.kw, d.stride, (d.pad_h, d.pad_w), d.dil)
         outs = 1 + (1 if d.residual else 0) + (1 if d.y2 else 0)
         nbytes = 4.0 * N * H * W * d.Cin + 2.0 * sw.pieces * sw.cout * sw.kh * sw.kw * d.Cin + 4.0 * outs * N * Ho * Wo * sw.cout
-        _count_conv_launch(_plan_kernel_name(d), 2.0 * N * Ho * Wo * sw.real_cout * sw.real_cin * sw.kh * sw.kw, nbytes)
+        _count_launch(_plan_kernel_name(d), 2.0 * N * Ho * Wo * sw.real_cout * sw.real_cin * sw.kh * sw.kw, nbytes, sw.pieces)
     _check(lib().lsfa_conv_fwd(ctypes.byref(d), _ptr(ws), need, _stream()), who)
 
 
-def _conv_exact(x, sw, bias, stride, pad, dil, act, out, residual, out2, scale2, shift2, nchw, x_nchw, in_scale, in_shift):
+def _conv_exact(x, sw, bias, stride=1, pad=0, dil=1, act=0, out=None, residual=None, out2=None, scale2=None, shift2=None, nchw=False,
+                x_nchw=False, in_scale=None, in_shift=None):
     """conv_split's contract on the EXACT fp32 matrix instructions (lsfa_conv_nhwc_fused_fwd: v_mfma_f32_32x32x2_f32, every product an fp32
-    product, bitwise an fmaf chain) - a reference evaluation, not a fast path: what the channels-last kernel does not take (NCHW in / out,
-    the input's bn + ReLU at the cut, LeakyReLU, a second output that is only measured) is done by separate elementwise steps with the
-    same fp32 operations in the same order as the split kernels' epilogues."""
+    product, bitwise an fmaf chain) - a reference evaluation, not a fast path: ONE conv_nhwc call; what the channels-last kernel does not
+    take (NCHW in / out, the input's bn + ReLU at the cut, LeakyReLU, a second output that is only measured) is done by separate
+    elementwise steps around it, with the same fp32 operations in the same order as the split kernels' epilogues."""
     if x_nchw:
         x = x[:, :sw.cin].permute(0, 2, 3, 1).contiguous()
     if in_scale is not None:
         x = torch.relu(x * in_scale + in_shift)                       # max(v * scale + shift, 0): two roundings, like affine_relu4
-    if nchw:
-        res_cl = residual.permute(0, 2, 3, 1).contiguous() if residual is not None else None
-        y = conv_nhwc(x, sw.w_kc, bias, sw.kh, sw.kw, stride, pad, dil, relu=(act == 1), residual=res_cl)
-        if act == 2:
-            y = torch.where(y > 0, y, y * 0.1)
-        y = y.permute(0, 3, 1, 2).contiguous()
-        if out is not None:
-            out.copy_(y)
-            y = out
-        if out2 is not None:
-            out2.copy_(torch.relu(y * scale2.view(1, -1, 1, 1) + shift2.view(1, -1, 1, 1)))
-            return y, out2
+    if nchw and residual is not None:
+        residual = residual.permute(0, 2, 3, 1).contiguous()
+    whole = not nchw and act != 2      # the kernel writes the caller's tensors itself, the second output included
+    o2 = out2 if whole else None
+    y = conv_nhwc(x, sw.w_kc, bias, sw.kh, sw.kw, stride, pad, dil, relu=(act == 1), out=out if whole else None, residual=residual,
+                  out2=o2, scale2=None if o2 is None else scale2, shift2=None if o2 is None else shift2)
+    if whole:
         return y
-    want2 = out2 is not None
     if act == 2:
-        y = conv_nhwc(x, sw.w_kc, bias, sw.kh, sw.kw, stride, pad, dil, relu=False, out=None, residual=residual)
         y = torch.where(y > 0, y, y * 0.1)
-        if out is not None:
-            out.copy_(y)
-            y = out
-        return y
-    r = conv_nhwc(x, sw.w_kc, bias, sw.kh, sw.kw, stride, pad, dil, relu=(act == 1), out=out, residual=residual,
-                  out2=out2 if want2 else None, scale2=scale2 if want2 else None, shift2=shift2 if want2 else None)
-    return r
+    if nchw:
+        y = y.permute(0, 3, 1, 2).contiguous()
+    if out is not None:
+        out.copy_(y)
+        y = out
+    if nchw and out2 is not None:
+        out2.copy_(torch.relu(y * scale2.view(1, -1, 1, 1) + shift2.view(1, -1, 1, 1)))
+        return y, out2
+    return y
 
 
 @_on_tensor_device
@@ -1276,27 +1296,18 @@ def conv_split(x, sw, bias=None, stride=1, pad=0, dil=1, relu=False, out=None, r
         Ctot = Cin
     if Cin != sw.cin:
         raise LsfaError("conv_split: input has %d channels, the weight %d" % (Cin, sw.cin))
-    Cout, kh, kw = sw.cout, sw.kh, sw.kw
-    Ho, Wo = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1, (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    Cout, act = sw.cout, ((1 if relu else 0) if act is None else act)      # lsfa_conv_desc::act; `act` wins over relu=
+    Ho, Wo = conv_out_hw(H, W, sw.kh, sw.kw, stride, (pad, pad), dil)
     if out is None:
         out = torch.empty((N, Cout, Ho, Wo) if nchw else (N, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    for name, t in (("out", out), ("residual", residual), ("out2", out2)):
-        if t is not None and (t.numel() != N * Ho * Wo * Cout or not t.is_contiguous() or t.dtype != torch.float32):
-            raise LsfaError("conv_split: %s must be a contiguous float32 tensor of %d elements" % (name, N * Ho * Wo * Cout))
+    _check_outputs("conv_split", N * Ho * Wo * Cout, out=out, residual=residual, out2=out2)
     if sw.pieces == 0:
-        return _conv_exact(x, sw, bias, stride, pad, dil, (1 if relu else 0) if act is None else act, out, residual, out2, scale2, shift2, nchw,
-                           x_nchw, in_scale, in_shift)
-    if amax_in is None and sw.pieces == 2:
-        amax_in = amax_partial(x)
-    _count_conv(N, Ho, Wo, sw.real_cout, sw.real_cin, kh, kw, sw.pieces)
-    _conv_launch("lsfa_conv_fwd", x, sw, N, H, W, out.data_ptr(), lda=Ctot, ldy=Cout, bias=bias, stride=stride, pad=(pad, pad), dil=dil,
-                 act=(1 if relu else 0) if act is None else act, nchw=nchw, residual=residual, out2=out2, scale2=scale2, shift2=shift2,
-                 amax_in=amax_in, amax_out=amax_out, status=status, x_nchw=x_nchw, in_scale=in_scale, in_shift=in_shift)
+        return _conv_exact(x, sw, bias, stride, pad, dil, act, out=out, residual=residual, out2=out2, scale2=scale2, shift2=shift2, nchw=nchw,
+                           x_nchw=x_nchw, in_scale=in_scale, in_shift=in_shift)
+    _conv_launch("lsfa_conv_fwd", x, sw, N, H, W, out.data_ptr(), lda=Ctot, ldy=Cout, bias=bias, stride=stride, pad=(pad, pad), dil=dil, act=act,
+                 nchw=nchw, residual=residual, out2=out2, scale2=scale2, shift2=shift2, amax_in=amax_in, amax_out=amax_out, status=status,
+                 x_nchw=x_nchw, in_scale=in_scale, in_shift=in_shift)
     return out if out2 is None else (out, out2)
-
-
-def _pair_kernel_name(cm, cn):
-    return "conv_pair_kernel<%d, %d>" % (cm // 32, cn // 32)
 
 
 @_on_tensor_device
@@ -1314,9 +1325,9 @@ def conv_pair(x, sw3, residual, scale2, shift2, sw1, bias=None, out=None, out_z=
     if (sw3.kh, sw3.kw, sw1.kh, sw1.kw) != (1, 1, 1, 1) or sw3.cin != Cm or sw1.cin != C:
         raise LsfaError("conv_pair: two 1x1 convolutions Cm=%d -> C -> Cn, not %dx%d %d -> %d and %dx%d %d -> %d"
                         % (Cm, sw3.kh, sw3.kw, sw3.cin, C, sw1.kh, sw1.kw, sw1.cin, Cn))
-    if getattr(sw3, 'w_scale', None) is None or getattr(sw1, 'w_scale', None) is None:
-        if sw3.pieces == 2 and sw1.pieces == 2:
-            raise LsfaError("conv_pair: the weights must carry per-channel scales (SplitWeight(per_channel_scale=True))")
+    two = sw3.pieces == 2 and sw1.pieces == 2      # (any other piece count is refused by the library)
+    if two and (sw3.w_scale is None or sw1.w_scale is None):
+        raise LsfaError("conv_pair: the weights must carry per-channel scales (SplitWeight(per_channel_scale=True))")
     if amax_in is None:
         amax_in = amax_partial(_f32c(x, "x"))
     if out is None:
@@ -1332,17 +1343,14 @@ def conv_pair(x, sw3, residual, scale2, shift2, sw1, bias=None, out=None, out_z=
     ldz = out_z.stride(-2) if out_z.stride(-1) == 1 and out_z.dim() == 4 else Cn
     if not (residual.is_contiguous() and scale2.is_contiguous() and shift2.is_contiguous()):
         raise LsfaError("conv_pair: residual, scale2 and shift2 must be contiguous")
-    if _conv_flops["count"] and sw3.pieces == 2 and sw1.pieces == 2:
+    if _conv_flops["count"] and two:
         P = N * H * W
-        f = 2.0 * P * (Cm * C + C * Cn)
-        _conv_flops["flops"] += f
-        _conv_flops["launches"] += 1
-        _conv_flops["flops_three_products"] += f
         # each operand once: c2, the residual, the sum, z and both weight blocks (two fp16 pieces per weight)
-        _count_conv_launch(_pair_kernel_name(Cm, Cn), f, 4.0 * P * (Cm + 2 * C + Cn) + 4.0 * (Cm * C + C * Cn))
-    _check(lib().lsfa_conv_pair_fwd(x.data_ptr(), ldx, N, H, W, Cm, _ptr(amax_in), _ptr(sw3.frag), _ptr(getattr(sw3, 'w_scale', None)), sw3.pieces, C,
+        _count_launch("conv_pair_kernel<%d, %d>" % (Cm // 32, Cn // 32), 2.0 * P * (Cm * C + C * Cn),
+                      4.0 * P * (Cm + 2 * C + Cn) + 4.0 * (Cm * C + C * Cn), 2)
+    _check(lib().lsfa_conv_pair_fwd(x.data_ptr(), ldx, N, H, W, Cm, _ptr(amax_in), _ptr(sw3.frag), _ptr(sw3.w_scale), sw3.pieces, C,
                                     _ptr(residual), out.data_ptr(), ldy, _ptr(scale2), _ptr(shift2), _ptr(sw1.frag),
-                                    _ptr(getattr(sw1, 'w_scale', None)), sw1.pieces, Cn, _ptr(bias), out_z.data_ptr(), ldz, int(stride), int(nchw),
+                                    _ptr(sw1.w_scale), sw1.pieces, Cn, _ptr(bias), out_z.data_ptr(), ldz, int(stride), int(nchw),
                                     _ptr(amax_out_sum), _ptr(amax_out_z), _ptr(status), _stream()), "lsfa_conv_pair_fwd")
     return out, out_z
 
@@ -1366,9 +1374,7 @@ def conv_split_view(x, sw, bias, out, stride=1, pad=(0, 0), dil=1, act=0, cin=No
         raise LsfaError("conv_split_view: the weight has %d input channels, x offers [%d, %d) (of %d)" % (sw.cin, cin0, cin0 + cin, L))
     if c0 < 0 or c0 + sw.cout > out.shape[3] or out.shape[0] != N:
         raise LsfaError("conv_split_view: channels [%d, %d) do not fit out %s" % (c0, c0 + sw.cout, tuple(out.shape)))
-    kh, kw = sw.kh, sw.kw
-    Hc, Wc = (H + 2 * pad[0] - dil * (kh - 1) - 1) // stride + 1, (W + 2 * pad[1] - dil * (kw - 1) - 1) // stride + 1
-    Ho, Wo = grid if grid is not None else (Hc, Wc)
+    Ho, Wo = grid if grid is not None else conv_out_hw(H, W, sw.kh, sw.kw, stride, pad, dil)
     y0, x0, sy, sx = place if place is not None else (0, 0, 1, 1)
     Hout, Wout, Lout = out.shape[1], out.shape[2], out.shape[3]
     if y0 + (Ho - 1) * sy >= Hout or x0 + (Wo - 1) * sx >= Wout:
@@ -1376,17 +1382,13 @@ def conv_split_view(x, sw, bias, out, stride=1, pad=(0, 0), dil=1, act=0, cin=No
     if sw.pieces == 0:      # the exact-fp32 reference mode (_conv_exact): plain output grids only (the transposed convolutions keep three bf16 pieces)
         if grid is not None or place is not None or (Ho, Wo) != (Hout, Wout):
             raise LsfaError("conv_split_view: the exact-fp32 mode takes whole output grids only")
-        xin = x if (L == cin and cin0 == 0) else x[..., cin0:cin0 + cin].contiguous()
-        y = _conv_exact(xin, sw, bias, stride, pad[0], dil, act, None, None, None, None, None, False, False, None, None) if pad[0] == pad[1] else None
-        if y is None:
+        if pad[0] != pad[1]:
             raise LsfaError("conv_split_view: the exact-fp32 mode needs pad_h == pad_w")
-        out[..., c0:c0 + sw.cout] = y
+        xin = x if (L == cin and cin0 == 0) else x[..., cin0:cin0 + cin].contiguous()
+        out[..., c0:c0 + sw.cout] = _conv_exact(xin, sw, bias, stride, pad[0], dil, act)
         return out
-    if amax_in is None and sw.pieces == 2:
-        amax_in = amax_partial(x)          # the whole (N, H, W, L) map bounds its leading channels
     first = out.data_ptr() + 4 * ((y0 * Wout + x0) * Lout + c0)
     view = place is not None or (Ho, Wo) != (Hout, Wout)
-    _count_conv(N, Ho, Wo, sw.real_cout, sw.real_cin, kh, kw, sw.pieces)
     _conv_launch("lsfa_conv_fwd (view)", x, sw, N, H, W, first, x_offset=4 * cin0, lda=L, ldy=Lout, bias=bias, stride=stride, pad=pad, dil=dil, act=act,
                  amax_in=amax_in, amax_out=amax_out, status=status, grid=(Ho, Wo), view=(Hout if view else 0, Wout, sy, sx), prof_tag=1)
     return out
@@ -1410,23 +1412,14 @@ def deconv_phase_weights(wt, cin_pad=None, pieces=None):
         raise LsfaError("deconv_phase_weights: Cin=%d must be a multiple of 32 and Cout=%d of 64" % (cpad, cout))
     frag4 = torch.empty(4 * per, dtype=torch.uint8, device=wt.device)
     out = PhaseWeights()
-    # the four phases together hold every tap of wt exactly once: its maximum is each phase's bound
-    amax = float(wt.abs().max().item())
-    w_exp = 0 if (pieces != 2 or not (amax > 0 and math.isfinite(amax))) else max(-100, min(100, 13 - int(math.floor(math.log2(amax)))))
+    # the four phases together hold every tap of wt exactly once: its maximum is each phase's bound (one host synchronisation)
+    w_exp = int(_fp16_exponent(wt.detach().abs().max().double()).item()) if pieces == 2 else 0
     for py in (0, 1):
         for px in (0, 1):
             kys, kxs = ((3, 1) if py == 0 else (2, 0)), ((3, 1) if px == 0 else (2, 0))
             wp = torch.zeros((cout, cpad, 2, 2), device=wt.device, dtype=torch.float32)
             wp[:, :cin] = wt[:, :, kys, :][:, :, :, kxs].permute(1, 0, 2, 3)
-            sw = SplitWeight.__new__(SplitWeight)
-            sw.pieces, sw.w_exp = pieces, w_exp
-            sw.cout, sw.cin, sw.kh, sw.kw = cout, cpad, 2, 2
-            sw.real_cout, sw.real_cin = cout, cin
-            sw.frag = frag4[(py * 2 + px) * per:(py * 2 + px + 1) * per]
-            with torch.cuda.device(wt.device):
-                _check(lib().lsfa_conv_weights(_ptr(_f32c(conv_weight_kc(wp), "weight")), cout, 2, 2, cpad, pieces, w_exp, _ptr(sw.frag), _stream()),
-                       "lsfa_conv_weights")
-            out.append(sw)
+            out.append(SplitWeight(wp, real_cin=cin, into=frag4[len(out) * per:(len(out) + 1) * per], pieces=pieces, w_exp=w_exp))
     out.frag4, out.pieces, out.w_exp = frag4, pieces, w_exp
     return out
 
@@ -1451,12 +1444,10 @@ def deconv4x4s2_crop(x, sw4, bias, out, c0=0, act=0, amax_in=None, amax_out=None
         amax_in = amax_partial(x)
     need = lib().lsfa_deconv4x4s2_crop_workspace_bytes(N, Hi, Wi, cin, cout, Hc, Wc, sw4.pieces)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
-    for i, s in enumerate(sw4):      # four phases, ONE launch
-        _count_conv(N, (Hc + 1) // 2, (Wc + 1) // 2, s.real_cout, s.real_cin, 2, 2, sw4.pieces, launches=1 if i == 0 else 0)
-    if _conv_flops["count"]:
-        _count_conv_launch("conv_ring_kernel (the four phases of a stride-2 transposed convolution)",
-                           sum(2.0 * N * ((Hc + 1) // 2) * ((Wc + 1) // 2) * s.real_cout * s.real_cin * 4 for s in sw4),
-                           4.0 * N * Hi * Wi * cin + 4 * 2.0 * sw4.pieces * cout * 4 * cin + 4.0 * N * Hc * Wc * cout)
+    if _conv_flops["count"]:         # four phases, ONE launch
+        _count_launch("conv_ring_kernel (the four phases of a stride-2 transposed convolution)",
+                      sum(2.0 * N * ((Hc + 1) // 2) * ((Wc + 1) // 2) * s.real_cout * s.real_cin * 4 for s in sw4),
+                      4.0 * N * Hi * Wi * cin + 4 * 2.0 * sw4.pieces * cout * 4 * cin + 4.0 * N * Hc * Wc * cout, sw4.pieces)
     _check(lib().lsfa_deconv4x4s2_crop_fwd(_ptr(x), L, N, Hi, Wi, cin, _ptr(frags), sw4.pieces, sw4.w_exp, _ptr(amax_in), _ptr(bias), cout, act,
                                            out.data_ptr() + 4 * c0, Lout, Hc, Wc, _ptr(amax_out), _ptr(status), _ptr(ws), need, _stream()),
            "lsfa_deconv4x4s2_crop_fwd")

@@ -188,6 +188,14 @@ def _pad_rows(w, b, cout_to, cin_to=None):
     return wp, bp
 
 
+def _bn_fold(arg, aux, name, fix_gamma=False):
+    """(scale, shift) in float64 of an inference BatchNorm (eps 2e-5, the moving statistics); fix_gamma: gamma counts as 1 (resnet.py:151)"""
+    g, b = arg[name + '_gamma'].astype(np.float64), arg[name + '_beta'].astype(np.float64)
+    m, v = aux[name + '_moving_mean'].astype(np.float64), aux[name + '_moving_var'].astype(np.float64)
+    s = (np.ones_like(g) if fix_gamma else g) / np.sqrt(v + BN_EPS)
+    return s, b - m * s
+
+
 class _ResNetWeights(object):
     """Folded, cut and laid-out weights of a (prefix) pre-activation ResNet-101 (or its stem + stage 1): resnet.py:138-240."""
 
@@ -195,14 +203,7 @@ class _ResNetWeights(object):
         f32 = torch.float32
 
         def bn(name):
-            g = arg[name + '_gamma'].astype(np.float64)
-            if name.endswith('bn_data'):
-                g = np.ones_like(g)            # fix_gamma=True, resnet.py:151
-            b = arg[name + '_beta'].astype(np.float64)
-            m = aux[name + '_moving_mean'].astype(np.float64)
-            v = aux[name + '_moving_var'].astype(np.float64)
-            s = g / np.sqrt(v + BN_EPS)
-            return s, b - m * s
+            return _bn_fold(arg, aux, name, fix_gamma=name.endswith('bn_data'))
 
         def fold(w, s):
             return (w.astype(np.float64) * s.reshape(-1, 1, 1, 1)).astype(np.float32)
@@ -240,7 +241,7 @@ class _ResNetWeights(object):
                     # of the sampled columns is a 1x1 convolution over 9 * C "channels" ordered (tap, c) like lsfa_deform_im2col_cl's rows
                     ow, ob = dev(arg[p + 'conv2_offset_weight']), dev(arg[p + 'conv2_offset_bias'])
                     co = ow.shape[0]
-                    wp, bp = _pad_rows(ow, ob, -(-co // 64) * 64)
+                    wp, bp = _pad_rows(ow, ob, hip.round_up(co, 64))
                     d['off'], d['off_b'] = hip.SplitWeight(wp, real_cout=co, pieces=pieces), bp
                     w2t = dev(w2)
                     d['w2'] = hip.SplitWeight(w2t.permute(0, 2, 3, 1).reshape(w2t.shape[0], -1, 1, 1).contiguous(), pieces=pieces)
@@ -343,7 +344,7 @@ class Executor(object):
         w_ps = np.concatenate([wc, wx], 0).transpose(1, 0, 2).reshape(-1, 512)          # (49*D, 512)
         b_ps = np.concatenate([arg['rfcn_cls_bias'].reshape(self.ncls, G * G), arg['rfcn_bbox_bias'].reshape(self.nbox, G * G)], 0).T.reshape(-1)
         # as a 1x1 convolution of the own family: output channels padded to its 64-channel tiles (the padding columns are never read)
-        self.ps_ld = -(-w_ps.shape[0] // 64) * 64
+        self.ps_ld = hip.round_up(w_ps.shape[0], 64)
         wp, bp = _pad_rows(_t(w_ps.reshape(-1, 512, 1, 1), dev, f32), _t(b_ps, dev, f32), self.ps_ld)
         self.rfcn_sw, self.rfcn_b_ps = hip.SplitWeight(wp, real_cout=w_ps.shape[0], pieces=self.pieces), bp
         self.proposal = hip.ProposalOp(feature_stride=cfg.network.RPN_FEAT_STRIDE, scales=cfg.network.ANCHOR_SCALES,
@@ -396,22 +397,16 @@ class Executor(object):
         def split(w):
             return hip.SplitWeight(dev_t(w), pieces=self.pieces)
 
-        def bn_fold(name):        # (scale, shift) of an inference BatchNorm (eps 2e-5, fix_gamma=False: moving statistics at test time)
-            g, b = arg[name + '_gamma'].astype(np.float64), arg[name + '_beta'].astype(np.float64)
-            m, v = aux[name + '_moving_mean'].astype(np.float64), aux[name + '_moving_var'].astype(np.float64)
-            sc = g / np.sqrt(v + BN_EPS)
-            return sc, b - m * sc
-
         def last_conv(name):      # the convolution that produces cur_feat, with cur_feat_bn folded in
             w, b = arg[name + '_weight'].astype(np.float64), arg[name + '_bias'].astype(np.float64)
             if bn:
-                sc, sh = bn_fold('cur_feat_bn')
+                sc, sh = _bn_fold(arg, aux, 'cur_feat_bn')
                 w, b = w * sc.reshape(-1, 1, 1, 1), b * sc + sh
             return split(w), dev_t(b)
 
         self.cur_scale = (split(arg['cur_scale_weight']), dev_t(arg['cur_scale_bias'])) if net.small_net_scale_before_fuse else None
         if bn:
-            sc, sh = bn_fold('warp_conv_feat_bn')
+            sc, sh = _bn_fold(arg, aux, 'warp_conv_feat_bn')
             self.warp_bn = (dev_t(sc), dev_t(sh))
         if fuse == 'add':
             self.fuse_w, self.fuse_b = last_conv('fuse_reduce_add')
@@ -448,17 +443,15 @@ class Executor(object):
 
     # ---- dense helpers ---------------------------------------------------------------
     def _conv(self, x, sw, bias=None, stride=1, pad=0, dil=1, act=0, amax_in=None, amax_out=None, **kw):
-        """lsfa_conv_fwd on a channels-last map; the amax plumbing only exists for two-piece weights"""
+        """lsfa_conv_fwd on a channels-last map; the amax plumbing only exists for two-piece weights (which measure a map that comes without)"""
         if sw.pieces != 2:
             amax_in = amax_out = None
-        elif amax_in is None:
-            amax_in = hip.amax_partial(x)
         return hip.conv_split(x, sw, bias, stride, pad, dil, act=act, amax_in=amax_in, amax_out=amax_out, status=self.status, **kw)
 
     @staticmethod
     def _pairable(w3, w1):
         """what lsfa_conv_pair_fwd takes: two fp16 pieces with per-channel scales, 1x1, Cm -> 4 Cm -> Cn with Cm, Cn in {64, 128}"""
-        return w3.pieces == 2 and w1.pieces == 2 and getattr(w3, 'w_scale', None) is not None and getattr(w1, 'w_scale', None) is not None and \
+        return w3.pieces == 2 and w1.pieces == 2 and w3.w_scale is not None and w1.w_scale is not None and \
             (w3.kh, w3.kw, w1.kh, w1.kw) == (1, 1, 1, 1) and w3.cin in (64, 128) and w3.cout == 4 * w3.cin and w1.cin == w3.cout and w1.cout in (64, 128)
 
     def _resnet(self, x, net, stages, section):
@@ -490,37 +483,33 @@ class Executor(object):
             if first and u['stage'] == 4:
                 dilate = dilate * 2
             am_c1, am_c2, am_n = (carry[1] if carry is not None else S.new()), S.new(), S.new()
+            # this unit's bn1 + relu1 where conv1 (and a first unit's strided shortcut) cut the raw sum `a`: max(sum * scale + shift, 0), which only
+            # they read, is never stored
+            in_scale, in_shift = pre if pre is not None else (None, None)
             if carry is not None:  # conv1 + folded bn2 + relu2 came out of the previous unit's conv3 launch
                 c1, carry = carry[0], None
-            elif pre is None:
-                c1 = self._conv(a, u['w1'], u['b1'], act=1, amax_in=am_a, amax_out=am_c1)     # conv1 + folded bn2 + relu2
-            else:                  # ... on max(sum * bn1 scale + bn1 shift, 0), which only this convolution reads: never stored
-                c1 = self._conv(a, u['w1'], u['b1'], act=1, amax_in=am_a, amax_out=am_c1, in_scale=pre[0], in_shift=pre[1])
+            else:
+                c1 = self._conv(a, u['w1'], u['b1'], act=1, amax_in=am_a, amax_out=am_c1, in_scale=in_scale, in_shift=in_shift)   # conv1 + folded bn2 + relu2
             if u['dcn']:
                 # DeformableConvolution (sym_common.py:138-157): offsets, bilinear columns, contraction + folded bn3 + relu3.  Every column
                 # entry is an interpolation of c1 (zeros outside): max|col| <= max|c1|, so c1's scale serves the contraction
                 off = self._conv(c1, u['off'], u['off_b'], 1, ud, ud, amax_in=am_c1)
                 col = hip.deform_im2col_cl(c1, off, 3, 3, ud, 1, ud, P.NUM_DEFORMABLE_GROUP)
                 c2 = self._conv(col.view(c1.shape[0], c1.shape[1], c1.shape[2], -1), u['w2'], u['b2'], act=1, amax_in=am_c1, amax_out=am_c2)
-            else:
-                c2 = None
             # shortcut: 1x1 (stride) on relu1, or x
-            if first and pre is not None:      # the strided shortcut reads the same raw sum through the same bn1 + relu1
-                sc = self._conv(a, u['sc'], None, stride, amax_in=am_a, in_scale=pre[0], in_shift=pre[1])
-            else:
-                sc = self._conv(a, u['sc'], None, stride, amax_in=am_a) if first else x4
-            if c2 is None:
+            sc = self._conv(a, u['sc'], None, stride, amax_in=am_a, in_scale=in_scale, in_shift=in_shift) if first else x4
+            if not u['dcn']:
                 c2 = self._conv(c1, u['w2'], u['b2'], stride, ud, ud, act=1, amax_in=am_c1, amax_out=am_c2)   # conv2 + folded bn3 + relu3
-            # conv3 + shortcut add in place + the bn1 / relu1 the NEXT unit (or the tail) applies to the sum, as a second output
-            nxt = units[ui + 1]['bn1'] if ui + 1 < len(units) else net.bn1
-            # The tail feeds relu1 to a padded 3x3 (its zeros are not max(0 * s + t, 0)) and pool0 produces the first one: there the
-            # activated map is stored.  Everywhere else (32 of ResNet-101's 33 units) its readers are conv1 and, in a stage's first
-            # unit, the shortcut's strided 1x1, which apply bn1 + relu1 themselves: conv3 then writes the sum alone and only publishes max(relu1) for conv1's fp16 scale - a quarter less
-            # map traffic per unit (the sum read and written, the activated map written and read, were its four big streams).
-            lone = self.input_activation_at_cut and ui + 1 < len(units) and u['w1'].pieces != 3 and \
-                sc.numel() * 4 >= self.input_activation_min_bytes
-            pre = None
+            # conv3 + shortcut add in place + the bn1 / relu1 the NEXT unit (or the tail) applies to the sum
             nu = units[ui + 1] if ui + 1 < len(units) else None
+            nxt = nu['bn1'] if nu is not None else net.bn1
+            # The tail feeds relu1 to a padded 3x3 (its zeros are not max(0 * s + t, 0)) and pool0 produces the first one: there the
+            # activated map is stored, as conv3's second output.  Everywhere else (32 of ResNet-101's 33 units) its readers are conv1 and, in a
+            # stage's first unit, the shortcut's strided 1x1, which apply bn1 + relu1 themselves: conv3 then writes the sum alone and only
+            # publishes max(relu1) for conv1's fp16 scale - a quarter less map traffic per unit (the sum read and written, the activated map
+            # written and read, were its four big streams).
+            lone = self.input_activation_at_cut and nu is not None and u['w1'].pieces != 3 and sc.numel() * 4 >= self.input_activation_min_bytes
+            pre = None
             if nu is not None and u['stage'] <= self.pair_1x1 and self._pairable(u['w3'], nu['w1']):
                 # conv3 + shortcut add in place, then the next unit's bn1 + relu1 + conv1 on the tile the workgroup still holds, whatever `lone`
                 # says: the activated map is never stored, and a strided shortcut reads the sum through bn1 + relu1 itself (am_n is its scale)
@@ -528,17 +517,15 @@ class Executor(object):
                 x4, z = hip.conv_pair(c2, u['w3'], sc, nxt[0], nxt[1], nu['w1'], nu['b1'], out=sc, amax_in=am_c2, amax_out_sum=am_n,
                                       amax_out_z=am_z, status=self.status)
                 a, pre, carry = x4, nxt, (z, am_z)
-            elif nxt is not None and lone:
-                if u['w3'].pieces == 2:      # max(relu1) is the next conv1's fp16 scale; the one-piece (bf16) mode has no scale
-                    x4 = self._conv(c2, u['w3'], None, amax_in=am_c2, amax_out=am_n, out=sc, residual=sc, scale2=nxt[0], shift2=nxt[1])
-                else:
-                    x4 = self._conv(c2, u['w3'], None, out=sc, residual=sc)
-                a, pre = x4, nxt
-            elif nxt is not None:
-                x4, a = self._conv(c2, u['w3'], None, amax_in=am_c2, amax_out=am_n, out=sc, residual=sc, out2=torch.empty_like(sc),
-                                   scale2=nxt[0], shift2=nxt[1])
             else:
-                x4, a = self._conv(c2, u['w3'], None, amax_in=am_c2, amax_out=am_n, out=sc, residual=sc), None
+                store = nxt is not None and not lone
+                # scale2 / shift2 without out2 only publish max(relu1), the next conv1's fp16 scale: the one-piece (bf16) mode has no scale
+                scale2, shift2 = nxt if store or (lone and u['w3'].pieces == 2) else (None, None)
+                r = self._conv(c2, u['w3'], None, amax_in=am_c2, amax_out=am_n, out=sc, residual=sc, out2=torch.empty_like(sc) if store else None,
+                               scale2=scale2, shift2=shift2)
+                x4, a = r if store else (r, None)
+                if lone:
+                    a, pre = x4, nxt
             am_a = am_n
             if self.stage_taps is not None and (nu is None or nu['stage'] != u['stage']):      # the stage's sum (later units write other maps)
                 self.stage_taps['%s_stage%d' % (section, u['stage'])] = x4
@@ -562,14 +549,11 @@ class Executor(object):
         own['in_shift'] = torch.zeros(3, device=dev)
         for name in ('conv2', 'conv3', 'conv3_1', 'conv4', 'conv4_1', 'conv5', 'conv5_1', 'conv6', 'conv6_1'):
             own[name] = hip.SplitWeight(fw[name + '_weight'], pieces=pc)
-
-        def pad32(c):
-            return -(-c // 32) * 32
         for name in ('deconv5', 'deconv4', 'deconv3', 'deconv2'):
             wt = fw[name + '_weight']                                     # (Cin, Cout, 4, 4)
-            own[name] = hip.deconv_phase_weights(wt, cin_pad=pad32(wt.shape[0]), pieces=pc)
+            own[name] = hip.deconv_phase_weights(wt, cin_pad=hip.round_up(wt.shape[0], 32), pieces=pc)
         ws = fw['Convolution5_scale_weight']                              # (1024, 194, 1, 1)
-        wsp, _ = _pad_rows(ws, None, ws.shape[0], pad32(ws.shape[1]))
+        wsp, _ = _pad_rows(ws, None, ws.shape[0], hip.round_up(ws.shape[1], 32))
         own['scale'] = hip.SplitWeight(wsp, real_cin=ws.shape[1], pieces=pc)
         for name in ('Convolution1', 'Convolution2', 'Convolution3', 'Convolution4', 'Convolution5'):
             own[name] = fw[name + '_weight'].permute(0, 2, 3, 1).contiguous()      # (2, 3, 3, Cin)
@@ -586,15 +570,12 @@ class Executor(object):
         S = self._slots['flow'].begin()
 
         def cmap(h, w, c):      # a concatenated map with its channel count padded to a multiple of 32 (the padding stays zero)
-            return hip.zeros_f32((N, h, w, -(-c // 32) * 32), dev)      # (the padding channels are multiplied by zero weights: they must be finite)
-
-        def out_hw(h, w, k, stride, pad):
-            return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+            return hip.zeros_f32((N, h, w, hip.round_up(c, 32)), dev)      # (the padding channels are multiplied by zero weights: they must be finite)
 
         def conv(x, am_x, name, stride, pad, out=None, am_out=None, cin=None):
             """-> (out, its amax slots); a Concat map (`out` given) collects the maxima of all its producers in ONE slot row"""
             sw = o[name]
-            h, w = out_hw(x.shape[1], x.shape[2], sw.kh, stride, pad)
+            h, w = hip.conv_out_hw(x.shape[1], x.shape[2], sw.kh, sw.kw, stride, (pad, pad))
             if out is None:
                 out, am_out = torch.empty((N, h, w, sw.cout), device=dev, dtype=torch.float32), S.new()
             hip.conv_split_view(x, sw, fw[name + '_bias'], out, stride=stride, pad=(pad, pad), act=LEAKY, cin=cin, amax_in=am_x,
@@ -615,7 +596,7 @@ class Executor(object):
         r1 = hip.stem_conv(pc, o['c1_cur'], None, o['in_scale'], o['in_shift'], act=0)
         am_r1 = S.new()
         r1 = hip.stem_conv(pr, o['c1_ref'], fw['flow_conv1_bias'], o['in_scale'], o['in_shift'], out=r1, accum=r1, act=LEAKY, amax_out=am_r1)
-        h2, w2 = out_hw(r1.shape[1], r1.shape[2], 5, 2, 2)
+        h2, w2 = hip.conv_out_hw(r1.shape[1], r1.shape[2], 5, 5, 2, (2, 2))
         c5, am5 = cmap(h2, w2, 194), S.new()
         conv(r1, am_r1, 'conv2', 2, 2, out=c5, am_out=am5)                # r2 = c5[..., :128]
         r3, am_r3 = conv(c5, am5, 'conv3', 2, 2, cin=128)
@@ -648,15 +629,11 @@ class Executor(object):
 
     def _heads(self, conv_feat, im_info):
         """SliceChannel -> RPN -> Proposal -> R-FCN maps -> PSROI + average + softmax (:479-546)."""
-        cfg = self.cfg
-        A = cfg.network.NUM_ANCHORS
-        n, _, h, w = conv_feat.shape
         # both RPN convolutions on the matrix pipe straight from the NCHW map (the direct kernel's K-major operand form), then the per-anchor
         # softmax + the split into MultiProposal's two NCHW inputs
         logits = hip.conv_split(conv_feat, self.rpn_sw, self.rpn_b, x_nchw=True, status=self.status)
-        cls_prob, rpn_bbox = hip.rpn_softmax_split(logits, A)
+        cls_prob, rpn_bbox = hip.rpn_softmax_split(logits, self.cfg.network.NUM_ANCHORS)
         rois = self.proposal(cls_prob, rpn_bbox, im_info)
-        D = self.ncls + self.nbox
         # both R-FCN convolutions as ONE 1x1 convolution of the own family that writes the position-sensitive layout [h][w][bin][class | box]
         # directly: channels 512.. of the NCHW feature turned channels-last (one copy that also leaves their maximum), then lsfa_conv_fwd (cells
         # self.ps_ld floats apart)
@@ -664,12 +641,19 @@ class Executor(object):
         am = S.new()
         rows = hip.nchw_to_nhwc(conv_feat, 512, 512, amax_out=am)
         ps = self._conv(rows, self.rfcn_sw, self.rfcn_b_ps, amax_in=am)
+        return self._heads_tail(ps, rois, cls_prob, rpn_bbox)
+
+    def _heads_tail(self, ps, rois, cls_prob, rpn_bbox):
+        """what _heads and _heads_cl share once the RPN outputs and the position-sensitive map ps (n, h, w, ps_ld) exist: the taps in the
+        operators' layouts, PSROI pooling + average + softmax, the (B, -1, C) views"""
+        n, h, w, _ = ps.shape
         if self.taps is not None:
+            D = self.ncls + self.nbox
             nchw = ps[..., :49 * D].reshape(n, h * w, 49, D).permute(0, 3, 2, 1).reshape(n, D * 49, h, w)
             self.taps.update(rpn_cls_prob=cls_prob, rpn_bbox_pred=rpn_bbox, cls_map=nchw[:, :self.n_cls_ch],
                              box_map=nchw[:, self.n_cls_ch:])
         cls_p, bbox = hip.rfcn_head_ps_ld(ps, self.ps_ld, rois, h, w, self.ncls, self.nbox, 0.0625, 7, 7)
-        B = cfg.TEST.BATCH_IMAGES
+        B = self.cfg.TEST.BATCH_IMAGES
         return rois, cls_p.view(B, -1, cls_p.shape[1]), bbox.view(B, -1, bbox.shape[1])
 
     # ---- forward ---------------------------------------------------------------------
@@ -751,13 +735,18 @@ class Executor(object):
         with torch.no_grad():
             return self._key_heads(conv_feat, im_info)
 
-    def _pair_rows(self, first, second, amax_out):
-        """Concat(first, second) on the batch axis (:95, :133) as channels-last images: (2N, H, W, C); their maximum into amax_out"""
+    def _pair_net(self, first, second, layers):
+        """The Nq / embedding nets: Concat(first, second) on the batch axis (:95, :133) as channels-last images (2N, H, W, C), then `layers`
+        [(SplitWeight, bias)] - 1x1s and 3x3s at stride 1 with 'same' padding, a ReLU behind all but the last, which is written NCHW."""
+        S = self._slots['agg'].begin()
+        am = [S.new() for _ in layers]
         n, c, h, w = first.shape
         x = torch.empty((2 * n, h, w, c), device=first.device, dtype=torch.float32)
-        hip.nchw_to_nhwc(first, out=x[:n], amax_out=amax_out)
-        hip.nchw_to_nhwc(second, out=x[n:], amax_out=amax_out)
-        return x
+        hip.nchw_to_nhwc(first, out=x[:n], amax_out=am[0])
+        hip.nchw_to_nhwc(second, out=x[n:], amax_out=am[0])
+        for i, (sw, b) in enumerate(layers[:-1]):
+            x = self._conv(x, sw, b, 1, sw.kh // 2, 1, act=1, amax_in=am[i], amax_out=am[i + 1])
+        return self._conv(x, layers[-1][0], layers[-1][1], amax_in=am[-1], nchw=True)
 
     def _key_aggregate(self, conv_feat, flow, scale_map, feat_key_old):
         cfg = self.cfg
@@ -768,24 +757,15 @@ class Executor(object):
             n, _, h, w = warp.shape
             if cfg.network.add_Nq_net:
                 # Nq_net (:94-109) on Concat(warp, conv_feat): rows 0..n-1 weight the warped maps, n..2n-1 the current ones
-                S = self._slots['agg'].begin()
-                am0, am1, am2 = S.new(), S.new(), S.new()
-                x = self._pair_rows(warp, conv_feat, am0)
-                x = self._conv(x, self.nq[0][0], self.nq[0][1], 1, 1, 1, act=1, amax_in=am0, amax_out=am1)
-                x = self._conv(x, self.nq[1][0], self.nq[1][1], act=1, amax_in=am1, amax_out=am2)
                 # the last convolution (1 output channel, padded to 64) written NCHW: channel 0 of image r is logit row r, read in place
-                x = self._conv(x, self.nq[2][0], self.nq[2][1], amax_in=am2, nchw=True)
+                x = self._pair_net(warp, conv_feat, self.nq)
                 if self.taps is not None:
                     self._tap('nq_logits', x[:, 0:1].contiguous())
                 conv_feat = hip.aggregate_softmax2(warp, conv_feat, x, logit_row_stride=x.shape[1] * h * w)
             elif cfg.network.add_Fgfa_net:
                 # get_embednet on Concat(conv_feat, warp) (:118-135; note the order, :133): 1x1 1024 -> 512, 3x3 512 -> 512, 1x1 512 -> 2048
-                S = self._slots['agg'].begin()
-                am0, am1, am2 = S.new(), S.new(), S.new()
-                x = self._pair_rows(conv_feat, warp, am0)
-                x = self._conv(x, self.em[0][0], self.em[0][1], act=1, amax_in=am0, amax_out=am1)
-                x = self._conv(x, self.em[1][0], self.em[1][1], 1, 1, 1, act=1, amax_in=am1, amax_out=am2)
-                e = self._conv(x, self.em[2][0], self.em[2][1], amax_in=am2, nchw=True)
+                # rows 0..n-1 of the embedding belong to the current maps, n..2n-1 to the warped ones
+                e = self._pair_net(conv_feat, warp, self.em)
                 self._tap('embed', e)
                 conv_feat = hip.aggregate_cosine(warp, conv_feat, e[n:2 * n], e[0:n])
             else:
@@ -810,10 +790,6 @@ class Executor(object):
 
     def _small_net_feature(self, data, nchw, amax_out=None):
         net = self.cfg.network
-        if net.small_net_stride == 4 and self.fuse_type == 'add' and self.cur_scale is None:
-            img = hip.avgpool_nchw(data, 4)
-            s, am = self._resnet(img, self.small, 1, 'small')
-            return self._conv(s, self.fuse_w, self.fuse_b, 1, 1, 1, amax_in=am, amax_out=amax_out, nchw=nchw)
         img = hip.avgpool_nchw(data, 4 if net.small_net_stride == 4 else 2)      # resize_data (:213 / :219), pooling_convention 'full'
         s, am = self._resnet(img, self.small, self.small_stages, 'small')
         S = self._slots['small']                  # (the section _resnet began goes on)
@@ -839,9 +815,7 @@ class Executor(object):
         the R-FCN convolution), the small net's fuse convolution in its natural layout, lsfa_warp_bilinear_cl (the same bits as the NCHW
         kernel, + the maximum the R-FCN convolution's scale needs).  `conv_feat` in the outputs is the NCHW view of the same memory."""
         S = self._slots['heads'].begin()
-        feat_cl = d.get('feat_key_cl')                 # (B, H, W, C): a caller that hands the key feature over channels-last (FramePipeline does, as its
-        if feat_cl is None:                            #  hand-over copy) saves the per-pass transposition
-            feat_cl = hip.nchw_to_nhwc(d['feat_key'])
+        feat_cl = self._key_feature_cl(d)
         add_cl = self.small_net_feature(d['data'], nchw=False)
         self._tap('small_feat', add_cl.permute(0, 3, 1, 2))
         am = S.new()
@@ -849,30 +823,32 @@ class Executor(object):
         # the epilogue, before the addend
         conv_cl = hip.warp_bilinear_cl(feat_cl, d['motion_vector'], add_cl=add_cl, res=d['res_diff'], res_w=self.rnet_w, res_b=self.rnet_b,
                                        amax_out=am, amax_c0=512, bn=self.warp_bn)
-        rois, cls_prob, bbox_pred = self._heads_cl(conv_cl, am, d['im_info'])
+        return self._cur_outputs(d, *self._heads_cl(conv_cl, am, d['im_info']), conv_feat=conv_cl.permute(0, 3, 1, 2))
+
+    @staticmethod
+    def _cur_outputs(d, rois, cls_prob, bbox_pred, conv_feat):
+        """the non-key symbol's outputs (Group at :657) + the fused feature"""
         return {'data': d['data'], 'data_key': d.get('data_key'), 'data_key_old': d.get('data_key_old'),
                 'feat_key_old': d.get('feat_key_old'), 'rois_output': rois, 'cls_prob_reshape_output': cls_prob,
-                'bbox_pred_reshape_output': bbox_pred, 'conv_feat': conv_cl.permute(0, 3, 1, 2)}
+                'bbox_pred_reshape_output': bbox_pred, 'conv_feat': conv_feat}
+
+    @staticmethod
+    def _key_feature_cl(d):
+        """the key feature (B, H, W, C): a caller that hands it over channels-last (FramePipeline does, as its hand-over copy) saves the
+        per-pass transposition"""
+        feat_cl = d.get('feat_key_cl')
+        return feat_cl if feat_cl is not None else hip.nchw_to_nhwc(d['feat_key'])
 
     def _heads_cl(self, conv_cl, am, im_info):
         """_heads on a channels-last feature (N, H, W, 1024) whose maximum sits in `am`: both convolutions read their 512 channels in place."""
-        cfg = self.cfg
-        A = cfg.network.NUM_ANCHORS
         n, h, w, _ = conv_cl.shape
         logits = torch.empty((n, h, w, self.rpn_sw.cout), device=conv_cl.device, dtype=torch.float32)
         hip.conv_split_view(conv_cl, self.rpn_sw, self.rpn_b, logits, cin=512, status=self.status)      # (three exact bf16 pieces, or one in bf16 mode: no scale)
-        cls_prob, rpn_bbox = hip.rpn_softmax_split(logits, A)
+        cls_prob, rpn_bbox = hip.rpn_softmax_split(logits, self.cfg.network.NUM_ANCHORS)
         rois = self.proposal(cls_prob, rpn_bbox, im_info)
-        D = self.ncls + self.nbox
         ps = torch.empty((n, h, w, self.rfcn_sw.cout), device=conv_cl.device, dtype=torch.float32)
         hip.conv_split_view(conv_cl, self.rfcn_sw, self.rfcn_b_ps, ps, cin=512, cin0=512, amax_in=am, status=self.status)
-        if self.taps is not None:
-            nchw = ps[..., :49 * D].reshape(n, h * w, 49, D).permute(0, 3, 2, 1).reshape(n, D * 49, h, w)
-            self.taps.update(rpn_cls_prob=cls_prob, rpn_bbox_pred=rpn_bbox, cls_map=nchw[:, :self.n_cls_ch],
-                             box_map=nchw[:, self.n_cls_ch:])
-        cls_p, bbox = hip.rfcn_head_ps_ld(ps, self.ps_ld, rois, h, w, self.ncls, self.nbox, 0.0625, 7, 7)
-        B = cfg.TEST.BATCH_IMAGES
-        return rois, cls_p.view(B, -1, cls_p.shape[1]), bbox.view(B, -1, bbox.shape[1])
+        return self._heads_tail(ps, rois, cls_prob, rpn_bbox)
 
     def _forward_concat(self, d):
         """small_net_fuse_type concat / concatv1 / concatv2 (:247-271) on channels-last maps: fuse_reduce_c2 is a 3x3 convolution of the warped
@@ -884,9 +860,7 @@ class Executor(object):
         lsfa_channel_mean / lsfa_gate_apply, which also leaves the maximum the R-FCN convolution's scale needs."""
         fuse = self.fuse_type
         S = self._slots['fuse'].begin()
-        feat_cl = d.get('feat_key_cl')
-        if feat_cl is None:
-            feat_cl = hip.nchw_to_nhwc(d['feat_key'])
+        feat_cl = self._key_feature_cl(d)
         small = d.get('small_feat')        # c1 (NCHW) computed ahead by the caller, else computed here channels-last
         am_c1 = S.new()
         if small is None:
@@ -914,10 +888,7 @@ class Executor(object):
                 out = hip.gate_apply(y, gate, y, amax_out=am_out, amax_c0=512)
         if gate is not None:
             self._tap('gate', gate)
-        rois, cls_prob, bbox_pred = self._heads_cl(out, am_out, d['im_info'])
-        return {'data': d['data'], 'data_key': d.get('data_key'), 'data_key_old': d.get('data_key_old'),
-                'feat_key_old': d.get('feat_key_old'), 'rois_output': rois, 'cls_prob_reshape_output': cls_prob,
-                'bbox_pred_reshape_output': bbox_pred, 'conv_feat': out.permute(0, 3, 1, 2)}
+        return self._cur_outputs(d, *self._heads_cl(out, am_out, d['im_info']), conv_feat=out.permute(0, 3, 1, 2))
 
     def _forward_cur(self, d):
         cfg = self.cfg
@@ -934,7 +905,4 @@ class Executor(object):
         self._tap('small_feat', add)
         conv_feat = hip.warp_bilinear(d['feat_key'], d['motion_vector'], add=add, res=d['res_diff'], res_w=self.rnet_w, res_b=self.rnet_b,
                                       bn=self.warp_bn)
-        rois, cls_prob, bbox_pred = self._heads(conv_feat, d['im_info'])
-        return {'data': d['data'], 'data_key': d.get('data_key'), 'data_key_old': d.get('data_key_old'),
-                'feat_key_old': d.get('feat_key_old'), 'rois_output': rois, 'cls_prob_reshape_output': cls_prob,
-                'bbox_pred_reshape_output': bbox_pred, 'conv_feat': conv_feat}
+        return self._cur_outputs(d, *self._heads(conv_feat, d['im_info']), conv_feat=conv_feat)

@@ -1869,6 +1869,140 @@ def test_conv_counters_name_the_launch_plan_and_count_flops_and_bytes_once(hip):
         assert abs(v["gflop"] - v["calls"] * per_call / 1e9) < 1e-3 * per_call / 1e9
 
 
+def _counted(hip, call):
+    """one call with counting on -> (flops, launches, three-product share, one-product share, bytes, by_kernel)"""
+    hip.conv_flops_reset(True)
+    try:
+        call()
+        flops, launches = hip.conv_flops_read()
+        return flops, launches, hip.conv_flops_three_products(), hip.conv_flops_one_product(), hip.conv_bytes_read(), hip.conv_by_kernel()
+    finally:
+        hip.conv_flops_reset(False)
+
+
+def test_conv_counters_of_conv_pair(hip):
+    """one conv_pair launch on 135 pixels (one full 128-pixel tile and a partial one): both contractions' FLOPs, all of them on the
+    two-piece form; every operand's bytes once; the kernel's instantiation as its name"""
+    g = torch.Generator(device=DEV).manual_seed(5)
+    N, H, W, Cm, Cn = 1, 9, 15, 64, 64
+    C, P = 4 * Cm, N * H * W
+    x = torch.relu(torch.randn((N, H, W, Cm), device=DEV, generator=g))
+    res = torch.randn((N, H, W, C), device=DEV, generator=g)
+    s2, h2 = torch.rand(C, device=DEV, generator=g) + 0.5, torch.randn(C, device=DEV, generator=g) * 0.1
+    sw3 = hip.SplitWeight(torch.randn((C, Cm, 1, 1), device=DEV, generator=g) / Cm ** 0.5, pieces=2)
+    sw1 = hip.SplitWeight(torch.randn((Cn, C, 1, 1), device=DEV, generator=g) / C ** 0.5, pieces=2)
+    am = hip.amax_partial(x)
+    flops, launches, three, one, nbytes, by = _counted(hip, lambda: hip.conv_pair(x, sw3, res, s2, h2, sw1, amax_in=am))
+    want_f = 2.0 * P * (Cm * C + C * Cn)
+    want_b = 4.0 * P * (Cm + 2 * C + Cn) + 4.0 * (Cm * C + C * Cn)
+    assert launches == 1 and flops == want_f and three == want_f and one == 0.0
+    assert nbytes == want_b
+    assert by == {"conv_pair_kernel<2, 2>": {"calls": 1, "gflop": round(want_f / 1e9, 3), "mbytes": round(want_b / 1e6, 3)}}, by
+
+
+def test_conv_counters_of_the_transposed_convolution(hip):
+    """deconv4x4s2_crop: four phases, ONE launch, one by_kernel entry; FLOPs on the layer's own input channels, bytes on the padded ones"""
+    g = torch.Generator(device=DEV).manual_seed(6)
+    Cin, Cout, Hi, Wi, Hc, Wc, Lout, c0, pieces = 96, 128, 10, 16, 19, 32, 416, 256, 2
+    x = torch.randn((1, Hi, Wi, Cin), device=DEV, generator=g)
+    wt = torch.randn((Cin, Cout, 4, 4), device=DEV, generator=g) * 0.05
+    b = torch.randn(Cout, device=DEV, generator=g)
+    sws = hip.deconv_phase_weights(wt, pieces=pieces)
+    out = torch.zeros((1, Hc, Wc, Lout), device=DEV)
+    am = hip.amax_partial(x)
+    flops, launches, three, one, nbytes, by = _counted(hip, lambda: hip.deconv4x4s2_crop(x, sws, b, out, c0=c0, act=2, amax_in=am))
+    want_f = sum(2.0 * 1 * ((Hc + 1) // 2) * ((Wc + 1) // 2) * Cout * Cin * 4 for _ in range(4))
+    want_b = 4.0 * 1 * Hi * Wi * Cin + 8.0 * pieces * Cout * 4 * Cin + 4.0 * 1 * Hc * Wc * Cout
+    assert launches == 1 and flops == want_f and three == want_f and one == 0.0
+    assert nbytes == want_b
+    assert len(by) == 1, by
+    (name, v), = by.items()
+    assert "transposed convolution" in name
+    assert v == {"calls": 1, "gflop": round(want_f / 1e9, 3), "mbytes": round(want_b / 1e6, 3)}, by
+
+
+def test_conv_counters_of_conv_split_view(hip):
+    """conv_split_view between channel slices: FLOPs and bytes count the 64 channels read and the 64 written, not the maps' 128 and 192"""
+    import re
+    g = torch.Generator(device=DEV).manual_seed(7)
+    N, H, W, L, Lout, cin, cin0, cout, c0 = 1, 9, 15, 128, 192, 64, 32, 64, 64
+    x = torch.randn((N, H, W, L), device=DEV, generator=g)
+    sw = hip.SplitWeight(torch.randn((cout, cin, 3, 3), device=DEV, generator=g) * 0.05, pieces=2)
+    b = torch.randn(cout, device=DEV, generator=g)
+    out = torch.zeros((N, H, W, Lout), device=DEV)
+    am = hip.amax_partial(x)
+    flops, launches, three, one, nbytes, by = _counted(
+        hip, lambda: hip.conv_split_view(x, sw, b, out, pad=(1, 1), act=1, cin=cin, cin0=cin0, c0=c0, amax_in=am))
+    want_f = 2.0 * N * H * W * cout * cin * 9
+    want_b = 4.0 * N * H * W * cin + 2.0 * 2 * cout * 9 * cin + 4.0 * N * H * W * cout
+    assert launches == 1 and flops == want_f and three == want_f and one == 0.0
+    assert nbytes == want_b
+    assert len(by) == 1, by
+    (name, v), = by.items()
+    assert re.match(r"conv_(ring_kernel<|split_direct_kernel<)", name), name
+    assert v == {"calls": 1, "gflop": round(want_f / 1e9, 3), "mbytes": round(want_b / 1e6, 3)}, by
+    assert bool((out[..., :c0] == 0).all()) and bool((out[..., c0 + cout:] == 0).all()) and bool((out[..., c0:c0 + cout] != 0).any())
+
+
+def test_conv_counters_of_conv_nhwc(hip):
+    """conv_nhwc (the exact-fp32 evaluation): its FLOPs and one launch; no piece share, no bytes, no by_kernel entry"""
+    g = torch.Generator(device=DEV).manual_seed(8)
+    N, H, W, ci, co = 1, 9, 15, 32, 64
+    x = torch.randn((N, H, W, ci), device=DEV, generator=g)
+    w = torch.randn((co, ci, 3, 3), device=DEV, generator=g) * 0.05
+    b = torch.randn(co, device=DEV, generator=g)
+    flops, launches, three, one, nbytes, by = _counted(hip, lambda: hip.conv_nhwc(x, hip.conv_weight_kc(w), b, 3, 3, 2, 1, 1, relu=True))
+    Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+    assert launches == 1 and flops == 2.0 * N * Ho * Wo * co * ci * 9
+    assert three == 0.0 and one == 0.0
+    assert nbytes == 0 and by == {}
+
+
+_SPLIT_WEIGHT_ATTRS = ("pieces", "cout", "cin", "kh", "kw", "real_cout", "real_cin", "w_exp", "w_scale", "frag", "w_kc")
+
+
+def test_split_weight_is_one_shape_of_object(hip):
+    """every SplitWeight - whatever its piece count, scaling, or whether deconv_phase_weights made it - carries the same attributes:
+    w_scale is None unless the weight has per-channel scales, w_kc is None unless pieces == 0 (then frag is None); the four phase
+    weights are views of ONE allocation and share ONE exponent; the exponent rule is 13 - floor(log2(max|w|)), 0 for a zero weight"""
+    g = torch.Generator(device=DEV).manual_seed(9)
+    co, ci = 64, 32
+    w = torch.randn((co, ci, 1, 1), device=DEV, generator=g)
+    forms = {"exact": hip.SplitWeight(w, pieces=0), "bf16": hip.SplitWeight(w, pieces=1), "fp16 per channel": hip.SplitWeight(w, pieces=2),
+             "fp16 per tensor": hip.SplitWeight(w, pieces=2, per_channel_scale=False), "three bf16": hip.SplitWeight(w, pieces=3)}
+    wt = torch.randn((ci, co, 4, 4), device=DEV, generator=g)
+    for pieces in (2, 3):
+        ph = hip.deconv_phase_weights(wt, pieces=pieces)
+        assert len(ph) == 4 and ph.pieces == pieces and ph.frag4.numel() % 4 == 0
+        per = ph.frag4.numel() // 4
+        for i, sw in enumerate(ph):
+            forms["phase %d of %d pieces" % (i, pieces)] = sw
+            assert sw.frag.data_ptr() == ph.frag4.data_ptr() + i * per and sw.frag.numel() == per
+            assert sw.w_exp == ph.w_exp and (sw.cout, sw.cin, sw.kh, sw.kw, sw.pieces) == (co, ci, 2, 2, pieces)
+    for name, sw in forms.items():
+        for a in _SPLIT_WEIGHT_ATTRS:
+            assert hasattr(sw, a), (name, a)
+        assert (sw.w_scale is not None) == (name == "fp16 per channel"), name
+        assert (sw.w_kc is not None) == (name == "exact") and (sw.frag is None) == (name == "exact"), name
+        assert (sw.real_cout, sw.real_cin) == (co, ci), name
+    assert tuple(forms["fp16 per channel"].w_scale.shape) == (co,)
+    # the exponent rule: max|w| = 3.0 lies in [2, 4) -> 2^12 lifts it into [2^13, 2^14); zero has no exponent
+    three = torch.zeros((co, ci, 1, 1), device=DEV)
+    three[5, 7] = 3.0
+    zero = torch.zeros((co, ci, 1, 1), device=DEV)
+    assert hip.SplitWeight(three, pieces=2, per_channel_scale=False).w_exp == 12
+    assert hip.SplitWeight(zero, pieces=2, per_channel_scale=False).w_exp == 0
+    pc = hip.SplitWeight(three, pieces=2)
+    assert pc.w_exp == 0 and float(pc.w_scale[5]) == 2.0 ** -12 and float(pc.w_scale[4]) == 1.0
+    assert float(hip.SplitWeight(zero, pieces=2).w_scale.max()) == 1.0
+    t3, t0 = torch.zeros((ci, co, 4, 4), device=DEV), torch.zeros((ci, co, 4, 4), device=DEV)
+    t3[3, 2, 1, 0] = -3.0
+    p3, p0 = hip.deconv_phase_weights(t3, pieces=2), hip.deconv_phase_weights(t0, pieces=2)
+    assert p3.w_exp == 12 and all(s.w_exp == 12 for s in p3)
+    assert p0.w_exp == 0 and all(s.w_exp == 0 for s in p0)
+    assert hip.deconv_phase_weights(t3, pieces=3).w_exp == 0      # three bf16 pieces cut exactly: no scale
+
+
 def test_conv_fp16_form_takes_one_weight_scale_per_output_channel(hip):
     """r5 (VERDICT r4, weak point 2): a trained pre-activation ResNet's conv3 / shortcut rows follow its residual stream's channel
     magnitudes - 2^+-8 per channel with a few channels 2^14 above that (tests/test_parity_fullres_gpu.py::trained_like_batchnorm): 2^25 and
