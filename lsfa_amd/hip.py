@@ -144,6 +144,54 @@ def _tensor(who, what, t, dtype, shape, device=None):
     return t
 
 
+def _arrived(t):
+    return "%s %s on %s" % (tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t).__name__), getattr(t, 'device', None))
+
+
+def _input(who, what, t, shape, device=None, dtype=torch.float32):
+    """An operand the wrapper only reads: `_tensor` without the contiguity condition -> t, or its contiguous copy.  Outputs and in-place
+    buffers never come through here: a copy would receive the result in the caller's place."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != len(shape) or not (t.is_cuda if device is None else t.device == device) or \
+            any(not isinstance(w, str) and int(v) != w for v, w in zip(t.shape, shape)):
+        raise LsfaError("%s: %s must be a (%s) %s tensor on %s, got %s" %
+                        (who, what, ", ".join(str(w) for w in shape), dtype, device or "a CUDA device", _arrived(t)))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _vector(who, what, t, n, device, dtype=torch.float32):
+    """A per-channel operand or a weight the kernel reads as `n` consecutive values (a bias, a scale, a shift; in any shape): `dtype`, on
+    `device` -> t, or its contiguous copy; None stays None (the optional ones)"""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != device or t.numel() != n:
+        raise LsfaError("%s: %s must be a %s tensor of %d elements on %s, got %s" % (who, what, dtype, n, device, _arrived(t)))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _amax_row(who, what, t, device, measured=False):
+    """None, or a row of amax_slots(): AMAX_SLOTS contiguous int32 words on `device`.  measured: an `amax_in`, which may also be
+    amax_partial()'s float32 row (the same bits)"""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not (t.dtype == torch.int32 or (measured and t.dtype == torch.float32)) or t.device != device or \
+            tuple(t.shape) != (AMAX_SLOTS,) or not t.is_contiguous():
+        raise LsfaError("%s: %s must be a row of amax_slots()%s: a contiguous (%d,) int32 tensor on %s, got %s" %
+                        (who, what, " or amax_partial()'s float32 row" if measured else "", AMAX_SLOTS, device, _arrived(t)))
+    return t
+
+
+def _status_word(who, t, device):
+    """None, or a new_status() word: (4,) contiguous int32 on `device`"""
+    return None if t is None else _tensor(who, "status (a new_status() word)", t, torch.int32, (4,), device)
+
+
+def _given(who, what, v, n):
+    """a caller's tuple / list of `n` buffers"""
+    if not isinstance(v, (tuple, list)) or len(v) != n:
+        raise LsfaError("%s: %s must be a tuple of %d tensors, got %s" % (who, what, n, type(v).__name__))
+    return v
+
+
 def _on_tensor_device(fn):
     """Run an op with the device of its first tensor argument current, so that `_stream()` (the CURRENT
     stream of the CURRENT device) and the C side's per-device state belong to the tensors' device even
@@ -158,14 +206,6 @@ def _on_tensor_device(fn):
         with torch.cuda.device(dev):
             return fn(*args, **kw)
     return wrapped
-
-
-def _f32c(t, name):
-    if t is None:
-        return None
-    if t.dtype != torch.float32 or not t.is_cuda:
-        raise LsfaError("%s must be a float32 CUDA tensor (got %s on %s)" % (name, t.dtype, t.device))
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def _means(pixel_means):
@@ -183,7 +223,8 @@ def _resized(H, W, im_scale, stride):
 # ------------------------------------------------------------------------------------
 @_on_tensor_device
 def psroi_pool(data, rois, spatial_scale, output_dim, pooled_size, group_size, with_mapping=False):
-    data, rois = _f32c(data, "data"), _f32c(rois, "rois")
+    data = _input("psroi_pool", "data", data, ("N", "C", "H", "W"))
+    rois = _input("psroi_pool", "rois", rois, ("R", 5), data.device)
     N, C, H, W = data.shape
     R = rois.shape[0]
     out = torch.empty((R, output_dim, pooled_size, pooled_size), device=data.device, dtype=torch.float32)
@@ -196,8 +237,10 @@ def psroi_pool(data, rois, spatial_scale, output_dim, pooled_size, group_size, w
 @_on_tensor_device
 def rfcn_head(cls_map, box_map, rois, spatial_scale=0.0625, pooled_size=7, group_size=7, want_score=False,
               out=None):
-    cls_map, box_map, rois = _f32c(cls_map, "cls_map"), _f32c(box_map, "box_map"), _f32c(rois, "rois")
+    cls_map = _input("rfcn_head", "cls_map", cls_map, ("N", "Cc", "H", "W"))
     N, Cc, H, W = cls_map.shape
+    box_map = _input("rfcn_head", "box_map (a map like cls_map)", box_map, (N, "Cb", H, W), cls_map.device)
+    rois = _input("rfcn_head", "rois", rois, ("R", 5), cls_map.device)
     gg = group_size * group_size
     ncls, nbox = Cc // gg, box_map.shape[1] // gg
     R = rois.shape[0]
@@ -205,7 +248,9 @@ def rfcn_head(cls_map, box_map, rois, spatial_scale=0.0625, pooled_size=7, group
         cls_prob = torch.empty((R, ncls), device=rois.device, dtype=torch.float32)
         bbox_pred = torch.empty((R, nbox), device=rois.device, dtype=torch.float32)
     else:
-        cls_prob, bbox_pred = out
+        out = _given("rfcn_head", "out", out, 2)
+        cls_prob = _tensor("rfcn_head", "output buffer out[0] (cls_prob)", out[0], torch.float32, (R, ncls), rois.device)
+        bbox_pred = _tensor("rfcn_head", "output buffer out[1] (bbox_pred)", out[1], torch.float32, (R, nbox), rois.device)
     cls_score = torch.empty((R, ncls), device=rois.device, dtype=torch.float32) if want_score else None
     _check(lib().lsfa_rfcn_head_fwd(_ptr(cls_map), _ptr(box_map), _ptr(rois), N, H, W, R, ncls, nbox, spatial_scale, pooled_size, group_size,
                                     _ptr(cls_prob), _ptr(cls_score), _ptr(bbox_pred), _stream()), "lsfa_rfcn_head_fwd")
@@ -215,7 +260,8 @@ def rfcn_head(cls_map, box_map, rois, spatial_scale=0.0625, pooled_size=7, group
 @_on_tensor_device
 def rfcn_head_ps(ps_map, rois, ncls, nbox, spatial_scale=0.0625, pooled_size=7, group_size=7, want_score=False):
     """ps_map (N, H, W, group^2, ncls+nbox) float32 — see lsfa_rfcn_head_ps_fwd."""
-    ps_map, rois = _f32c(ps_map, "ps_map"), _f32c(rois, "rois")
+    ps_map = _input("rfcn_head_ps", "ps_map", ps_map, ("N", "H", "W", group_size * group_size, ncls + nbox))
+    rois = _input("rfcn_head_ps", "rois", rois, ("R", 5), ps_map.device)
     N, H, W = ps_map.shape[0], ps_map.shape[1], ps_map.shape[2]
     R = rois.shape[0]
     cls_prob = torch.empty((R, ncls), device=rois.device, dtype=torch.float32)
@@ -228,30 +274,41 @@ def rfcn_head_ps(ps_map, rois, ncls, nbox, spatial_scale=0.0625, pooled_size=7, 
 
 def _warp(name, cl, feat, flow, mul, add, res, res_w, res_b, bn, out, amax_out=None, amax_c0=0):
     """The four lsfa_warp_bilinear* entry points: `cl` picks the layout, `bn` = (scale, shift) the form with warp_conv_feat_bn."""
-    feat, flow = _f32c(feat, "feat_cl" if cl else "feat"), _f32c(flow, "flow")
-    mul, add, res = _f32c(mul, "mul"), _f32c(add, "add_cl" if cl else "add"), _f32c(res, "res")
+    flow = _input(name, "flow", flow, ("N", 2, "H", "W"))
     N, _, H, W = flow.shape
+    dev = flow.device
+    feat = _input(name, "feat_cl" if cl else "feat", feat, ("feat_n", H, W, "C") if cl else ("feat_n", "C", H, W), dev)
     feat_n, C = feat.shape[0], feat.shape[3 if cl else 1]
-    if cl and (tuple(feat.shape[1:3]) != (H, W) or (add is not None and tuple(add.shape) != (N, H, W, C))):
-        raise LsfaError("%s: feat_cl %s / add_cl %s do not match a (%d, 2, %d, %d) flow" % (
-            name, tuple(feat.shape), None if add is None else tuple(add.shape), N, H, W))
+    maps = (N, H, W, C) if cl else (N, C, H, W)
+    if mul is not None:
+        mul = _input(name, "mul", mul, maps, dev)
+    if add is not None:
+        add = _input(name, "add_cl" if cl else "add", add, maps, dev)
     res_c = 0
     if res is not None:
-        res_w, res_b = _f32c(res_w, "res_w").reshape(C, -1), _f32c(res_b, "res_b")
+        res = _input(name, "res", res, (N, "res_c", H, W), dev)
         res_c = res.shape[1]
+        if res_w is None or res_b is None:
+            raise LsfaError("%s: res needs res_w and res_b (rnet_conv0), got %s and %s" % (name, _arrived(res_w), _arrived(res_b)))
+        res_w, res_b = _vector(name, "res_w", res_w, C * res_c, dev), _vector(name, "res_b", res_b, C, dev)
+    if bn is not None:
+        if mul is not None:
+            raise LsfaError("%s: mul together with bn: the library has no such kernel" % name)
+        bn = _given(name, "bn", bn, 2)
+        if bn[0] is None or bn[1] is None:
+            raise LsfaError("%s: bn must be (scale, shift), got %s and %s" % (name, _arrived(bn[0]), _arrived(bn[1])))
+        bn_scale, bn_shift = _vector(name, "bn scale", bn[0], C, dev), _vector(name, "bn shift", bn[1], C, dev)
+    amax_out = _amax_row(name, "amax_out", amax_out, dev)
     if out is None:
-        out = torch.empty((N, H, W, C) if cl else (N, C, H, W), device=feat.device, dtype=torch.float32)
+        out = torch.empty(maps, device=feat.device, dtype=torch.float32)
+    else:
+        _tensor(name, "output buffer out", out, torch.float32, maps, dev)
     sym = "lsfa_warp_bilinear" + ("_bn" if bn is not None else "") + ("_cl" if cl else "")
     args = [_ptr(feat), feat_n, _ptr(flow), N, C, H, W]
     if bn is None and not cl:                     # `mul` is an argument of lsfa_warp_bilinear alone
         args.append(_ptr(mul))
     args += [_ptr(add), _ptr(res), res_c, _ptr(res_w), _ptr(res_b)]
     if bn is not None:
-        bn_scale, bn_shift = _f32c(bn[0], "bn scale"), _f32c(bn[1], "bn shift")
-        if mul is not None:
-            raise LsfaError("%s: mul together with bn: the library has no such kernel" % name)
-        if bn_scale.numel() != C or bn_shift.numel() != C:
-            raise LsfaError("%s: bn scale / shift must have %d elements" % (name, C))
         args += [_ptr(bn_scale), _ptr(bn_shift)]
     args.append(_ptr(out))
     if cl:
@@ -280,16 +337,17 @@ def warp_bilinear_cl(feat_cl, flow, add_cl=None, res=None, res_w=None, res_b=Non
 def channel_mean(x1, x2=None, out=None):
     """lsfa_channel_mean: per-image channel means of channels-last maps, (N, H, W, C1) [and (N, H, W, C2) read as the concatenation
     [x1 | x2] without storing it] -> (N, C1 + C2).  Deterministic; the order is documented in include/lsfa_hip.h."""
-    x1, x2 = _f32c(x1, "x1"), _f32c(x2, "x2")
+    x1 = _input("channel_mean", "x1", x1, ("N", "H", "W", "C1"))
     N, H, W, C1 = x1.shape
     C2 = 0
     if x2 is not None:
-        if tuple(x2.shape[:3]) != (N, H, W):
-            raise LsfaError("channel_mean: x2 %s does not match x1 %s" % (tuple(x2.shape), tuple(x1.shape)))
+        x2 = _input("channel_mean", "x2 (a map like x1)", x2, (N, H, W, "C2"), x1.device)
         C2 = x2.shape[3]
     C = C1 + C2
     if out is None:
         out = torch.empty((N, C), device=x1.device, dtype=torch.float32)
+    else:
+        _tensor("channel_mean", "output buffer out", out, torch.float32, (N, C), x1.device)
     need = lib().lsfa_channel_mean_workspace_bytes(N, C, H * W)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x1.device)
     _check(lib().lsfa_channel_mean(_ptr(x1), C1, _ptr(x2), C2, N, H * W, _ptr(out), _ptr(ws), need, _stream()), "lsfa_channel_mean")
@@ -299,11 +357,17 @@ def channel_mean(x1, x2=None, out=None):
 @_on_tensor_device
 def channel_gate(m, w1, b1, w2, b2, out=None):
     """lsfa_channel_gate: sigmoid(w2 relu(w1 m + b1) + b2) for the N rows of m (N, K); w1 (M, K), w2 (O, M) fp32 -> (N, O)."""
-    m, w1, b1, w2, b2 = (_f32c(t, n) for t, n in ((m, "m"), (w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")))
+    m = _input("channel_gate", "m", m, ("N", "K"))
     N, K = m.shape
-    M, O = w1.shape[0], w2.shape[0]
-    if w1.numel() != M * K or w2.numel() != O * M or b1.numel() != M or b2.numel() != O:
-        raise LsfaError("channel_gate: weights %s / %s do not chain from %d inputs" % (tuple(w1.shape), tuple(w2.shape), K))
+    dev = m.device
+    for what, t in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+        if not isinstance(t, torch.Tensor) or t.dim() < 1:
+            raise LsfaError("channel_gate: %s must be a float32 tensor on %s, got %s" % (what, dev, _arrived(t)))
+    M, O = int(w1.shape[0]), int(w2.shape[0])
+    w1, b1 = _vector("channel_gate", "w1 (M, %d)" % K, w1, M * K, dev), _vector("channel_gate", "b1 (M)", b1, M, dev)
+    w2, b2 = _vector("channel_gate", "w2 (O, M = %d)" % M, w2, O * M, dev), _vector("channel_gate", "b2 (O)", b2, O, dev)
+    if out is not None:
+        _tensor("channel_gate", "output buffer out", out, torch.float32, (N, O), dev)
     hidden = torch.empty((N, M), device=m.device, dtype=torch.float32)
     if out is None:
         out = torch.empty((N, O), device=m.device, dtype=torch.float32)
@@ -316,12 +380,15 @@ def channel_gate(m, w1, b1, w2, b2, out=None):
 def gate_apply(x, gate, y, out=None, amax_out=None, amax_c0=0):
     """lsfa_gate_apply: x * gate[n, c] + y (two roundings) on channels-last (N, H, W, C) maps; gate (N, C).  amax_out: a zeroed row of
     amax_slots() that receives max|out| over channels [amax_c0, C)."""
-    x, gate, y = _f32c(x, "x"), _f32c(gate, "gate"), _f32c(y, "y")
+    x = _input("gate_apply", "x", x, ("N", "H", "W", "C"))
     N, H, W, C = x.shape
-    if tuple(y.shape) != tuple(x.shape) or tuple(gate.shape) != (N, C):
-        raise LsfaError("gate_apply: x %s, y %s, gate %s" % (tuple(x.shape), tuple(y.shape), tuple(gate.shape)))
+    gate = _input("gate_apply", "gate", gate, (N, C), x.device)
+    y = _input("gate_apply", "y (a map like x)", y, (N, H, W, C), x.device)
+    amax_out = _amax_row("gate_apply", "amax_out", amax_out, x.device)
     if out is None:
         out = torch.empty_like(x)
+    else:
+        _tensor("gate_apply", "output buffer out", out, torch.float32, (N, H, W, C), x.device)
     _check(lib().lsfa_gate_apply(_ptr(x), _ptr(gate), _ptr(y), N, H * W, C, _ptr(out), _ptr(amax_out), amax_c0, _stream()), "lsfa_gate_apply")
     return out
 
@@ -337,21 +404,25 @@ def aggregate_softmax2(a, b, logits, out=None, logit_row_stride=None):
     """a, b (N, C, H, W); logits (2N, 1, H, W): rows [0, N) weight a, rows [N, 2N) weight b.
     logit_row_stride (r5): `logits` is any float32 tensor whose 2N rows of H*W logits start that many floats apart (the Nq net's
     last convolution written NCHW with 64 padded output channels: channel 0 of each image, stride 64*H*W) - no strided copy."""
-    a, b = _f32c(a, "a"), _f32c(b, "b")
+    a = _input("aggregate_softmax2", "a", a, ("N", "C", "H", "W"))
     N, C, H, W = a.shape
+    b = _input("aggregate_softmax2", "b (a map like a)", b, (N, C, H, W), a.device)
     if out is None:
         out = torch.empty_like(a)
+    else:
+        _tensor("aggregate_softmax2", "output buffer out", out, torch.float32, (N, C, H, W), a.device)
     if logit_row_stride is not None:
-        if (logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != a.device or logit_row_stride < H * W or
+        if (not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.device != a.device or logit_row_stride < H * W or
                 logits.numel() < (2 * N - 1) * logit_row_stride + H * W):
             raise LsfaError("aggregate_softmax2: logits %s (%s, %s) must be contiguous float32 on %s with %d rows of %d logits >= %d floats apart, got stride %d" % (
-                tuple(logits.shape), logits.dtype, logits.device, a.device, 2 * N, H * W, H * W, logit_row_stride))
+                tuple(getattr(logits, 'shape', ())), getattr(logits, 'dtype', type(logits)), getattr(logits, 'device', None), a.device, 2 * N, H * W,
+                H * W, logit_row_stride))
         _check(lib().lsfa_aggregate_softmax2_rows(_ptr(a), _ptr(b), _ptr(logits), logit_row_stride, N, C, H, W, _ptr(out), _stream()),
                "lsfa_aggregate_softmax2_rows")
         return out
-    logits = _f32c(logits, "logits")
-    if logits.numel() != 2 * N * H * W:
-        raise LsfaError("aggregate_softmax2: logits %s do not match a %s" % (tuple(logits.shape), tuple(a.shape)))
+    logits = _vector("aggregate_softmax2", "logits (2N = %d rows of H * W = %d)" % (2 * N, H * W), logits, 2 * N * H * W, a.device)
+    if logits is None:
+        raise LsfaError("aggregate_softmax2: logits must be a float32 tensor, got None")
     if N == 1:
         _check(lib().lsfa_aggregate_softmax2(_ptr(a), _ptr(b), _ptr(logits), C, H, W, _ptr(out), _stream()), "lsfa_aggregate_softmax2")
     else:
@@ -362,11 +433,15 @@ def aggregate_softmax2(a, b, logits, out=None, logit_row_stride=None):
 
 @_on_tensor_device
 def aggregate_cosine(a, b, emb_warp, emb_cur, out=None):
-    a, b = _f32c(a, "a"), _f32c(b, "b")
-    emb_warp, emb_cur = _f32c(emb_warp, "emb_warp"), _f32c(emb_cur, "emb_cur")
+    a = _input("aggregate_cosine", "a", a, (1, "C", "H", "W"))
     _, C, H, W = a.shape
+    b = _input("aggregate_cosine", "b (a map like a)", b, (1, C, H, W), a.device)
+    emb_warp = _input("aggregate_cosine", "emb_warp", emb_warp, (1, "E", H, W), a.device)
+    emb_cur = _input("aggregate_cosine", "emb_cur (a map like emb_warp)", emb_cur, (1, emb_warp.shape[1], H, W), a.device)
     if out is None:
         out = torch.empty_like(a)
+    else:
+        _tensor("aggregate_cosine", "output buffer out", out, torch.float32, (1, C, H, W), a.device)
     _check(lib().lsfa_aggregate_cosine(_ptr(a), _ptr(b), _ptr(emb_warp), _ptr(emb_cur), C, emb_warp.shape[1], H, W, _ptr(out), _stream()),
            "lsfa_aggregate_cosine")
     return out
@@ -387,15 +462,20 @@ class ProposalOp(object):
         self.output_score = output_score
 
     def __call__(self, cls_prob, bbox_pred, im_info, out=None):
-        if cls_prob.is_cuda and cls_prob.device.index != torch.cuda.current_device():
+        cls_prob = _input("Proposal", "cls_prob", cls_prob, ("B", "2A", "H", "W"))
+        if cls_prob.device.index != torch.cuda.current_device():
             with torch.cuda.device(cls_prob.device):
                 return self(cls_prob, bbox_pred, im_info, out)
-        cls_prob, bbox_pred, im_info = _f32c(cls_prob, "cls_prob"), _f32c(bbox_pred, "bbox_pred"), _f32c(im_info, "im_info")
         B, A2, H, W = cls_prob.shape
         A = A2 // 2
-        if bbox_pred.shape != (B, 4 * A, H, W) or im_info.shape != (B, 3):
-            raise LsfaError("Proposal: expected bbox_pred %s and im_info %s, got %s and %s (multi_proposal-inl.h:179-187)"
-                            % ((B, 4 * A, H, W), (B, 3), tuple(bbox_pred.shape), tuple(im_info.shape)))
+        # (multi_proposal-inl.h:179-187)
+        bbox_pred = _input("Proposal", "bbox_pred", bbox_pred, (B, 4 * A, H, W), cls_prob.device)
+        im_info = _input("Proposal", "im_info", im_info, (B, 3), cls_prob.device)
+        if out is not None:
+            n_out = B * min(self.post_n, min(self.pre_n if self.pre_n > 0 else A * H * W, A * H * W))
+            out = _given("Proposal", "out", out, 2)
+            _tensor("Proposal", "output buffer out[0] (rois)", out[0], torch.float32, (n_out, 5), cls_prob.device)
+            _tensor("Proposal", "output buffer out[1] (scores)", out[1], torch.float32, (n_out, 1), cls_prob.device)
         need = lib().lsfa_proposal_workspace_bytes(B, A, H, W, self.pre_n)
         ws = torch.empty(need, dtype=torch.uint8, device=cls_prob.device)
         count = A * H * W
@@ -435,8 +515,10 @@ _lab_filled = set()
 
 def nms_sorted(boxes, thresh):
     """boxes (n, >=4) float32 CUDA, sorted by score descending -> (keep int32 (n,), num_keep int32 (1,)) on device."""
-    boxes = _f32c(boxes, "boxes")
+    boxes = _input("nms_sorted", "boxes", boxes, ("n", "d >= 4"))
     n, d = boxes.shape
+    if d < 4:
+        raise LsfaError("nms_sorted: boxes of %d values" % d)
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=boxes.device)
     num = torch.zeros(1, dtype=torch.int32, device=boxes.device)
     need = lib().lsfa_nms_workspace_bytes(n)
@@ -449,10 +531,10 @@ def nms_sorted(boxes, thresh):
 def nms_sorted_f64(boxes, thresh):
     """boxes (n, >=4) float64 CUDA, sorted by score descending -> (keep, num_keep) like nms_sorted; numpy's
     float64 arithmetic and `ovr <= thresh` keep rule (lib/nms/nms.py:47-72)."""
-    if boxes.dtype != torch.float64 or not boxes.is_cuda:
-        raise LsfaError("boxes must be a float64 CUDA tensor (got %s on %s)" % (boxes.dtype, boxes.device))
-    boxes = boxes.contiguous()
+    boxes = _input("nms_sorted_f64", "boxes", boxes, ("n", "d >= 4"), dtype=torch.float64)
     n, d = boxes.shape
+    if d < 4:
+        raise LsfaError("nms_sorted_f64: boxes of %d values" % d)
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=boxes.device)
     num = torch.zeros(1, dtype=torch.int32, device=boxes.device)
     need = lib().lsfa_nms_workspace_bytes(n)
@@ -473,8 +555,9 @@ def nms_host(boxes_np, thresh, device_id=0):
 
 @_on_tensor_device
 def bbox_pred_clip(rois, deltas, im_h, im_w, scale):
-    rois, deltas = _f32c(rois, "rois"), _f32c(deltas, "deltas")
+    rois = _input("bbox_pred_clip", "rois", rois, ("R", 5))
     R = rois.shape[0]
+    deltas = _input("bbox_pred_clip", "deltas", deltas, (R, "4 nreg"), rois.device)
     nreg = deltas.shape[1] // 4
     out = torch.empty((R, 4 * nreg), dtype=torch.float64, device=rois.device)
     _check(lib().lsfa_bbox_pred_clip(_ptr(rois), _ptr(deltas), R, nreg, im_h, im_w, scale, _ptr(out), _stream()), "lsfa_bbox_pred_clip")
@@ -484,15 +567,21 @@ def bbox_pred_clip(rois, deltas, im_h, im_w, scale):
 @_on_tensor_device
 def det_postprocess(rois, deltas, probs, im_h, im_w, scale, score_thresh=1e-4, nms_thresh=0.3, max_per_image=300,
                     class_agnostic=True, out=None):
-    rois, deltas, probs = _f32c(rois, "rois"), _f32c(deltas, "deltas"), _f32c(probs, "probs")
-    R, ncls = probs.shape
+    rois = _input("det_postprocess", "rois", rois, ("R", 5))
+    R, dev = rois.shape[0], rois.device
+    deltas = _input("det_postprocess", "deltas", deltas, (R, "4 nreg"), dev)
+    probs = _input("det_postprocess", "probs", probs, (R, "ncls"), dev)
+    ncls = probs.shape[1]
     nreg = deltas.shape[1] // 4
     if out is None:
         dets = torch.zeros((ncls, R, 5), dtype=torch.float64, device=rois.device)
         counts = torch.zeros(ncls, dtype=torch.int32, device=rois.device)
         keep_idx = torch.full((ncls, R), -1, dtype=torch.int32, device=rois.device)
     else:
-        dets, counts, keep_idx = out
+        out = _given("det_postprocess", "out", out, 3)
+        dets = _tensor("det_postprocess", "output buffer out[0] (dets)", out[0], torch.float64, (ncls, R, 5), dev)
+        counts = _tensor("det_postprocess", "output buffer out[1] (counts)", out[1], torch.int32, (ncls,), dev)
+        keep_idx = _tensor("det_postprocess", "output buffer out[2] (keep_idx)", out[2], torch.int32, (ncls, R), dev)
     if LAB_SKIP_DET:
         return dets, counts, keep_idx
     _check(lib().lsfa_det_postprocess(_ptr(rois), _ptr(deltas), _ptr(probs), R, ncls, nreg, int(class_agnostic), im_h, im_w, scale, score_thresh,
@@ -505,8 +594,10 @@ def det_postprocess(rois, deltas, probs, im_h, im_w, scale, score_thresh=1e-4, n
 def rpn_softmax_split(logits, A):
     """lsfa_rpn_softmax_split: logits (N, H, W, L >= 6A) channels-last [score 2A | delta 4A | padding] -> (rpn_cls_prob (N, 2A, H, W),
     rpn_bbox_pred (N, 4A, H, W)): the per-anchor two-way softmax and the split into MultiProposal's NCHW inputs."""
-    logits = _f32c(logits, "logits")
+    logits = _input("rpn_softmax_split", "logits", logits, ("N", "H", "W", "L >= 6A"))
     N, H, W, L = logits.shape
+    if A < 1 or L < 6 * A:
+        raise LsfaError("rpn_softmax_split: %d channels do not hold the scores and deltas of A = %r anchors" % (L, A))
     cls_prob = torch.empty((N, 2 * A, H, W), device=logits.device, dtype=torch.float32)
     bbox = torch.empty((N, 4 * A, H, W), device=logits.device, dtype=torch.float32)
     _check(lib().lsfa_rpn_softmax_split(_ptr(logits), N, H, W, L, A, _ptr(cls_prob), _ptr(bbox), _stream()), "lsfa_rpn_softmax_split")
@@ -518,13 +609,19 @@ def det_postprocess_batch(rois, deltas, probs, B, im_h, im_w, scale, out, score_
                           class_agnostic=True):
     """lsfa_det_postprocess_batch: det_postprocess for the B images of a batch in one launch pair.  rois (B*R, 5), deltas (B*R, 4*nreg),
     probs (B*R, ncls), image b's rows [b*R, (b+1)*R); out = (dets (B, ncls, R, 5) f64, counts (B, ncls) i32, keep_idx (B, ncls, R) i32)."""
-    rois, deltas, probs = _f32c(rois, "rois"), _f32c(deltas, "deltas"), _f32c(probs, "probs")
-    R, ncls = probs.shape[0] // B, probs.shape[1]
+    who = "det_postprocess_batch"
+    rois = _input(who, "rois", rois, ("B R", 5))
+    BR, dev = int(rois.shape[0]), rois.device
+    if int(B) < 1 or BR % int(B):
+        raise LsfaError("%s: %d rois do not divide into B = %r images" % (who, BR, B))
+    deltas = _input(who, "deltas", deltas, (BR, "4 nreg"), dev)
+    probs = _input(who, "probs", probs, (BR, "ncls"), dev)
+    R, ncls = BR // B, probs.shape[1]
     nreg = deltas.shape[1] // 4
-    dets, counts, keep_idx = out
-    if tuple(dets.shape) != (B, ncls, R, 5) or tuple(counts.shape) != (B, ncls) or not (dets.is_contiguous() and counts.is_contiguous() and
-                                                                                       keep_idx.is_contiguous()):
-        raise LsfaError("det_postprocess_batch: out must be contiguous (B, ncls, R, 5) / (B, ncls) / (B, ncls, R) buffers")
+    out = _given(who, "out", out, 3)
+    dets = _tensor(who, "output buffer out[0] (dets)", out[0], torch.float64, (B, ncls, R, 5), dev)
+    counts = _tensor(who, "output buffer out[1] (counts)", out[1], torch.int32, (B, ncls), dev)
+    keep_idx = _tensor(who, "output buffer out[2] (keep_idx)", out[2], torch.int32, (B, ncls, R), dev)
     if LAB_SKIP_DET:
         return dets, counts, keep_idx
     _check(lib().lsfa_det_postprocess_batch(_ptr(rois), _ptr(deltas), _ptr(probs), B, R, ncls, nreg, int(class_agnostic), im_h, im_w, scale,
@@ -535,11 +632,15 @@ def det_postprocess_batch(rois, deltas, probs, B, im_h, im_w, scale, out, score_
 
 @_on_tensor_device
 def deform_im2col(data, offset, kh, kw, pad, stride, dilate, deform_groups, out=None):
-    data, offset = _f32c(data, "data"), _f32c(offset, "offset")
+    data = _input("deform_im2col", "data", data, ("N", "C", "H", "W"))
     N, C, H, W = data.shape
-    Ho, Wo = offset.shape[2], offset.shape[3]
+    Ho, Wo = conv_out_hw(H, W, kh, kw, stride, (pad, pad), dilate)
+    offset = _input("deform_im2col", "offset (2 * kh * kw * deform_groups channels on the convolution's output grid)", offset,
+                    (N, 2 * kh * kw * deform_groups, Ho, Wo), data.device)
     if out is None:
         out = torch.empty((N, C * kh * kw, Ho * Wo), dtype=torch.float32, device=data.device)
+    else:
+        _tensor("deform_im2col", "output buffer out", out, torch.float32, (N, C * kh * kw, Ho * Wo), data.device)
     _check(lib().lsfa_deform_im2col(_ptr(data), _ptr(offset), N, C, H, W, kh, kw, pad, stride, dilate, deform_groups, Ho, Wo, _ptr(out), _stream()),
            "lsfa_deform_im2col")
     return out
@@ -549,36 +650,49 @@ def deform_im2col(data, offset, kh, kw, pad, stride, dilate, deform_groups, out=
 def deform_im2col_cl(data, offset, kh, kw, pad, stride, dilate, deform_groups, out=None):
     """data (N,H,W,C), offset (N,Ho,Wo,L) contiguous with L >= 2*kh*kw*dg (channels past those are padding)
     -> col (N, Ho*Wo, kh*kw*C), k = tap*C + c."""
-    data, offset = _f32c(data, "data"), _f32c(offset, "offset")
+    data = _input("deform_im2col_cl", "data", data, ("N", "H", "W", "C"))
     N, H, W, C = data.shape
-    Ho, Wo = offset.shape[1], offset.shape[2]
+    Ho, Wo = conv_out_hw(H, W, kh, kw, stride, (pad, pad), dilate)
+    offset = _input("deform_im2col_cl", "offset (on the convolution's output grid)", offset, (N, Ho, Wo, "L"), data.device)
     if offset.shape[3] < 2 * kh * kw * deform_groups:
         raise LsfaError("deform_im2col_cl: offset has %d channels, expected %d" % (offset.shape[3], 2 * kh * kw * deform_groups))
     if out is None:
         out = torch.empty((N, Ho * Wo, kh * kw * C), dtype=torch.float32, device=data.device)
+    else:
+        _tensor("deform_im2col_cl", "output buffer out", out, torch.float32, (N, Ho * Wo, kh * kw * C), data.device)
     _check(lib().lsfa_deform_im2col_cl_ld(_ptr(data), _ptr(offset), offset.shape[3], N, C, H, W, kh, kw, pad, stride, dilate, deform_groups, Ho, Wo,
                                           _ptr(out), _stream()), "lsfa_deform_im2col_cl_ld")
     return out
 
 
-@_on_tensor_device
-def scale_shift_relu(x, scale, shift, relu=True, out=None):
-    x = _f32c(x, "x")
-    N, C = x.shape[0], x.shape[1]
-    HW = x.numel() // (N * C)
+def _scale_shift(who, x, scale, shift, out, axis):
+    """The operands of the three lsfa_scale_shift_*: x float32 with its channels on `axis` (1: (N, C, ...), -1: (..., C)), scale and shift
+    of C values, out like x -> (x, scale, shift, out, rows in front of the channel axis, C, values behind it)"""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda or x.dim() < 2 or x.numel() == 0:
+        raise LsfaError("%s: x must be a non-empty float32 CUDA tensor of at least 2 dimensions, got %s" % (who, _arrived(x)))
+    C = int(x.shape[axis])
+    if scale is None or shift is None:
+        raise LsfaError("%s: scale and shift must be float32 tensors of %d elements, got %s and %s" % (who, C, _arrived(scale), _arrived(shift)))
+    scale, shift = _vector(who, "scale", scale, C, x.device), _vector(who, "shift", shift, C, x.device)
+    if out is not None:
+        _tensor(who, "output buffer out", out, torch.float32, tuple(int(v) for v in x.shape), x.device)
+    x = x if x.is_contiguous() else x.contiguous()
     if out is None:
         out = torch.empty_like(x)
+    lead = int(x.shape[0]) if axis == 1 else x.numel() // C
+    return x, scale, shift, out, lead, C, x.numel() // (lead * C)
+
+
+@_on_tensor_device
+def scale_shift_relu(x, scale, shift, relu=True, out=None):
+    x, scale, shift, out, N, C, HW = _scale_shift("scale_shift_relu", x, scale, shift, out, 1)
     _check(lib().lsfa_scale_shift_relu(_ptr(x), _ptr(scale), _ptr(shift), N, C, HW, int(relu), _ptr(out), _stream()), "lsfa_scale_shift_relu")
     return out
 
 
 @_on_tensor_device
 def scale_shift_leaky(x, scale, shift, slope, out=None):
-    x = _f32c(x, "x")
-    N, C = x.shape[0], x.shape[1]
-    HW = x.numel() // (N * C)
-    if out is None:
-        out = torch.empty_like(x)
+    x, scale, shift, out, N, C, HW = _scale_shift("scale_shift_leaky", x, scale, shift, out, 1)
     _check(lib().lsfa_scale_shift_leaky(_ptr(x), _ptr(scale), _ptr(shift), N, C, HW, slope, _ptr(out), _stream()), "lsfa_scale_shift_leaky")
     return out
 
@@ -586,11 +700,7 @@ def scale_shift_leaky(x, scale, shift, slope, out=None):
 @_on_tensor_device
 def scale_shift_relu_cl(x, scale, shift, relu=True, out=None):
     """Channels-last form: x (..., C) contiguous with the channel the fastest axis, C % 4 == 0."""
-    x = _f32c(x, "x")
-    C = x.shape[-1]
-    rows = x.numel() // C
-    if out is None:
-        out = torch.empty_like(x)
+    x, scale, shift, out, rows, C, _ = _scale_shift("scale_shift_relu_cl", x, scale, shift, out, -1)
     _check(lib().lsfa_scale_shift_relu_cl(_ptr(x), _ptr(scale), _ptr(shift), rows, C, int(relu), _ptr(out), _stream()), "lsfa_scale_shift_relu_cl")
     return out
 
@@ -670,15 +780,16 @@ def conv_out_hw(H, W, kh, kw, stride=1, pad=(0, 0), dil=1):
     return tuple((n + 2 * p - dil * (k - 1) - 1) // stride + 1 for n, p, k in ((H, pad[0], kh), (W, pad[1], kw)))
 
 
-def _check_outputs(who, numel, **tensors):
-    """the tensors a convolution writes into or adds (None = not given): contiguous float32 of the output's size"""
+def _check_outputs(who, numel, device, **tensors):
+    """the tensors a convolution writes into or adds (None = not given): contiguous float32 of the output's size on `device`"""
     for name, t in tensors.items():
-        if t is not None and (t.numel() != numel or not t.is_contiguous() or t.dtype != torch.float32):
-            raise LsfaError("%s: %s must be a contiguous float32 tensor of %d elements" % (who, name, numel))
+        if t is not None and (not isinstance(t, torch.Tensor) or t.numel() != numel or not t.is_contiguous() or t.dtype != torch.float32 or
+                              t.device != device):
+            raise LsfaError("%s: %s must be a contiguous float32 tensor of %d elements on %s, got %s" % (who, name, numel, device, _arrived(t)))
 
 
 def conv_weight_kc(weight):
-    """(Cout, Cin, kh, kw) -> (Cout, kh*kw, Cin) contiguous: the layout lsfa_conv_nhwc_fwd reads (K contiguous)."""
+    """(Cout, Cin, kh, kw) -> (Cout, kh*kw, Cin) contiguous: the layout conv_nhwc reads (K contiguous)."""
     co, ci, kh, kw = weight.shape
     return weight.permute(0, 2, 3, 1).reshape(co, kh * kw, ci).contiguous()
 
@@ -689,15 +800,16 @@ def conv_nhwc(x, w_kc, bias, kh, kw, stride=1, pad=0, dil=1, relu=False, out=Non
     """x (N, H, W, Cin) contiguous fp32; w_kc from conv_weight_kc; -> (N, Ho, Wo, Cout).
     residual (same shape as the output; may BE `out`): added before the ReLU / store.  out2 + scale2 + shift2: second
     output max(out*scale2[c] + shift2[c], 0) (the next ResNet unit's bn1 + relu1).  Returns out, or (out, out2)."""
-    x, w_kc = _f32c(x, "x"), _f32c(w_kc, "w_kc")
+    x = _input("conv_nhwc", "x", x, ("N", "H", "W", "Cin"))
     N, H, W, Cin = x.shape
+    w_kc = _input("conv_nhwc", "w_kc (from conv_weight_kc)", w_kc, ("Cout", kh * kw, Cin), x.device)
     Cout = w_kc.shape[0]
-    if tuple(w_kc.shape) != (Cout, kh * kw, Cin):
-        raise LsfaError("conv_nhwc: weight %s does not match (Cout, %d, %d)" % (tuple(w_kc.shape), kh * kw, Cin))
+    bias = _vector("conv_nhwc", "bias", bias, Cout, x.device)
+    scale2, shift2 = _vector("conv_nhwc", "scale2", scale2, Cout, x.device), _vector("conv_nhwc", "shift2", shift2, Cout, x.device)
     Ho, Wo = conv_out_hw(H, W, kh, kw, stride, (pad, pad), dil)
+    _check_outputs("conv_nhwc", N * Ho * Wo * Cout, x.device, out=out, residual=residual, out2=out2)
     if out is None:
         out = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    _check_outputs("conv_nhwc", N * Ho * Wo * Cout, out=out, residual=residual, out2=out2)
     if _conv_flops["count"]:
         _count_launch(None, 2.0 * N * Ho * Wo * Cout * Cin * kh * kw)
     need = lib().lsfa_conv_nhwc_workspace_bytes(N, H, W, Cout, kh, kw, stride, pad, dil)
@@ -710,6 +822,10 @@ def conv_nhwc(x, w_kc, bias, kh, kw, stride=1, pad=0, dil=1, relu=False, out=Non
 def copy_many(pairs):
     """[(dst, src), ...] (at most 32; same shapes, contiguous, 4-byte dtypes, one device) as ONE launch on the current stream.
     src None (r5): dst is zero-filled - the frame path's amax slots and padded maps are cleared by this kernel, not by a PyTorch fill."""
+    pairs = list(pairs)
+    for d, s in pairs:
+        if not isinstance(d, torch.Tensor) or not (s is None or isinstance(s, torch.Tensor)):
+            raise LsfaError("copy_many: (dst, src) pairs of tensors (src may be None) expected, got %s <- %s" % (_arrived(d), _arrived(s)))
     pairs = [(d, s) for d, s in pairs if d.numel()]
     if not pairs:
         return
@@ -717,11 +833,11 @@ def copy_many(pairs):
     if n > 32:
         raise LsfaError("copy_many: at most 32 copies per launch")
     for d, s in pairs:
-        if d.element_size() != 4 or not d.is_contiguous() or d.device != pairs[0][0].device:
-            raise LsfaError("copy_many: %s: need a 4-byte dtype, contiguous, one device" % (tuple(d.shape),))
+        if d.element_size() != 4 or not d.is_contiguous() or not d.is_cuda or d.device != pairs[0][0].device:
+            raise LsfaError("copy_many: %s: need a 4-byte dtype, contiguous, one CUDA device; got %s" % (tuple(d.shape), _arrived(d)))
         if s is not None and (d.shape != s.shape or d.dtype != s.dtype or not s.is_contiguous() or d.device != s.device):
-            raise LsfaError("copy_many: %s <- %s: need equal shapes, 4-byte dtype, contiguous, one device"
-                            % (tuple(d.shape), tuple(s.shape)))
+            raise LsfaError("copy_many: %s <- %s: need equal shapes, 4-byte dtype, contiguous, one device; got %s <- %s"
+                            % (tuple(d.shape), tuple(s.shape), _arrived(d), _arrived(s)))
     if 'copy' in LAB_SKIP:      # ablation: copies of >= 1 KB into a buffer that has been filled once are dropped (zero fills stay)
         kept = []
         for d, s_ in pairs:
@@ -745,6 +861,8 @@ def transform_mv_res(motion_vector, res_diff, im_scale, pixel_means=(0.0, 0.0, 0
     `res_diff` (1, 3, h, w) float32 (transform_mv_res, lib/utils/image.py:202-228), one launch.  negate_mv: get_image's
     `motion_vector = - motion_vector` (:54) applied to the source values.  out: a pair of contiguous float32 tensors of those shapes."""
     mv, res = motion_vector, res_diff
+    if not isinstance(mv, torch.Tensor) or not isinstance(res, torch.Tensor) or not mv.is_cuda or res.device != mv.device:
+        raise LsfaError("transform_mv_res: motion_vector and res_diff must be tensors on one CUDA device, got %s / %s" % (_arrived(mv), _arrived(res)))
     if mv.dtype != res.dtype or mv.dtype not in (torch.int32, torch.float32):
         raise LsfaError("transform_mv_res: int32 or float32 maps expected, got %s / %s" % (mv.dtype, res.dtype))
     if mv.dim() != 3 or res.dim() != 3 or mv.shape[2] != 2 or res.shape[2] != 3 or mv.shape[:2] != res.shape[:2] or not (mv.is_contiguous() and res.is_contiguous()):
@@ -754,6 +872,7 @@ def transform_mv_res(motion_vector, res_diff, im_scale, pixel_means=(0.0, 0.0, 0
     oh, ow = ph // rcnn_stride, pw // rcnn_stride
     if out is None:
         out = (torch.empty((1, 2, oh, ow), device=mv.device, dtype=torch.float32), torch.empty((1, 3, oh, ow), device=mv.device, dtype=torch.float32))
+    out = _given("transform_mv_res", "out", out, 2)
     out_mv = _tensor("transform_mv_res", "output buffer out[0]", out[0], torch.float32, (1, 2, oh, ow), mv.device)
     out_res = _tensor("transform_mv_res", "output buffer out[1]", out[1], torch.float32, (1, 3, oh, ow), mv.device)
     _check(lib().lsfa_transform_mv_res(_ptr(mv), _ptr(res), int(mv.dtype == torch.int32) | (2 if negate_mv else 0), H, W, float(im_scale), h1, w1,
@@ -768,10 +887,11 @@ def image_resize_transform(im, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scal
     resize (lib/utils/image.py:266-294) + transform (:296-308) in one launch.  u8_fixed_point (uint8 frames only): interpolate on OpenCV's
     fixed-point uint8 path and subtract the means in float64 - what the reference does to the LAST frame of a video, which it reads with
     cv2.imread (:45); the default treats a uint8 frame like the decoder's (converted to float first, :52)."""
-    if im.dim() == 3:
+    if isinstance(im, torch.Tensor) and im.dim() == 3:
         im = im.unsqueeze(0)
-    if im.dtype not in (torch.uint8, torch.float32) or im.dim() != 4 or im.shape[3] != 3 or not im.is_contiguous():
-        raise LsfaError("image_resize_transform: (N, H, W, 3) contiguous uint8 or float32 expected, got %s %s" % (tuple(im.shape), im.dtype))
+    if not isinstance(im, torch.Tensor) or im.dtype not in (torch.uint8, torch.float32) or im.dim() != 4 or im.shape[3] != 3 or \
+            not im.is_contiguous() or not im.is_cuda:
+        raise LsfaError("image_resize_transform: (N, H, W, 3) contiguous uint8 or float32 on a CUDA device expected, got %s" % _arrived(im))
     N, H, W, _ = [int(v) for v in im.shape]
     h1, w1, ph, pw = _resized(H, W, im_scale, stride)
     out = torch.empty((N, 3, ph, pw), device=im.device, dtype=torch.float32)
@@ -787,11 +907,12 @@ def image_resize_transform(im, im_scale, pixel_means=(0.0, 0.0, 0.0), pixel_scal
 def image_transform_u8(im, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, out=None):
     """lsfa_image_transform_u8: decoded frames (N, H, W, 3) uint8 BGR on the device -> (N, 3, H, W) float32 RGB minus means, times scale
     (transform, lib/utils/image.py:296-308).  pixel_means in B, G, R order (config.network.PIXEL_MEANS)."""
-    if im.dtype != torch.uint8 or im.dim() != 4 or im.shape[3] != 3 or not im.is_contiguous():
-        raise LsfaError("image_transform_u8: (N, H, W, 3) contiguous uint8 expected, got %s %s" % (tuple(im.shape), im.dtype))
+    _tensor("image_transform_u8", "im", im, torch.uint8, ("N", "H", "W", 3))
     N, H, W, _ = im.shape
     if out is None:
         out = torch.empty((N, 3, H, W), device=im.device, dtype=torch.float32)
+    else:
+        _tensor("image_transform_u8", "output buffer out", out, torch.float32, (N, 3, H, W), im.device)
     _check(lib().lsfa_image_transform_u8(_ptr(im), N, H, W, _means(pixel_means), pixel_scale, _ptr(out), _stream()), "lsfa_image_transform_u8")
     return out
 
@@ -843,9 +964,7 @@ def _yuv_planes(who, y, uv, u, v, matrix):
 
 
 def _yuv_out(who, name, t, shape, dtype, device):
-    if t.dtype != dtype or tuple(t.shape) != shape or t.device != device or not t.is_contiguous():
-        raise LsfaError("%s: %s must be a contiguous %s %s tensor on %s, got %s %s on %s" % (who, name, shape, dtype, device, tuple(t.shape), t.dtype, t.device))
-    return t
+    return _tensor(who, name, t, dtype, shape, device)
 
 
 @_on_tensor_device
@@ -938,10 +1057,10 @@ class ImageTable(object):
         if len(images) != n:
             raise LsfaError("ImageTable.set: %d images for a table of %d" % (len(images), n))
         for t in images:
-            if t.dtype != torch.float32 or not t.is_cuda or t.device != self.device or not t.is_contiguous() or t.numel() != c * h * w or \
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != self.device or not t.is_contiguous() or t.numel() != c * h * w or \
                     tuple(t.shape[-3:]) != (c, h, w) or t.data_ptr() % 4:
                 raise LsfaError("ImageTable.set: every image must be a contiguous float32 (%d, %d, %d) tensor on %s, got %s %s on %s" % (
-                    c, h, w, self.device, tuple(t.shape), t.dtype, t.device))
+                    c, h, w, self.device, tuple(getattr(t, 'shape', ())), getattr(t, 'dtype', type(t)), getattr(t, 'device', None)))
         arr = (ctypes.c_void_p * n)(*[t.data_ptr() for t in images])
         with torch.cuda.device(self.device):
             _check(lib().lsfa_ptr_table_set(_ptr(self.ptrs), n, arr, _stream()), "lsfa_ptr_table_set")
@@ -959,11 +1078,13 @@ def avgpool_nchw(x, k, out=None):
     (lsfa_avgpool_nchw / lsfa_avgpool_nchw_tbl)."""
     tbl = isinstance(x, ImageTable)
     if not tbl:
-        x = _f32c(x, "x")
+        x = _input("avgpool_nchw", "x", x, ("N", "C", "H", "W"))
     N, C, H, W = x.shape
     Ho, Wo = -(-H // k), -(-W // k)
     if out is None:
         out = torch.empty((N, C, Ho, Wo), device=x.device, dtype=torch.float32)
+    else:
+        _tensor("avgpool_nchw", "output buffer out", out, torch.float32, (N, C, Ho, Wo), x.device)
     if tbl:
         with torch.cuda.device(x.device):
             _check(lib().lsfa_avgpool_nchw_tbl(_ptr(x.ptrs), N, C, H, W, k, _ptr(out), _stream()), "lsfa_avgpool_nchw_tbl")
@@ -976,9 +1097,8 @@ def avgpool_nchw(x, k, out=None):
 def stem_weight_layout(weight):
     """conv0's (64, 3, 7, 7) weight (bn0 folded) -> the fragments lsfa_stem_conv7x7s2 reads (lsfa_stem_weights: a uint8 tensor of
     lsfa_stem_weight_bytes())."""
-    co, ci, kh, kw = weight.shape
-    if (co, ci, kh, kw) != (64, 3, 7, 7):
-        raise LsfaError("stem_weight_layout: expected a (64, 3, 7, 7) weight, got %s" % (tuple(weight.shape),))
+    if not isinstance(weight, torch.Tensor) or tuple(weight.shape) != (64, 3, 7, 7) or not weight.is_cuda or not weight.is_floating_point():
+        raise LsfaError("stem_weight_layout: expected a (64, 3, 7, 7) floating-point weight on a CUDA device, got %s" % _arrived(weight))
     w_l = weight.float().permute(1, 2, 3, 0).contiguous()
     frag = torch.empty((int(lib().lsfa_stem_weight_bytes()),), dtype=torch.uint8, device=weight.device)
     _check(lib().lsfa_stem_weights(_ptr(w_l), _ptr(frag), _stream()), "lsfa_stem_weights")
@@ -991,15 +1111,22 @@ def stem_conv(x, w_l, bias, in_scale=None, in_shift=None, out=None, accum=None, 
     x (N, 3, H, W) NCHW -> (N, Ho, Wo, 64) channels-last.  amax_out: a zeroed row of amax_slots() for max|out|."""
     tbl = isinstance(x, ImageTable)      # the N images given by a table of device pointers (lsfa_stem_conv7x7s2_tbl)
     if not tbl:
-        x = _f32c(x, "x")
+        x = _input("stem_conv", "x", x, ("N", 3, "H", "W"))
     N, C, H, W = x.shape
-    if C != 3 or w_l.dtype != torch.uint8 or w_l.numel() != int(lib().lsfa_stem_weight_bytes()) or not w_l.is_contiguous():
-        raise LsfaError("stem_conv: x must have 3 channels and w_l must come from stem_weight_layout")
+    dev = x.device
+    if C != 3:
+        raise LsfaError("stem_conv: x must have 3 channels, the table holds images of %d" % C)
+    _tensor("stem_conv", "w_l (from stem_weight_layout)", w_l, torch.uint8, (int(lib().lsfa_stem_weight_bytes()),), dev)
+    bias = _vector("stem_conv", "bias", bias, 64, dev)
+    in_scale, in_shift = _vector("stem_conv", "in_scale", in_scale, 3, dev), _vector("stem_conv", "in_shift", in_shift, 3, dev)
+    amax_out = _amax_row("stem_conv", "amax_out", amax_out, dev)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is not None:
+        _tensor("stem_conv", "output buffer out", out, torch.float32, (N, Ho, Wo, 64), dev)
+    if accum is not None:
+        _tensor("stem_conv", "accum (a map like the output; may be `out`)", accum, torch.float32, (N, Ho, Wo, 64), dev)
     if out is None:
         out = torch.empty((N, Ho, Wo, 64), device=x.device, dtype=torch.float32)
-    if accum is not None and (tuple(accum.shape) != tuple(out.shape) or not accum.is_contiguous()):
-        raise LsfaError("stem_conv: accum must be a contiguous %s tensor" % (tuple(out.shape),))
     if tbl:
         with torch.cuda.device(x.device):
             _check(lib().lsfa_stem_conv7x7s2_tbl(_ptr(x.ptrs), N, H, W, _ptr(in_scale), _ptr(in_shift), _ptr(w_l), _ptr(bias), _ptr(accum), act,
@@ -1014,13 +1141,21 @@ def stem_conv(x, w_l, bias, in_scale=None, in_shift=None, out=None, accum=None, 
 def head_conv3x3(x, w, bias, cin=None, mul=1.0, out=None, c0=0, nchw=False):
     """lsfa_head_conv3x3: 3x3 / pad 1 convolution to <= 4 channels (FlowNet's flow heads).  x (N,H,W,L) channels-last, w (Cout,3,3,Cin);
     nchw: returns (N,Cout,H,W); else writes channels [c0, c0+Cout) of `out` (N,H,W,Lout) (a fresh (N,H,W,Cout) map by default)."""
-    x, w = _f32c(x, "x"), _f32c(w, "w")
+    x = _input("head_conv3x3", "x", x, ("N", "H", "W", "L"))
     N, H, W, L = x.shape
+    w = _input("head_conv3x3", "w", w, ("Cout", 3, 3, "Cin"), x.device)
     Cout, cin = w.shape[0], (w.shape[3] if cin is None else cin)
-    if tuple(w.shape[1:3]) != (3, 3) or w.shape[3] != cin or cin > L:
+    if w.shape[3] != cin or cin > L:
         raise LsfaError("head_conv3x3: weight %s does not fit %d input channels of %d" % (tuple(w.shape), cin, L))
+    bias = _vector("head_conv3x3", "bias", bias, Cout, x.device)
     if out is None:
+        if c0 != 0:
+            raise LsfaError("head_conv3x3: c0 = %r needs the `out` whose channels [c0, c0 + %d) it names" % (c0, Cout))
         out = torch.empty((N, Cout, H, W) if nchw else (N, H, W, Cout), device=x.device, dtype=torch.float32)
+    else:
+        _tensor("head_conv3x3", "output buffer out", out, torch.float32, (N, Cout, H, W) if nchw else (N, H, W, "Lout"), x.device)
+        if not nchw and not 0 <= c0 <= out.shape[3] - Cout:
+            raise LsfaError("head_conv3x3: channels [%d, %d) do not fit out %s" % (c0, c0 + Cout, tuple(out.shape)))
     _check(lib().lsfa_head_conv3x3(_ptr(x), L, N, H, W, cin, _ptr(w), _ptr(bias), Cout, mul, _ptr(out), int(nchw), out.shape[3] if not nchw else 0,
                                    c0, _stream()), "lsfa_head_conv3x3")
     return out
@@ -1029,11 +1164,14 @@ def head_conv3x3(x, w, bias, cin=None, mul=1.0, out=None, c0=0, nchw=False):
 @_on_tensor_device
 def upsample_flow(x, w, bias, out, c0, amax_out=None):
     """lsfa_upsample_flow: Deconvolution(4x4, stride 2) + Crop(offset 1) of a (N,Hi,Wi,C) flow into channels [c0, c0+C) of out (N,Hc,Wc,L)."""
-    x, w = _f32c(x, "x"), _f32c(w, "w")
+    x = _input("upsample_flow", "x", x, ("N", "Hi", "Wi", "C"))
     N, Hi, Wi, C = x.shape
-    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda or out.dim() != 4 or out.shape[0] != N
-            or not out.is_contiguous()):
-        raise LsfaError("upsample_flow: out must be a contiguous float32 CUDA tensor (%d, Hc, Wc, L)" % N)
+    w = _input("upsample_flow", "w", w, (C, C, 4, 4), x.device)
+    bias = _vector("upsample_flow", "bias", bias, C, x.device)
+    amax_out = _amax_row("upsample_flow", "amax_out", amax_out, x.device)
+    _tensor("upsample_flow", "out", out, torch.float32, (N, "Hc", "Wc", "L"), x.device)
+    if not 0 <= c0 <= out.shape[3] - C:
+        raise LsfaError("upsample_flow: channels [%d, %d) do not fit out %s" % (c0, c0 + C, tuple(out.shape)))
     _check(lib().lsfa_upsample_flow(_ptr(x), N, Hi, Wi, C, _ptr(w), _ptr(bias), out.shape[1], out.shape[2], _ptr(out), out.shape[3], c0,
                                     _ptr(amax_out), _stream()), "lsfa_upsample_flow")
     return out
@@ -1043,13 +1181,16 @@ def upsample_flow(x, w, bias, out, c0, amax_out=None):
 def nchw_to_nhwc(x, c0=0, c=None, out=None, amax_out=None):
     """channels [c0, c0 + c) of an (N, C, H, W) map -> (N, H, W, c) channels-last (lsfa_nchw_to_nhwc), into `out` when given (a contiguous
     (N, H, W, c) tensor or leading slice of one); amax_out: a zeroed row of amax_slots() that receives max|.| of the copied values."""
-    x = _f32c(x, "x")
+    x = _input("nchw_to_nhwc", "x", x, ("N", "C", "H", "W"))
     N, C, H, W = x.shape
     c = C - c0 if c is None else c
+    if c0 < 0 or c < 1 or c0 + c > C:
+        raise LsfaError("nchw_to_nhwc: channels [%d, %d) of a map of %d" % (c0, c0 + c, C))
+    amax_out = _amax_row("nchw_to_nhwc", "amax_out", amax_out, x.device)
     if out is None:
         out = torch.empty((N, H, W, c), device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != (N, H, W, c) or not out.is_contiguous() or out.dtype != torch.float32:
-        raise LsfaError("nchw_to_nhwc: out must be a contiguous float32 %s tensor" % ((N, H, W, c),))
+    else:
+        _tensor("nchw_to_nhwc", "output buffer out", out, torch.float32, (N, H, W, c), x.device)
     if 'nhwc' in LAB_SKIP and out.data_ptr() in _lab_filled:
         return out
     if LAB_SKIP:
@@ -1060,10 +1201,11 @@ def nchw_to_nhwc(x, c0=0, c=None, out=None, amax_out=None):
 
 def rfcn_head_ps_ld(ps_map, cell_ld, rois, H, W, ncls, nbox, spatial_scale=0.0625, pooled_size=7, group_size=7):
     """rfcn_head_ps on a position-sensitive map whose cells are `cell_ld` floats apart (N, H, W, cell_ld)."""
-    ps_map, rois = _f32c(ps_map, "ps_map"), _f32c(rois, "rois")
+    ps_map = _input("rfcn_head_ps_ld", "ps_map (N, H, W, cell_ld)", ps_map, ("N", H, W, cell_ld))
+    rois = _input("rfcn_head_ps_ld", "rois", rois, ("R", 5), ps_map.device)
     N, R = ps_map.shape[0], rois.shape[0]
-    if ps_map.shape[-1] != cell_ld or ps_map.numel() != N * H * W * cell_ld:
-        raise LsfaError("rfcn_head_ps_ld: ps_map %s is not (%d, %d, %d, cell_ld = %d)" % (tuple(ps_map.shape), N, H, W, cell_ld))
+    if cell_ld < group_size * group_size * (ncls + nbox):
+        raise LsfaError("rfcn_head_ps_ld: cells of %d floats do not hold %d x (%d + %d) scores" % (cell_ld, group_size * group_size, ncls, nbox))
     cls_prob = torch.empty((R, ncls), device=rois.device, dtype=torch.float32)
     bbox_pred = torch.empty((R, nbox), device=rois.device, dtype=torch.float32)
     if LAB_SKIP_HEAD:
@@ -1077,7 +1219,7 @@ def rfcn_head_ps_ld(ps_map, cell_ld, rois, H, W, ncls, nbox, spatial_scale=0.062
 @_on_tensor_device
 def avgpool2_nhwc(x):
     """(N,H,W,C) -> (N,ceil(H/2),ceil(W/2),C), 2x2 / 2 average with clipped edge windows (lsfa_avgpool2_nhwc)."""
-    x = _f32c(x, "x")
+    x = _input("avgpool2_nhwc", "x", x, ("N", "H", "W", "C"))
     N, H, W, C = x.shape
     y = torch.empty((N, (H + 1) // 2, (W + 1) // 2, C), device=x.device, dtype=torch.float32)
     _check(lib().lsfa_avgpool2_nhwc(_ptr(x), N, H, W, C, _ptr(y), _stream()), "lsfa_avgpool2_nhwc")
@@ -1090,11 +1232,17 @@ def maxpool3x3s2_nhwc(x, out=None, scale2=None, shift2=None, amax_out=None):
     With scale2 / shift2 (C): returns (pooled, max(pooled*scale2 + shift2, 0)) — the first unit's bn1 + relu1 in the same launch.
     amax_out: a zeroed row of amax_slots() that receives the maximum of the map the next convolution reads (the second output
     when there is one)."""
-    x = _f32c(x, "x")
+    x = _input("maxpool3x3s2_nhwc", "x", x, ("N", "H", "W", "C"))
     N, H, W, C = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if (scale2 is None) != (shift2 is None):
+        raise LsfaError("maxpool3x3s2_nhwc: scale2 and shift2 come together, got %s and %s" % (_arrived(scale2), _arrived(shift2)))
+    scale2, shift2 = _vector("maxpool3x3s2_nhwc", "scale2", scale2, C, x.device), _vector("maxpool3x3s2_nhwc", "shift2", shift2, C, x.device)
+    amax_out = _amax_row("maxpool3x3s2_nhwc", "amax_out", amax_out, x.device)
     if out is None:
         out = torch.empty((N, Ho, Wo, C), device=x.device, dtype=torch.float32)
+    else:
+        _tensor("maxpool3x3s2_nhwc", "output buffer out", out, torch.float32, (N, Ho, Wo, C), x.device)
     out2 = torch.empty_like(out) if scale2 is not None else None
     _check(lib().lsfa_maxpool3x3s2_nhwc(_ptr(x), N, H, W, C, _ptr(out), _ptr(out2), _ptr(scale2), _ptr(shift2), _ptr(amax_out), _stream()),
            "lsfa_maxpool3x3s2_nhwc")
@@ -1126,7 +1274,8 @@ class SplitWeight(object):
         channel counts when `weight` was zero-padded to the kernel's tile sizes (algorithmic FLOPs are counted on those).
         into: the fragments' storage (a slice of a shared allocation); w_exp: the two-piece form's exponent when the caller knows it (one
         shared by several weights: deconv_phase_weights) - then the tensor is not measured and carries no per-channel scale."""
-        w_kc = _f32c(conv_weight_kc(weight), "weight")
+        _input("SplitWeight", "weight", weight, ("Cout", "Cin", "kh", "kw"))
+        w_kc = conv_weight_kc(weight)
         self.pieces = int(DEFAULT_PIECES if pieces is None else pieces)
         self.cout, self.cin, self.kh, self.kw = [int(v) for v in weight.shape]
         self.real_cout, self.real_cin = int(real_cout or self.cout), int(real_cin or self.cin)
@@ -1141,9 +1290,9 @@ class SplitWeight(object):
         need = lib().lsfa_conv_weight_bytes(self.cout, self.kh, self.kw, self.cin, self.pieces)
         if need == 0:
             raise LsfaError("SplitWeight: Cin=%d must be a multiple of 32, Cout=%d of 64, pieces=%d one of 1, 2, 3" % (self.cin, self.cout, self.pieces))
+        if into is not None:
+            _tensor("SplitWeight", "into (the fragments' storage)", into, torch.uint8, (need,), weight.device)
         self.frag = torch.empty(need, dtype=torch.uint8, device=weight.device) if into is None else into
-        if self.frag.numel() != need or not self.frag.is_contiguous():
-            raise LsfaError("SplitWeight: `into` must be a contiguous uint8 tensor of %d bytes" % need)
         if self.pieces == 2 and per_channel_scale and w_exp is None:
             # r5: one power of two per OUTPUT channel, from the channel's own maximum (a BatchNorm folded into trained weights spreads the
             # channels over many octaves: with one scale per tensor the small channels' lo pieces go subnormal).  An all-zero (padding)
@@ -1165,9 +1314,13 @@ class SplitWeight(object):
 def amax_partial(x, out=None):
     """lsfa_amax_partial: 256 partial maxima of |x| (float32, contiguous, numel % 4 == 0): an `amax_in` for a map that no convolution
     of this library produced (those leave theirs in `amax_out`)."""
-    x = _f32c(x, "x")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda:
+        raise LsfaError("amax_partial: x must be a float32 CUDA tensor, got %s" % _arrived(x))
+    x = x if x.is_contiguous() else x.contiguous()
     if out is None:
         out = torch.empty(AMAX_SLOTS, device=x.device, dtype=torch.float32)
+    else:
+        _tensor("amax_partial", "output buffer out", out, torch.float32, (AMAX_SLOTS,), x.device)
     _check(lib().lsfa_amax_partial(_ptr(x), x.numel(), _ptr(out), _stream()), "lsfa_amax_partial")
     return out
 
@@ -1201,6 +1354,7 @@ def new_status(device):
 def check_status(status):
     """lsfa_status_check: raises LsfaError if a convolution raised the status word (non-finite output: the fp16 form's scale was an
     under-estimate, or the input held inf / NaN).  Synchronises the current stream."""
+    _tensor("check_status", "status (a new_status() word)", status, torch.int32, (4,))
     if LAB_SKIP:      # an ablation run's maps are garbage by construction
         return
     _check(lib().lsfa_status_check(_ptr(status), _stream()), "lsfa_status_check")
@@ -1272,6 +1426,14 @@ def _conv_exact(x, sw, bias, stride=1, pad=0, dil=1, act=0, out=None, residual=N
     return y
 
 
+def _split_weight(who, what, sw, device=None):
+    """sw, if it is a SplitWeight whose storage lies on `device`"""
+    t = getattr(sw, 'w_kc', None) if getattr(sw, 'pieces', None) == 0 else getattr(sw, 'frag', None)
+    if not isinstance(sw, SplitWeight) or not isinstance(t, torch.Tensor) or not t.is_cuda or (device is not None and t.device != device):
+        raise LsfaError("%s: %s must be a SplitWeight on %s, got %s" % (who, what, device or "a CUDA device", type(sw).__name__))
+    return sw
+
+
 @_on_tensor_device
 def conv_split(x, sw, bias=None, stride=1, pad=0, dil=1, relu=False, out=None, residual=None, out2=None, scale2=None,
                shift2=None, nchw=False, act=None, amax_in=None, amax_out=None, status=None, x_nchw=False, in_scale=None, in_shift=None):
@@ -1284,7 +1446,9 @@ def conv_split(x, sw, bias=None, stride=1, pad=0, dil=1, relu=False, out=None, r
     maximum published (amax_out) - for a consumer that applies the same affine + ReLU itself through in_scale / in_shift (Cin floats each:
     the input becomes max(x*in_scale[k] + in_shift[k], 0) where it is cut; 1x1, pad 0, two-piece or one-piece weights; amax_in must bound
     the ACTIVATED input).  Returns out, or (out, out2)."""
-    x = _f32c(x, "x")
+    x = _input("conv_split", "x", x, ("N", "C", "H", "W") if x_nchw else ("N", "H", "W", "Cin"))
+    dev = x.device
+    _split_weight("conv_split", "sw", sw, dev)
     if x_nchw:
         # the input is channels [0, sw.cin) of an NCHW map (N, Ctot, H, W): 1x1 / stride 1 / no padding, small weights (the RPN head)
         N, Ctot, H, W = x.shape
@@ -1298,9 +1462,14 @@ def conv_split(x, sw, bias=None, stride=1, pad=0, dil=1, relu=False, out=None, r
         raise LsfaError("conv_split: input has %d channels, the weight %d" % (Cin, sw.cin))
     Cout, act = sw.cout, ((1 if relu else 0) if act is None else act)      # lsfa_conv_desc::act; `act` wins over relu=
     Ho, Wo = conv_out_hw(H, W, sw.kh, sw.kw, stride, (pad, pad), dil)
+    _check_outputs("conv_split", N * Ho * Wo * Cout, dev, out=out, residual=residual, out2=out2)
+    bias = _vector("conv_split", "bias", bias, Cout, dev)
+    scale2, shift2 = _vector("conv_split", "scale2", scale2, Cout, dev), _vector("conv_split", "shift2", shift2, Cout, dev)
+    in_scale, in_shift = _vector("conv_split", "in_scale", in_scale, Cin, dev), _vector("conv_split", "in_shift", in_shift, Cin, dev)
+    amax_in, amax_out = _amax_row("conv_split", "amax_in", amax_in, dev, measured=True), _amax_row("conv_split", "amax_out", amax_out, dev)
+    status = _status_word("conv_split", status, dev)
     if out is None:
         out = torch.empty((N, Cout, Ho, Wo) if nchw else (N, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    _check_outputs("conv_split", N * Ho * Wo * Cout, out=out, residual=residual, out2=out2)
     if sw.pieces == 0:
         return _conv_exact(x, sw, bias, stride, pad, dil, act, out=out, residual=residual, out2=out2, scale2=scale2, shift2=shift2, nchw=nchw,
                            x_nchw=x_nchw, in_scale=in_scale, in_shift=in_shift)
@@ -1318,9 +1487,11 @@ def conv_pair(x, sw3, residual, scale2, shift2, sw1, bias=None, out=None, out_z=
     residual (N, H, W, C), may BE `out`.  -> (y, z): y = conv3(x) + residual (bit-identical to conv_split's), z = max(conv1(max(y * scale2 +
     shift2, 0)) + bias, 0); the activated map is never stored.  amax_out_sum receives its maximum, amax_out_z that of z.  Channel counts
     outside Cm, Cn in {64, 128}, other piece counts, non-contiguous operands, NCHW or a stride raise LsfaError (LSFA_ENOTSUP)."""
-    if x.dim() != 4 or x.dtype != torch.float32:
-        raise LsfaError("conv_pair: x must be a (N, H, W, Cm) float32 tensor")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda:
+        raise LsfaError("conv_pair: x must be a (N, H, W, Cm) float32 CUDA tensor, got %s" % _arrived(x))
     N, H, W, Cm = x.shape
+    dev = x.device
+    _split_weight("conv_pair", "sw3", sw3, dev), _split_weight("conv_pair", "sw1", sw1, dev)
     C, Cn = sw3.cout, sw1.cout
     if (sw3.kh, sw3.kw, sw1.kh, sw1.kw) != (1, 1, 1, 1) or sw3.cin != Cm or sw1.cin != C:
         raise LsfaError("conv_pair: two 1x1 convolutions Cm=%d -> C -> Cn, not %dx%d %d -> %d and %dx%d %d -> %d"
@@ -1328,20 +1499,28 @@ def conv_pair(x, sw3, residual, scale2, shift2, sw1, bias=None, out=None, out_z=
     two = sw3.pieces == 2 and sw1.pieces == 2      # (any other piece count is refused by the library)
     if two and (sw3.w_scale is None or sw1.w_scale is None):
         raise LsfaError("conv_pair: the weights must carry per-channel scales (SplitWeight(per_channel_scale=True))")
+    for name, t, c in (("out", out, C), ("residual", residual, C), ("out_z", out_z, Cn)):
+        if (t is None and name == "residual") or (t is not None and (not isinstance(t, torch.Tensor) or t.numel() != N * H * W * c or
+                                                                      t.dtype != torch.float32 or t.device != dev or not t.is_contiguous())):
+            raise LsfaError("conv_pair: %s must be a contiguous float32 tensor of %d elements on %s, got %s" % (name, N * H * W * c, dev, _arrived(t)))
+    for name, t, c in (("scale2", scale2, C), ("shift2", shift2, C), ("bias", bias, Cn)):
+        if (t is None and name != "bias") or (t is not None and (not isinstance(t, torch.Tensor) or t.numel() != c or t.dtype != torch.float32 or
+                                                                  t.device != dev or not t.is_contiguous())):
+            raise LsfaError("conv_pair: %s must be a contiguous float32 tensor of %d elements on %s, got %s" % (name, c, dev, _arrived(t)))
+    amax_in = _amax_row("conv_pair", "amax_in", amax_in, dev, measured=True)
+    amax_out_sum, amax_out_z = _amax_row("conv_pair", "amax_out_sum", amax_out_sum, dev), _amax_row("conv_pair", "amax_out_z", amax_out_z, dev)
+    status = _status_word("conv_pair", status, dev)
     if amax_in is None:
-        amax_in = amax_partial(_f32c(x, "x"))
+        amax_in = amax_partial(x)
     if out is None:
         out = torch.empty((N, H, W, C), device=x.device, dtype=torch.float32)
     if out_z is None:
         out_z = torch.empty((N, H, W, Cn), device=x.device, dtype=torch.float32)
-    for name, t, c in (("out", out, C), ("residual", residual, C), ("out_z", out_z, Cn)):
-        if t is None or t.numel() != N * H * W * c or t.dtype != torch.float32:
-            raise LsfaError("conv_pair: %s must be a float32 tensor of %d elements" % (name, N * H * W * c))
     # a view is described to the library by its pixel pitch (which then refuses it): dense operands have pitch = channel count
     ldx = x.stride(2) if x.stride(3) == 1 else 0
     ldy = out.stride(-2) if out.stride(-1) == 1 and out.dim() == 4 else C
     ldz = out_z.stride(-2) if out_z.stride(-1) == 1 and out_z.dim() == 4 else Cn
-    if not (residual.is_contiguous() and scale2.is_contiguous() and shift2.is_contiguous()):
+    if not residual.is_contiguous():
         raise LsfaError("conv_pair: residual, scale2 and shift2 must be contiguous")
     if _conv_flops["count"] and two:
         P = N * H * W
@@ -1365,10 +1544,14 @@ def conv_split_view(x, sw, bias, out, stride=1, pad=(0, 0), dil=1, act=0, cin=No
     grid (Ho, Wo): the output grid of this launch when smaller than the convolution's; place (y0, x0, sy, sx): output pixel
          (oy, ox) is written to out[:, y0 + oy*sy, x0 + ox*sx] (default: out[:, oy, ox]) - a phase of a transposed convolution;
     pad  (pad_h, pad_w); act 0 none / 1 ReLU / 2 LeakyReLU(0.1)."""
-    x = _f32c(x, "x")
-    if not (out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 4):
-        raise LsfaError("conv_split_view: out must be a contiguous float32 (N, H, W, C) tensor")
+    x = _input("conv_split_view", "x", x, ("N", "H", "W", "L"))
     N, H, W, L = x.shape
+    dev = x.device
+    _split_weight("conv_split_view", "sw", sw, dev)
+    _tensor("conv_split_view", "out", out, torch.float32, (N, "Hout", "Wout", "Lout"), dev)
+    bias = _vector("conv_split_view", "bias", bias, sw.cout, dev)
+    amax_in = _amax_row("conv_split_view", "amax_in", amax_in, dev, measured=True)
+    amax_out, status = _amax_row("conv_split_view", "amax_out", amax_out, dev), _status_word("conv_split_view", status, dev)
     cin = sw.cin if cin is None else cin
     if cin != sw.cin or L < cin0 + cin or cin0 < 0 or cin0 % 4:
         raise LsfaError("conv_split_view: the weight has %d input channels, x offers [%d, %d) (of %d)" % (sw.cin, cin0, cin0 + cin, L))
@@ -1402,6 +1585,7 @@ def deconv_phase_weights(wt, cin_pad=None, pieces=None):
     """wt: MXNet Deconvolution weight (Cin, Cout, 4, 4) -> PhaseWeights for lsfa_deconv4x4s2_crop_fwd (input channels zero-padded to
     cin_pad).  Output row 2m + py of the cropped map reads input rows (m - 1, m) through taps ky = (3, 1) when py = 0 and rows
     (m, m + 1) through ky = (2, 0) when py = 1; columns alike.  With two pieces all four phases share ONE weight scale (w_exp)."""
+    _input("deconv_phase_weights", "wt", wt, ("Cin", "Cout", 4, 4))      # (read by torch here: only the phase weights go to the library)
     cin, cout = int(wt.shape[0]), int(wt.shape[1])
     cpad = int(cin_pad or cin)
     pieces = int(DEFAULT_PIECES if pieces is None else pieces)
@@ -1429,17 +1613,23 @@ def deconv4x4s2_crop(x, sw4, bias, out, c0=0, act=0, amax_in=None, amax_out=None
     """lsfa_deconv4x4s2_crop_fwd: Deconvolution(4x4, stride 2) + Crop(offset 1) + bias + activation as one launch.
     x (N, Hi, Wi, L) channels-last (the weights' Cin channels read, L >= Cin); sw4: deconv_phase_weights(...); the result fills
     channels [c0, c0 + Cout) of out (N, Hc, Wc, Lout)."""
-    x = _f32c(x, "x")
+    x = _input("deconv4x4s2_crop", "x", x, ("N", "Hi", "Wi", "L"))
     N, Hi, Wi, L = x.shape
+    dev = x.device
+    frags = getattr(sw4, 'frag4', None)
+    if not isinstance(sw4, PhaseWeights) or not isinstance(frags, torch.Tensor) or frags.device != dev:
+        raise LsfaError("deconv4x4s2_crop: the phase weights must come from hip.deconv_phase_weights (one allocation) on %s, got %s" %
+                        (dev, type(sw4).__name__))
     cin, cout = sw4[0].cin, sw4[0].cout
     if len(sw4) != 4 or any((s.cin, s.cout, s.kh, s.kw) != (cin, cout, 2, 2) for s in sw4) or cin > L:
         raise LsfaError("deconv4x4s2_crop: four (Cout, Cin, 2, 2) phase weights with Cin <= %d expected" % L)
-    if not (out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 4) or c0 + cout > out.shape[3] or out.shape[0] != N:
+    _tensor("deconv4x4s2_crop", "out", out, torch.float32, (N, "Hc", "Wc", "Lout"), dev)
+    if c0 < 0 or c0 + cout > out.shape[3]:
         raise LsfaError("deconv4x4s2_crop: bad out %s for channels [%d, %d)" % (tuple(out.shape), c0, c0 + cout))
     Hc, Wc, Lout = out.shape[1], out.shape[2], out.shape[3]
-    frags = getattr(sw4, 'frag4', None)
-    if frags is None:
-        raise LsfaError("deconv4x4s2_crop: the phase weights must come from hip.deconv_phase_weights (one allocation)")
+    bias = _vector("deconv4x4s2_crop", "bias", bias, cout, dev)
+    amax_in = _amax_row("deconv4x4s2_crop", "amax_in", amax_in, dev, measured=True)
+    amax_out, status = _amax_row("deconv4x4s2_crop", "amax_out", amax_out, dev), _status_word("deconv4x4s2_crop", status, dev)
     if amax_in is None and sw4.pieces == 2:
         amax_in = amax_partial(x)
     need = lib().lsfa_deconv4x4s2_crop_workspace_bytes(N, Hi, Wi, cin, cout, Hc, Wc, sw4.pieces)
@@ -1494,8 +1684,8 @@ class MotionVectorAccumulator(object):
     def add_frame(self, mvs, max_block_area=None):
         """mvs (n, 7) int32.  max_block_area: an upper bound of w*h over the blocks (256 for 16x16 macroblocks);
         when omitted it is read from `mvs`, which costs a device-to-host synchronisation if mvs is on the device."""
-        if mvs.dtype != torch.int32 or mvs.dim() != 2 or mvs.shape[1] != 7:
-            raise LsfaError("mvs must be (n, 7) int32, got %s %s" % (tuple(mvs.shape), mvs.dtype))
+        if not isinstance(mvs, torch.Tensor) or mvs.dtype != torch.int32 or mvs.dim() != 2 or mvs.shape[1] != 7:
+            raise LsfaError("MotionVectorAccumulator.add_frame: mvs must be (n, 7) int32, got %s" % _arrived(mvs))
         n = mvs.shape[0]
         if max_block_area is not None:
             area = int(max_block_area)
@@ -1523,8 +1713,8 @@ class MotionVectorAccumulator(object):
 
     def residual(self, bgr_cur, bgr_ref, out=None):
         for t in (bgr_cur, bgr_ref):
-            if t.dtype != torch.uint8 or tuple(t.shape) != (self.height, self.width, 3):
-                raise LsfaError("frames must be (H, W, 3) uint8")
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or tuple(t.shape) != (self.height, self.width, 3):
+                raise LsfaError("MotionVectorAccumulator.residual: frames must be (%d, %d, 3) uint8, got %s" % (self.height, self.width, _arrived(t)))
         bgr_cur, bgr_ref = bgr_cur.to(self.device).contiguous(), bgr_ref.to(self.device).contiguous()
         res = self._map("MotionVectorAccumulator.residual", 3, out)
         with torch.cuda.device(self.device):
@@ -2039,6 +2229,17 @@ class SegmentMotionEstimator(object):
                             (who, n, have, self.frames))
         return n
 
+    def _outputs(self, who, n, im_scale, rcnn_stride, out):
+        """the caller's `out` pair, checked BEFORE the first launch of a segment (mv_segment_inputs, the last one, checks it again)"""
+        if out is None:
+            return
+        if not float(im_scale) > 0.0 or rcnn_stride < 1:
+            raise LsfaError("%s: im_scale %r must be positive and rcnn_stride %r at least 1" % (who, im_scale, rcnn_stride))
+        _, _, ph, pw = _resized(self.height, self.width, im_scale, rcnn_stride)
+        out = _given(who, "out", out, 2)
+        for i, c in enumerate((2, 3)):
+            _tensor(who, "output buffer out[%d]" % i, out[i], torch.float32, (n, self.clips, c, ph // rcnn_stride, pw // rcnn_stride), self.device)
+
     def _run(self, bgr, n, im_scale, pixel_means, pixel_scale, rcnn_stride, out, luma_done):
         H, W, C, s = self.height, self.width, self.clips, self._search
         N, blocks = C * (n + 1), self.mbh * self.mbw
@@ -2090,6 +2291,7 @@ class SegmentMotionEstimator(object):
                 raise LsfaError("SegmentMotionEstimator.segment: n = %d of a stack of %d frames needs clips = 1 (with more, hand over a stack of "
                                 "n + 1 frames per clip)" % (n, have))
             t = t[:, :n + 1]
+        self._outputs(who, n, im_scale, int(rcnn_stride), out)
         return self._run(t, n, im_scale, pixel_means, pixel_scale, int(rcnn_stride), out, False)
 
     def segment_yuv(self, y, uv=None, u=None, v=None, im_scale=1.0, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, rcnn_stride=16, out=None):
@@ -2102,6 +2304,7 @@ class SegmentMotionEstimator(object):
             raise LsfaError("SegmentMotionEstimator.segment_yuv: a (%d * (n + 1), %d, %d) uint8 Y stack on %s expected, got %s on %s" %
                             (C, H, W, self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
         n = self._length(int(y.shape[0]) // C - 1, None, 'segment_yuv')
+        self._outputs("SegmentMotionEstimator.segment_yuv", n, im_scale, int(rcnn_stride), out)
         if self._bgr is None:
             self._bgr = torch.empty(C * (self.frames + 1) * H * W * 3, dtype=torch.uint8, device=self.device)
         N = C * (n + 1)
