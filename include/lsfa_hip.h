@@ -667,6 +667,32 @@ int lsfa_mv_refine_chain(const unsigned char* luma, long long plane_stride, int 
 int lsfa_mv_cut_score(const unsigned char* luma, long long plane_stride, int n_chains, int n_frames, int width, int height,
                       const int* sad /* (n_chains, n_frames, mbh, mbw) */, int bias, int* intra /* (n_chains, n_frames, mbh, mbw) */,
                       int* unmatched /* (n_chains, n_frames) */, void* stream);
+/* Stale key frames (lsfa_amd/csrc/me_key.hip): a fourth, opt-in mode of the front end.  It stands in for an encoder's decision to spend an
+ * I-frame where the reference picture has stopped predicting - a fade or dissolve, content that pans in, occlusion that builds up, the
+ * drift of chained vectors: all invisible to the pair rule above, which no single pair of consecutive frames crosses.  Like the other three
+ * modes it replaces nothing of the reference (its key frames are a property of its dataset) and is comparable with nothing in it; no parity
+ * with any encoder's I-frame decision is claimed.  Defined by its own specification (DESIGN.md "Stale key frames", restated in numpy as
+ * tests/ref_me_stale.py) and bit-exact with that.  For chain c with planes P_0 (its key frame) .. P_F and the level-0 rows of frames 1..F as
+ * any of the searches wrote them:
+ *   q_f(p) = the walk back of lsfa_mv_segment_inputs above for pixel p of frame f through the rows of frames f .. 1, a step that would
+ *            leave the frame not taken: always inside the frame;
+ *   keysad[c][f - 1][b] = sum over the covered pixels p of macroblock b of |P_f[p] - P_0[q_f(p)]|  (<= 65,280): `res_diff` before its resize,
+ *            per block;
+ *   the decision is lsfa_mv_cut_score's, unchanged, with keysad as its `sad`: intra_b over the CURRENT plane f; b is unmatched against the key
+ *   iff keysad_b > intra_b + bias * n_b; frame f is stale iff unmatched * 100 > percent * mbh * mbw (the caller's).  bias (0..255) and percent
+ *   (1..100) are the mode's own, independent of the pair rule's.
+ * lsfa_mv_key_sad: the segment form.  luma is the stack lsfa_mv_estimate_chain takes, addressed and refused as there (negative plane_stride
+ *   included); rows (n_chains, n_frames, mbh * mbw, 7) under the CONTRACT of lsfa_mv_segment_inputs (other rows: the walk as stated, defined
+ *   and memory-safe); keysad (n_chains, n_frames, mbh, mbw) int32, written in full.  One launch (a wave per macroblock of every pair), no
+ *   workspace, no memset, no atomics, nothing read back.
+ * lsfa_mv_key_sad_accu: the per-frame form, for a frame whose source map exists: luma_cur (4-byte aligned) and luma_key (height, width)
+ *   uint8, accu (height, width, 2) int32 = the (x, y) in the key frame every pixel comes from, as lsfa_mv_accumulate leaves it (8-byte
+ *   aligned); keysad (mbh, mbw).  A source position outside the plane reads as 0 (lsfa_mv_accumulate never produces one).  On the map
+ *   accumulated from the rows of frames 1..f it equals lsfa_mv_key_sad's frame f bit for bit (the walk-back identity).  One launch. */
+int lsfa_mv_key_sad(const unsigned char* luma, long long plane_stride, int n_chains, int n_frames, int width, int height,
+                    const int* rows /* (n_chains, n_frames, mbh*mbw, 7) */, int* keysad /* (n_chains, n_frames, mbh, mbw) */, void* stream);
+int lsfa_mv_key_sad_accu(const unsigned char* luma_cur, const unsigned char* luma_key, const int* accu /* (height, width, 2) */, int width,
+                         int height, int* keysad /* (mbh, mbw) */, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip): the planes a decoder hands over - libav, the VCN decode engines, a raw .yuv dump - straight to

@@ -18,6 +18,13 @@ search says a new scene starts (hip.SegmentMotionEstimator(cut=...), DESIGN.md "
 its cut frames.  A cut frame is handed out with flag 1 like any key frame and the segment behind it is estimated from it; the pairs a
 segment estimated beyond its first cut are discarded.  Finding a segment's cut costs one readback (4 bytes per frame), and
 upcoming_key_frames estimates the coming segments ahead, as far as it has to, to announce the key frames that will really come.
+
+estimate_mv=dict(..., stale=dict(bias=..., percent=...)) (hip.SegmentMotionEstimator(stale=...), DESIGN.md "Stale key frames") also places
+one where the segment's key frame has stopped predicting the frame - a fade, a dissolve, content that pans in.  A stale frame is treated
+exactly like a cut frame: everything said of `cut` here holds for "cut or stale", and the frame the loader acts on is the first of a
+segment flagged by either rule (the estimator's first_cuts).  The key rule depends on where the segment started, so a video's key frames
+are no longer a function of a fixed set of frames: key_plan / next_key_frame are given, per segment, the first flagged frame behind its
+key frame - all the loader uses.
 """
 import numpy as np
 import torch
@@ -56,7 +63,8 @@ class TestLoader(object):
             estimate_mv = config.TEST.get('ESTIMATE_MV')
         self.estimate_mv = None if estimate_mv is None else dict(estimate_mv)
         self._estimators = {}           # (width, height) -> SegmentMotionEstimator
-        self.cut = self.estimate_mv is not None and self.estimate_mv.get('cut') is not None
+        # `cut` below: the pair rule (cut=) or the key rule (stale=) is on - a segment may end early, at its first flagged frame
+        self.cut = self.estimate_mv is not None and (self.estimate_mv.get('cut') is not None or self.estimate_mv.get('stale') is not None)
         # ((roidb index, key frame), n, mv (n, 1, 2, h, w), res (n, 1, 3, h, w), cut frame or None) of the segment under way
         self._segment = None
         self._segments = {}             # `cut`: (roidb index, key frame) -> such a tuple (None: nothing to estimate), the segments estimated ahead

@@ -55,6 +55,14 @@ __device__ __forceinline__ void wave_min(unsigned long long& best) {
   }
 }
 
+// the sum over `width` adjacent lanes (a power of two, the group aligned to it), in every lane of the group
+template <int width>
+__device__ __forceinline__ int lanes_sum(int v) {
+#pragma unroll
+  for (int o = width / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // the row of the block at (x0, y0) with the vector (dx, dy)
 __device__ __forceinline__ void store_row(int* __restrict__ row, int x0, int y0, int dx, int dy) {
   row[0] = -1; row[1] = 16; row[2] = 16;

@@ -39,14 +39,6 @@ struct CutArgs {
   long groups;                  // pairs * blocks: sixteen lanes each
 };
 
-// the sum over `width` adjacent lanes (a power of two, the group aligned to it), in every lane of the group
-template <int width>
-__device__ __forceinline__ int lanes_sum(int v) {
-#pragma unroll
-  for (int o = width / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kThreads) void cut_intra_kernel(const unsigned char* __restrict__ luma, CutArgs a, int* __restrict__ intra) {
   long g = ((long)blockIdx.x * kThreads + threadIdx.x) >> 4;       // sixteen lanes per macroblock
   const bool live = g < a.groups;

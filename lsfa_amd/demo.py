@@ -7,6 +7,7 @@ score above 0.7 after per-class NMS.
     python -m lsfa_amd.demo --frames DIR [--mv DIR] [--prefix P --epoch E] [--out dets.json]
     python -m lsfa_amd.demo --frames DIR --estimate-mv [--search 16 --mv-lambda 4] [--mv-levels L --mv-refine r] [--dump-mv DIR]
     python -m lsfa_amd.demo --frames DIR --estimate-mv --scene-cut [PERCENT] [--cut-bias B]     # a key frame wherever a new scene starts
+    python -m lsfa_amd.demo --frames DIR --estimate-mv --stale-key [PERCENT] [--stale-bias B]   # ... and wherever the key frame stops predicting (fades, pans)
 
     python -m lsfa_amd.demo --yuv clip.nv12 --size 1280x720 [--yuv-format nv12|i420] [--yuv-matrix bt601|bt709|jpeg] [--estimate-mv ...]
 
@@ -49,7 +50,8 @@ from lsfa_amd.utils.synthetic import SyntheticClip
 class FrameDirClip(object):
     """Frames of one clip from a directory, preprocessed like the reference's demo (:73-82).  estimate: None, or a dict of
     hip.MotionEstimator's parameters (search, lam, max_sad) - motion vectors and residuals are then estimated from the frames on
-    `device`; with cut=dict(...) among them mv_res returns None for a frame the estimator finds to start a new scene; dump_mv: a directory that receives them as the .npz files `mv_dir` is read from."""
+    `device`; with cut=dict(...) or stale=dict(...) among them mv_res returns None for a frame the estimator finds to start a new scene or to be
+    no longer predicted by its key frame; dump_mv: a directory that receives them as the .npz files `mv_dir` is read from."""
 
     def __init__(self, frame_dir, mv_dir, cfg, estimate=None, device='cuda:0', dump_mv=None):
         from PIL import Image
@@ -102,8 +104,8 @@ class FrameDirClip(object):
         for f in range(self._me_last + 1, i + 1):             # the P-frame chain: every frame against the one before it
             me.next_frame(self._frame_u8(f))
         self._me_last = i
-        if self.estimate.get('cut') is not None and me.is_cut():
-            return None                                       # frame i starts a new scene: the caller makes it a key frame
+        if (self.estimate.get('cut') is not None or self.estimate.get('stale') is not None) and me.is_cut():
+            return None                                       # frame i starts a new scene, or its key frame is stale: the caller makes it a key frame
         cfg = self.cfg
         cur, key = self._frame_u8(i), self._frame_u8(key_i)
         if self.dump_mv is not None:
@@ -196,8 +198,8 @@ class YuvFileClip(object):
         for f in range(self._me_last + 1, i + 1):             # the P-frame chain: every frame against the one before it
             me.next_frame_yuv(**self.planes(f))
         self._me_last = i
-        if self.estimate.get('cut') is not None and me.is_cut():
-            return None                                       # frame i starts a new scene: the caller makes it a key frame
+        if (self.estimate.get('cut') is not None or self.estimate.get('stale') is not None) and me.is_cut():
+            return None                                       # frame i starts a new scene, or its key frame is stale: the caller makes it a key frame
         cfg = self.cfg
         cur, key = me.bgr_cur, me.bgr_key
         if self.dump_mv is not None:
@@ -247,6 +249,13 @@ def parse_args(argv=None):
                          'becomes a key frame (DESIGN.md "Scene cuts"; a parameter, not a tuned value)')
     ap.add_argument('--cut-bias', type=int, default=4,
                     help='--scene-cut: grey levels per pixel a block\'s search residual may exceed its intra cost by, 0..255 (a parameter, not a tuned value)')
+    ap.add_argument('--stale-key', type=int, nargs='?', const=50, default=None, metavar='PERCENT',
+                    help='--estimate-mv: a frame more than PERCENT (1..100, default 50) of whose macroblocks the KEY frame, compensated with the '
+                         'accumulated vectors, does not predict becomes a key frame: fades, dissolves, slow pans (DESIGN.md "Stale key frames"; a '
+                         'parameter, not a tuned value).  Combines with --scene-cut')
+    ap.add_argument('--stale-bias', type=int, default=4,
+                    help='--stale-key: grey levels per pixel a block\'s residual against the key frame may exceed its intra cost by, 0..255 (a '
+                         'parameter, not a tuned value)')
     ap.add_argument('--dump-mv', default=None, help='--estimate-mv: write the estimated mv / res as the .npz files --mv reads')
     ap.add_argument('--num', type=int, default=30, help='frames of the synthetic clip')
     ap.add_argument('--interval', type=int, default=10, help='key frame interval (demo.py:68)')
@@ -282,6 +291,8 @@ def parse_args(argv=None):
         ap.error('--dump-mv needs --estimate-mv')
     if args.scene_cut is not None and (not args.estimate_mv or not 1 <= args.scene_cut <= 100 or not 0 <= args.cut_bias <= 255):
         ap.error('--scene-cut PERCENT (1..100) needs --estimate-mv; --cut-bias is 0..255')
+    if args.stale_key is not None and (not args.estimate_mv or not 1 <= args.stale_key <= 100 or not 0 <= args.stale_bias <= 255):
+        ap.error('--stale-key PERCENT (1..100) needs --estimate-mv; --stale-bias is 0..255')
     return args
 
 
@@ -297,6 +308,8 @@ def main(argv=None):
     estimate = dict(search=args.search, lam=args.mv_lambda, levels=args.mv_levels, refine=args.mv_refine) if args.estimate_mv else None
     if args.scene_cut is not None:
         estimate['cut'] = dict(bias=args.cut_bias, percent=args.scene_cut)
+    if args.stale_key is not None:
+        estimate['stale'] = dict(bias=args.stale_bias, percent=args.stale_key)
     if args.yuv:
         clip = YuvFileClip(args.yuv, args.yuv_size[0], args.yuv_size[1], cfg, args.yuv_format, args.yuv_matrix, estimate, dev, args.dump_mv)
     else:
@@ -315,12 +328,12 @@ def main(argv=None):
     classes = None       # class names live in the dataset (imdb.classes); ids are reported without one
 
     results, total, count = [], 0.0, 0
-    key_idx = 0          # the running key frame: every `interval` frames behind the last one - or, with --scene-cut, where a scene starts
+    key_idx = 0          # the running key frame: every `interval` frames behind the last one - or, with --scene-cut / --stale-key, where a scene starts or the key frame is stale
     for idx in range(clip.num_frames):
         data = clip.frame(idx).to(dev)
         is_key = idx == 0 or idx - key_idx == args.interval
         mv_res = None if is_key else clip.mv_res(idx, key_idx)
-        if mv_res is None:       # --scene-cut: the estimator's next_frame* found a cut; the clip starts its chain over at this frame (key_frame*)
+        if mv_res is None:       # --scene-cut / --stale-key: the estimator's next_frame* found a cut or a stale key frame; the clip starts its chain over at this frame (key_frame*)
             is_key, key_idx = True, idx
         mv, res = (None, None) if is_key else [t.to(dev) for t in mv_res]
         torch.cuda.synchronize()

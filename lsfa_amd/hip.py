@@ -1743,6 +1743,11 @@ ME_LEVELS, ME_REFINE = 0, 2
 # unmatched is a cut.
 ME_CUT_BIAS, ME_CUT_PERCENT = 4, 50
 
+# ---- stale key frames (lsfa_amd/csrc/me_key.hip) ------------------------------------------------------------------------------------------------
+# The same rule against the KEY frame (the block's SAD against its walked-back source there), with parameters of its own - parameters, not
+# tuned values, and independent of the pair rule's.
+ME_STALE_BIAS, ME_STALE_PERCENT = 4, 50
+
 
 def me_reach(levels, search, refine=ME_REFINE):
     """the longest vector component, in pixels, the search can return: search * 2^levels + refine * (2^levels - 1)"""
@@ -1916,14 +1921,16 @@ def cut_flags(unmatched, blocks, percent=ME_CUT_PERCENT):
     return np.asarray(unmatched, dtype=np.int64) * 100 > int(percent) * int(blocks)
 
 
-def _cut_params(who, cut):
-    """cut=None | dict(bias=..., percent=...) -> None | (bias, percent), checked"""
+def _cut_params(who, cut, name='cut', defaults=(ME_CUT_BIAS, ME_CUT_PERCENT)):
+    """cut=None | dict(bias=..., percent=...) -> None | (bias, percent), checked (`name`: the keyword, cut or stale)"""
     if cut is None:
         return None
+    if not isinstance(cut, dict):
+        raise LsfaError("%s: %s takes a dict of bias (0..255) and percent (1..100), got %r" % (who, name, cut))
     extra = set(cut) - {'bias', 'percent'}
-    bias, percent = int(cut.get('bias', ME_CUT_BIAS)), int(cut.get('percent', ME_CUT_PERCENT))
+    bias, percent = int(cut.get('bias', defaults[0])), int(cut.get('percent', defaults[1]))
     if extra or not 0 <= bias <= 255 or not 1 <= percent <= 100:
-        raise LsfaError("%s: cut takes bias (0..255) and percent (1..100), got %r" % (who, dict(cut)))
+        raise LsfaError("%s: %s takes bias (0..255) and percent (1..100), got %r" % (who, name, dict(cut)))
     return bias, percent
 
 
@@ -1956,8 +1963,10 @@ class _MotionSearch(object):
     every level for `planes` luma planes and `pairs` pairs - flat, so that any run of planes is a stack of its own in front of the same
     memory - and the coarse-to-fine sequence on a stack of them."""
 
-    def __init__(self, who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes, pairs, cut=None):
+    def __init__(self, who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes, pairs, cut=None, stale=None,
+                 keep_key=False):
         self.cut = _cut_params(who, cut)
+        self.stale = _cut_params(who, stale, 'stale', (ME_STALE_BIAS, ME_STALE_PERCENT))
         self.levels, self.refine = int(levels), int(refine)
         if not 0 <= self.levels <= 2:
             raise LsfaError("%s: levels %d is outside 0..2" % (who, self.levels))
@@ -1983,7 +1992,17 @@ class _MotionSearch(object):
         self.sad = torch.empty(pairs * self.blocks[0], dtype=torch.int32, device=self.device)
         # scene cuts (cut=dict(bias, percent)): every block's intra cost and every pair's count of unmatched blocks
         self.intra = torch.empty(pairs * self.blocks[0], dtype=torch.int32, device=self.device) if self.cut else None
-        self.unmatched = torch.empty(pairs, dtype=torch.int32, device=self.device) if self.cut else None
+        # stale key frames (stale=dict(bias, percent)): every block's SAD against the key frame, its intra cost once more (lsfa_mv_cut_score
+        # writes it with every call; DESIGN.md "Stale key frames") and every frame's count of blocks the key frame does not predict
+        self.keysad = torch.empty(pairs * self.blocks[0], dtype=torch.int32, device=self.device) if self.stale else None
+        self.key_intra = torch.empty(pairs * self.blocks[0], dtype=torch.int32, device=self.device) if self.stale else None
+        # the counts of both rules lie in one buffer, the pair rule's first: read_cuts reads them back together
+        modes = (1 if self.cut else 0) + (1 if self.stale else 0)
+        self._counts = torch.empty(modes * pairs, dtype=torch.int32, device=self.device) if modes else None
+        self.unmatched = self._counts[:pairs] if self.cut else None
+        self.key_unmatched = self._counts[modes * pairs - pairs:] if self.stale else None
+        # frame by frame (keep_key) the key frame's luma outlives the two ping-pong planes: a third level-0 plane
+        self.key_plane = torch.empty(self.plane[0], dtype=torch.uint8, device=self.device) if self.stale and keep_key else None
 
     def planes(self, k, first, count):
         """planes first .. first + count - 1 of level k as (count, h_k, w_k)"""
@@ -2023,11 +2042,39 @@ class _MotionSearch(object):
                                                self.height, _ptr(self.sad), self.cut[0], _ptr(self.intra), _ptr(self.unmatched), _stream()),
                        "lsfa_mv_cut_score")
 
+    def keep_key_plane(self, index):
+        """level-0 plane `index` holds a key frame: with `stale` and keep_key it is copied to the third plane (one launch), else nothing"""
+        if self.key_plane is not None:
+            ps = self.plane[0]
+            copy_many([(self.key_plane.view(torch.int32), self.flat[0][index * ps:(index + 1) * ps].view(torch.int32))])
+
+    def key_score(self, chains, frames, first=0, step=1, accu=None):
+        """The key rule behind run() on the same stack (nothing without `stale`): every block's SAD against its chain's key frame -
+        lsfa_mv_key_sad, the walk back through self.rows[0]; or, with accu (H, W, 2) the accumulated source map of ONE pair whose key
+        frame lies in self.key_plane, lsfa_mv_key_sad_accu - into the front of self.keysad, then lsfa_mv_cut_score with it in the place
+        of the search's SAD: self.key_intra, self.key_unmatched."""
+        if not self.stale:
+            return
+        luma, stride = _ptr(self.flat[0][first * self.plane[0]:]), step * self.plane[0]
+        with torch.cuda.device(self.device):
+            if accu is None:
+                _check(lib().lsfa_mv_key_sad(luma, stride, chains, frames, self.width, self.height, _ptr(self.rows[0]), _ptr(self.keysad), _stream()),
+                       "lsfa_mv_key_sad")
+            else:
+                _tensor("_MotionSearch.key_score", "accu", accu, torch.int32, (self.height, self.width, 2), self.device)
+                _check(lib().lsfa_mv_key_sad_accu(_ptr(self.flat[0][(first + step) * self.plane[0]:]), _ptr(self.key_plane), _ptr(accu), self.width,
+                                                  self.height, _ptr(self.keysad), _stream()), "lsfa_mv_key_sad_accu")
+            _check(lib().lsfa_mv_cut_score(luma, stride, chains, frames, self.width, self.height, _ptr(self.keysad), self.stale[0], _ptr(self.key_intra),
+                                           _ptr(self.key_unmatched), _stream()), "lsfa_mv_cut_score")
+
     def read_cuts(self, count):
-        """the one readback: synchronises the current stream and returns the first `count` pairs' cut flags as a numpy bool array"""
+        """the one readback: synchronises the current stream and returns the first `count` pairs' flags - the pair rule's (`cut`) OR the key
+        rule's (`stale`), whichever are on - as a numpy bool array; 4 * count bytes per rule"""
         with torch.cuda.device(self.device):
             torch.cuda.current_stream().synchronize()
-        return cut_flags(self.unmatched[:count].cpu().numpy(), self.blocks[0], self.cut[1])
+        rules = [r for r in (self.cut, self.stale) if r]
+        counts = self._counts.view(len(rules), -1)[:, :count].cpu().numpy()
+        return np.logical_or.reduce([cut_flags(c, self.blocks[0], r[1]) for c, r in zip(counts, rules)])
 
 
 class MotionEstimator(object):
@@ -2062,13 +2109,23 @@ class MotionEstimator(object):
     cut=dict(bias=..., percent=...) (either may be left out; default None: every launch and every bit as without it) adds scene-cut
     detection (lsfa_mv_cut_score, two launches behind the search; DESIGN.md "Scene cuts"): after next_frame / next_frame_yuv, self.unmatched
     is the (1,) int32 device count of blocks the previous frame does not predict, and is_cut() - the one readback, a synchronisation -
-    says whether the frame starts a new scene: the caller then hands the same frame to key_frame / key_frame_yuv."""
+    says whether the frame starts a new scene: the caller then hands the same frame to key_frame / key_frame_yuv.
+
+    stale=dict(bias=..., percent=...) (either may be left out; default None: every launch and every bit as without it) adds the key rule
+    (DESIGN.md "Stale key frames"): the same decision on every block's SAD against the KEY frame, compensated with the accumulated vectors -
+    what a fade, a dissolve or a slow pan spoils although no pair of consecutive frames shows it.  key_frame / key_frame_yuv keep the key
+    frame's luma in a third plane (one copy launch); next_frame / next_frame_yuv run three more launches behind the accumulation (the key
+    SAD from self.acc.accu, the intra cost and the count).  self.keysad is the (mbh, mbw) SAD against the key frame, self.key_unmatched
+    the (1,) int32 device count, and is_cut() is true where either rule flags the frame (one readback for both).  Every buffer is
+    allocated at construction."""
 
     def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr', matrix='bt601',
-                 levels=ME_LEVELS, refine=ME_REFINE, cut=None):
+                 levels=ME_LEVELS, refine=ME_REFINE, cut=None, stale=None):
         s = self._search = _MotionSearch("MotionEstimator", width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes=2, pairs=1,
-                                         cut=cut)
+                                         cut=cut, stale=stale, keep_key=True)
         self.cut, self.unmatched = s.cut, s.unmatched
+        self.stale, self.key_unmatched = s.stale, s.key_unmatched
+        self.keysad = s.keysad.view(s.mbh, s.mbw) if s.stale else None
         self.width, self.height, self.device = s.width, s.height, s.device
         self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
         self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
@@ -2088,6 +2145,7 @@ class MotionEstimator(object):
     def _key(self):
         """the reference plane holds a key frame: its pyramid, and the accumulation starts over"""
         self._search.pyramid(self._ref, 1)
+        self._search.keep_key_plane(self._ref)
         self.acc.reset()
 
     def _next(self, cur):
@@ -2100,6 +2158,7 @@ class MotionEstimator(object):
         else:
             self._search.run(1, 1, self._ref, cur - self._ref, built=1)
         self.acc.add_frame(self.rows, max_block_area=256)      # the explicit area: no device-to-host read
+        self._search.key_score(1, 1, self._ref, cur - self._ref, accu=self.acc.accu)
         self._ref = cur
 
     def key_frame(self, bgr):
@@ -2115,10 +2174,11 @@ class MotionEstimator(object):
         return self.rows
 
     def is_cut(self):
-        """Does the frame the last next_frame / next_frame_yuv took start a new scene?  Synchronises the current stream and reads
-        self.unmatched (4 bytes): the one readback of the mode."""
-        if not self.cut:
-            raise LsfaError("MotionEstimator.is_cut: the estimator was built without cut=")
+        """Does the frame the last next_frame / next_frame_yuv took start a new scene (`cut`), or has its key frame stopped predicting it
+        (`stale`)?  Synchronises the current stream and reads self.unmatched / self.key_unmatched (4 bytes each): the one readback of the
+        modes."""
+        if not self.cut and not self.stale:
+            raise LsfaError("MotionEstimator.is_cut: the estimator was built without cut= or stale=")
         return bool(self._search.read_cuts(1)[0])
 
     @property
@@ -2199,17 +2259,25 @@ class SegmentMotionEstimator(object):
     stream, into buffers allocated up front.  segment / segment_yuv return what they return without it; self.unmatched is the (C, n)
     device view of the last call's counts of unmatched blocks, self.intra (C, n, mbh, mbw) the blocks' intra costs, and first_cuts() - the
     one readback, a synchronisation - gives per clip the first frame that starts a new scene.  The inputs of the frames from a cut on
-    were estimated across it: the caller discards them and makes the cut frame a key frame."""
+    were estimated across it: the caller discards them and makes the cut frame a key frame.
+
+    stale=dict(bias=..., percent=...) (either may be left out; default None, as above) adds the key rule (DESIGN.md "Stale key frames"): the
+    same decision on every block's SAD against the segment's KEY frame, compensated with the walk back through the rows - `res_diff` before
+    its resize - which a fade, a dissolve or a slow pan spoils although no pair of consecutive frames shows it.  Three more launches
+    between the search and the inputs (the key SAD, the intra cost and the count), into buffers allocated up front: self.keysad (C, n, mbh,
+    mbw), self.key_unmatched (C, n).  first_cuts() then gives per clip the first frame EITHER rule flags, still with one readback."""
 
     def __init__(self, width, height, frames=9, clips=1, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr',
-                 matrix='bt601', levels=ME_LEVELS, refine=ME_REFINE, cut=None):
+                 matrix='bt601', levels=ME_LEVELS, refine=ME_REFINE, cut=None, stale=None):
         who = "SegmentMotionEstimator"
         self.frames, self.clips = int(frames), int(clips)
         if self.frames < 1 or self.clips < 1 or int(width) < 1 or int(height) < 1:
             raise LsfaError("%s: frames %d, clips %d and the %d x %d frame must all be at least 1" % (who, self.frames, self.clips, int(width), int(height)))
         s = self._search = _MotionSearch(who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine,
-                                         planes=self.clips * (self.frames + 1), pairs=self.clips * self.frames, cut=cut)
+                                         planes=self.clips * (self.frames + 1), pairs=self.clips * self.frames, cut=cut,
+                                         stale=stale)
         self.cut, self.intra, self.unmatched = s.cut, None, None
+        self.stale, self.keysad, self.key_unmatched = s.stale, None, None
         self.width, self.height, self.device = s.width, s.height, s.device
         self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
         self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
@@ -2247,6 +2315,8 @@ class SegmentMotionEstimator(object):
         self.sad = s.sad[:C * n * blocks].view(C, n, self.mbh, self.mbw)
         if self.cut:
             self.intra, self.unmatched = s.intra[:C * n * blocks].view(C, n, self.mbh, self.mbw), s.unmatched[:C * n].view(C, n)
+        if self.stale:
+            self.keysad, self.key_unmatched = s.keysad[:C * n * blocks].view(C, n, self.mbh, self.mbw), s.key_unmatched[:C * n].view(C, n)
         luma = s.planes(0, 0, N)
         if not luma_done and s.plane[0] == H * W:
             luma_u8(bgr.view(N * H, W, 3), out=luma.view(N * H, W))     # pointwise: a stack is one tall frame
@@ -2254,6 +2324,7 @@ class SegmentMotionEstimator(object):
             for i, frame in enumerate(bgr.view(N, H, W, 3)):
                 luma_u8(frame, out=luma[i])
         s.run(C, n)
+        s.key_score(C, n)
         if out is None:
             h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
             key = (n, ph // rcnn_stride, pw // rcnn_stride)
@@ -2264,11 +2335,12 @@ class SegmentMotionEstimator(object):
         return mv_segment_inputs(self.rows, bgr, im_scale, pixel_means, pixel_scale, rcnn_stride, out=out)
 
     def first_cuts(self, n=None):
-        """Per clip the first frame f = 1..n (default: the last call's length) of the last segment whose pair (f, f - 1) is a cut, or None.
-        Synchronises the current stream and reads self.unmatched (4 * C * n bytes) once: the one readback of the mode."""
-        if not self.cut or self.unmatched is None:
-            raise LsfaError("SegmentMotionEstimator.first_cuts: needs cut= and a segment() / segment_yuv() call before it")
-        C, have = int(self.unmatched.shape[0]), int(self.unmatched.shape[1])
+        """Per clip the first frame f = 1..n (default: the last call's length) of the last segment whose pair (f, f - 1) is a cut (`cut`) or
+        which its key frame has stopped predicting (`stale`), or None.  Synchronises the current stream and reads self.unmatched /
+        self.key_unmatched (4 * C * n bytes each) once: the one readback of the modes."""
+        if not (self.cut or self.stale) or self.rows is None:
+            raise LsfaError("SegmentMotionEstimator.first_cuts: needs cut= or stale= and a segment() / segment_yuv() call before it")
+        C, have = int(self.rows.shape[0]), int(self.rows.shape[1])
         n = have if n is None else int(n)
         if not 1 <= n <= have:
             raise LsfaError("SegmentMotionEstimator.first_cuts: n = %d; the last segment holds %d frames" % (n, have))

@@ -5,6 +5,7 @@ parse --cfg, build the test symbols, shard videos over the ranks, run pred_eval,
     python -m lsfa_amd.test [--cfg YAML] [--clips N] [--frames F] [--height H] [--width W] [--prefix P --epoch E]
     python -m lsfa_amd.test --segment -1 --key-group 2 --estimate-mv [--search R --mv-lambda L --mv-levels L --mv-refine r]      # frames alone: no motion vectors handed in
     python -m lsfa_amd.test --estimate-mv --scene-cut [PERCENT] [--cut-bias B] [--synthetic-cuts 7,15]      # key frames where a new scene starts
+    python -m lsfa_amd.test --estimate-mv --stale-key [PERCENT] [--stale-bias B] [--synthetic-dissolves 7:6]      # ... and where the key frame stops predicting
     python -m torch.distributed.run --nproc-per-node 8 -m lsfa_amd.test --clips 8
 
 Without a dataset or weights in the image, clips are synthetic (lsfa_amd.utils.synthetic) and the
@@ -57,7 +58,16 @@ def parse_args():
                          'becomes a key frame (DESIGN.md "Scene cuts"; a parameter, not a tuned value)')
     ap.add_argument('--cut-bias', type=int, default=4,
                     help='--scene-cut: grey levels per pixel a block\'s search residual may exceed its intra cost by, 0..255 (a parameter, not a tuned value)')
+    ap.add_argument('--stale-key', type=int, nargs='?', const=50, default=None, metavar='PERCENT',
+                    help='--estimate-mv: a frame more than PERCENT (1..100, default 50) of whose macroblocks the KEY frame, compensated with the '
+                         'accumulated vectors, does not predict becomes a key frame: fades, dissolves, slow pans (DESIGN.md "Stale key frames"; a '
+                         'parameter, not a tuned value).  Combines with --scene-cut')
+    ap.add_argument('--stale-bias', type=int, default=4,
+                    help='--stale-key: grey levels per pixel a block\'s residual against the key frame may exceed its intra cost by, 0..255 (a '
+                         'parameter, not a tuned value)')
     ap.add_argument('--synthetic-cuts', default='', help='frames at which every synthetic clip starts a new scene, e.g. 7,15 (default: none)')
+    ap.add_argument('--synthetic-dissolves', default='',
+                    help='START:LENGTH of the dissolves of every synthetic clip into a new scene, separated by commas, e.g. 7:6 (default: none)')
     ap.add_argument('--out', default=None, help='rank 0 saves the gathered detection rows (n,7) here (.npy)')
     ap.add_argument('--shards-out', default=None, help='rank 0 saves which videos each rank ran (a JSON list per rank, gathered from the ranks themselves)')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'],
@@ -65,10 +75,18 @@ def parse_args():
     args = ap.parse_args()
     if args.scene_cut is not None and (not args.estimate_mv or not 1 <= args.scene_cut <= 100 or not 0 <= args.cut_bias <= 255):
         ap.error('--scene-cut PERCENT (1..100) needs --estimate-mv; --cut-bias is 0..255')
+    if args.stale_key is not None and (not args.estimate_mv or not 1 <= args.stale_key <= 100 or not 0 <= args.stale_bias <= 255):
+        ap.error('--stale-key PERCENT (1..100) needs --estimate-mv; --stale-bias is 0..255')
     try:
         args.synthetic_cuts = tuple(int(v) for v in args.synthetic_cuts.split(',') if v.strip())
     except ValueError:
         ap.error('--synthetic-cuts takes frame numbers separated by commas, got %r' % (args.synthetic_cuts,))
+    try:
+        args.synthetic_dissolves = tuple(tuple(int(n) for n in v.split(':')) for v in args.synthetic_dissolves.split(',') if v.strip())
+        if any(len(d) != 2 for d in args.synthetic_dissolves):
+            raise ValueError
+    except ValueError:
+        ap.error('--synthetic-dissolves takes START:LENGTH pairs separated by commas, got %r' % (args.synthetic_dissolves,))
     return args
 
 
@@ -85,6 +103,8 @@ def main():
         cfg.TEST.ESTIMATE_MV = dict(search=args.search, lam=args.mv_lambda, levels=args.mv_levels, refine=args.mv_refine)
         if args.scene_cut is not None:
             cfg.TEST.ESTIMATE_MV['cut'] = dict(bias=args.cut_bias, percent=args.scene_cut)
+        if args.stale_key is not None:
+            cfg.TEST.ESTIMATE_MV['stale'] = dict(bias=args.stale_bias, percent=args.stale_key)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     # one-GPU boxes: LSFA_BENCH_BACKEND=gloo LSFA_BENCH_ONE_DEVICE=1 puts every rank on cuda:0 and runs the final
@@ -103,7 +123,8 @@ def main():
             dist.init_process_group(backend)
     logging.basicConfig(level=logging.INFO, format='%(asctime)s %(message)s')
     logger = logging.getLogger('lsfa')
-    roidb = synthetic_roidb(args.clips, args.frames, args.height, args.width, cfg.TEST.KEY_FRAME_INTERVAL, cuts=args.synthetic_cuts)
+    roidb = synthetic_roidb(args.clips, args.frames, args.height, args.width, cfg.TEST.KEY_FRAME_INTERVAL, cuts=args.synthetic_cuts,
+                            dissolves=args.synthetic_dissolves)
     if args.prefix:
         arg_params, aux_params = load_param(args.prefix, args.epoch, process=True)
         net = resnet_v1_101_flownet_rfcn(cfg)

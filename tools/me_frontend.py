@@ -27,7 +27,13 @@ configuration whose reach is at least 32 takes no longer per segment than the fu
 "Scene cuts") at L = 0 / R = 16 and L = 2 / R = 8 in the same alternating rounds, then lsfa_mv_cut_score alone (both its launches) next to
 the luma launch of the same stack.  With --kernels-only the cut form is run a few times without timing (for a kernel trace that splits the
 two launches).  Nothing is gated: the figures to read off are the difference of the medians against the spreads, and the cut launches
-against the luma launch."""
+against the luma launch.
+
+--segment --stale [--levels 2] [--size WxH] runs the stale-key leg instead (profiles/r11/me_stale.txt): the segment form without and with
+stale= (DESIGN.md "Stale key frames") at L = 0 / R = 16, or with --levels 2 at L = 2 / R = 8, in the same alternating rounds, then alone: the
+level-0 search launch of that configuration (mv_estimate_chain, or the level-0 mv_refine_chain), lsfa_mv_key_sad, the mode's three
+launches together, and lsfa_mv_key_sad on the same planes as five chains of one frame (no table walk: what the walk costs per pair).  The expectation to read off - not gated: what the mode adds per segment stays below that level-0 search launch,
+beyond the spread.  With --kernels-only the stale form is run a few times without timing (for a kernel trace)."""
 import argparse
 import json
 import os
@@ -239,6 +245,65 @@ def cut_leg(reps, time_limit, kernels_only):
     print(json.dumps(out))
 
 
+def stale_leg(reps, time_limit, levels, refine, kernels_only):
+    import signal
+
+    def too_long(signum, frame):
+        raise SystemExit('the stale-key leg ran into its time limit of %d s' % time_limit)
+
+    signal.signal(signal.SIGALRM, too_long)
+    signal.alarm(time_limit)
+    F, R = 9, 8 if levels else 16
+    clip = SyntheticClip(0, F + 1, H, W)
+    stack = torch.stack([clip.frame_u8(f) for f in range(F + 1)]).unsqueeze(0).to(DEV)
+    out = dict(device=torch.cuda.get_device_name(0), frame='%dx%d' % (W, H), frames=F, clips=1, segments_per_graph=reps, levels=levels, search=R)
+    kw = dict(frames=F, device=DEV, search=R, levels=levels, refine=refine)
+    plain, stale = hip.SegmentMotionEstimator(W, H, **kw), hip.SegmentMotionEstimator(W, H, stale=dict(), **kw)
+    want = [x.clone() for x in plain.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)]
+    got = stale.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(stale.rows, plain.rows)
+    if kernels_only:
+        for _ in range(20):
+            stale.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)
+        torch.cuda.synchronize()
+        signal.alarm(0)
+        return
+    r = alternating([('segment', lambda: plain.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0)),
+                     ('segment_stale', lambda: stale.segment(stack, 1.0, (0.0, 0.0, 0.0), 1.0))], reps)
+    a, b = r['segment'], r['segment_stale']
+    r['stale_costs_us'] = round(b['median'] - a['median'], 2)
+    r['spread_us'] = round(max(a['max'] - a['min'], b['max'] - b['min']), 2)
+    r['launches'] = dict(segment=levels + (4 if levels else 3), segment_stale=levels + (4 if levels else 3) + 3)
+    r['key_unmatched'] = stale.key_unmatched.cpu().tolist()
+    s = stale._search
+    luma = s.planes(0, 0, F + 1).unsqueeze(0)
+    rows0 = s.rows[0][:F * s.blocks[0] * 7].view(1, F, s.blocks[0], 7)
+    if levels:
+        rows1 = s.rows[1][:F * s.blocks[1] * 7].view(1, F, s.blocks[1], 7)
+        search = ('mv_refine_chain_level0', lambda: hip.mv_refine_chain(luma, rows1, refine, 4, 0, out=rows0))
+    else:
+        search = ('mv_estimate_chain', lambda: hip.mv_estimate_chain(luma, R, 4, 0, out=rows0))
+
+    def key_sad():
+        hip._check(hip.lib().lsfa_mv_key_sad(luma.data_ptr(), s.plane[0], 1, F, W, H, rows0.data_ptr(), s.keysad.data_ptr(), hip._stream()), 'lsfa_mv_key_sad')
+
+    def key_sad_no_walk():
+        # the same ten planes as five chains of ONE frame: five pairs whose only step is the block's own row (scalar loads), no table gather
+        hip._check(hip.lib().lsfa_mv_key_sad(luma.data_ptr(), s.plane[0], 5, 1, W, H, rows0.data_ptr(), s.keysad.data_ptr(), hip._stream()), 'lsfa_mv_key_sad')
+
+    r['alone'] = alternating([search, ('mv_key_sad', key_sad), ('key_score(three launches)', lambda: s.key_score(1, F)),
+                              ('mv_key_sad_five_pairs_of_one_step', key_sad_no_walk)], reps)
+    # per pair: nine pairs that walk 0..8 table steps against five that walk none - what the walk's table loads cost
+    r['key_sad_us_per_pair'] = dict(walking=round(r['alone']['mv_key_sad']['median'] / F, 2),
+                                    one_step=round(r['alone']['mv_key_sad_five_pairs_of_one_step']['median'] / 5, 2))
+    r['level0_search_us'] = r['alone'][search[0]]['median']
+    r['adds_less_than_the_level0_search_beyond_spread'] = bool(r['stale_costs_us'] + r['spread_us'] < r['level0_search_us'])
+    out['L%d_R%d' % (levels, R)] = r
+    signal.alarm(0)
+    print(json.dumps(out))
+
+
 def non_key_frame(iters):
     from lsfa_amd.config.config import lsfa_test_config
     from lsfa_amd.symbols import params as P
@@ -275,6 +340,7 @@ def main():
     ap.add_argument('--levels', type=int, default=0, choices=(0, 1, 2), help='--segment: the pyramid leg with this many extra levels (0: the segment leg)')
     ap.add_argument('--refine', type=int, default=2, choices=(1, 2, 3), help='--levels: the refinement radius')
     ap.add_argument('--cut', action='store_true', help='--segment: the scene-cut leg (the segment form without and with cut=)')
+    ap.add_argument('--stale', action='store_true', help='--segment: the stale-key leg (the segment form without and with stale=), at --levels 0 or 2')
     ap.add_argument('--size', default=None, help='--segment: the frame size as WxH (default 1000x600)')
     args = ap.parse_args()
     if args.size:
@@ -285,6 +351,10 @@ def main():
         if not args.segment:
             ap.error('--cut belongs to --segment')
         return cut_leg(args.segment_reps, args.time_limit, args.kernels_only)
+    if args.stale:
+        if not args.segment:
+            ap.error('--stale belongs to --segment')
+        return stale_leg(args.segment_reps, args.time_limit, args.levels, args.refine, args.kernels_only)
     if args.segment and args.levels:
         return pyramid_leg(args.segment_reps, args.time_limit, args.levels, args.refine)
     if args.segment:
