@@ -26,8 +26,15 @@ segment flagged by either rule (the estimator's first_cuts).  The key rule depen
 are no longer a function of a fixed set of frames: key_plan / next_key_frame are given, per segment, the first flagged frame behind its
 key frame - all the loader uses.
 """
+import collections
+
 import numpy as np
 import torch
+
+from lsfa_amd.utils.motion_options import ends_early
+
+# the estimated segment behind a key frame: tag = (roidb index, key frame), n non-key frames, mv (n, 1, 2, h, w), res (n, 1, 3, h, w), cut frame or None
+Segment = collections.namedtuple('Segment', 'tag n mv res cut_f')
 
 
 def next_key_frame(key_f, length, interval, cuts):
@@ -64,10 +71,9 @@ class TestLoader(object):
         self.estimate_mv = None if estimate_mv is None else dict(estimate_mv)
         self._estimators = {}           # (width, height) -> SegmentMotionEstimator
         # `cut` below: the pair rule (cut=) or the key rule (stale=) is on - a segment may end early, at its first flagged frame
-        self.cut = self.estimate_mv is not None and (self.estimate_mv.get('cut') is not None or self.estimate_mv.get('stale') is not None)
-        # ((roidb index, key frame), n, mv (n, 1, 2, h, w), res (n, 1, 3, h, w), cut frame or None) of the segment under way
-        self._segment = None
-        self._segments = {}             # `cut`: (roidb index, key frame) -> such a tuple (None: nothing to estimate), the segments estimated ahead
+        self.cut = ends_early(self.estimate_mv)
+        self._segment = None            # the Segment under way
+        self._segments = {}             # `cut`: (roidb index, key frame) -> Segment (None: nothing to estimate), the segments estimated ahead
         self.cfg, self.roidb, self.batch_size, self.shuffle, self.has_rpn = config, roidb, batch_size, shuffle, has_rpn
         self.device = device
         self.size = int(np.sum([x['frame_seg_len'] for x in self.roidb]))
@@ -162,10 +168,10 @@ class TestLoader(object):
 
     def _compute_segment(self, index, entry, key_f):
         """One SegmentMotionEstimator.segment call on the current stream for key frame key_f of video `index` and the non-key frames behind
-        it - key_f + 1 .. key_f + n with n = KEY_FRAME_INTERVAL - 1, fewer in front of the video's last frame (a key frame) -> ((index,
-        key_f), n, mv (n, 1, 2, h, w), res (n, 1, 3, h, w), cut frame or None), or None where no frame follows the key frame.  The result
-        is copied out of the estimator's buffers: a pipeline that groups key frames holds a segment's inputs while the next segment is
-        estimated.  With `cut` the segment ends in front of its first cut frame (one readback) and the pairs from there on are dropped."""
+        it - key_f + 1 .. key_f + n with n = KEY_FRAME_INTERVAL - 1, fewer in front of the video's last frame (a key frame) -> a Segment,
+        or None where no frame follows the key frame.  The result is copied out of the estimator's buffers: a pipeline that groups key
+        frames holds a segment's inputs while the next segment is estimated.  With `cut` the segment ends in front of its first cut
+        frame (one readback) and the pairs from there on are dropped."""
         n = min(key_f + self.cfg.TEST.KEY_FRAME_INTERVAL - 1, entry['frame_seg_len'] - 2) - key_f
         if n < 1:
             return None
@@ -180,13 +186,13 @@ class TestLoader(object):
             first = self._estimators[key].first_cuts()[0]
             if first is not None:        # frame key_f + first starts a new scene: it becomes a key frame
                 cut_f, n = key_f + first, first - 1
-        return ((index, key_f), n, mv[:n].clone(), res[:n].clone(), cut_f)
+        return Segment((index, key_f), n, mv[:n].clone(), res[:n].clone(), cut_f)
 
     def _estimate_segment(self, entry, key_f):
         """Key frame key_f is being handed out: the segment behind it becomes the one under way - estimated now, or taken from what
         upcoming_key_frames estimated ahead (`cut` only)."""
         tag = (self.cur_roidb_index, key_f)
-        if self._segment is not None and self._segment[0] == tag:
+        if self._segment is not None and self._segment.tag == tag:
             return                       # get_batch runs twice for the very first frame (the constructor's shape probe)
         self._segment = None
         for old in [t for t in self._segments if t < tag]:       # the iteration has passed them
@@ -196,7 +202,7 @@ class TestLoader(object):
     def _segment_ahead(self, entry, key_f):
         """`cut`: the segment behind a coming key frame of the current video, estimated once and kept until the iteration reaches it"""
         tag = (self.cur_roidb_index, key_f)
-        if self._segment is not None and self._segment[0] == tag:
+        if self._segment is not None and self._segment.tag == tag:
             return self._segment
         if tag not in self._segments:
             self._segments[tag] = self._compute_segment(self.cur_roidb_index, entry, key_f)
@@ -205,14 +211,14 @@ class TestLoader(object):
     def _cut_at(self, key_f):
         """the cut frame that ends the segment under way behind key frame key_f of the current video, or None"""
         seg = self._segment
-        return seg[4] if self.cut and seg is not None and seg[0] == (self.cur_roidb_index, key_f) else None
+        return seg.cut_f if self.cut and seg is not None and seg.tag == (self.cur_roidb_index, key_f) else None
 
     def _estimated(self, entry, f, key_f):
         seg = self._segment
-        if seg is None or seg[0] != (self.cur_roidb_index, key_f) or not 1 <= f - key_f <= seg[1]:
+        if seg is None or seg.tag != (self.cur_roidb_index, key_f) or not 1 <= f - key_f <= seg.n:
             raise RuntimeError("TestLoader: frame %d of video %d is not part of the segment estimated behind key frame %s" %
-                               (f, self.cur_roidb_index, None if seg is None else seg[0]))
-        return seg[2][f - key_f - 1], seg[3][f - key_f - 1]
+                               (f, self.cur_roidb_index, None if seg is None else seg.tag))
+        return seg.mv[f - key_f - 1], seg.res[f - key_f - 1]
 
     def upcoming_key_frames(self, n):
         """Call right after a KEY frame was returned: the images of the next `n` key frames of the same video (fewer near its end), for a
@@ -228,7 +234,7 @@ class TestLoader(object):
         while len(out) < n and prev < L - 1:
             seg = self._segment_ahead(entry, prev) if self.cut else None
             # the next multiple of the interval, or the video's last frame if that comes first - or, with `cut`, the segment's cut frame
-            f = next_key_frame(prev, L, K, () if seg is None or seg[4] is None else (seg[4],))
+            f = next_key_frame(prev, L, K, () if seg is None or seg.cut_f is None else (seg.cut_f,))
             key = (self.cur_roidb_index, f)
             if key not in self._ahead:
                 self._ahead[key] = entry['clip'].frame(f, self.device)

@@ -42,12 +42,63 @@ from lsfa_amd.config.config import config, lsfa_test_config, update_config, upda
 from lsfa_amd.core.graphs import FrameGraphs
 from lsfa_amd.symbols import params as P
 from lsfa_amd.symbols.resnet_v1_101_flownet_rfcn import resnet_v1_101_flownet_rfcn
+from lsfa_amd.utils import motion_options
 from lsfa_amd.utils.image import resize, transform, transform_mv_res
 from lsfa_amd.utils.load_model import load_param
 from lsfa_amd.utils.synthetic import SyntheticClip
 
 
-class FrameDirClip(object):
+def yuv_file_frames(path, width, height):
+    """-> the bytes of one width x height 4:2:0 frame, the file's size, the frames it holds (None: not a whole number of them, or none)"""
+    frame_bytes = width * height + 2 * (-(-width // 2)) * (-(-height // 2))
+    size = os.path.getsize(path)
+    return frame_bytes, size, (None if size == 0 or size % frame_bytes else size // frame_bytes)
+
+
+class _EstimatedClip(object):
+    """What FrameDirClip and YuvFileClip share: mv_res, and behind it the chain of one hip.MotionEstimator over the frames of the current
+    key-frame interval.  A clip says what is its own: _new_estimator (the frame size, its extra keywords), _feed (frame i to key_frame* /
+    next_frame*), _bgr_pair (frames i and key_i as uint8 BGR, for the dump and network_inputs) and _stems (the names of the .npz files).
+    self._kept: frame -> what the clip keeps of it on the device, trimmed in place to the interval under way."""
+
+    def __init__(self, estimate, device, dump_mv):
+        if dump_mv is not None and estimate is None:
+            raise ValueError('dump_mv writes the ESTIMATED motion vectors: it needs estimate')
+        self.estimate, self.device, self.dump_mv = estimate, device, dump_mv
+        self._me, self._me_key, self._me_last, self._kept = None, None, None, {}
+        if dump_mv is not None:
+            os.makedirs(dump_mv, exist_ok=True)
+
+    def _estimated(self, i, key_i):
+        from lsfa_amd import hip
+        if self._me is None:
+            self._me = self._new_estimator(hip, key_i)
+        me = self._me
+        if self._me_key != key_i or i < self._me_last:        # a new interval (or a step back): start from the key frame again
+            for f in [f for f in self._kept if not key_i <= f <= i]:
+                del self._kept[f]
+            self._feed(me, key_i, True)
+            self._me_key, self._me_last = key_i, key_i
+        for f in range(self._me_last + 1, i + 1):             # the P-frame chain: every frame against the one before it
+            self._feed(me, f, False)
+        self._me_last = i
+        if motion_options.ends_early(self.estimate) and me.is_cut():
+            return None                                       # frame i starts a new scene, or its key frame is stale: the caller makes it a key frame
+        cfg, (cur, key) = self.cfg, self._bgr_pair(me, i, key_i)
+        if self.dump_mv is not None:
+            np.savez(os.path.join(self.dump_mv, self._stems[i] + '.npz'), mv=(-me.acc.motion_vectors()).cpu().numpy(),
+                     res=me.acc.residual(cur, key).cpu().numpy())
+        mv, res = me.network_inputs(cur, key, self.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE)
+        return mv.clone(), res.clone()                        # the estimator reuses its output buffers
+
+    def mv_res(self, i, key_i):
+        if self.estimate is not None:
+            return self._estimated(i, key_i)
+        fh, fw = -(-self.height // 16), -(-self.width // 16)
+        return torch.zeros(1, 2, fh, fw), torch.zeros(1, 3, fh, fw)        # zero motion, zero residual
+
+
+class FrameDirClip(_EstimatedClip):
     """Frames of one clip from a directory, preprocessed like the reference's demo (:73-82).  estimate: None, or a dict of
     hip.MotionEstimator's parameters (search, lam, max_sad) - motion vectors and residuals are then estimated from the frames on
     `device`; with cut=dict(...) or stale=dict(...) among them mv_res returns None for a frame the estimator finds to start a new scene or to be
@@ -60,17 +111,14 @@ class FrameDirClip(object):
             raise FileNotFoundError('no frames under %s' % frame_dir)
         if estimate is not None and mv_dir is not None:
             raise ValueError('either read motion vectors (mv_dir) or estimate them, not both')
-        if dump_mv is not None and estimate is None:
-            raise ValueError('dump_mv writes the ESTIMATED motion vectors: it needs estimate')
         self.names, self.mv_dir, self.cfg = names, mv_dir, cfg
+        self._stems = [os.path.splitext(os.path.basename(n))[0] for n in names]
         self._open = Image.open
         self.num_frames = len(names)
         f0, self.im_scale = self._load(0)
         self.height, self.width = f0.shape[2], f0.shape[3]
-        self.estimate, self.device, self.dump_mv = estimate, device, dump_mv
-        self._me, self._me_key, self._me_last, self._u8 = None, None, None, {}
-        if dump_mv is not None:
-            os.makedirs(dump_mv, exist_ok=True)
+        _EstimatedClip.__init__(self, estimate, device, dump_mv)
+        self._u8 = self._kept           # the decoded frames as (H, W, 3) uint8 BGR
 
     def _decode(self, i):
         return np.asarray(self._open(self.names[i]).convert('RGB'))          # (H, W, 3) uint8 RGB
@@ -91,43 +139,24 @@ class FrameDirClip(object):
             self._u8[i] = torch.from_numpy(np.ascontiguousarray(self._decode(i)[:, :, ::-1])).to(self.device)
         return self._u8[i]
 
-    def _estimated(self, i, key_i):
-        from lsfa_amd import hip
-        if self._me is None:
-            k = self._frame_u8(key_i)
-            self._me = hip.MotionEstimator(int(k.shape[1]), int(k.shape[0]), self.device, **self.estimate)
-        me = self._me
-        if self._me_key != key_i or i < self._me_last:        # a new interval (or a step back): start from the key frame again
-            self._u8 = {f: t for f, t in self._u8.items() if key_i <= f <= i}
-            me.key_frame(self._frame_u8(key_i))
-            self._me_key, self._me_last = key_i, key_i
-        for f in range(self._me_last + 1, i + 1):             # the P-frame chain: every frame against the one before it
-            me.next_frame(self._frame_u8(f))
-        self._me_last = i
-        if (self.estimate.get('cut') is not None or self.estimate.get('stale') is not None) and me.is_cut():
-            return None                                       # frame i starts a new scene, or its key frame is stale: the caller makes it a key frame
-        cfg = self.cfg
-        cur, key = self._frame_u8(i), self._frame_u8(key_i)
-        if self.dump_mv is not None:
-            stem = os.path.splitext(os.path.basename(self.names[i]))[0]
-            np.savez(os.path.join(self.dump_mv, stem + '.npz'), mv=(-me.acc.motion_vectors()).cpu().numpy(),
-                     res=me.acc.residual(cur, key).cpu().numpy())
-        mv, res = me.network_inputs(cur, key, self.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE)
-        return mv.clone(), res.clone()                        # the estimator reuses its output buffers
+    def _new_estimator(self, hip, key_i):
+        k = self._frame_u8(key_i)
+        return hip.MotionEstimator(int(k.shape[1]), int(k.shape[0]), self.device, **self.estimate)
+
+    def _feed(self, me, i, key):
+        (me.key_frame if key else me.next_frame)(self._frame_u8(i))
+
+    def _bgr_pair(self, me, i, key_i):
+        return self._frame_u8(i), self._frame_u8(key_i)
 
     def mv_res(self, i, key_i):
-        if self.estimate is not None:
-            return self._estimated(i, key_i)
-        fh, fw = -(-self.height // 16), -(-self.width // 16)
         if self.mv_dir is None:
-            return torch.zeros(1, 2, fh, fw), torch.zeros(1, 3, fh, fw)
-        stem = os.path.splitext(os.path.basename(self.names[i]))[0]
-        z = np.load(os.path.join(self.mv_dir, stem + '.npz'))
-        cfg = self.cfg
+            return _EstimatedClip.mv_res(self, i, key_i)
+        z, cfg = np.load(os.path.join(self.mv_dir, self._stems[i] + '.npz')), self.cfg
         return transform_mv_res(z['mv'], z['res'], self.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE)
 
 
-class YuvFileClip(object):
+class YuvFileClip(_EstimatedClip):
     """Frames of one clip from a raw YUV 4:2:0 file (fmt 'nv12': Y plane, then interleaved U, V; 'i420': Y, U, V planes), frames back to
     back without a header.  Same interface as FrameDirClip: frame(i) is hip.image_resize_transform_yuv420 of the frame's planes on `device`,
     mv_res(i, key_i) the estimator's *_yuv chain when `estimate` (a dict of hip.MotionEstimator's parameters) is given, zero motion and
@@ -136,20 +165,17 @@ class YuvFileClip(object):
     def __init__(self, path, width, height, cfg, fmt='nv12', matrix='bt601', estimate=None, device='cuda:0', dump_mv=None):
         if fmt not in ('nv12', 'i420'):
             raise ValueError('fmt %r is not nv12 or i420' % (fmt,))
-        if dump_mv is not None and estimate is None:
-            raise ValueError('dump_mv writes the ESTIMATED motion vectors: it needs estimate')
         self.src_w, self.src_h, self.fmt, self.matrix, self.cfg = int(width), int(height), fmt, matrix, cfg
         if self.src_w <= 0 or self.src_h <= 0:
             raise ValueError('bad frame size %d x %d' % (self.src_w, self.src_h))
         self.cw, self.ch = -(-self.src_w // 2), -(-self.src_h // 2)
-        self.frame_bytes = self.src_w * self.src_h + 2 * self.cw * self.ch
-        size = os.path.getsize(path)
-        if size == 0 or size % self.frame_bytes:
+        self.frame_bytes, size, self.num_frames = yuv_file_frames(path, self.src_w, self.src_h)
+        if self.num_frames is None:
             raise ValueError('%s holds %d bytes: not a whole number of %d x %d %s frames of %d bytes' % (path, size, self.src_w, self.src_h, fmt,
                                                                                                      self.frame_bytes))
         self._map = np.memmap(path, dtype=np.uint8, mode='r')
-        self.num_frames = size // self.frame_bytes
-        self.names = ['%s/%06d' % (os.path.basename(path), i) for i in range(self.num_frames)]
+        self._stems = ['%06d' % i for i in range(self.num_frames)]
+        self.names = ['%s/%s' % (os.path.basename(path), stem) for stem in self._stems]
         # `resize`'s scale (lib/utils/image.py:266-280) from the frame size alone
         target, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
         lo, hi = min(self.src_h, self.src_w), max(self.src_h, self.src_w)
@@ -159,10 +185,8 @@ class YuvFileClip(object):
         st = cfg.network.IMAGE_STRIDE
         h1, w1 = int(np.rint(self.src_h * self.im_scale)), int(np.rint(self.src_w * self.im_scale))
         self.height, self.width = (-(-h1 // st) * st, -(-w1 // st) * st) if st else (h1, w1)
-        self.estimate, self.device, self.dump_mv = estimate, device, dump_mv
-        self._me, self._me_key, self._me_last, self._dev = None, None, None, {}
-        if dump_mv is not None:
-            os.makedirs(dump_mv, exist_ok=True)
+        _EstimatedClip.__init__(self, estimate, device, dump_mv)
+        self._dev = self._kept          # the frames' bytes as they lie in the file
 
     def planes(self, i):
         """frame i as the keyword arguments of the hip.*yuv420* functions: views of ONE device tensor holding the frame's bytes"""
@@ -184,35 +208,19 @@ class YuvFileClip(object):
         return hip.image_resize_transform_yuv420(im_scale=self.im_scale, matrix=self.matrix, pixel_means=cfg.network.PIXEL_MEANS,
                                                  pixel_scale=cfg.network.PIXEL_SCALE, stride=cfg.network.IMAGE_STRIDE, **self.planes(i))
 
+    def _new_estimator(self, hip, key_i):
+        return hip.MotionEstimator(self.src_w, self.src_h, self.device, matrix=self.matrix, **self.estimate)
+
+    def _feed(self, me, i, key):
+        (me.key_frame_yuv if key else me.next_frame_yuv)(**self.planes(i))
+
+    def _bgr_pair(self, me, i, key_i):
+        return me.bgr_cur, me.bgr_key            # the estimator converted them
+
     def _estimated(self, i, key_i):
-        from lsfa_amd import hip
         if i <= key_i:
             raise ValueError('frame %d has no motion vectors against key frame %d' % (i, key_i))
-        if self._me is None:
-            self._me = hip.MotionEstimator(self.src_w, self.src_h, self.device, matrix=self.matrix, **self.estimate)
-        me = self._me
-        if self._me_key != key_i or i < self._me_last:        # a new interval (or a step back): start from the key frame again
-            self._dev = {f: t for f, t in self._dev.items() if key_i <= f <= i}
-            me.key_frame_yuv(**self.planes(key_i))
-            self._me_key, self._me_last = key_i, key_i
-        for f in range(self._me_last + 1, i + 1):             # the P-frame chain: every frame against the one before it
-            me.next_frame_yuv(**self.planes(f))
-        self._me_last = i
-        if (self.estimate.get('cut') is not None or self.estimate.get('stale') is not None) and me.is_cut():
-            return None                                       # frame i starts a new scene, or its key frame is stale: the caller makes it a key frame
-        cfg = self.cfg
-        cur, key = me.bgr_cur, me.bgr_key
-        if self.dump_mv is not None:
-            np.savez(os.path.join(self.dump_mv, '%06d.npz' % i), mv=(-me.acc.motion_vectors()).cpu().numpy(),
-                     res=me.acc.residual(cur, key).cpu().numpy())
-        mv, res = me.network_inputs(cur, key, self.im_scale, cfg.network.PIXEL_MEANS, cfg.network.PIXEL_SCALE)
-        return mv.clone(), res.clone()                        # the estimator reuses its output buffers
-
-    def mv_res(self, i, key_i):
-        if self.estimate is not None:
-            return self._estimated(i, key_i)
-        fh, fw = -(-self.height // 16), -(-self.width // 16)
-        return torch.zeros(1, 2, fh, fw), torch.zeros(1, 3, fh, fw)
+        return _EstimatedClip._estimated(self, i, key_i)
 
 
 class _Synthetic(object):
@@ -237,25 +245,7 @@ def parse_args(argv=None):
     ap.add_argument('--size', default=None, help='--yuv: the frame size as WxH, e.g. 1280x720')
     ap.add_argument('--yuv-format', default='nv12', choices=('nv12', 'i420'), help='--yuv: semi-planar (interleaved U, V) or planar chroma')
     ap.add_argument('--yuv-matrix', default='bt601', choices=('bt601', 'bt709', 'jpeg'), help='--yuv: the colour matrix of the stream')
-    ap.add_argument('--estimate-mv', action='store_true', help='estimate block motion vectors from the frames on the GPU (needs --frames or --yuv)')
-    ap.add_argument('--search', type=int, default=16,
-                    help='--estimate-mv: search range in pixels, 1..32, with --mv-levels the range on the top level (a parameter, not a tuned value)')
-    ap.add_argument('--mv-lambda', type=int, default=4, help='--estimate-mv: cost per pixel of vector length (a parameter, not a tuned value)')
-    ap.add_argument('--mv-levels', type=int, default=0, choices=(0, 1, 2),
-                    help='--estimate-mv: extra pyramid levels; the reach is search * 2^L + refine * (2^L - 1) pixels (0: the full search alone)')
-    ap.add_argument('--mv-refine', type=int, default=2, choices=(1, 2, 3), help='--mv-levels: refinement radius per level (a parameter, not a tuned value)')
-    ap.add_argument('--scene-cut', type=int, nargs='?', const=50, default=None, metavar='PERCENT',
-                    help='--estimate-mv: a frame more than PERCENT (1..100, default 50) of whose macroblocks the previous frame does not predict '
-                         'becomes a key frame (DESIGN.md "Scene cuts"; a parameter, not a tuned value)')
-    ap.add_argument('--cut-bias', type=int, default=4,
-                    help='--scene-cut: grey levels per pixel a block\'s search residual may exceed its intra cost by, 0..255 (a parameter, not a tuned value)')
-    ap.add_argument('--stale-key', type=int, nargs='?', const=50, default=None, metavar='PERCENT',
-                    help='--estimate-mv: a frame more than PERCENT (1..100, default 50) of whose macroblocks the KEY frame, compensated with the '
-                         'accumulated vectors, does not predict becomes a key frame: fades, dissolves, slow pans (DESIGN.md "Stale key frames"; a '
-                         'parameter, not a tuned value).  Combines with --scene-cut')
-    ap.add_argument('--stale-bias', type=int, default=4,
-                    help='--stale-key: grey levels per pixel a block\'s residual against the key frame may exceed its intra cost by, 0..255 (a '
-                         'parameter, not a tuned value)')
+    motion_options.add_arguments(ap, 'estimate block motion vectors from the frames on the GPU (needs --frames or --yuv)')
     ap.add_argument('--dump-mv', default=None, help='--estimate-mv: write the estimated mv / res as the .npz files --mv reads')
     ap.add_argument('--num', type=int, default=30, help='frames of the synthetic clip')
     ap.add_argument('--interval', type=int, default=10, help='key frame interval (demo.py:68)')
@@ -277,11 +267,10 @@ def parse_args(argv=None):
             ap.error('--yuv needs --size WxH (got %r)' % (args.size,))
         args.yuv_size = (int(m.group(1)), int(m.group(2)))
         w, h = args.yuv_size
-        frame_bytes = w * h + 2 * (-(-w // 2)) * (-(-h // 2))
         if not os.path.isfile(args.yuv):
             ap.error('--yuv: no such file: %s' % args.yuv)
-        size = os.path.getsize(args.yuv)
-        if size == 0 or size % frame_bytes:
+        frame_bytes, size, frames = yuv_file_frames(args.yuv, w, h)
+        if frames is None:
             ap.error('--yuv: %s holds %d bytes, not a whole number of %dx%d frames of %d bytes' % (args.yuv, size, w, h, frame_bytes))
     elif args.size:
         ap.error('--size belongs to --yuv')
@@ -289,10 +278,7 @@ def parse_args(argv=None):
         ap.error('--estimate-mv needs --frames or --yuv and excludes --mv')
     if args.dump_mv and not args.estimate_mv:
         ap.error('--dump-mv needs --estimate-mv')
-    if args.scene_cut is not None and (not args.estimate_mv or not 1 <= args.scene_cut <= 100 or not 0 <= args.cut_bias <= 255):
-        ap.error('--scene-cut PERCENT (1..100) needs --estimate-mv; --cut-bias is 0..255')
-    if args.stale_key is not None and (not args.estimate_mv or not 1 <= args.stale_key <= 100 or not 0 <= args.stale_bias <= 255):
-        ap.error('--stale-key PERCENT (1..100) needs --estimate-mv; --stale-bias is 0..255')
+    args.estimate = motion_options.estimate_of(ap, args)
     return args
 
 
@@ -305,15 +291,10 @@ def main(argv=None):
         cfg = lsfa_test_config()
     cfg.TEST.KEY_FRAME_INTERVAL = args.interval
     dev = 'cuda:0'
-    estimate = dict(search=args.search, lam=args.mv_lambda, levels=args.mv_levels, refine=args.mv_refine) if args.estimate_mv else None
-    if args.scene_cut is not None:
-        estimate['cut'] = dict(bias=args.cut_bias, percent=args.scene_cut)
-    if args.stale_key is not None:
-        estimate['stale'] = dict(bias=args.stale_bias, percent=args.stale_key)
     if args.yuv:
-        clip = YuvFileClip(args.yuv, args.yuv_size[0], args.yuv_size[1], cfg, args.yuv_format, args.yuv_matrix, estimate, dev, args.dump_mv)
+        clip = YuvFileClip(args.yuv, args.yuv_size[0], args.yuv_size[1], cfg, args.yuv_format, args.yuv_matrix, args.estimate, dev, args.dump_mv)
     else:
-        clip = FrameDirClip(args.frames, args.mv, cfg, estimate, dev, args.dump_mv) if args.frames else _Synthetic(args.num, 600, 1000)
+        clip = FrameDirClip(args.frames, args.mv, cfg, args.estimate, dev, args.dump_mv) if args.frames else _Synthetic(args.num, 600, 1000)
     if args.prefix:
         arg_params, aux_params = load_param(args.prefix, args.epoch, process=True)
     else:

@@ -220,6 +220,12 @@ def _resized(H, W, im_scale, stride):
     return (h1, w1, -(-h1 // stride) * stride, -(-w1 // stride) * stride) if stride else (h1, w1, h1, w1)
 
 
+def _resized_map(H, W, im_scale, rcnn_stride):
+    """-> _resized's h1, w1, then the height and width of the `motion_vector` / `res_diff` maps: its padded size in steps of rcnn_stride"""
+    h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
+    return h1, w1, ph // rcnn_stride, pw // rcnn_stride
+
+
 # ------------------------------------------------------------------------------------
 @_on_tensor_device
 def psroi_pool(data, rois, spatial_scale, output_dim, pooled_size, group_size, with_mapping=False):
@@ -1946,8 +1952,7 @@ def mv_segment_inputs(rows, bgr_stack, im_scale, pixel_means=(0.0, 0.0, 0.0), pi
     if not float(im_scale) > 0.0 or int(rcnn_stride) < 1:
         raise LsfaError("%s: im_scale %r must be positive and rcnn_stride %r at least 1" % (who, im_scale, rcnn_stride))
     rcnn_stride = int(rcnn_stride)
-    h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
-    oh, ow = ph // rcnn_stride, pw // rcnn_stride
+    h1, w1, oh, ow = _resized_map(H, W, im_scale, rcnn_stride)
     if out is None:
         out = (torch.empty((F, C, 2, oh, ow), device=bgr_stack.device, dtype=torch.float32),
                torch.empty((F, C, 3, oh, ow), device=bgr_stack.device, dtype=torch.float32))
@@ -2077,7 +2082,19 @@ class _MotionSearch(object):
         return np.logical_or.reduce([cut_flags(c, self.blocks[0], r[1]) for c, r in zip(counts, rules)])
 
 
-class MotionEstimator(object):
+class _SearchFront(object):
+    """What MotionEstimator and SegmentMotionEstimator show of the _MotionSearch they stand in front of: its checked parameters and its
+    geometry, under its names.  The buffers of the modes (unmatched, keysad, ...) are the subclass's: views of the search's in its own shape."""
+
+    def __init__(self, s):
+        self._search = s
+        self.cut, self.stale = s.cut, s.stale
+        self.width, self.height, self.device = s.width, s.height, s.device
+        self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
+        self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
+
+
+class MotionEstimator(_SearchFront):
     """Decoded uint8 frames in, the network's `motion_vector` / `res_diff` out: block motion estimation (lsfa_luma_u8 + lsfa_mv_estimate) in
     front of a MotionVectorAccumulator, for clips without compressed-stream side data.
 
@@ -2121,14 +2138,11 @@ class MotionEstimator(object):
 
     def __init__(self, width, height, device='cuda:0', search=ME_SEARCH, lam=ME_LAMBDA, max_sad=ME_MAX_SAD, luma_from='bgr', matrix='bt601',
                  levels=ME_LEVELS, refine=ME_REFINE, cut=None, stale=None):
-        s = self._search = _MotionSearch("MotionEstimator", width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes=2, pairs=1,
-                                         cut=cut, stale=stale, keep_key=True)
-        self.cut, self.unmatched = s.cut, s.unmatched
-        self.stale, self.key_unmatched = s.stale, s.key_unmatched
+        s = _MotionSearch("MotionEstimator", width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine, planes=2, pairs=1,
+                          cut=cut, stale=stale, keep_key=True)
+        _SearchFront.__init__(self, s)
+        self.unmatched, self.key_unmatched = s.unmatched, s.key_unmatched
         self.keysad = s.keysad.view(s.mbh, s.mbw) if s.stale else None
-        self.width, self.height, self.device = s.width, s.height, s.device
-        self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
-        self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
         self.bgr_key, self._bgr_pp, self._bgr_i = None, None, 0
         H, W = self.height, self.width
         self.acc = MotionVectorAccumulator(W, H, self.device)
@@ -2223,8 +2237,7 @@ class MotionEstimator(object):
         """`motion_vector` (1, 2, h, w) and `res_diff` (1, 3, h, w) of the current frame against the key frame: MotionVectorAccumulator's
         network_inputs (lsfa_mv_field, lsfa_mv_residual, lsfa_transform_mv_res) into buffers of its own."""
         bgr_cur, bgr_key = self._frame(bgr_cur, 'network_inputs'), self._frame(bgr_key, 'network_inputs')
-        _, _, ph, pw = _resized(self.height, self.width, im_scale, rcnn_stride)
-        oh, ow = ph // rcnn_stride, pw // rcnn_stride
+        oh, ow = _resized_map(self.height, self.width, im_scale, rcnn_stride)[2:]
         if (oh, ow) not in self._out:
             self._out[(oh, ow)] = (torch.empty((1, 2, oh, ow), device=self.device, dtype=torch.float32),
                                    torch.empty((1, 3, oh, ow), device=self.device, dtype=torch.float32))
@@ -2232,7 +2245,7 @@ class MotionEstimator(object):
                                 pixel_scale, rcnn_stride, negate_mv=True, out=self._out[(oh, ow)])
 
 
-class SegmentMotionEstimator(object):
+class SegmentMotionEstimator(_SearchFront):
     """A key frame and the non-key frames behind it in, the `motion_vector` / `res_diff` of every one of them out - what MotionEstimator builds
     frame by frame in seven launches each, for a whole segment of `clips` lock-step clips in three: luma of the stack (lsfa_luma_u8; one
     launch where W * H % 4 == 0, else one per frame), the search of every (frame, previous frame) pair (lsfa_mv_estimate_chain), the inputs
@@ -2273,14 +2286,10 @@ class SegmentMotionEstimator(object):
         self.frames, self.clips = int(frames), int(clips)
         if self.frames < 1 or self.clips < 1 or int(width) < 1 or int(height) < 1:
             raise LsfaError("%s: frames %d, clips %d and the %d x %d frame must all be at least 1" % (who, self.frames, self.clips, int(width), int(height)))
-        s = self._search = _MotionSearch(who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine,
-                                         planes=self.clips * (self.frames + 1), pairs=self.clips * self.frames, cut=cut,
-                                         stale=stale)
-        self.cut, self.intra, self.unmatched = s.cut, None, None
-        self.stale, self.keysad, self.key_unmatched = s.stale, None, None
-        self.width, self.height, self.device = s.width, s.height, s.device
-        self.search, self.lam, self.max_sad, self.levels, self.refine = s.search, s.lam, s.max_sad, s.levels, s.refine
-        self.luma_from, self.matrix, self.reach, self.mbh, self.mbw = s.luma_from, s.matrix, s.reach, s.mbh, s.mbw
+        s = _MotionSearch(who, width, height, device, search, lam, max_sad, luma_from, matrix, levels, refine,
+                          planes=self.clips * (self.frames + 1), pairs=self.clips * self.frames, cut=cut, stale=stale)
+        _SearchFront.__init__(self, s)
+        self.intra, self.unmatched, self.keysad, self.key_unmatched = None, None, None, None      # views of the last segment's, set by _run
         # the search wants every plane 4-byte aligned: a frame of W * H % 4 != 0 (no 4:2:0 video has one) gets its planes padded apart and
         # its luma frame by frame
         if s.plane[0] != self.height * self.width and luma_from == 'y':
@@ -2303,10 +2312,10 @@ class SegmentMotionEstimator(object):
             return
         if not float(im_scale) > 0.0 or rcnn_stride < 1:
             raise LsfaError("%s: im_scale %r must be positive and rcnn_stride %r at least 1" % (who, im_scale, rcnn_stride))
-        _, _, ph, pw = _resized(self.height, self.width, im_scale, rcnn_stride)
+        oh, ow = _resized_map(self.height, self.width, im_scale, rcnn_stride)[2:]
         out = _given(who, "out", out, 2)
         for i, c in enumerate((2, 3)):
-            _tensor(who, "output buffer out[%d]" % i, out[i], torch.float32, (n, self.clips, c, ph // rcnn_stride, pw // rcnn_stride), self.device)
+            _tensor(who, "output buffer out[%d]" % i, out[i], torch.float32, (n, self.clips, c, oh, ow), self.device)
 
     def _run(self, bgr, n, im_scale, pixel_means, pixel_scale, rcnn_stride, out, luma_done):
         H, W, C, s = self.height, self.width, self.clips, self._search
@@ -2326,8 +2335,7 @@ class SegmentMotionEstimator(object):
         s.run(C, n)
         s.key_score(C, n)
         if out is None:
-            h1, w1, ph, pw = _resized(H, W, im_scale, rcnn_stride)
-            key = (n, ph // rcnn_stride, pw // rcnn_stride)
+            key = (n,) + _resized_map(H, W, im_scale, rcnn_stride)[2:]
             if key not in self._out:
                 self._out[key] = (torch.empty((n, C, 2) + key[1:], device=self.device, dtype=torch.float32),
                                   torch.empty((n, C, 3) + key[1:], device=self.device, dtype=torch.float32))
