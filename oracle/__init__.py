@@ -10,9 +10,22 @@ reference too (``np_ref.py``) and the torch-CPU statement of the conv graph
 Pinning status (see lsfa_oracle.c header and DESIGN.md §Oracle):
   pinned by tests/golden/ref_golden.npz (generated from the reference's own numpy
   helpers by tests/golden/make_golden.py): anchors, IoU, NMS survivor lists, box
-  decode/clip.  PARITY UNPINNED: warp, PSROI pooling, the decode/sort stages of
-  Proposal, DCN, every conv — the reference holds no test or golden vector for
-  them and their implementation is CUDA / un-vendored MXNet.
+  decode/clip.
+  pinned by tests/golden/ref_native.npz (tests/golden/make_native_golden.py): PSROI
+  pooling, every stage of Proposal (anchors, decode, order, keep, rois, scores) and
+  the coviar accumulation / field / residual, against the reference's OWN functions.
+  ``build()`` cuts them out of the reference tree and compiles them for the host
+  into oracle/_ref (``oracle/ref_native``; never committed, nothing happens where
+  the tree is absent).  One emulated thread per index with the reference's launch
+  geometry: PSROIPoolForwardKernel advances its bottom_rois parameter inside its
+  grid-stride loop and is wrong when a thread's loop runs twice.  Restated there,
+  not sliced: MultiProposalGPUOp::Forward's call order (multi_proposal.cu:428-551),
+  thrust's stable sort as std::stable_sort, _nms's mask sweep (:338-354),
+  decode_video's frame loop.  Two declared substitutions: exp(float) is
+  (float)exp((double)x); contraction is -ffp-contract=on (authoritative), with the
+  counts of values that =off / =fast change measured and kept in the npz
+  (DESIGN.md §5 quotes them).
+  PARITY UNPINNED: warp, DCN, every conv, cv2's resize — un-vendored MXNet / OpenCV.
 """
 import ctypes
 import os
@@ -25,9 +38,12 @@ _SO = os.path.join(_HERE, "liblsfa_oracle.so")
 
 
 def build(force=False):
+    """liblsfa_oracle.so, and oracle/_ref where the reference tree is at hand (ref_native.build does nothing elsewhere)."""
     src = os.path.join(_HERE, "lsfa_oracle.c")
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
         subprocess.check_call(["make", "-s", "-C", _HERE, "liblsfa_oracle.so"])
+    from . import ref_native
+    ref_native.build(force=force)
     return _SO
 
 

@@ -7,8 +7,9 @@ own op, every 1x1 convolution is a convolution, rpn_inv_normalize is applied aft
   dff_rfcn/symbols/resnet_v1_101_flownet_rfcn.py:44-236  feat conv, rnet, Nq, FlowNet, small net
   :448-551 key symbol, :553-659 cur symbol
 The dense ops are torch.nn.functional on the CPU in fp32; the custom stages (warp, aggregate,
-Proposal, PSROI, DCN im2col) are the C oracle.  PARITY UNPINNED for all of it: MXNet is not
-vendored and the reference holds no golden outputs for these graphs.
+Proposal, PSROI, DCN im2col) are the C oracle.  PARITY UNPINNED for the graphs: MXNet is not
+vendored and the reference holds no golden outputs for them (Proposal and PSROI on their own are
+pinned to the reference's own functions, see oracle/__init__.py).
 
 `dtype=torch.float64` (r4) runs every DENSE op (convolutions, BatchNorm, pooling, softmax, the DCN contraction) in
 float64 and hands float32-rounded maps to the custom stages at exactly the boundaries where the reference's operators

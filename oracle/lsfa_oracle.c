@@ -12,17 +12,28 @@
  * or Python helper line by line; the file:line it follows is cited on each
  * function.  Pinning: the anchor table, IoU/NMS and box decode are checked
  * against golden vectors captured from the reference's importable numpy
- * helpers (tests/golden/make_golden.py -> tests/golden/ npz files).  The warp
- * (GridGenerator + BilinearSampler) lives in un-vendored MXNet@75a9e187d and
- * has no golden vector in the reference: PARITY UNPINNED for orc_warp_bilinear,
- * orc_psroi_pool and the non-NMS stages of orc_proposal (they restate the
- * published kernels; nothing in the reference pins their outputs).
+ * helpers (tests/golden/make_golden.py -> tests/golden/ npz files).
+ * orc_psroi_pool, orc_generate_anchors, orc_proposal_decode, orc_proposal and
+ * orc_coviar_* are checked bit for bit against the reference's own functions,
+ * cut out of the reference tree and compiled for the host (oracle/ref_native ->
+ * oracle/_ref, never committed; tests/golden/make_native_golden.py ->
+ * tests/golden/ref_native.npz; tests/test_oracle_native_cpu.py).  That build runs
+ * one emulated thread per index (PSROIPoolForwardKernel advances its bottom_rois
+ * parameter in its grid-stride loop), restates only Forward's call order, the
+ * stable sort and _nms's mask sweep, and makes two declared substitutions: the
+ * exp() below, and -ffp-contract=on as the authoritative contraction rule (the
+ * counts of values that =off / =fast change are in the npz and DESIGN.md §5).
+ * The warp (GridGenerator + BilinearSampler) lives in un-vendored MXNet@75a9e187d
+ * and has no golden vector in the reference: PARITY UNPINNED for
+ * orc_warp_bilinear, orc_deform_im2col and the convolutions.
  *
  * Floating-point contract shared with the HIP kernels (so that results are
  * bit-identical and index decisions cannot flip):
  *   - compiled with -ffp-contract=off; fused multiply-adds appear ONLY where
  *     written as fmaf(), at the places where nvcc's default -fmad=true
- *     contracts the reference's CUDA expression `a*b + c` inside one statement;
+ *     contracts the reference's CUDA expression `a*b + c` inside one statement
+ *     (for PSROI and Proposal a compiler applies that rule to the reference's
+ *     own text in oracle/_ref, and the fmaf()s here agree with it);
  *   - exp() of a float is the correctly rounded float exponential, obtained
  *     as (float)exp((double)x)  (CUDA's expf is within 2 ulp of this; no
  *     bit-level statement of it exists);
