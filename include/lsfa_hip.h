@@ -217,7 +217,7 @@ int lsfa_proposal(const float* cls_prob, const float* bbox_pred, const float* im
  * Replaces: nms_kernel + the host sweep of _nms   lib/nms/nms_kernel.cu:40-84, :97-150
  *           and multi_proposal.cu:262-357.
  * boxes (n, box_dim>=4) sorted by score descending; keep (n) int32 indices into
- * boxes, num_keep (1) int32; both device.  ws >= lsfa_nms_workspace_bytes(n).
+ * boxes, num_keep (1) int32; both device.  keep[num_keep:] is not written (undefined).  ws >= lsfa_nms_workspace_bytes(n).
  * ------------------------------------------------------------------------ */
 size_t lsfa_nms_workspace_bytes(int n);
 int lsfa_nms_sorted(const float* boxes, int n, int box_dim, float thresh,
