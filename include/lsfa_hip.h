@@ -710,8 +710,8 @@ int lsfa_mv_key_sad_accu(const unsigned char* luma_cur, const unsigned char* lum
  *        R = clip((298 C + 459 E + 128) >> 8)   G = clip((298 C -  55 D - 136 E + 128) >> 8)   B = clip((298 C + 541 D + 128) >> 8)
  *     matrix 2, BT.601 full range (JFIF), o = 0:
  *        R = clip((256 C + 359 E + 128) >> 8)   G = clip((256 C -  88 D - 183 E + 128) >> 8)   B = clip((256 C + 454 D + 128) >> 8)
- * Out of scope: NV21, P010 (10-bit), 4:2:2 and 4:4:4; interpolated chroma; any binding to rocDecode (a decoded surface's base, pitch and
- * height ARE the arguments: INTEGRATION.md).
+ * Out of scope: NV21, 4:2:2 and 4:4:4; interpolated chroma; any binding to rocDecode (a decoded surface's base, pitch and
+ * height ARE the arguments: INTEGRATION.md).  10-bit samples (P010, yuv420p10le) have entry points of their own at the end of this header.
  * Planes: a base pointer, a row pitch in bytes and, for N frames, a frame stride in bytes each; a pitch wider than the row is normal
  * (y_pitch >= W; c_pitch >= 2 ceil(W / 2) for NV12, >= ceil(W / 2) for I420), a frame stride may be anything that does not overlap.
  * v == NULL: u_or_uv is the interleaved U, V plane (NV12); otherwise u_or_uv and v are I420's two chroma planes, with one pitch and stride.
@@ -768,6 +768,46 @@ enum {
 int lsfa_prof_enable(int mask);
 int lsfa_prof_read(double* ms_host /*LSFA_OP_COUNT*/, int* launches_host /*LSFA_OP_COUNT*/);
 const char* lsfa_op_name(int op_id);
+
+/* ------------------------------------------------------------------------ *
+ * 10-bit YUV 4:2:0 intake (lsfa_amd/csrc/yuv10.hip): what HEVC Main10, VP9 profile 2 and AV1 10-bit decode to - the VCN engines' P010 /
+ * P016 surfaces, libav's yuv420p10le - to the same three outputs as the 8-bit intake above, which it mirrors argument for argument with
+ * `shift` behind `matrix`.  Everything behind the intake stays 8-bit.  Defined by the specification below (DESIGN.md "YUV intake", "10-bit
+ * planes"; restated in numpy as tests/ref_yuv10.py) and bit-exact with THAT; parity with swscale is unpinned and not claimed.
+ *   A sample is a 16-bit little-endian word w, and s = (w >> shift) & 1023.  shift = 6 is P010: the value sits in the high ten bits and the
+ *   low six are ignored whatever they hold (so a P016 surface is read as its high ten bits).  shift = 0 is yuv420p10le / I010: the value
+ *   sits in the low ten bits and the high six are masked.  Any word is defined input.
+ *   Geometry as above: pixel (x, y) takes Y[y][x] and the chroma sample (x >> 1, y >> 1); chroma planes are ceil(W / 2) x ceil(H / 2); odd
+ *   W and H are allowed.  v == NULL: u_or_uv holds interleaved U, V words (P010's layout); otherwise u_or_uv and v are two planes with one
+ *   pitch and one frame stride.  Either layout goes with either shift.
+ *   C = Y - 4 o, D = U - 512, E = V - 512 with o and the coefficients of the 8-bit table above (o = 64, 64, 0 for matrices 0, 1, 2):
+ *     matrix 0:  R = clip((298 C + 409 E + 512) >> 10)   G = clip((298 C - 100 D - 208 E + 512) >> 10)   B = clip((298 C + 516 D + 512) >> 10)
+ *   and likewise for matrices 1 and 2: the 8-bit formulas with rounding constant 512 and shift 10, so the conversion is done in ten bits and
+ *   rounded once; clip clamps to 0..255; every intermediate stays below 2^20 in magnitude.  Planes that are exactly 4 x an 8-bit plane give
+ *   the 8-bit specification's BGR bit for bit.
+ *   y_packed (uint8, what lsfa_mv_estimate searches) = min(255, (Y + 2) >> 2); on 4 x an 8-bit plane it gives that plane back.
+ * Planes are const void*: bases of 16-bit words.  Pitches and frame strides are in BYTES.  LSFA_EINVAL, before anything is launched, for a NULL
+ * plane or output, N, H or W below 1, a matrix outside 0..2, a shift other than 0 or 6, an odd base, pitch or frame stride, and a pitch below
+ * its row (2 W for Y; 4 ceil(W / 2) for interleaved, 2 ceil(W / 2) for planar chroma).
+ * One launch each, on `stream`, no workspace, nothing allocated; reported under LSFA_OP_STEM.  8-byte aligned planes (4-byte aligned planar
+ * chroma) of W % 4 == 0, H % 2 == 0 take the kernel that reads four pixels of two rows per thread; anything else takes an element-wise
+ * kernel, picked per launch.
+ * lsfa_yuv420p10_to_bgr_u8: bgr (N, H, W, 3) uint8, packed; y_packed (N, H, W) uint8 or NULL.
+ * lsfa_image_transform_yuv420p10: `data` (N, 3, H, W) float32: lsfa_image_transform_u8 of lsfa_yuv420p10_to_bgr_u8's frame, bit for bit
+ *   (subtraction and product in float64, rounded once), without storing the frame.
+ * lsfa_image_resize_transform_yuv420p10: lsfa_image_resize_transform with is_u8 = 1 of that frame, bit for bit, reading its taps from the
+ *   planes; h1, w1, stride, out_h, out_w as there - checked.
+ * ------------------------------------------------------------------------ */
+int lsfa_yuv420p10_to_bgr_u8(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v /* NULL: interleaved */,
+                             long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int shift, unsigned char* bgr,
+                             unsigned char* y_packed /* may be NULL */, void* stream);
+int lsfa_image_transform_yuv420p10(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v /* NULL: interleaved */,
+                                   long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int shift,
+                                   const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw, void* stream);
+int lsfa_image_resize_transform_yuv420p10(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv,
+                                          const void* v /* NULL: interleaved */, long long c_pitch, long long c_frame_stride, int N, int H, int W,
+                                          int matrix, int shift, double im_scale, int h1, int w1, int stride, const double* pixel_means_bgr_host,
+                                          double pixel_scale, float* data_nchw, int out_h, int out_w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,15 +11,16 @@
 //   matrix 0 (BT.601 limited)  o = 16  R = clip((298 C + 409 E + 128) >> 8)  G = clip((298 C - 100 D - 208 E + 128) >> 8)  B = clip((298 C + 516 D + 128) >> 8)
 //   matrix 1 (BT.709 limited)  o = 16  R = clip((298 C + 459 E + 128) >> 8)  G = clip((298 C -  55 D - 136 E + 128) >> 8)  B = clip((298 C + 541 D + 128) >> 8)
 //   matrix 2 (BT.601 full)     o = 0   R = clip((256 C + 359 E + 128) >> 8)  G = clip((256 C -  88 D - 183 E + 128) >> 8)  B = clip((256 C + 454 D + 128) >> 8)
-// Out of scope: NV21, P010 (10-bit), 4:2:2 and 4:4:4, interpolated chroma, any binding to rocDecode.
+// Out of scope: NV21, 4:2:2 and 4:4:4, interpolated chroma, any binding to rocDecode.  10-bit samples (P010, yuv420p10le): yuv10.hip.
 //
 // Bandwidth kernels.  yuv420_quad_kernel gives a thread four horizontally adjacent pixels of two rows: two Y dwords, one dword holding two
 // U, V pairs (two half-words for I420) - every chroma sample is read once - and, for `data`, six 16-byte stores.  yuv420_bytes_kernel is the
 // byte-wise form (a thread per pixel) for bases or pitches that are not aligned, W % 4 != 0 and an odd last row; the host picks one of the
 // two per launch.  The resize form gathers its four taps per output pixel like resize_transform_kernel (mv.hip) and shares its tap and
-// weight arithmetic (resize_kernels.h).
+// weight arithmetic (resize_kernels.h).  The two output forms of the plane kernels (BgrOut, DataOut) are yuv_out.h's, shared with yuv10.hip.
 #include "common.h"
 #include "resize_kernels.h"
+#include "yuv_out.h"
 
 using namespace lsfa;
 
@@ -35,10 +36,6 @@ struct YuvPlanes {
   int N, H, W;
   int o, cy, rv, gu, gv, bu;    // the matrix' row of the table above
 };
-
-struct Bgr { int b, g, r; };
-
-__device__ __forceinline__ int clip255(int v) { return min(max(v, 0), 255); }
 
 __device__ __forceinline__ Bgr yuv_to_bgr(const YuvPlanes& p, int Y, int U, int V) {
   const int c = p.cy * (Y - p.o) + 128, d = U - 128, e = V - 128;
@@ -59,49 +56,6 @@ __device__ __forceinline__ Bgr yuv_pixel(const YuvPlanes& p, long n, int y, int 
   *luma = Y;
   return yuv_to_bgr(p, Y, U, V);
 }
-
-// the packed (N, H, W, 3) uint8 BGR frame and, optionally, the Y plane with the pitch removed
-struct BgrOut {
-  unsigned char* bgr;
-  unsigned char* y_packed;      // may be nullptr
-  long hw;
-  __device__ __forceinline__ void px(long n, long pix, const Bgr& c, int Y) const {
-    unsigned char* o = bgr + (n * hw + pix) * 3;
-    o[0] = (unsigned char)c.b; o[1] = (unsigned char)c.g; o[2] = (unsigned char)c.r;
-    if (y_packed) y_packed[n * hw + pix] = (unsigned char)Y;
-  }
-  // pix % 4 == 0, hw % 4 == 0, both bases dword aligned: twelve bytes as three dwords, b0 g0 r0 b1 | g1 r1 b2 g2 | r2 b3 g3 r3
-  __device__ __forceinline__ void quad(long n, long pix, const Bgr (&c)[4], uint32_t ydw) const {
-    uint32_t* o = reinterpret_cast<uint32_t*>(bgr + (n * hw + pix) * 3);
-    o[0] = (uint32_t)c[0].b | ((uint32_t)c[0].g << 8) | ((uint32_t)c[0].r << 16) | ((uint32_t)c[1].b << 24);
-    o[1] = (uint32_t)c[1].g | ((uint32_t)c[1].r << 8) | ((uint32_t)c[2].b << 16) | ((uint32_t)c[2].g << 24);
-    o[2] = (uint32_t)c[2].r | ((uint32_t)c[3].b << 8) | ((uint32_t)c[3].g << 16) | ((uint32_t)c[3].r << 24);
-    if (y_packed) *reinterpret_cast<uint32_t*>(y_packed + n * hw + pix) = ydw;
-  }
-};
-
-// `data` (N, 3, H, W) float32: image_transform_u8_kernel's arithmetic (stem.hip) - subtraction and product in float64, one rounding
-struct DataOut {
-  float* out;
-  long hw;
-  double m0, m1, m2, scale;     // pixel_means in B, G, R order
-  __device__ __forceinline__ void px(long n, long pix, const Bgr& c, int) const {
-    float* o = out + n * 3 * hw + pix;
-    o[0] = (float)(((double)c.r - m2) * scale);
-    o[hw] = (float)(((double)c.g - m1) * scale);
-    o[2 * hw] = (float)(((double)c.b - m0) * scale);
-  }
-  // pix % 4 == 0, hw % 4 == 0, the base 16-byte aligned: one float4 per plane
-  __device__ __forceinline__ void quad(long n, long pix, const Bgr (&c)[4], uint32_t) const {
-    float* o = out + n * 3 * hw + pix;
-    *reinterpret_cast<float4*>(o) = make_float4((float)(((double)c[0].r - m2) * scale), (float)(((double)c[1].r - m2) * scale),
-                                                (float)(((double)c[2].r - m2) * scale), (float)(((double)c[3].r - m2) * scale));
-    *reinterpret_cast<float4*>(o + hw) = make_float4((float)(((double)c[0].g - m1) * scale), (float)(((double)c[1].g - m1) * scale),
-                                                     (float)(((double)c[2].g - m1) * scale), (float)(((double)c[3].g - m1) * scale));
-    *reinterpret_cast<float4*>(o + 2 * hw) = make_float4((float)(((double)c[0].b - m0) * scale), (float)(((double)c[1].b - m0) * scale),
-                                                         (float)(((double)c[2].b - m0) * scale), (float)(((double)c[3].b - m0) * scale));
-  }
-};
 
 // W % 4 == 0, H % 2 == 0, Y base / pitch / stride dword aligned, chroma dword (NV12) or half-word (I420) aligned: the host checks
 template <class Out>
@@ -169,9 +123,6 @@ __global__ __launch_bounds__(kThreads) void resize_transform_yuv420_kernel(YuvPl
   resize_transform_store(out + (size_t)n * 3 * plane + r, plane, b, g, rr, m0, m1, m2, pixel_scale, sub_f64);
 }
 
-// {o, cy, rv, gu, gv, bu} per matrix
-const int kMatrix[3][6] = {{16, 298, 409, 100, 208, 516}, {16, 298, 459, 55, 136, 541}, {0, 256, 359, 88, 183, 454}};
-
 int fill_planes(const char* who, YuvPlanes& p, const unsigned char* y, long long y_pitch, long long y_frame_stride, const unsigned char* u_or_uv,
                 const unsigned char* v, long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix) {
   LSFA_REQUIRE(y && u_or_uv, "%s: NULL plane", who);
@@ -184,7 +135,7 @@ int fill_planes(const char* who, YuvPlanes& p, const unsigned char* y, long long
   p.y = y; p.u = u_or_uv; p.v = v;
   p.y_pitch = y_pitch; p.y_stride = y_frame_stride; p.c_pitch = c_pitch; p.c_stride = c_frame_stride;
   p.N = N; p.H = H; p.W = W;
-  const int* m = kMatrix[matrix];
+  const int* m = kYuvMatrix[matrix];
   p.o = m[0]; p.cy = m[1]; p.rv = m[2]; p.gu = m[3]; p.gv = m[4]; p.bu = m[5];
   return LSFA_OK;
 }

@@ -10,6 +10,7 @@ score above 0.7 after per-class NMS.
     python -m lsfa_amd.demo --frames DIR --estimate-mv --stale-key [PERCENT] [--stale-bias B]   # ... and wherever the key frame stops predicting (fades, pans)
 
     python -m lsfa_amd.demo --yuv clip.nv12 --size 1280x720 [--yuv-format nv12|i420] [--yuv-matrix bt601|bt709|jpeg] [--estimate-mv ...]
+    python -m lsfa_amd.demo --yuv clip.p010 --size 1920x1080 --yuv-format p010|yuv420p10le [--yuv-matrix ...] [--estimate-mv ...]   # 10-bit
 
 --frames: a directory of *.JPEG / *.jpg / *.png frames in display order (decoded with PIL; the
 reference uses cv2.imread, :75).  --mv: one `<frame stem>.npz` per non-key frame holding `mv`
@@ -27,6 +28,9 @@ and `res` (H, W, 3) int32 is lsfa_mv_residual's output as it stands.  Running --
 header - in place of --frames.  The file is memory-mapped, each frame's 1.5 bytes per pixel are uploaded once and everything behind the
 upload runs on the device: `data` is hip.image_resize_transform_yuv420 of the planes, and with --estimate-mv the estimator's *_yuv
 methods convert and search them (DESIGN.md "YUV intake"; the conversion is this project's own integer specification).
+--yuv-format p010 | yuv420p10le: a 10-bit file of 16-bit little-endian words as `-pix_fmt p010le` (Y plane, then interleaved U, V; the
+sample in the high ten bits) or `-pix_fmt yuv420p10le` (Y, U, V planes; the sample in the low ten bits) writes it: 3 bytes per pixel
+uploaded, the same path through lsfa_amd/yuv10.py (image_resize_transform_yuv420p10, MotionEstimator10), no host-side conversion.
 Drawing boxes into images (draw_boxes, :150-156) is left to the caller: the output is JSON.
 """
 import argparse
@@ -48,9 +52,13 @@ from lsfa_amd.utils.load_model import load_param
 from lsfa_amd.utils.synthetic import SyntheticClip
 
 
-def yuv_file_frames(path, width, height):
-    """-> the bytes of one width x height 4:2:0 frame, the file's size, the frames it holds (None: not a whole number of them, or none)"""
-    frame_bytes = width * height + 2 * (-(-width // 2)) * (-(-height // 2))
+YUV_FORMATS = {'nv12': 1, 'i420': 1, 'p010': 2, 'yuv420p10le': 2}          # format -> bytes per sample
+
+
+def yuv_file_frames(path, width, height, sample_bytes=1):
+    """-> the bytes of one width x height 4:2:0 frame of `sample_bytes` bytes per sample, the file's size, the frames it holds (None: not a
+    whole number of them, or none)"""
+    frame_bytes = (width * height + 2 * (-(-width // 2)) * (-(-height // 2))) * sample_bytes
     size = os.path.getsize(path)
     return frame_bytes, size, (None if size == 0 or size % frame_bytes else size // frame_bytes)
 
@@ -157,19 +165,22 @@ class FrameDirClip(_EstimatedClip):
 
 
 class YuvFileClip(_EstimatedClip):
-    """Frames of one clip from a raw YUV 4:2:0 file (fmt 'nv12': Y plane, then interleaved U, V; 'i420': Y, U, V planes), frames back to
+    """Frames of one clip from a raw YUV 4:2:0 file (fmt 'nv12': Y plane, then interleaved U, V; 'i420': Y, U, V planes; 'p010' and
+    'yuv420p10le': the same two layouts in 16-bit little-endian words holding 10-bit samples, in the high and the low ten bits), frames back to
     back without a header.  Same interface as FrameDirClip: frame(i) is hip.image_resize_transform_yuv420 of the frame's planes on `device`,
     mv_res(i, key_i) the estimator's *_yuv chain when `estimate` (a dict of hip.MotionEstimator's parameters) is given, zero motion and
-    zero residual otherwise.  The file is memory-mapped; a frame's bytes are uploaded once and the frames of the current interval are kept."""
+    zero residual otherwise.  The file is memory-mapped; a frame's bytes are uploaded once and the frames of the current interval are kept.
+    A 10-bit format goes through lsfa_amd/yuv10.py instead: the uploaded buffer is viewed as int16 words."""
 
     def __init__(self, path, width, height, cfg, fmt='nv12', matrix='bt601', estimate=None, device='cuda:0', dump_mv=None):
-        if fmt not in ('nv12', 'i420'):
-            raise ValueError('fmt %r is not nv12 or i420' % (fmt,))
+        if fmt not in YUV_FORMATS:
+            raise ValueError('fmt %r is not one of %s' % (fmt, ', '.join(sorted(YUV_FORMATS))))
+        self.sample_bytes, self.semi_planar = YUV_FORMATS[fmt], fmt in ('nv12', 'p010')
         self.src_w, self.src_h, self.fmt, self.matrix, self.cfg = int(width), int(height), fmt, matrix, cfg
         if self.src_w <= 0 or self.src_h <= 0:
             raise ValueError('bad frame size %d x %d' % (self.src_w, self.src_h))
         self.cw, self.ch = -(-self.src_w // 2), -(-self.src_h // 2)
-        self.frame_bytes, size, self.num_frames = yuv_file_frames(path, self.src_w, self.src_h)
+        self.frame_bytes, size, self.num_frames = yuv_file_frames(path, self.src_w, self.src_h, self.sample_bytes)
         if self.num_frames is None:
             raise ValueError('%s holds %d bytes: not a whole number of %d x %d %s frames of %d bytes' % (path, size, self.src_w, self.src_h, fmt,
                                                                                                      self.frame_bytes))
@@ -189,26 +200,36 @@ class YuvFileClip(_EstimatedClip):
         self._dev = self._kept          # the frames' bytes as they lie in the file
 
     def planes(self, i):
-        """frame i as the keyword arguments of the hip.*yuv420* functions: views of ONE device tensor holding the frame's bytes"""
+        """frame i as the keyword arguments of the hip.*yuv420* (yuv10.*yuv420p10*) functions: views of ONE device tensor holding the
+        frame's bytes (its 16-bit words)"""
         if i not in self._dev:
             if self.estimate is None:
                 self._dev.clear()                             # nothing looks back at earlier frames
             raw = np.array(self._map[i * self.frame_bytes:(i + 1) * self.frame_bytes])         # one read of the mapped pages
             self._dev[i] = torch.from_numpy(raw).to(self.device)
         buf, n = self._dev[i], self.src_w * self.src_h
+        if self.sample_bytes == 2:
+            buf = buf.view(torch.int16)
         y = buf[:n].view(self.src_h, self.src_w)
-        if self.fmt == 'nv12':
+        if self.semi_planar:
             return dict(y=y, uv=buf[n:].view(self.ch, 2 * self.cw))
         c = self.ch * self.cw
         return dict(y=y, u=buf[n:n + c].view(self.ch, self.cw), v=buf[n + c:].view(self.ch, self.cw))
 
     def frame(self, i):
-        from lsfa_amd import hip
         cfg = self.cfg
-        return hip.image_resize_transform_yuv420(im_scale=self.im_scale, matrix=self.matrix, pixel_means=cfg.network.PIXEL_MEANS,
-                                                 pixel_scale=cfg.network.PIXEL_SCALE, stride=cfg.network.IMAGE_STRIDE, **self.planes(i))
+        kw = dict(im_scale=self.im_scale, matrix=self.matrix, pixel_means=cfg.network.PIXEL_MEANS, pixel_scale=cfg.network.PIXEL_SCALE,
+                  stride=cfg.network.IMAGE_STRIDE)
+        if self.sample_bytes == 2:
+            from lsfa_amd import yuv10
+            return yuv10.image_resize_transform_yuv420p10(msb_aligned=self.fmt == 'p010', **kw, **self.planes(i))
+        from lsfa_amd import hip
+        return hip.image_resize_transform_yuv420(**kw, **self.planes(i))
 
     def _new_estimator(self, hip, key_i):
+        if self.sample_bytes == 2:
+            from lsfa_amd import yuv10
+            return yuv10.MotionEstimator10(self.src_w, self.src_h, self.device, msb_aligned=self.fmt == 'p010', matrix=self.matrix, **self.estimate)
         return hip.MotionEstimator(self.src_w, self.src_h, self.device, matrix=self.matrix, **self.estimate)
 
     def _feed(self, me, i, key):
@@ -243,7 +264,9 @@ def parse_args(argv=None):
     ap.add_argument('--mv', default=None, help='directory of per-frame .npz with mv / res arrays')
     ap.add_argument('--yuv', default=None, help='a raw YUV 4:2:0 file (frames back to back, no header) in place of --frames; needs --size')
     ap.add_argument('--size', default=None, help='--yuv: the frame size as WxH, e.g. 1280x720')
-    ap.add_argument('--yuv-format', default='nv12', choices=('nv12', 'i420'), help='--yuv: semi-planar (interleaved U, V) or planar chroma')
+    ap.add_argument('--yuv-format', default='nv12', choices=('nv12', 'i420', 'p010', 'yuv420p10le'),
+                    help='--yuv: semi-planar (interleaved U, V) or planar chroma of bytes; p010 / yuv420p10le: the same two of 10-bit samples in '
+                         '16-bit words, in the high / the low ten bits')
     ap.add_argument('--yuv-matrix', default='bt601', choices=('bt601', 'bt709', 'jpeg'), help='--yuv: the colour matrix of the stream')
     motion_options.add_arguments(ap, 'estimate block motion vectors from the frames on the GPU (needs --frames or --yuv)')
     ap.add_argument('--dump-mv', default=None, help='--estimate-mv: write the estimated mv / res as the .npz files --mv reads')
@@ -269,7 +292,7 @@ def parse_args(argv=None):
         w, h = args.yuv_size
         if not os.path.isfile(args.yuv):
             ap.error('--yuv: no such file: %s' % args.yuv)
-        frame_bytes, size, frames = yuv_file_frames(args.yuv, w, h)
+        frame_bytes, size, frames = yuv_file_frames(args.yuv, w, h, YUV_FORMATS[args.yuv_format])
         if frames is None:
             ap.error('--yuv: %s holds %d bytes, not a whole number of %dx%d frames of %d bytes' % (args.yuv, size, w, h, frame_bytes))
     elif args.size:

@@ -2084,7 +2084,11 @@ class _MotionSearch(object):
 
 class _SearchFront(object):
     """What MotionEstimator and SegmentMotionEstimator show of the _MotionSearch they stand in front of: its checked parameters and its
-    geometry, under its names.  The buffers of the modes (unmatched, keysad, ...) are the subclass's: views of the search's in its own shape."""
+    geometry, under its names.  The buffers of the modes (unmatched, keysad, ...) are the subclass's: views of the search's in its own shape.
+    _to_bgr is the one conversion behind the *_yuv methods of both: (y, uv, u, v, matrix, out=, y_packed=) -> out.  A subclass for planes
+    of another sample format overrides it (lsfa_amd/yuv10.py)."""
+
+    _to_bgr = staticmethod(yuv420_to_bgr_u8)
 
     def __init__(self, s):
         self._search = s
@@ -2210,9 +2214,9 @@ class MotionEstimator(_SearchFront):
             raise LsfaError("MotionEstimator.%s: a (%d, %d) uint8 Y plane on %s expected, got %s on %s" %
                             (who, self.height, self.width, self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
         if self.luma_from == 'y':
-            yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=bgr, y_packed=luma)
+            self._to_bgr(y, uv, u, v, self.matrix, out=bgr, y_packed=luma)
         else:
-            yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=bgr)
+            self._to_bgr(y, uv, u, v, self.matrix, out=bgr)
             luma_u8(bgr, out=luma)
         return bgr
 
@@ -2390,7 +2394,7 @@ class SegmentMotionEstimator(_SearchFront):
         N = C * (n + 1)
         self.bgr = self._bgr[:N * H * W * 3].view(C, n + 1, H, W, 3)
         from_y = self.luma_from == 'y'
-        yuv420_to_bgr_u8(y, uv, u, v, self.matrix, out=self.bgr.view(N, H, W, 3), y_packed=self._luma[:N * H * W].view(N, H, W) if from_y else None)
+        self._to_bgr(y, uv, u, v, self.matrix, out=self.bgr.view(N, H, W, 3), y_packed=self._luma[:N * H * W].view(N, H, W) if from_y else None)
         return self._run(self.bgr, n, im_scale, pixel_means, pixel_scale, int(rcnn_stride), out, from_y)
 
 

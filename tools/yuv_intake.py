@@ -1,16 +1,19 @@
 #!/usr/bin/env python
-"""Frame intake at 1000 x 600, packed BGR against NV12, N = 1, 9, 12 frames per call, in ONE process on one device (device events,
+"""Frame intake at 1000 x 600, packed BGR against NV12 and against 10-bit planes (P010 and planar 16-bit words), N = 1, 9, 12 frames per call, in ONE process on one device (device events,
 `--iters` calls per figure after a warm-up, `--rounds` rounds with the two paths alternating; every figure is printed as min / median / max
 over the rounds, which IS the run-to-run spread to judge a difference by):
 
     upload + intake      pinned host memory -> device copy -> `data`:  3 B/pixel + lsfa_image_transform_u8  against
-                         1.5 B/pixel + lsfa_image_transform_yuv420
+                         1.5 B/pixel + lsfa_image_transform_yuv420  and  3 B/pixel (16-bit words) + lsfa_image_transform_yuv420p10
     kernels alone        each intake kernel as a replayed graph of `--iters` launches (no host enqueue between them), with the bytes the
                          algorithm reads and writes over that time: lsfa_image_transform_u8, lsfa_image_transform_yuv420 (NV12, I420),
                          lsfa_yuv420_to_bgr_u8 (with and without y_packed), lsfa_luma_u8 (what y_packed saves), and the resize forms
-                         lsfa_image_resize_transform (uint8) / lsfa_image_resize_transform_yuv420 at scale 1, stride 16
+                         lsfa_image_resize_transform (uint8) / lsfa_image_resize_transform_yuv420 at scale 1, stride 16; and the 10-bit legs,
+                         semi-planar (P010) and planar: lsfa_image_transform_yuv420p10, lsfa_yuv420p10_to_bgr_u8 (with and without y_packed)
+                         and lsfa_image_resize_transform_yuv420p10
 
-The one expectation: the NV12 transform kernel is not slower than the u8 one beyond the spread - it writes the same bytes and reads half.
+The expectations: the NV12 transform kernel is not slower than the u8 one beyond the spread - it writes the same bytes and reads half - and
+neither is the 10-bit transform kernel (either layout), which reads the u8 kernel's 3 B and writes its 12 B per pixel.
 Prints one JSON object per line.  Ends itself after --time-limit seconds."""
 import argparse
 import ctypes
@@ -23,7 +26,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-from lsfa_amd import hip
+from lsfa_amd import hip, yuv10
 
 DEV = 'cuda:0'
 W, H = 1000, 600
@@ -83,7 +86,7 @@ def main():
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--frames', type=int, nargs='*', default=[1, 9, 12])
-    ap.add_argument('--time-limit', type=int, default=240, help='seconds after which the process ends itself')
+    ap.add_argument('--time-limit', type=int, default=420, help='seconds after which the process ends itself')
     args = ap.parse_args()
     signal.alarm(args.time_limit)
     if not torch.cuda.is_available():
@@ -111,6 +114,17 @@ def main():
         bgr_out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=DEV)
         y_packed = torch.empty((N, H, W), dtype=torch.uint8, device=DEV)
         luma = torch.empty((H, W), dtype=torch.uint8, device=DEV)
+        # 10-bit: the same surfaces in 16-bit words, the sample in the high ten bits (P010) - every word is defined input
+        h_p010 = torch.from_numpy(rs.randint(0, 1 << 16, (N, H * 3 // 2, W)).astype(np.uint16).view(np.int16)).pin_memory()
+        d_p010 = torch.empty((N, H * 3 // 2, W), dtype=torch.int16, device=DEV)
+        d_p010.copy_(h_p010)
+        y10, uv10 = d_p010[:, :H], d_p010[:, H:]
+        d_pl10 = d_p010.clone()
+        u10 = d_pl10[:, H:].reshape(N, 2, H // 2, W // 2)[:, 0]
+        v10 = d_pl10[:, H:].reshape(N, 2, H // 2, W // 2)[:, 1]
+        y10p = d_pl10[:, :H]
+        assert torch.equal(yuv10.image_transform_yuv420p10(y10, uv10, pixel_means=MEANS, pixel_scale=SCALE),
+                           hip.image_transform_u8(yuv10.yuv420p10_to_bgr_u8(y10, uv10), MEANS, SCALE))
         assert torch.equal(hip.image_transform_yuv420(y, uv, pixel_means=MEANS, pixel_scale=SCALE),
                            hip.image_transform_u8(hip.yuv420_to_bgr_u8(y, uv), MEANS, SCALE))
 
@@ -122,10 +136,15 @@ def main():
             d_nv12.copy_(h_nv12, non_blocking=True)
             hip.image_transform_yuv420(y, uv, pixel_means=MEANS, pixel_scale=SCALE, out=data)
 
-        r = eager_rounds(dict(bgr_upload_transform_u8=up_bgr, nv12_upload_transform_yuv420=up_nv12,
+        def up_p010():
+            d_p010.copy_(h_p010, non_blocking=True)
+            yuv10.image_transform_yuv420p10(y10, uv10, pixel_means=MEANS, pixel_scale=SCALE, out=data)
+
+        r = eager_rounds(dict(bgr_upload_transform_u8=up_bgr, nv12_upload_transform_yuv420=up_nv12, p010_upload_transform_yuv420p10=up_p010,
+                              p010_upload_only=lambda: d_p010.copy_(h_p010, non_blocking=True),
                               bgr_upload_only=lambda: d_bgr.copy_(h_bgr, non_blocking=True),
                               nv12_upload_only=lambda: d_nv12.copy_(h_nv12, non_blocking=True)), args.iters, args.rounds)
-        print(json.dumps(dict(N=N, what='upload + intake, eager', upload_bytes=dict(bgr=3 * px * N, nv12=px * N * 3 // 2), us=r)), flush=True)
+        print(json.dumps(dict(N=N, what='upload + intake, eager', upload_bytes=dict(bgr=3 * px * N, nv12=px * N * 3 // 2, p010=3 * px * N), us=r)), flush=True)
 
         def resize_u8():          # the C entry point itself: hip.image_resize_transform allocates its output at every call
             hip._check(hip.lib().lsfa_image_resize_transform(hip._ptr(d_bgr), 1, N, H, W, ctypes.c_double(1.0), H, W, 16, means_c, ctypes.c_double(SCALE),
@@ -142,6 +161,20 @@ def main():
             'image_resize_transform_u8': (resize_u8, (3 * px + 12 * 608 * 1008) * N),
             'image_resize_transform_yuv420': (lambda: hip.image_resize_transform_yuv420(y, uv, im_scale=1.0, pixel_means=MEANS, pixel_scale=SCALE, stride=16,
                                                                                        out=rdata), (1.5 * px + 12 * 608 * 1008) * N),
+            'image_transform_yuv420p10_semi': (lambda: yuv10.image_transform_yuv420p10(y10, uv10, pixel_means=MEANS, pixel_scale=SCALE, out=data),
+                                               (3 + 12) * px * N),
+            'image_transform_yuv420p10_planar': (lambda: yuv10.image_transform_yuv420p10(y10p, u=u10, v=v10, pixel_means=MEANS, pixel_scale=SCALE, out=data),
+                                                 (3 + 12) * px * N),
+            'yuv420p10_to_bgr_u8_semi': (lambda: yuv10.yuv420p10_to_bgr_u8(y10, uv10, out=bgr_out), (3 + 3) * px * N),
+            'yuv420p10_to_bgr_u8_semi+y_packed': (lambda: yuv10.yuv420p10_to_bgr_u8(y10, uv10, out=bgr_out, y_packed=y_packed), (3 + 4) * px * N),
+            'yuv420p10_to_bgr_u8_planar': (lambda: yuv10.yuv420p10_to_bgr_u8(y10p, u=u10, v=v10, out=bgr_out), (3 + 3) * px * N),
+            'yuv420p10_to_bgr_u8_planar+y_packed': (lambda: yuv10.yuv420p10_to_bgr_u8(y10p, u=u10, v=v10, out=bgr_out, y_packed=y_packed), (3 + 4) * px * N),
+            'image_resize_transform_yuv420p10_semi': (lambda: yuv10.image_resize_transform_yuv420p10(y10, uv10, im_scale=1.0, pixel_means=MEANS,
+                                                                                                     pixel_scale=SCALE, stride=16, out=rdata),
+                                                      (3 * px + 12 * 608 * 1008) * N),
+            'image_resize_transform_yuv420p10_planar': (lambda: yuv10.image_resize_transform_yuv420p10(y10p, u=u10, v=v10, im_scale=1.0, pixel_means=MEANS,
+                                                                                                       pixel_scale=SCALE, stride=16, out=rdata),
+                                                        (3 * px + 12 * 608 * 1008) * N),
         }
         r = graph_rounds({k: f for k, (f, _) in kernels.items()}, args.iters, args.rounds)
         for k, (_, nbytes) in kernels.items():
@@ -152,6 +185,11 @@ def main():
         print(json.dumps(dict(N=N, what='expectation: NV12 transform not slower than u8 beyond the spread',
                               u8=a['median'], nv12=b['median'], u8_spread=round(a['max'] - a['min'], 2), nv12_spread=round(b['max'] - b['min'], 2),
                               holds=bool(b['median'] <= a['median'] + max(a['max'] - a['min'], b['max'] - b['min'])))), flush=True)
+        for layout in ('semi', 'planar'):
+            b = r['image_transform_yuv420p10_' + layout]
+            print(json.dumps(dict(N=N, what='expectation: 10-bit transform (%s) not slower than u8 beyond the spread' % layout,
+                                  u8=a['median'], p10=b['median'], u8_spread=round(a['max'] - a['min'], 2), p10_spread=round(b['max'] - b['min'], 2),
+                                  holds=bool(b['median'] <= a['median'] + max(a['max'] - a['min'], b['max'] - b['min'])))), flush=True)
 
 
 if __name__ == '__main__':
