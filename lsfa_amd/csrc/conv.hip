@@ -117,6 +117,8 @@ Force force_for(const convsplit::Args& a) {
   return f;
 }
 
+// the st [A | B] stages the plan reasons with (conv_ring_kernel<4, 2, 2, false, false, 4> keeps a third A stage of 16 KB behind them, out of the
+// LDS its two workgroups per CU left unused: Ring::kDepthA - no plan, workspace or answer of these functions depends on it)
 size_t ring_lds_bytes(int nt, int pieces, int st) { return (size_t)st * (16384 + (size_t)nt * pieces * 2048); }
 bool ring_ok(int nt, int pieces, int st) {
   if (st < 2 || st > 4 || (nt != 2 && nt != 4) || pieces < 1 || pieces > 3) return false;

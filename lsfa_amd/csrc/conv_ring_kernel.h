@@ -3,7 +3,8 @@
 //                                2 = two fp16 pieces + a power-of-two scale per map, three products;
 //                                1 = one bf16 piece (round to nearest even), one product: the bf16 mode of BASELINE configs[2]
 //   NT  32-column accumulator tiles per wave (2: 128 x 64 workgroup tiles, 4: 128 x 128)
-//   ST  stages of the LDS ring (2 ... 4): ST - 1 chunks of K in flight per workgroup
+//   ST  stages of the LDS ring (2 ... 4): ST - 1 chunks of K in flight per workgroup (r14: <4, 2, 2, false, false, 4> holds A one stage deeper than
+//       B - ST stays B's depth, Ring::kDepthA is A's - and has a chunk and a half in flight: "the asymmetric ring" below)
 //   SP  split roles: waves 4-7 of a 512-thread workgroup issue the copies, waves 0-3 cut and multiply
 //   AF  the input's bn + ReLU applied where the operand is cut (Args::in_scale)
 //   WV  waves that multiply: 4 (128-pixel tiles) or 8 (r5: 256-pixel tiles, eight mixed-role waves, two per SIMD)
@@ -26,6 +27,10 @@
 // which the LDS-DMA path delivers at 45-75 GB/s per CU for this access pattern (120 from an L2-resident megabyte, 27 from the Infinity
 // Cache), against the 768 matrix cycles (0.41 us at the 1.88 GHz the part holds under this load) the chunk is worth: the two sides are
 // balanced within 25 %, and neither a deeper ring, tile order, wave priorities nor the pinned step move the sum by more than 5-8 %.
+// r14 (profiles/r14/ring_a_depth.txt): <4, 2, 2, false, false, 4>'s waves sat in a counted wait for 28-40 % of their cycles with the LDS array
+// active in 14-21 % of the CU's - the step waited for its one chunk in flight, not for LDS.  With A a stage deeper the launches take 2-15 %
+// fewer CU cycles (matrix duty 0.50 -> 0.54-0.59 on the long-K ones) but only 0-8 % less time: the part clocks down under the denser
+// step, and the kernels behind it in a backbone pass run ~2 % slower for it.  bench.py gains 1.1-1.3 %, the segment pass 1.6 %.
 #pragma once
 #include "conv_split_kernel.h"
 
@@ -48,18 +53,43 @@ constexpr int kRingIssueA = 2;
 constexpr int kRingIssueA = 4;
 #endif
 
-template <int NT, int PC, int ST, int WV = 4> struct Ring {     // WV: waves that multiply (4: 128-pixel tiles; 8: 256-pixel tiles, mixed roles only)
+// r14: the ASYMMETRIC ring of the four-wave mixed-role 128 x 128 two-piece kernel <4, 2, 2, false, false, 4>: B stays ST = 2 stages deep, A
+// gets a third stage (ring_step_deep_a below).  Two workgroups took 2 x 64 KB of the CU's 160 KB; the 32 KB left over are one more A stage
+// (16 KB) each.  LSFA_RING_DEEP_A=0 builds the symmetric ring of before from the same source (tools/lab/build_variant.sh), for an A/B.
+#ifndef LSFA_RING_DEEP_A
+#define LSFA_RING_DEEP_A 1
+#endif
+template <int NT, int PC, int ST, bool SP, bool AF, int WV> constexpr int ring_depth_a() {
+  return (LSFA_RING_DEEP_A && NT == 4 && PC == 2 && ST == 2 && !SP && !AF && WV == 4) ? ST + 1 : ST;
+}
+
+// DA: stages of A (ST everywhere but in the asymmetric ring).  The LDS image is ST stages of [A | B] and, behind them, DA - ST further A
+// stages: ONE array, stage index ST .. DA - 1 of `R[stage][wave * 256]` names those (their B half does not exist).
+template <int NT, int PC, int ST, int WV = 4, int DA = ST> struct Ring {     // WV: waves that multiply (4: 128-pixel tiles; 8: 256-pixel tiles, mixed roles only)
   static constexpr int kColTile = 128 * PC;                 // uint4 of one 32-column tile of one chunk: 2 steps x PC pieces x 64 lanes
   static constexpr int kStageA = WV * 256;                  // uint4 of A per stage: WV waves x 32 pixels x 8 slots (4 KB per wave)
   static constexpr int kStageBn = NT * kColTile;
   static constexpr int kStageN = kStageA + kStageBn;        // uint4 per stage: 4 WV KB of A + NT x PC x 2 KB of B
   static constexpr int kDmaB = (NT * kColTile) / (WV * 64); // B DMA instructions per wave and chunk: NT * PC / 2 (WV = 8: / 4)
   static constexpr int kDma = kRingIssueA + kDmaB;          // all DMA instructions per wave and chunk (4 of A + B's)
-  static constexpr int kLdsBytes = ST * kStageN * 16;
+  static constexpr int kStages = ST, kDepthA = DA;
+  static constexpr int kLdsN = ST * kStageN + (DA - ST) * kStageA;      // uint4 of the whole ring
+  static constexpr int kLdsBytes = kLdsN * 16;
   static constexpr int kWgPerCu = (2 * kLdsBytes <= 160 * 1024) ? 2 : 1;
   static_assert((NT * kColTile) % (WV * 64) == 0, "NT * PC must be a multiple of WV / 2");
   static_assert(kLdsBytes <= 160 * 1024, "ring does not fit the CU's LDS");
-  static_assert((ST - 1) * kDma <= 63, "vmcnt is a 6-bit counter");
+  static_assert((ST - 1) * kDma + (DA - ST) * kRingIssueA <= 63, "vmcnt is a 6-bit counter");
+  static_assert(DA == ST || DA == ST + 1, "at most one A stage beyond the [A | B] stages");
+};
+
+// the type of a kernel's LDS image: the array of stages itself, or (asymmetric ring) that array with the further A stages behind it in one object
+template <class RG, bool DEEP = (RG::kDepthA > RG::kStages)> struct RingImage {
+  typedef uint4 type[RG::kStages][RG::kStageN];
+  __device__ static __forceinline__ type& stages(type& img) { return img; }
+};
+template <class RG> struct RingImage<RG, true> {
+  struct type { uint4 s[RG::kStages][RG::kStageN]; uint4 a[(RG::kDepthA - RG::kStages) * RG::kStageA]; };
+  __device__ static __forceinline__ uint4 (&stages(type& img))[RG::kStages][RG::kStageN] { return img.s; }
 };
 
 // r4 (Args::in_scale): the 16 channels a lane cuts from chunk `gch` are 32 gch + 16 (lane >> 5) + 0..15 (r0..r3, four each).  T holds
@@ -178,11 +208,12 @@ template <int NT, int PC, bool AF, int DMA = 0, int WV = 4> __device__ __forcein
 // they are wanted back.  k-step 0 of every column tile first, then k-step 1 (per accumulator the order of the products is unchanged:
 // bit-identical), so that the first k-step's pieces die halfway through the step and the second half of the raw rows is read late: the
 // step's peak is ~16 registers lower, which is what lets the pinned order fit 256 registers where two waves share a SIMD.
-template <int NT, int PC, int ST, int WV, int S, bool AF, int DMA = 0>
+// SA: the stage whose A half holds A(v + 1) (the asymmetric ring: another one than B(v)'s).
+template <int NT, int PC, int ST, int WV, int S, bool AF, int DMA = 0, int SA = S>
 __device__ __forceinline__ Cut ring_mma_cut(const uint4 (*R)[(Ring<NT, PC, ST, WV>::kStageN)], const Geom& g, const Cut& p, f32x16 (&acc)[NT], float a_scale,
                                             int gch_next, const float* T) {
   const uint4* B = &R[S][Ring<NT, PC, ST, WV>::kStageA + g.lane];
-  const uint4* A = &R[S][g.wave * 256];
+  const uint4* A = &R[SA][g.wave * 256];
   uint4 bf[NT * 2][PC];      // fragment (col tile t, step s, piece q) at ((t*2 + s)*PC + q)*64 + lane
 #pragma unroll
   for (int q = 0; q < PC; ++q) bf[0][q] = B[q * 64];
@@ -233,6 +264,44 @@ __device__ __forceinline__ void ring_step_uniform(uint4 (*R)[(Ring<NT, PC, ST, W
   ring_issue_a<NT, PC, ST, WV, SN>(R, x, g, cur, v + ST < n);
   ring_issue_b<NT, PC, ST, WV, SN, 0, RG::kDmaB>(R, wblock, g, cur.bprev);      // B(v + ST - 1); past the slice's end: some valid block, into a stage nobody reads
   p = ring_mma_cut<NT, PC, ST, WV, S, AF, RG::kDma>(R, g, p, acc, a_scale, g.chunk0 + v + 1, T);
+}
+
+// ---- r14: the uniform step on the asymmetric ring (ST = 2 stages of B, three of A) ---------------------------------------------------------
+// With two symmetric stages the step above opens with vmcnt(0) and issues A(v + 2), B(v + 1) behind the barrier: a workgroup has ONE 32 KB
+// chunk in flight, and that chunk has one step (~0.4 us of matrix work) to land.  Here B(v) lives in B stage v % 2 and A(k) in A stage k % 3
+// (the A halves of stages 0 and 1, and stage index 2: 16 KB behind the ring), and step v issues B(v + 1), then A(v + 3): a chunk and a half
+// in flight, and an A chunk has two steps to land.  The stage pair of a step repeats with period 6 (V6 = v % 6), which divides kFlush.
+// WHY EVERY ACCESS IS ORDERED (by the counts, cdna_hip_programming.md "Read a staged buffer one phase AFTER the wait that retires it"; an
+// LDS read is ordered behind an LDS-DMA only by the issuing wave's vmcnt, plus a barrier for other waves' reads).  A wave's vector-memory
+// operations, oldest first, when step v opens: ..., A(v + 1) [step v - 2], B(v) [step v - 1], A(v + 2) [step v - 1]; they retire in order.
+//   read of B(v), step v     every wave issued its share of B(v) in step v - 1 (the prologue for v = 0); vmcnt(kRingIssueA) at the top of step v
+//                            leaves only the wave's A(v + 2) outstanding, so its share has landed; the barrier behind that wait makes it
+//                            every wave's share.  The reads sit behind the barrier.
+//   read of A(v + 1), step v A is wave-private (written and read by the same wave): issued in step v - 2 (the prologue for v <= 1), older than
+//                            B(v), retired by the same vmcnt(kRingIssueA).  No barrier is needed (one follows anyway).
+//   issue of B(v + 1)        into B stage (v + 1) % 2, which held B(v - 1), read by every wave in step v - 1: each wave's lgkmcnt(0) at the top
+//                            of step v retires its reads, the barrier behind it collects them all; the issue sits behind the barrier.
+//   issue of A(v + 3)        into A stage v % 3, which held A(v), read by this wave alone in step v - 1: retired by its lgkmcnt(0).
+//   first cut (A(0))         the prologue issues A(0), A(1), B(0), A(2); vmcnt(kDma + kRingIssueA) leaves the last three groups outstanding.
+// Past the slice's end A comes from the block of zeros (the last TWO issues now) and B from some valid block, into stages nobody reads:
+// every step is the same count of DMAs, drained before the epilogue as before.  `bq` is the weight block of B(v + 1) (the walk stands at
+// A(v + 3), two blocks further); it is handed on from the walk's `bprev`.  Same cut, same MFMAs in the same order: bit-identical results.
+template <int NT, int PC, int ST, int WV, int V6, bool AF>
+__device__ __forceinline__ void ring_step_deep_a(uint4 (*R)[(Ring<NT, PC, ST, WV>::kStageN)], const float* __restrict__ x, const uint4* __restrict__ wblock,
+                                                 const Geom& g, Walk& wk, int& bq, int v, int n, f32x16 (&acc)[NT], Cut& p, float a_scale, const float* T) {
+  typedef Ring<NT, PC, ST, WV, ST + 1> RG;
+  static_assert(ST == 2, "B stage v % 2, A stage k % 3");
+  constexpr int SB = V6 % 2, SBN = (V6 + 1) % 2;      // B(v), B(v + 1)
+  constexpr int SA = (V6 + 1) % 3, SAN = V6 % 3;      // A(v + 1), A(v + 3)
+  wait_vmcnt<kRingIssueA>();
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  const Walk cur = wk;
+  wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
+  ring_issue_b<NT, PC, ST, WV, SBN, 0, RG::kDmaB>(R, wblock, g, bq);
+  ring_issue_a<NT, PC, ST, WV, SAN>(R, x, g, cur, v + 3 < n);
+  bq = cur.bprev;
+  p = ring_mma_cut<NT, PC, ST, WV, SB, AF, RG::kDma, SA>(R, g, p, acc, a_scale, g.chunk0 + v + 1, T);
 }
 
 // ---- split roles (SP): waves 4-7 of a 512-thread workgroup issue the copies, waves 0-3 cut and multiply ------------------------------
@@ -325,11 +394,18 @@ __device__ __forceinline__ void ring_step_r4(uint4 (*R)[(Ring<NT, PC, ST, 4>::kS
 template <int NT, int PC, int ST, bool SP = false, bool AF = false, int WV = 4>
 // (two resident workgroups only where their registers allow it: a 128 x 128 tile with loader waves needs ~230 per lane; WV = 8: 512 threads, 256 registers)
 static __global__ __launch_bounds__((SP || WV == 8 ? 2 : 1) * kThreads,
-    WV == 8 ? 2 : (((AF ? 2 * (Ring<NT, PC, ST, WV>::kLdsBytes + 16384) <= 160 * 1024 : Ring<NT, PC, ST, WV>::kWgPerCu == 2) && !(SP && NT == 4)) ? 2 : 1) * (SP ? 2 : 1))
+    WV == 8 ? 2 : (((AF ? 2 * (Ring<NT, PC, ST, WV>::kLdsBytes + 16384) <= 160 * 1024 : Ring<NT, PC, ST, WV, ring_depth_a<NT, PC, ST, SP, AF, WV>()>::kWgPerCu == 2) && !(SP && NT == 4)) ? 2 : 1) * (SP ? 2 : 1))
 void conv_ring_kernel(Args a, int nx, int ny, int nz) {
-  typedef Ring<NT, PC, ST, WV> RG;
-  __shared__ __attribute__((aligned(16))) uint4 R[ST][RG::kStageN];
+  constexpr bool kDeepA = ring_depth_a<NT, PC, ST, SP, AF, WV>() > ST;      // the asymmetric ring (r14): one A stage more than B stages
+  typedef Ring<NT, PC, ST, WV, ring_depth_a<NT, PC, ST, SP, AF, WV>()> RG;
+  // ONE object holds the ring: the ST [A | B] stages, as everywhere, and behind them the asymmetric ring's third A stage (80 KB: two workgroups
+  // are the CU's 160 KB exactly).  The table's four-float placeholder of the kernels without AF is never referenced and takes no LDS (the
+  // kernels' resource usage reads 65536 / 81920 bytes, profiles/r14/ring_a_depth.txt); the AF kernels keep their ring and their table.
+  __shared__ __attribute__((aligned(16))) typename RingImage<RG>::type Rimg;
+  uint4 (&R)[ST][RG::kStageN] = RingImage<RG>::stages(Rimg);
   __shared__ __attribute__((aligned(16))) float T[AF ? 2 * kAffineMaxCin : 4];
+  static_assert(sizeof(Rimg) == RG::kLdsBytes, "the ring's image is what Ring says it is");
+  static_assert(!kDeepA || (RG::kWgPerCu == 2 && !AF), "the third A stage must not cost the second workgroup of a CU");
   Tile tile = xcd_tile(blockIdx.x, nx, ny, nz, a.tile_order, a.inv_nx, a.inv_ny);
   if (tile.x < 0) return;
   if (a.nphase > 1) { const int slices = nz / a.nphase, phase = tile.z / slices; tile.z -= phase * slices; apply_phase(a, phase, slices); }
@@ -494,7 +570,21 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
     }
     return;                 // the epilogue is the consumers'
   }
-  if (kUniform) {
+  int bq = 0;      // asymmetric ring: the weight block of the next B to issue (ring_step_deep_a)
+  if constexpr (kDeepA) {
+    // A(0), A(1), then [B(0), A(2)]: A(k) into A stage k % 3, B(0) into B stage 0; the walk ends at A(3), bq = B(1)'s block
+    const int b0 = wk.bidx;
+    ring_issue_a<NT, PC, ST, WV, 0>(R, a.x, g, wk, true);
+    wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
+    bq = wk.bidx;
+    ring_issue_a<NT, PC, ST, WV, 1>(R, a.x, g, wk, 1 < nchunks);
+    wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
+    ring_issue_b<NT, PC, ST, WV, 0, 0, RG::kDmaB>(R, wblock, g, b0);
+    ring_issue_a<NT, PC, ST, WV, 2>(R, a.x, g, wk, 2 < nchunks);
+    wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
+    wait_vmcnt<RG::kDma + kRingIssueA>();      // A(0) has landed: A(1), B(0), A(2) may be outstanding
+    LSFA_SCALES_READY(RG::kDma + kRingIssueA)  // (older than every copy: landed with A(0))
+  } else if (kUniform) {
     ring_issue_a<NT, PC, ST, WV, ST - 1>(R, a.x, g, wk, true);
     wk.next(g.kh, g.kw, g.chunks_per_tap, g.k_order);
     ring_prologue<NT, PC, ST, WV, 0, true, false>(R, a.x, wblock, g, wk, nchunks);
@@ -507,8 +597,28 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // AF: this wave's share of the table is written
   __builtin_amdgcn_s_barrier();                            // v-chunk -1 has landed
-  Cut p = ring_cut<NT, PC, ST, WV, ST - 1, AF>(R, g, a_scale, g.chunk0, T);
-  {
+  Cut p = ring_cut<NT, PC, ST, WV, kDeepA ? 0 : ST - 1, AF>(R, g, a_scale, g.chunk0, T);
+  if constexpr (kDeepA) {
+    // unrolled over the six (B stage, A stage) pairs of a step; kFlush = 12 is two turns, so the flush points are those of every other plan
+    static_assert(kFlush % 6 == 0, "the flush points must not depend on the ring");
+    int since = 0;
+    for (int c = 0; c < nchunks; c += 6) {
+      ring_step_deep_a<NT, PC, ST, WV, 0, AF>(R, a.x, wblock, g, wk, bq, c, nchunks, acc, p, a_scale, T);
+      if (c + 1 < nchunks) ring_step_deep_a<NT, PC, ST, WV, 1, AF>(R, a.x, wblock, g, wk, bq, c + 1, nchunks, acc, p, a_scale, T);
+      if (c + 2 < nchunks) ring_step_deep_a<NT, PC, ST, WV, 2, AF>(R, a.x, wblock, g, wk, bq, c + 2, nchunks, acc, p, a_scale, T);
+      if (c + 3 < nchunks) ring_step_deep_a<NT, PC, ST, WV, 3, AF>(R, a.x, wblock, g, wk, bq, c + 3, nchunks, acc, p, a_scale, T);
+      if (c + 4 < nchunks) ring_step_deep_a<NT, PC, ST, WV, 4, AF>(R, a.x, wblock, g, wk, bq, c + 4, nchunks, acc, p, a_scale, T);
+      if (c + 5 < nchunks) ring_step_deep_a<NT, PC, ST, WV, 5, AF>(R, a.x, wblock, g, wk, bq, c + 5, nchunks, acc, p, a_scale, T);
+      since += 6;
+      if (since >= kFlush) {
+        since = 0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) { sum[t][i] = sum[t][i] + acc[t][i]; acc[t][i] = 0.f; }
+      }
+    }
+  } else {
     int since = 0;
     for (int c = 0; c < nchunks; c += ST) {
       if (SP) {
@@ -546,7 +656,8 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
   // region and reads them back as float4 along the channels - lane -> (row 8k + lane / 8, channels 4 (lane % 8) ..): whole 128-byte
   // rows per 8 lanes, 16 bytes per lane, a quarter of the memory instructions.  Same values, same arithmetic per element.
   if (kUniform) wait_vmcnt<0>();      // the copies issued past the end must have landed before the ring becomes the epilogue's staging area
-  constexpr bool kRowsFit = RG::kLdsBytes >= WV * NT * 4096;       // the ring holds the waves' tiles
+  // (both "fit"s ask the ST [A | B] stages, not the asymmetric ring's 16 KB more: which way a tile leaves does not depend on A's depth)
+  constexpr bool kRowsFit = Ring<NT, PC, ST, WV>::kLdsBytes >= WV * NT * 4096;       // the ring holds the waves' tiles
   const bool rows_ok = kRowsFit && rows_path_ok(a);
   if (rows_ok) {
     float* part = a.part ? a.part + (size_t)tile.z * P * a.Cout : nullptr;
@@ -563,7 +674,7 @@ void conv_ring_kernel(Args a, int nx, int ny, int nz) {
     if (!part) publish_amax(m, a.amax_out, a.status, blockIdx.x * WV + g.wave);
     return;
   }
-  constexpr bool kColsFit = RG::kLdsBytes >= WV * NT * 32 * kColPitch * 4;       // ... or their padded column-major images
+  constexpr bool kColsFit = Ring<NT, PC, ST, WV>::kLdsBytes >= WV * NT * 32 * kColPitch * 4;      // ... or their padded column-major images
   if (kColsFit && a.y_nchw && !a.part && !a.view) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                       // every wave is done reading the ring

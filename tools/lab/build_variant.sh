@@ -2,6 +2,7 @@
 # A variant build of the library for A/B runs: the named sources (default conv.hip) recompiled with extra flags, every other object taken from
 # the product build.
 #   tools/lab/build_variant.sh NAME "-DLSFA_RING_B_AUX=16" [conv.hip ...]   ->  tools/lab/_build/var/liblsfa_hip_NAME.so   (select it with LSFA_HIP_LIBRARY)
+#   tools/lab/build_variant.sh symring "-DLSFA_RING_DEEP_A=0"                ->  ... the symmetric two-stage ring of conv_ring_kernel<4, 2, 2, false, false, 4> (r14 A/B)
 # Built HERE (hipcc cross-compiles without a GPU); the .so travels to the GPU box with the snapshot.
 set -eu
 cd "$(dirname "$0")/../.."
