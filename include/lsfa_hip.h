@@ -710,8 +710,9 @@ int lsfa_mv_key_sad_accu(const unsigned char* luma_cur, const unsigned char* lum
  *        R = clip((298 C + 459 E + 128) >> 8)   G = clip((298 C -  55 D - 136 E + 128) >> 8)   B = clip((298 C + 541 D + 128) >> 8)
  *     matrix 2, BT.601 full range (JFIF), o = 0:
  *        R = clip((256 C + 359 E + 128) >> 8)   G = clip((256 C -  88 D - 183 E + 128) >> 8)   B = clip((256 C + 454 D + 128) >> 8)
- * Out of scope: NV21, 4:2:2 and 4:4:4; interpolated chroma; any binding to rocDecode (a decoded surface's base, pitch and
- * height ARE the arguments: INTEGRATION.md).  10-bit samples (P010, yuv420p10le) have entry points of their own at the end of this header.
+ * Out of scope: interpolated chroma; any binding to rocDecode (a decoded surface's base, pitch and height ARE the arguments:
+ * INTEGRATION.md).  10-bit samples (P010, yuv420p10le) and the other chroma formats (NV21, 4:2:2, 4:4:4, packed YUYV / UYVY) have entry
+ * points of their own at the end of this header.
  * Planes: a base pointer, a row pitch in bytes and, for N frames, a frame stride in bytes each; a pitch wider than the row is normal
  * (y_pitch >= W; c_pitch >= 2 ceil(W / 2) for NV12, >= ceil(W / 2) for I420), a frame stride may be anything that does not overlap.
  * v == NULL: u_or_uv is the interleaved U, V plane (NV12); otherwise u_or_uv and v are I420's two chroma planes, with one pitch and stride.
@@ -808,6 +809,62 @@ int lsfa_image_resize_transform_yuv420p10(const void* y, long long y_pitch, long
                                           const void* v /* NULL: interleaved */, long long c_pitch, long long c_frame_stride, int N, int H, int W,
                                           int matrix, int shift, double im_scale, int h1, int w1, int stride, const double* pixel_means_bgr_host,
                                           double pixel_scale, float* data_nchw, int out_h, int out_w, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * YUV intake, other chroma formats (lsfa_amd/csrc/yuvfmt.hip): 4:2:2 and 4:4:4, chroma interleaved V, U, packed YUYV / UYVY - what capture
+ * cards and webcams (YUYV / YUY2, UYVY), MJPEG cameras (yuvj422p, yuvj444p: matrix 2), contribution codecs (yuv422p10le, P210), screen
+ * content (4:4:4) and Android cameras (NV21) hand over - to the same three outputs as the two intakes above.  The three exports mirror the
+ * 10-bit prototypes argument for argument with `format` where those have `shift`.  The specification is the shipped one with the chroma
+ * address generalised (DESIGN.md "YUV intake", "Other chroma formats"; restated in numpy as tests/ref_yuvfmt.py on tests/ref_yuv.py's and
+ * tests/ref_yuv10.py's conversions) and is bit-exact with THAT.  format = sub | layout << 4 | sample << 8, three independent choices:
+ *   sub: pixel (x, y) takes Y[y][x] and the chroma sample (x >> sx, y >> sy), nearest neighbour; chroma planes are
+ *     ceil(W / 2^sx) x ceil(H / 2^sy); any W, H >= 1.   0: 4:2:0 (sx, sy) = (1, 1)   1: 4:2:2 (1, 0)   2: 4:4:4 (0, 0)
+ *   layout: 0: two planes U (u_or_uv) and V (v) with one pitch and one frame stride   1: one interleaved plane U, V (v == NULL)
+ *     2: one interleaved plane V, U (v == NULL: NV21 / NV61 / NV42)   3: packed Y0 U Y1 V (YUYV / YUY2)   4: packed U Y0 V Y1 (UYVY).
+ *     Packed (3, 4): a row is ceil(W / 2) four-byte groups; `y` is the packed plane and y_pitch its pitch, at least 4 ceil(W / 2); both
+ *     chroma pointers are NULL and both chroma pitches and strides 0; with odd W the last group's second Y is never part of the result.
+ *   sample: 0: bytes, converted by the 8-bit table ("YUV 4:2:0 intake" above), y_packed = Y   1: 16-bit words with the value in the low ten
+ *     bits: the 10-bit specification's conversion, rounding and y_packed rule with shift = 0   2: in the high ten bits: shift = 6.
+ *   Packed layouts exist only with sub = 1 and sample = 0; every other combination is valid: 27 + 2 formats.  Matrices 0..2 as above.
+ *   The 4:2:0 formats of the two intakes above (layouts 0 and 1) are taken too and give their bytes.
+ * Out of scope: interpolated or sited chroma; packed 10-bit (v210, Y210, Y410); 12-bit; 4:1:1 / 4:1:0; YVYU; alpha; BT.2020 / HDR transfer; RGB
+ * surfaces.
+ * Pitches and frame strides are in BYTES.  LSFA_EINVAL, before anything is launched, for: a format outside the above; a NULL plane or output;
+ * v given with layouts 1 and 2 or missing with layout 0; a chroma pointer, pitch or stride with a packed layout; N, H or W below 1; a matrix
+ * outside 0..2; for words an odd base, pitch or frame stride; a pitch below its row (Y: W samples; planar chroma ceil(W / 2^sx) samples,
+ * interleaved twice that; packed 4 ceil(W / 2) bytes).
+ * One launch each, on `stream`, no workspace, nothing allocated; reported under LSFA_OP_STEM.  W % 4 == 0 (and for 4:2:0 an even H) with
+ * every base, pitch and frame stride a multiple of the load it feeds takes the four-pixel kernel compiled for the format; anything else -
+ * odd bases, pitches or strides, any other W, an odd H of 4:2:0 - the element-wise kernel, which takes layout and subsampling at run time
+ * (compiled for bytes and for words), as the resize kernel does.  The loads, in bytes (words: twice): Y 4; packed 8; planar chroma 2 (4:4:4: 4) per plane; interleaved chroma 4 (4:4:4: 8).
+ * The outputs as above: bgr and y_packed dword aligned, `data` 16-byte aligned for the four-pixel kernel.
+ * lsfa_yuv_to_bgr_u8: bgr (N, H, W, 3) uint8, packed; y_packed (N, H, W) uint8 or NULL.
+ * lsfa_image_transform_yuv: `data` (N, 3, H, W) float32: DEFINED as lsfa_image_transform_u8 of lsfa_yuv_to_bgr_u8's frame, bit for bit.
+ * lsfa_image_resize_transform_yuv: DEFINED as lsfa_image_resize_transform with is_u8 = 1 of that frame, bit for bit, reading its taps from the
+ *   planes; h1, w1, stride, out_h, out_w as there - checked.
+ * ------------------------------------------------------------------------ */
+#define LSFA_YUV_420 0
+#define LSFA_YUV_422 1
+#define LSFA_YUV_444 2
+#define LSFA_YUV_PLANAR 0
+#define LSFA_YUV_UV 1
+#define LSFA_YUV_VU 2
+#define LSFA_YUV_YUYV 3
+#define LSFA_YUV_UYVY 4
+#define LSFA_YUV_U8 0
+#define LSFA_YUV_LO10 1
+#define LSFA_YUV_HI10 2
+#define LSFA_YUV_FORMAT(sub, layout, sample) ((sub) | (layout) << 4 | (sample) << 8)
+int lsfa_yuv_to_bgr_u8(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
+                       long long c_frame_stride, int N, int H, int W, int matrix, int format, unsigned char* bgr,
+                       unsigned char* y_packed /* may be NULL */, void* stream);
+int lsfa_image_transform_yuv(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
+                             long long c_frame_stride, int N, int H, int W, int matrix, int format, const double* pixel_means_bgr_host,
+                             double pixel_scale, float* data_nchw, void* stream);
+int lsfa_image_resize_transform_yuv(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v,
+                                    long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int format, double im_scale,
+                                    int h1, int w1, int stride, const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw,
+                                    int out_h, int out_w, void* stream);
 
 #ifdef __cplusplus
 }

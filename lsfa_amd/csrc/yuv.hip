@@ -11,7 +11,7 @@
 //   matrix 0 (BT.601 limited)  o = 16  R = clip((298 C + 409 E + 128) >> 8)  G = clip((298 C - 100 D - 208 E + 128) >> 8)  B = clip((298 C + 516 D + 128) >> 8)
 //   matrix 1 (BT.709 limited)  o = 16  R = clip((298 C + 459 E + 128) >> 8)  G = clip((298 C -  55 D - 136 E + 128) >> 8)  B = clip((298 C + 541 D + 128) >> 8)
 //   matrix 2 (BT.601 full)     o = 0   R = clip((256 C + 359 E + 128) >> 8)  G = clip((256 C -  88 D - 183 E + 128) >> 8)  B = clip((256 C + 454 D + 128) >> 8)
-// Out of scope: NV21, 4:2:2 and 4:4:4, interpolated chroma, any binding to rocDecode.  10-bit samples (P010, yuv420p10le): yuv10.hip.
+// Out of scope: interpolated chroma, any binding to rocDecode.  10-bit samples (P010, yuv420p10le): yuv10.hip.  NV21, 4:2:2, 4:4:4: yuvfmt.hip.
 //
 // Bandwidth kernels.  yuv420_quad_kernel gives a thread four horizontally adjacent pixels of two rows: two Y dwords, one dword holding two
 // U, V pairs (two half-words for I420) - every chroma sample is read once - and, for `data`, six 16-byte stores.  yuv420_bytes_kernel is the

@@ -12,7 +12,7 @@
 //   - the 8-bit formulas with rounding constant 512 and shift 10: converted in ten bits, rounded once; |intermediate| < 2^20;
 //   y_packed = min(255, (Y + 2) >> 2).
 // Planes that are exactly 4 x an 8-bit plane give yuv.hip's BGR and Y bit for bit.
-// Out of scope: 12-bit and P016's low bits as signal, NV21, 4:2:2 and 4:4:4, interpolated chroma, HDR transfer functions, rocDecode.
+// Out of scope: 12-bit and P016's low bits as signal, interpolated chroma, HDR transfer functions, rocDecode.  NV21, 4:2:2, 4:4:4: yuvfmt.hip.
 //
 // Bandwidth kernels in yuv.hip's shape.  yuv420p10_quad_kernel gives a thread four horizontally adjacent pixels of two rows: two 8-byte Y
 // loads, one 8-byte load of two U, V pairs (two 4-byte loads for planar chroma) - every chroma sample is read once - and yuv_out.h's quad

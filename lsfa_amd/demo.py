@@ -11,6 +11,8 @@ score above 0.7 after per-class NMS.
 
     python -m lsfa_amd.demo --yuv clip.nv12 --size 1280x720 [--yuv-format nv12|i420] [--yuv-matrix bt601|bt709|jpeg] [--estimate-mv ...]
     python -m lsfa_amd.demo --yuv clip.p010 --size 1920x1080 --yuv-format p010|yuv420p10le [--yuv-matrix ...] [--estimate-mv ...]   # 10-bit
+    python -m lsfa_amd.demo --yuv cam.yuyv --size 1280x720 --yuv-format yuyv422 [--estimate-mv ...]      # a capture card's packed 4:2:2
+    python -m lsfa_amd.demo --yuv clip.yuv --size 1920x1080 --yuv-format yuv422p10le|yuv444p|nv21|... [--yuv-matrix ...] [--estimate-mv ...]
 
 --frames: a directory of *.JPEG / *.jpg / *.png frames in display order (decoded with PIL; the
 reference uses cv2.imread, :75).  --mv: one `<frame stem>.npz` per non-key frame holding `mv`
@@ -31,6 +33,9 @@ methods convert and search them (DESIGN.md "YUV intake"; the conversion is this 
 --yuv-format p010 | yuv420p10le: a 10-bit file of 16-bit little-endian words as `-pix_fmt p010le` (Y plane, then interleaved U, V; the
 sample in the high ten bits) or `-pix_fmt yuv420p10le` (Y, U, V planes; the sample in the low ten bits) writes it: 3 bytes per pixel
 uploaded, the same path through lsfa_amd/yuv10.py (image_resize_transform_yuv420p10, MotionEstimator10), no host-side conversion.
+--yuv-format with any other name of lsfa_amd.yuvfmt.FORMATS (nv21; yuv422p, nv16, nv61, yuyv422 / yuy2, uyvy422; yuv444p, nv24, nv42;
+yuv422p10le, p210, yuv444p10le, p410): the file as `-f rawvideo -pix_fmt X` writes it (yuvfmt.frame_bytes: planes back to back, no pitch),
+through lsfa_amd/yuvfmt.py (image_resize_transform_yuv, MotionEstimatorYuv).
 Drawing boxes into images (draw_boxes, :150-156) is left to the caller: the output is JSON.
 """
 import argparse
@@ -42,6 +47,7 @@ import time
 import numpy as np
 import torch
 
+from lsfa_amd import yuvfmt
 from lsfa_amd.config.config import config, lsfa_test_config, update_config, update_network_config
 from lsfa_amd.core.graphs import FrameGraphs
 from lsfa_amd.symbols import params as P
@@ -55,10 +61,10 @@ from lsfa_amd.utils.synthetic import SyntheticClip
 YUV_FORMATS = {'nv12': 1, 'i420': 1, 'p010': 2, 'yuv420p10le': 2}          # format -> bytes per sample
 
 
-def yuv_file_frames(path, width, height, sample_bytes=1):
-    """-> the bytes of one width x height 4:2:0 frame of `sample_bytes` bytes per sample, the file's size, the frames it holds (None: not a
-    whole number of them, or none)"""
-    frame_bytes = (width * height + 2 * (-(-width // 2)) * (-(-height // 2))) * sample_bytes
+def yuv_file_frames(path, width, height, sample_bytes=1, fmt=None):
+    """-> the bytes of one width x height 4:2:0 frame of `sample_bytes` bytes per sample - or of format `fmt` (yuvfmt.frame_bytes) - the
+    file's size, the frames it holds (None: not a whole number of them, or none)"""
+    frame_bytes = (width * height + 2 * (-(-width // 2)) * (-(-height // 2))) * sample_bytes if fmt is None else yuvfmt.frame_bytes(fmt, width, height)
     size = os.path.getsize(path)
     return frame_bytes, size, (None if size == 0 or size % frame_bytes else size // frame_bytes)
 
@@ -170,17 +176,22 @@ class YuvFileClip(_EstimatedClip):
     back without a header.  Same interface as FrameDirClip: frame(i) is hip.image_resize_transform_yuv420 of the frame's planes on `device`,
     mv_res(i, key_i) the estimator's *_yuv chain when `estimate` (a dict of hip.MotionEstimator's parameters) is given, zero motion and
     zero residual otherwise.  The file is memory-mapped; a frame's bytes are uploaded once and the frames of the current interval are kept.
-    A 10-bit format goes through lsfa_amd/yuv10.py instead: the uploaded buffer is viewed as int16 words."""
+    A 10-bit format goes through lsfa_amd/yuv10.py instead: the uploaded buffer is viewed as int16 words.  Any other name of
+    yuvfmt.FORMATS (4:2:2, 4:4:4, V before U, packed) goes through lsfa_amd/yuvfmt.py: planes(i) lays the file's planes out as its functions
+    take them, a packed frame as the one plane y."""
 
     def __init__(self, path, width, height, cfg, fmt='nv12', matrix='bt601', estimate=None, device='cuda:0', dump_mv=None):
-        if fmt not in YUV_FORMATS:
-            raise ValueError('fmt %r is not one of %s' % (fmt, ', '.join(sorted(YUV_FORMATS))))
-        self.sample_bytes, self.semi_planar = YUV_FORMATS[fmt], fmt in ('nv12', 'p010')
+        if fmt not in yuvfmt.FORMATS:
+            raise ValueError('fmt %r is not one of %s' % (fmt, ', '.join(sorted(yuvfmt.FORMATS))))
+        _, _, layout, sample = yuvfmt.fields(fmt)
+        self.other = fmt not in YUV_FORMATS          # not one of the shipped 4:2:0 four: through lsfa_amd/yuvfmt.py
+        self.packed = layout >= yuvfmt.YUYV
+        self.sample_bytes, self.semi_planar = 1 if sample == yuvfmt.U8 else 2, layout in (yuvfmt.UV, yuvfmt.VU)
         self.src_w, self.src_h, self.fmt, self.matrix, self.cfg = int(width), int(height), fmt, matrix, cfg
         if self.src_w <= 0 or self.src_h <= 0:
             raise ValueError('bad frame size %d x %d' % (self.src_w, self.src_h))
-        self.cw, self.ch = -(-self.src_w // 2), -(-self.src_h // 2)
-        self.frame_bytes, size, self.num_frames = yuv_file_frames(path, self.src_w, self.src_h, self.sample_bytes)
+        self.ch, self.cw = yuvfmt.chroma_shape(fmt, self.src_h, self.src_w)
+        self.frame_bytes, size, self.num_frames = yuv_file_frames(path, self.src_w, self.src_h, fmt=fmt)
         if self.num_frames is None:
             raise ValueError('%s holds %d bytes: not a whole number of %d x %d %s frames of %d bytes' % (path, size, self.src_w, self.src_h, fmt,
                                                                                                      self.frame_bytes))
@@ -210,6 +221,8 @@ class YuvFileClip(_EstimatedClip):
         buf, n = self._dev[i], self.src_w * self.src_h
         if self.sample_bytes == 2:
             buf = buf.view(torch.int16)
+        if self.packed:
+            return dict(y=buf.view(self.src_h, 4 * self.cw))
         y = buf[:n].view(self.src_h, self.src_w)
         if self.semi_planar:
             return dict(y=y, uv=buf[n:].view(self.ch, 2 * self.cw))
@@ -220,6 +233,8 @@ class YuvFileClip(_EstimatedClip):
         cfg = self.cfg
         kw = dict(im_scale=self.im_scale, matrix=self.matrix, pixel_means=cfg.network.PIXEL_MEANS, pixel_scale=cfg.network.PIXEL_SCALE,
                   stride=cfg.network.IMAGE_STRIDE)
+        if self.other:
+            return yuvfmt.image_resize_transform_yuv(self.fmt, width=self.src_w, **kw, **self.planes(i))
         if self.sample_bytes == 2:
             from lsfa_amd import yuv10
             return yuv10.image_resize_transform_yuv420p10(msb_aligned=self.fmt == 'p010', **kw, **self.planes(i))
@@ -227,6 +242,8 @@ class YuvFileClip(_EstimatedClip):
         return hip.image_resize_transform_yuv420(**kw, **self.planes(i))
 
     def _new_estimator(self, hip, key_i):
+        if self.other:
+            return yuvfmt.MotionEstimatorYuv(self.src_w, self.src_h, self.device, fmt=self.fmt, matrix=self.matrix, **self.estimate)
         if self.sample_bytes == 2:
             from lsfa_amd import yuv10
             return yuv10.MotionEstimator10(self.src_w, self.src_h, self.device, msb_aligned=self.fmt == 'p010', matrix=self.matrix, **self.estimate)
@@ -262,11 +279,12 @@ def parse_args(argv=None):
     ap.add_argument('--cfg', default=None)
     ap.add_argument('--frames', default=None, help='directory of frames (default: a synthetic clip)')
     ap.add_argument('--mv', default=None, help='directory of per-frame .npz with mv / res arrays')
-    ap.add_argument('--yuv', default=None, help='a raw YUV 4:2:0 file (frames back to back, no header) in place of --frames; needs --size')
+    ap.add_argument('--yuv', default=None, help='a raw YUV file (4:2:0 unless --yuv-format says otherwise; frames back to back, no header) in place of --frames; needs --size')
     ap.add_argument('--size', default=None, help='--yuv: the frame size as WxH, e.g. 1280x720')
-    ap.add_argument('--yuv-format', default='nv12', choices=('nv12', 'i420', 'p010', 'yuv420p10le'),
+    ap.add_argument('--yuv-format', default='nv12', choices=('nv12', 'i420', 'p010', 'yuv420p10le') + tuple(sorted(set(yuvfmt.FORMATS) - set(YUV_FORMATS))),
                     help='--yuv: semi-planar (interleaved U, V) or planar chroma of bytes; p010 / yuv420p10le: the same two of 10-bit samples in '
-                         '16-bit words, in the high / the low ten bits')
+                         '16-bit words, in the high / the low ten bits; any other name of lsfa_amd.yuvfmt.FORMATS: 4:2:2, 4:4:4, V before U, '
+                         'packed YUYV / UYVY, as ffmpeg -f rawvideo -pix_fmt NAME writes it')
     ap.add_argument('--yuv-matrix', default='bt601', choices=('bt601', 'bt709', 'jpeg'), help='--yuv: the colour matrix of the stream')
     motion_options.add_arguments(ap, 'estimate block motion vectors from the frames on the GPU (needs --frames or --yuv)')
     ap.add_argument('--dump-mv', default=None, help='--estimate-mv: write the estimated mv / res as the .npz files --mv reads')
@@ -292,7 +310,7 @@ def parse_args(argv=None):
         w, h = args.yuv_size
         if not os.path.isfile(args.yuv):
             ap.error('--yuv: no such file: %s' % args.yuv)
-        frame_bytes, size, frames = yuv_file_frames(args.yuv, w, h, YUV_FORMATS[args.yuv_format])
+        frame_bytes, size, frames = yuv_file_frames(args.yuv, w, h, fmt=args.yuv_format)
         if frames is None:
             ap.error('--yuv: %s holds %d bytes, not a whole number of %dx%d frames of %d bytes' % (args.yuv, size, w, h, frame_bytes))
     elif args.size:

@@ -2086,9 +2086,13 @@ class _SearchFront(object):
     """What MotionEstimator and SegmentMotionEstimator show of the _MotionSearch they stand in front of: its checked parameters and its
     geometry, under its names.  The buffers of the modes (unmatched, keysad, ...) are the subclass's: views of the search's in its own shape.
     _to_bgr is the one conversion behind the *_yuv methods of both: (y, uv, u, v, matrix, out=, y_packed=) -> out.  A subclass for planes
-    of another sample format overrides it (lsfa_amd/yuv10.py)."""
+    of another sample format overrides it (lsfa_amd/yuv10.py).  _y_plane is the (rows, columns) of the `y` argument of the *_yuv methods: the
+    frame's, unless a subclass takes a plane of another width (a packed 4:2:2 row of lsfa_amd/yuvfmt.py)."""
 
     _to_bgr = staticmethod(yuv420_to_bgr_u8)
+
+    def _y_plane(self):
+        return self.height, self.width
 
     def __init__(self, s):
         self._search = s
@@ -2210,9 +2214,9 @@ class MotionEstimator(_SearchFront):
             self._bgr_pp = [torch.empty_like(self.bgr_key) for _ in range(2)]
 
     def _yuv_to(self, bgr, luma, y, uv, u, v, who):
-        if not isinstance(y, torch.Tensor) or tuple(y.shape) != (self.height, self.width) or y.device != self.device:
+        if not isinstance(y, torch.Tensor) or tuple(y.shape) != self._y_plane() or y.device != self.device:
             raise LsfaError("MotionEstimator.%s: a (%d, %d) uint8 Y plane on %s expected, got %s on %s" %
-                            (who, self.height, self.width, self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
+                            (who, self._y_plane()[0], self._y_plane()[1], self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
         if self.luma_from == 'y':
             self._to_bgr(y, uv, u, v, self.matrix, out=bgr, y_packed=luma)
         else:
@@ -2383,10 +2387,10 @@ class SegmentMotionEstimator(_SearchFront):
         frame first.  One conversion launch into a BGR stack the estimator owns (self.bgr, (C, n + 1, H, W, 3)); luma_from='y' searches the
         decoder's Y plane (the conversion's y_packed, no luma launch: three launches in all), 'bgr' lsfa_luma_u8 of the converted frames."""
         H, W, C = self.height, self.width, self.clips
-        if not isinstance(y, torch.Tensor) or y.dim() != 3 or tuple(y.shape[1:]) != (H, W) or y.device != self.device or int(y.shape[0]) % C or \
+        if not isinstance(y, torch.Tensor) or y.dim() != 3 or tuple(y.shape[1:]) != self._y_plane() or y.device != self.device or int(y.shape[0]) % C or \
                 int(y.shape[0]) < 2 * C:
             raise LsfaError("SegmentMotionEstimator.segment_yuv: a (%d * (n + 1), %d, %d) uint8 Y stack on %s expected, got %s on %s" %
-                            (C, H, W, self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
+                            (C, self._y_plane()[0], self._y_plane()[1], self.device, tuple(getattr(y, 'shape', ())), getattr(y, 'device', type(y))))
         n = self._length(int(y.shape[0]) // C - 1, None, 'segment_yuv')
         self._outputs("SegmentMotionEstimator.segment_yuv", n, im_scale, int(rcnn_stride), out)
         if self._bgr is None:

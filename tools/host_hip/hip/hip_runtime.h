@@ -1,6 +1,6 @@
 // A stand-in for <hip/hip_runtime.h> that lets a plane kernel's source compile for the HOST with an ordinary C++ compiler: the qualifiers
 // vanish, the built-in indices are thread-local variables, and hipLaunchKernelGGL runs the kernel as nested loops over a grid of up to two
-// dimensions and one-dimensional blocks.  Only what tools/san_yuv10_host.cpp needs; vector types keep the device's alignment so that a misaligned wide access is seen by the
+// dimensions and one-dimensional blocks.  Only what tools/san_yuv10_host.cpp and tools/san_yuvfmt_host.cpp need; vector types keep the device's alignment so that a misaligned wide access is seen by the
 // undefined-behaviour sanitiser.  Never part of the library's build.
 #pragma once
 #include <math.h>
@@ -23,6 +23,7 @@ struct dim3 {
   dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {}
 };
 struct alignas(8) uint2 { uint32_t x, y; };
+struct alignas(16) uint4 { uint32_t x, y, z, w; };
 struct alignas(16) float4 { float x, y, z, w; };
 inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
 

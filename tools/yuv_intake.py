@@ -14,6 +14,12 @@ over the rounds, which IS the run-to-run spread to judge a difference by):
 
 The expectations: the NV12 transform kernel is not slower than the u8 one beyond the spread - it writes the same bytes and reads half - and
 neither is the 10-bit transform kernel (either layout), which reads the u8 kernel's 3 B and writes its 12 B per pixel.
+
+--formats: instead of the above, the other chroma formats (lsfa_amd/csrc/yuvfmt.hip) at 1000 x 600 and 1920 x 1080: the nv16, yuyv422,
+yuv444p and p210 legs of lsfa_yuv_to_bgr_u8, lsfa_image_transform_yuv and lsfa_image_resize_transform_yuv (scale 1, stride 16) as replayed
+graphs, each beside the shipped NV12 (for p210: P010) leg of the same kernel measured in the same run.  The expectation printed per leg:
+its median is at most 1.10 x the yardstick's median scaled by the ratio of the algorithmic bytes per pixel (image_transform: NV16 reads 2
+and writes 12 B, NV12 1.5 and 12 B, so 14 / 13.5); `ratio` is the measured time over that scaled time and `holds` says ratio <= 1.10.
 Prints one JSON object per line.  Ends itself after --time-limit seconds."""
 import argparse
 import ctypes
@@ -26,7 +32,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-from lsfa_amd import hip, yuv10
+from lsfa_amd import hip, yuv10, yuvfmt
 
 DEV = 'cuda:0'
 W, H = 1000, 600
@@ -81,8 +87,67 @@ def graph_rounds(fns, iters, rounds):
     return {k: stats(v) for k, v in us.items()}
 
 
+def format_legs(args):
+    """the --formats section: see the module docstring"""
+    rs = np.random.RandomState(1)
+    margin = 1.10
+    for w, h in ((1000, 600), (1920, 1080)):
+        px, ph, pw = h * w, -(-h // 16) * 16, -(-w // 16) * 16
+        for N in args.frames:
+            def planes(rows, cols, words=False):
+                a = rs.randint(0, 1 << 16, (N, rows, cols)).astype(np.uint16).view(np.int16) if words else rs.randint(0, 256, (N, rows, cols)).astype(np.uint8)
+                return torch.from_numpy(a).to(DEV)
+            # name: (format of yuvfmt or None for the shipped export, plane arguments, bytes read per pixel)
+            nv12, p010 = planes(h * 3 // 2, w), planes(h * 3 // 2, w, True)
+            nv16, p210 = planes(2 * h, w), planes(2 * h, w, True)
+            i444 = planes(3 * h, w)
+            legs = {
+                'nv12': (None, dict(y=nv12[:, :h], uv=nv12[:, h:]), 1.5),
+                'p010': (None, dict(y=p010[:, :h], uv=p010[:, h:]), 3.0),
+                'nv16': ('nv16', dict(y=nv16[:, :h], uv=nv16[:, h:]), 2.0),
+                'yuyv422': ('yuyv422', dict(y=planes(h, 2 * w)), 2.0),
+                'yuv444p': ('yuv444p', dict(y=i444[:, :h], u=i444[:, h:2 * h], v=i444[:, 2 * h:]), 3.0),
+                'p210': ('p210', dict(y=p210[:, :h], uv=p210[:, h:]), 4.0),
+            }
+            data = torch.empty((N, 3, h, w), dtype=torch.float32, device=DEV)
+            rdata = torch.empty((N, 3, ph, pw), dtype=torch.float32, device=DEV)
+            bgr_out = torch.empty((N, h, w, 3), dtype=torch.uint8, device=DEV)
+            tf = dict(pixel_means=MEANS, pixel_scale=SCALE)
+            kernels, nbytes = {}, {}
+            for name, (fmt, kw, read) in legs.items():
+                if fmt is None:
+                    to_bgr, transform, resize = ((hip.yuv420_to_bgr_u8, hip.image_transform_yuv420, hip.image_resize_transform_yuv420) if name == 'nv12' else
+                                                 (yuv10.yuv420p10_to_bgr_u8, yuv10.image_transform_yuv420p10, yuv10.image_resize_transform_yuv420p10))
+                    kernels['to_bgr_' + name] = lambda f=to_bgr, kw=kw: f(out=bgr_out, **kw)
+                    kernels['transform_' + name] = lambda f=transform, kw=kw: f(out=data, **tf, **kw)
+                    kernels['resize_' + name] = lambda f=resize, kw=kw: f(im_scale=1.0, stride=16, out=rdata, **tf, **kw)
+                else:
+                    assert torch.equal(yuvfmt.image_transform_yuv(fmt, **tf, **kw), hip.image_transform_u8(yuvfmt.yuv_to_bgr_u8(fmt, **kw), MEANS, SCALE))
+                    kernels['to_bgr_' + name] = lambda fmt=fmt, kw=kw: yuvfmt.yuv_to_bgr_u8(fmt, out=bgr_out, **kw)
+                    kernels['transform_' + name] = lambda fmt=fmt, kw=kw: yuvfmt.image_transform_yuv(fmt, out=data, **tf, **kw)
+                    kernels['resize_' + name] = lambda fmt=fmt, kw=kw: yuvfmt.image_resize_transform_yuv(fmt, im_scale=1.0, stride=16, out=rdata, **tf, **kw)
+                nbytes['to_bgr_' + name] = (read + 3) * px * N
+                nbytes['transform_' + name] = (read + 12) * px * N
+                nbytes['resize_' + name] = (read * px + 12 * ph * pw) * N
+            r = graph_rounds(kernels, args.iters, args.rounds)
+            for k in kernels:
+                r[k]['bytes'] = int(nbytes[k])
+                r[k]['GB_per_s_at_median'] = round(nbytes[k] / (r[k]['median'] * 1e-6) / 1e9, 1)
+            print(json.dumps(dict(frame='%dx%d' % (w, h), N=N, what='kernels alone, replayed graph', us=r)), flush=True)
+            for kernel in ('to_bgr', 'transform', 'resize'):
+                for name in ('nv16', 'yuyv422', 'yuv444p', 'p210'):
+                    yard = 'p010' if name == 'p210' else 'nv12'
+                    a, b = r['%s_%s' % (kernel, yard)], r['%s_%s' % (kernel, name)]
+                    scaled = a['median'] * nbytes['%s_%s' % (kernel, name)] / nbytes['%s_%s' % (kernel, yard)]
+                    print(json.dumps(dict(frame='%dx%d' % (w, h), N=N, what='expectation: %s %s within %.2f x the %s leg scaled by bytes' % (kernel, name, margin, yard),
+                                          us=b['median'], yardstick_us=a['median'], scaled_us=round(scaled, 2), ratio=round(b['median'] / scaled, 3),
+                                          spread=round(b['max'] - b['min'], 2), yardstick_spread=round(a['max'] - a['min'], 2),
+                                          holds=bool(b['median'] <= margin * scaled))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--formats', action='store_true', help='the other chroma formats at 1000x600 and 1920x1080 in place of the 4:2:0 report')
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--frames', type=int, nargs='*', default=[1, 9, 12])
@@ -91,8 +156,10 @@ def main():
     signal.alarm(args.time_limit)
     if not torch.cuda.is_available():
         raise SystemExit('no GPU: nothing to measure')
-    print(json.dumps(dict(device=torch.cuda.get_device_name(0), frame='%dx%d' % (W, H), iters=args.iters, rounds=args.rounds,
+    print(json.dumps(dict(device=torch.cuda.get_device_name(0), frame='1000x600 and 1920x1080' if args.formats else '%dx%d' % (W, H), iters=args.iters, rounds=args.rounds,
                           unit='microseconds per call: min / median / max over the rounds')), flush=True)
+    if args.formats:
+        return format_legs(args)
     rs = np.random.RandomState(0)
     px = H * W
     means_c = (ctypes.c_double * 3)(*MEANS)
