@@ -866,6 +866,70 @@ int lsfa_image_resize_transform_yuv(const void* y, long long y_pitch, long long 
                                     int h1, int w1, int stride, const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw,
                                     int out_h, int out_w, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * Detection overlay (lsfa_amd/csrc/overlay.hip): the detections lsfa_det_postprocess(_batch) left on the device, burnt into the frame that is
+ * already on the device - a packed BGR frame, or the 8-bit 4:2:0 planes of "YUV 4:2:0 intake" (NV12 / I420), e.g. the surface a hardware
+ * encoder takes next.  Nothing is read back and every call can sit inside a captured graph.
+ * Replaces (in function, NOT in pixels): draw_boxes + cv2.imwrite at the end of the reference's demo.py:150-157.  cv2's rasteriser is not
+ * part of this project - no Hershey fonts, no anti-aliasing, none of cv2's line joins - and draw_boxes picks random colours.  The overlay
+ * is defined by the integer specification below (DESIGN.md "Detection overlay"; restated in numpy as tests/ref_overlay.py) and is bit-exact
+ * with THAT; parity with cv2 is not claimed.
+ *   Input per image: dets (ncls, R, 5) float64 rows [x1, y1, x2, y2, score] in pixels of the frame that is drawn into; counts (ncls) int32.
+ *   Draw order: classes j = 1 .. ncls-1 ascending (class 0 is never drawn), rows 0 .. min(max(counts[j], 0), R) - 1 ascending inside a class.
+ *   A row is eligible when all five values are finite and score >= thresh.  Its corners are trunc() of the coordinates (`map(int, bbox)`),
+ *   each double clamped to [-2^30, 2^30] first and NOT clamped to the frame.  An eligible row is skipped when x2 < x1 or y2 < y1, or when the
+ *   box lies wholly outside [0, W-1] x [0, H-1] (x2 < 0, y2 < 0, x1 > W-1 or y1 > H-1).  The first max_boxes eligible rows that are not
+ *   skipped become records, in draw order; n = {records written, eligible rows that are not skipped} goes to the device.
+ *   Outline, thickness t in 1..8 (the reference: 3), centred on the edge: o = (t - 1) / 2, i = t - o; the pixels inside
+ *   [x1-o, x2+o] x [y1-o, y2+o] and not inside [x1+i, x2-i] x [y1+i, y2-i]; an empty inner rectangle fills the outer one.
+ *   Label, scale z in 0..4 (0: none): the characters are the class's name - at most LSFA_OVERLAY_NAME_LEN glyph indices of row j of `names`,
+ *   0xFF ends a name, an index above 41 reads as '?'; names == NULL: the decimal digits of j - then, if with_score, " d.ddd" (a space first)
+ *   from m = clamp(floor(score * 1000 + 0.5), 0, 9999), the product rounded to float64 before the addition (no fused multiply-add).
+ *   L characters (L = 0: no label) give the rectangle w = z (6L + 1), h = 9z at lx = x1 - o, ly = y1 - o - h; if ly < 0 then ly = y1 + i
+ *   (inside the box, under its top edge); if lx + w > W then lx = W - w; then if lx < 0 then lx = 0.
+ *   Glyphs are 5 x 7 in a 6 x 8 cell, this project's own drawings (lsfa_amd/overlay.py): index 0 space, 1..10 '0'..'9', 11..36 'a'..'z',
+ *   37 '_', 38 '-', 39 '.', 40 '%', 41 '?'.  `font` is LSFA_OVERLAY_GLYPH_BYTES bytes: glyph g, row v at byte 8 g + v, bit 4 its left column.
+ *   A pixel (x, y) of the label rectangle is a TEXT pixel when, with dx = x - lx - z, dy = y - ly - z, u = dx / z, v = dy / z: dx >= 0,
+ *   dy >= 0, u < 6L, u % 6 < 5, v < 7 and bit 4 - u % 6 of row v of glyph u / 6 is set; every other pixel of it is background.
+ *   A pixel's result comes from the LAST record in draw order whose outline or label rectangle contains it: colors[ncls] (the text colour)
+ *   for a text pixel, else colors[j].  Opaque, clipped to the frame pixel by pixel.  A pixel no record covers is never written.
+ *   colors: (ncls + 1, 3) uint8 in the component order of the surface: B, G, R or Y, U, V (made on the host, lsfa_amd/overlay.py bgr_to_yuv).
+ *   4:2:0 surfaces: Y[y][x] takes component 0 of pixel (x, y)'s result; chroma sample (cx, cy) takes components 1 and 2 of the result of
+ *   pixel (2cx, 2cy) and is untouched when that pixel is uncovered - the intake's nearest-neighbour rule.  Odd W, H: chroma is ceil / 2.
+ * Out of scope: blending, transparency, anti-aliasing; 10-bit, 4:2:2, 4:4:4 and packed surfaces (draw on their converted BGR frame); masks
+ * and tracks.
+ * A record is LSFA_OVERLAY_REC_INTS ints: x1, y1, x2, y2, lx, ly, w, h, j, L, then the L glyph indices four to an int (character k in bits
+ * 8 (k % 4) of int 10 + k / 4), unused bits 0.  The caller sizes the buffers: records (N, max_boxes, LSFA_OVERLAY_REC_INTS) int32 and
+ * n (N, 2) int32, max_boxes in 1..LSFA_OVERLAY_MAX_BOXES.  The paint calls read only the first min(n[0], max_boxes) records of an image and
+ * are memory-safe whatever those hold.
+ * lsfa_overlay_plan: one workgroup per image; compaction on the device as a prefix over (class, row) - only the rows under counts are
+ *   walked, so a frame without detections costs the launch - no atomics.  One launch.
+ * lsfa_overlay_paint_bgr: bgr (N, H, W, 3) uint8 with a row pitch and a frame stride in BYTES, in place.  One launch for the N frames.
+ * lsfa_overlay_paint_yuv420: the planes, pitches and strides of lsfa_yuv420_to_bgr_u8 (v == NULL: NV12), in place.  One launch.
+ *   One 256-lane workgroup per 64 x 16 tile; a tile no record can touch leaves before it touches the frame.  thickness and label_scale
+ *   must be the plan's.
+ * LSFA_EINVAL, before anything is launched, for: a NULL pointer (but names, and v for NV12); N, H, W, R or max_boxes below 1; ncls below 1 or
+ * above LSFA_OVERLAY_MAX_CLASSES; H or W above 65536, N above 65535, max_boxes above LSFA_OVERLAY_MAX_BOXES, (ncls - 1) * R at or above 2^31; thickness outside 1..8;
+ * label_scale outside 0..4; a pitch below its row (3 W; Y: W; chroma 2 ceil(W / 2) interleaved, ceil(W / 2) planar); a negative frame stride.
+ * On `stream`, no workspace, nothing allocated; not reported under a profiling id.
+ * ------------------------------------------------------------------------ */
+#define LSFA_OVERLAY_REC_INTS 16
+#define LSFA_OVERLAY_NAME_LEN 12
+#define LSFA_OVERLAY_GLYPHS 42
+#define LSFA_OVERLAY_GLYPH_BYTES 336
+#define LSFA_OVERLAY_MAX_BOXES 4096
+#define LSFA_OVERLAY_MAX_CLASSES 4096
+int lsfa_overlay_plan(const double* dets, const int* counts, int N, int ncls, int R, double thresh, int H, int W, int thickness, int label_scale,
+                      int with_score, const unsigned char* names /* (ncls, LSFA_OVERLAY_NAME_LEN) or NULL */, int max_boxes, int* records, int* n,
+                      void* stream);
+int lsfa_overlay_paint_bgr(unsigned char* bgr, long long pitch, long long frame_stride, int N, int H, int W, const int* records, const int* n,
+                           int max_boxes, int thickness, int label_scale, const unsigned char* font, const unsigned char* colors, int ncls,
+                           void* stream);
+int lsfa_overlay_paint_yuv420(unsigned char* y, long long y_pitch, long long y_frame_stride, unsigned char* u_or_uv,
+                              unsigned char* v /* NULL: NV12 */, long long c_pitch, long long c_frame_stride, int N, int H, int W,
+                              const int* records, const int* n, int max_boxes, int thickness, int label_scale, const unsigned char* font,
+                              const unsigned char* colors, int ncls, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,13 @@ uploaded, the same path through lsfa_amd/yuv10.py (image_resize_transform_yuv420
 --yuv-format with any other name of lsfa_amd.yuvfmt.FORMATS (nv21; yuv422p, nv16, nv61, yuyv422 / yuy2, uyvy422; yuv444p, nv24, nv42;
 yuv422p10le, p210, yuv444p10le, p410): the file as `-f rawvideo -pix_fmt X` writes it (yuvfmt.frame_bytes: planes back to back, no pitch),
 through lsfa_amd/yuvfmt.py (image_resize_transform_yuv, MotionEstimatorYuv).
-Drawing boxes into images (draw_boxes, :150-156) is left to the caller: the output is JSON.
+--draw DIR: the counterpart of draw_boxes + cv2.imwrite (:150-157) - every frame's detections are drawn on the device into its uint8
+BGR frame (a --yuv frame converted by the shipped *_to_bgr_u8) by lsfa_amd/overlay.py and the frame is written as DIR/<frame stem>.png
+with PIL.  --draw-yuv FILE (--yuv-format nv12 | i420 only): the detections are drawn into a COPY of the frame's planes - the motion
+estimator still needs the pristine frames - and the annotated raw stream is written in the input's layout, e.g. for an encoder.
+--classes FILE: one class name per line (the foreground classes, or all with the background first); without it a label is the class
+id.  --draw-thickness / --draw-scale: the outline's thickness and the label's scale (0: no label).  The drawing is this project's own
+integer specification (DESIGN.md "Detection overlay"), not cv2's, and runs outside the timed region like the reference's.
 """
 import argparse
 import glob
@@ -47,7 +53,7 @@ import time
 import numpy as np
 import torch
 
-from lsfa_amd import yuvfmt
+from lsfa_amd import overlay, yuvfmt
 from lsfa_amd.config.config import config, lsfa_test_config, update_config, update_network_config
 from lsfa_amd.core.graphs import FrameGraphs
 from lsfa_amd.symbols import params as P
@@ -153,6 +159,12 @@ class FrameDirClip(_EstimatedClip):
             self._u8[i] = torch.from_numpy(np.ascontiguousarray(self._decode(i)[:, :, ::-1])).to(self.device)
         return self._u8[i]
 
+    def bgr_u8(self, i):
+        """a (H, W, 3) uint8 BGR frame on the device that is the caller's to draw into"""
+        if i in self._u8:
+            return self._u8[i].clone()
+        return torch.from_numpy(np.ascontiguousarray(self._decode(i)[:, :, ::-1])).to(self.device)
+
     def _new_estimator(self, hip, key_i):
         k = self._frame_u8(key_i)
         return hip.MotionEstimator(int(k.shape[1]), int(k.shape[0]), self.device, **self.estimate)
@@ -218,7 +230,11 @@ class YuvFileClip(_EstimatedClip):
                 self._dev.clear()                             # nothing looks back at earlier frames
             raw = np.array(self._map[i * self.frame_bytes:(i + 1) * self.frame_bytes])         # one read of the mapped pages
             self._dev[i] = torch.from_numpy(raw).to(self.device)
-        buf, n = self._dev[i], self.src_w * self.src_h
+        return self._views(self._dev[i])
+
+    def _views(self, buf):
+        """the planes of one frame's bytes `buf`"""
+        n = self.src_w * self.src_h
         if self.sample_bytes == 2:
             buf = buf.view(torch.int16)
         if self.packed:
@@ -228,6 +244,22 @@ class YuvFileClip(_EstimatedClip):
             return dict(y=y, uv=buf[n:].view(self.ch, 2 * self.cw))
         c = self.ch * self.cw
         return dict(y=y, u=buf[n:n + c].view(self.ch, self.cw), v=buf[n + c:].view(self.ch, self.cw))
+
+    def planes_copy(self, i):
+        """-> (a copy of frame i's bytes on the device, its planes as planes(i) gives them): what --draw-yuv draws into and writes"""
+        self.planes(i)
+        buf = self._dev[i].clone()
+        return buf, self._views(buf)
+
+    def bgr_u8(self, i):
+        """frame i converted by the shipped *_to_bgr_u8 of its format: a new (H, W, 3) uint8 BGR frame on the device"""
+        if self.other:
+            return yuvfmt.yuv_to_bgr_u8(self.fmt, matrix=self.matrix, width=self.src_w, **self.planes(i))
+        if self.sample_bytes == 2:
+            from lsfa_amd import yuv10
+            return yuv10.yuv420p10_to_bgr_u8(matrix=self.matrix, msb_aligned=self.fmt == 'p010', **self.planes(i))
+        from lsfa_amd import hip
+        return hip.yuv420_to_bgr_u8(matrix=self.matrix, **self.planes(i))
 
     def frame(self, i):
         cfg = self.cfg
@@ -270,6 +302,9 @@ class _Synthetic(object):
     def frame(self, i):
         return self.c.frame(i)
 
+    def bgr_u8(self, i):
+        return self.c.frame_u8(i).to('cuda:0')
+
     def mv_res(self, i, key_i):
         return self.c.motion_vector(i, key_i), self.c.res_diff(i)
 
@@ -295,7 +330,28 @@ def parse_args(argv=None):
     ap.add_argument('--score', type=float, default=0.7, help='report threshold (demo.py:147)')
     ap.add_argument('--out', default=None, help='write the detections as JSON here')
     ap.add_argument('--no-graph', action='store_true')
+    ap.add_argument('--draw', default=None, help='a directory that receives every frame with its detections drawn in, as <frame stem>.png')
+    ap.add_argument('--draw-yuv', default=None, help='--yuv with --yuv-format nv12 | i420: write the annotated raw stream, in the input\'s layout, here')
+    ap.add_argument('--classes', default=None, help='--draw / --draw-yuv: a file of class names, one per line; the default labels are class ids')
+    ap.add_argument('--draw-thickness', type=int, default=None, help='--draw / --draw-yuv: the outline\'s thickness in pixels, 1..8 (default 3, the reference\'s)')
+    ap.add_argument('--draw-scale', type=int, default=None, help='--draw / --draw-yuv: the label\'s scale, 1..4, or 0 for no label (default 2)')
     args = ap.parse_args(argv)
+    if args.draw_yuv and not (args.yuv and args.yuv_format in ('nv12', 'i420')):
+        ap.error('--draw-yuv writes the input\'s own layout and needs --yuv with --yuv-format nv12 or i420; draw any other input with --draw')
+    if args.draw_yuv and os.path.abspath(args.draw_yuv) == os.path.abspath(args.yuv):
+        ap.error('--draw-yuv would overwrite its input %s' % args.yuv)
+    drawing = bool(args.draw or args.draw_yuv)
+    for name, v in (('--classes', args.classes), ('--draw-thickness', args.draw_thickness), ('--draw-scale', args.draw_scale)):
+        if v is not None and not drawing:
+            ap.error('%s belongs to --draw / --draw-yuv' % name)
+    if args.draw_thickness is not None and not 1 <= args.draw_thickness <= 8:
+        ap.error('--draw-thickness %d is outside 1..8' % args.draw_thickness)
+    if args.draw_scale is not None and not 0 <= args.draw_scale <= 4:
+        ap.error('--draw-scale %d is outside 0..4' % args.draw_scale)
+    if args.classes is not None and not os.path.isfile(args.classes):
+        ap.error('--classes: no such file: %s' % args.classes)
+    args.draw_thickness = 3 if args.draw_thickness is None else args.draw_thickness
+    args.draw_scale = 2 if args.draw_scale is None else args.draw_scale
     if args.yuv and args.frames:
         ap.error('--yuv excludes --frames')
     if args.yuv and args.mv:
@@ -323,6 +379,50 @@ def parse_args(argv=None):
     return args
 
 
+def class_names(path, ncls):
+    """the lines of a --classes file as Overlay's `names`: ncls - 1 foreground names, or ncls with the background's first"""
+    with open(path) as f:
+        lines = [ln.strip() for ln in f if ln.strip()]
+    if len(lines) == ncls - 1:
+        return ['background'] + lines
+    if len(lines) != ncls:
+        raise ValueError('%s names %d classes; the network has %d and the background' % (path, len(lines), ncls - 1))
+    return lines
+
+
+class _Drawer(object):
+    """--draw / --draw-yuv: one overlay.Overlay for the clip, made at the first frame from the detection buffers' shape"""
+
+    def __init__(self, args, clip):
+        self.args, self.clip, self.ov, self.yuv_out = args, clip, None, None
+        if args.draw:
+            os.makedirs(args.draw, exist_ok=True)
+        if args.draw_yuv:
+            self.yuv_out = open(args.draw_yuv, 'wb')
+
+    def frame(self, idx, dets, counts):
+        """draws frame idx's detections (the device buffers fg.*_frame returned) and writes the frame"""
+        args, clip = self.args, self.clip
+        if self.ov is None:
+            ncls, R = int(dets.shape[0]), int(dets.shape[1])
+            names = class_names(args.classes, ncls) if args.classes else None
+            self.ov = overlay.Overlay(ncls, R, max_boxes=min(overlay.MAX_BOXES, max(1, (ncls - 1) * R)), thickness=args.draw_thickness,
+                                      label_scale=args.draw_scale, names=names, device=dets.device)
+        if args.draw:
+            from PIL import Image
+            bgr = self.ov.draw_bgr(clip.bgr_u8(idx), dets, counts, args.score)
+            stem = os.path.splitext(os.path.basename(clip.names[idx]))[0]
+            Image.fromarray(np.ascontiguousarray(bgr.cpu().numpy()[:, :, ::-1])).save(os.path.join(args.draw, stem + '.png'))
+        if self.yuv_out is not None:
+            buf, planes = clip.planes_copy(idx)
+            self.ov.draw_yuv420(planes.pop('y'), dets, counts, args.score, matrix=clip.matrix, **planes)
+            self.yuv_out.write(buf.cpu().numpy().tobytes())
+
+    def close(self):
+        if self.yuv_out is not None:
+            self.yuv_out.close()
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.cfg:
@@ -348,6 +448,7 @@ def main(argv=None):
     fg.scale = float(clip.im_scale)
     fg.im_info[0, 2] = fg.scale
     classes = None       # class names live in the dataset (imdb.classes); ids are reported without one
+    drawer = _Drawer(args, clip) if args.draw or args.draw_yuv else None
 
     results, total, count = [], 0.0, 0
     key_idx = 0          # the running key frame: every `interval` frames behind the last one - or, with --scene-cut / --stale-key, where a scene starts or the key frame is stale
@@ -378,6 +479,10 @@ def main(argv=None):
                 frame_dets.append({'class': classes[j] if classes else j, 'score': float(s),
                                    'box': [float(x1), float(y1), float(x2), float(y2)]})
         results.append({'frame': clip.names[idx], 'key': is_key, 'dets': frame_dets})
+        if drawer is not None:       # after the frame's time is taken, on the device buffers: the reference's tic/toc excludes draw_boxes too
+            drawer.frame(idx, dets, counts)
+    if drawer is not None:
+        drawer.close()
     print('done: {} frames, {} detections above {:.2f}'.format(len(results), sum(len(r['dets']) for r in results),
                                                                 args.score))
     if args.out:
