@@ -897,7 +897,7 @@ int lsfa_image_resize_transform_yuv(const void* y, long long y_pitch, long long 
  *   4:2:0 surfaces: Y[y][x] takes component 0 of pixel (x, y)'s result; chroma sample (cx, cy) takes components 1 and 2 of the result of
  *   pixel (2cx, 2cy) and is untouched when that pixel is uncovered - the intake's nearest-neighbour rule.  Odd W, H: chroma is ceil / 2.
  * Out of scope: blending, transparency, anti-aliasing; 10-bit, 4:2:2, 4:4:4 and packed surfaces (draw on their converted BGR frame); masks
- * and tracks.
+ * and tracks.  (Tracks are drawn by lsfa_overlay_plan_ids, declared under "Tracks" below, from the ids lsfa_track_steps assigns.)
  * A record is LSFA_OVERLAY_REC_INTS ints: x1, y1, x2, y2, lx, ly, w, h, j, L, then the L glyph indices four to an int (character k in bits
  * 8 (k % 4) of int 10 + k / 4), unused bits 0.  The caller sizes the buffers: records (N, max_boxes, LSFA_OVERLAY_REC_INTS) int32 and
  * n (N, 2) int32, max_boxes in 1..LSFA_OVERLAY_MAX_BOXES.  The paint calls read only the first min(n[0], max_boxes) records of an image and
@@ -929,6 +929,64 @@ int lsfa_overlay_paint_yuv420(unsigned char* y, long long y_pitch, long long y_f
                               unsigned char* v /* NULL: NV12 */, long long c_pitch, long long c_frame_stride, int N, int H, int W,
                               const int* records, const int* n, int max_boxes, int thickness, int label_scale, const unsigned char* font,
                               const unsigned char* colors, int ncls, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * Tracks (lsfa_amd/csrc/tracks.hip): which detection of frame f is the same object as which detection of frame f - 1, decided on the device
+ * from what lsfa_det_postprocess(_batch) left there and, optionally, from the block rows lsfa_mv_estimate / lsfa_mv_estimate_chain wrote, which
+ * are in the same pixel coordinates: a row says "the block now at dst came from src", a forward prediction of where last frame's boxes went.
+ * Replaces nothing in the reference, which has no tracker, and is comparable with nothing there.  It is not SORT, not Seq-NMS and not a
+ * Kalman filter; it does not rescore or remove detections: dets and counts are read-only.  It is defined by the float64 / integer
+ * specification below (DESIGN.md "Tracks"; restated in numpy as tests/ref_tracks.py) and is bit-exact with THAT.
+ *   One call advances S independent streams (the clips of a lock-step batch) by F consecutive frames each (1 frame by frame, or e.g. the 9
+ *   non-key frames of a segment).  Streams never interact; the frames of a stream are processed in order f = 0 .. F-1.
+ *   State per stream, the caller's device tensors: tbox (S, T, 5) float64 [x1, y1, x2, y2, score]; tint (S, T, 4) int32 [id, class, hits,
+ *   misses], id == 0: the slot is free; issued (S) int32, the number of ids handed out so far.  All zero is the empty tracker.  T = max_tracks
+ *   in 1..LSFA_TRACK_MAX_TRACKS.
+ *   Input for frame f of stream s: dets[s][f] (ncls, R, 5) float64 and counts[s][f] (ncls) int32 as lsfa_det_postprocess_batch leaves them,
+ *   and optionally the first row_n[s][f] rows of rows + s * rows_stream_stride + f * rows_frame_stride (strides in ints), each 7 int32
+ *   {.., .., .., srcx, srcy, dstx, dsty}: what lsfa_mv_estimate(_chain) writes and lsfa_mv_accumulate reads; columns 0..2 are not read.
+ *   rows == NULL, row_n == NULL or row_n[s][f] <= 0: no prediction for that frame (a key frame that starts a new chain).  row_n is clamped to
+ *   n_max.
+ *   1. Eligible detections E, in draw order: classes j = 1 .. ncls-1 ascending (class 0 never), rows r = 0 .. min(max(counts[j], 0), R) - 1
+ *      ascending; a row is eligible when all five values are finite, score >= score_thresh, x2 >= x1 and y2 >= y1 (the overlay's rule without
+ *      its outside-the-frame skip).
+ *   2. Predict, every active track independently: a row participates when x1 <= (double)srcx <= x2 and y1 <= (double)srcy <= y2 (content
+ *      that was inside the box in the previous frame).  With c participating rows, sx = sum(dstx - srcx), sy = sum(dsty - srcy) in int64: if
+ *      c > 0 and sx != 0 then dx = (double)sx / (double)c, x1 += dx, x2 += dx; likewise sy, dy, y1, y2.  Every operation is rounded once,
+ *      nothing is contracted; a zero sum leaves the coordinates bit for bit; boxes are not clipped to the frame.
+ *   3. Associate, each detection of E in draw order: the candidates are the active tracks of the same class that no earlier detection of
+ *      this frame took, with IoU >= iou_thresh; the largest IoU wins, a tie goes to the lowest slot.  IoU is the reference's py_nms arithmetic
+ *      in float64: areas (x2 - x1 + 1) * (y2 - y1 + 1), w = max(0, min(x2a, x2b) - max(x1a, x1b) + 1), h likewise, inter / (area_a + area_b
+ *      - inter); min, max and >= are comparisons and a comparison with NaN is false: no match.  A matched track takes the detection's five
+ *      values, hits += 1, misses = 0.
+ *   4. Age: every active track that was not matched: misses += 1; if misses > max_age the slot is freed and its nine values are zeroed.
+ *   5. Birth, every unmatched detection of E in draw order: it goes into the lowest free slot (slots freed in step 4 count) with
+ *      id = ++issued[s], class j, the five values, hits = 1, misses = 0.  With no free slot it is dropped: counted, and no id is consumed.
+ *      (hits, misses and issued are 32-bit and wrap.)
+ *   6. Output: ids[s][f] (ncls, R) int32, all ncls * R entries written every frame: -1 for a row that is not eligible, the track's id when
+ *      its hits >= min_hits, else 0 (tentative, or dropped); n[s][f] (4) int32 {eligible, matched, born, dropped}.
+ * Out of scope: re-identification after a track died; matching across classes; appearance features; velocity models; clipping or killing
+ * tracks that left the frame (ageing does that); rescoring or suppressing detections.
+ * lsfa_track_steps: one launch, one workgroup per stream, the table in LDS for the F frames; no workspace, nothing allocated, no atomics,
+ *   nothing read back; on `stream`, capturable; not reported under a profiling id.  Memory-safe whatever the state tensors and the rows hold:
+ *   a class outside 1..ncls-1 in a slot never matches, and row values are only compared and summed.
+ * LSFA_EINVAL, before anything is launched, for: a NULL pointer other than rows / row_n; S, F, R or T below 1; ncls below 1 or above 4096;
+ *   T above LSFA_TRACK_MAX_TRACKS, S above 65535, F above 4096; (ncls - 1) * R at or above 2^31; n_max < 0; a negative stride; max_age < 0;
+ *   min_hits < 1; a threshold that is not finite.
+ * lsfa_overlay_plan_ids: lsfa_overlay_plan (the same body; that export is the ids == NULL case) for ids (N, ncls, R) int32: a row is
+ *   eligible only if, in addition, ids[j][r] > 0; the record's colour field holds 1 + (id - 1) % (ncls - 1) instead of j - one stable colour per
+ *   track from the same `colors` table; the label is the class name, then '-', then the decimal digits of id % 100000, then the score as before:
+ *   at most 12 + 6 + 6 = 24 characters, which is what a record holds.  The paint calls are the overlay's.  LSFA_EINVAL as lsfa_overlay_plan,
+ *   and for ids == NULL or ncls < 2.
+ * ------------------------------------------------------------------------ */
+#define LSFA_TRACK_MAX_TRACKS 1024
+int lsfa_track_steps(const double* dets, const int* counts, int S, int F, int ncls, int R, const int* rows /* or NULL */,
+                     const int* row_n /* (S, F) or NULL */, int n_max, long long rows_stream_stride, long long rows_frame_stride,
+                     double score_thresh, double iou_thresh, int max_age, int min_hits, int T, double* tbox, int* tint, int* issued, int* ids,
+                     int* n, void* stream);
+int lsfa_overlay_plan_ids(const double* dets, const int* counts, const int* ids, int N, int ncls, int R, double thresh, int H, int W,
+                          int thickness, int label_scale, int with_score, const unsigned char* names, int max_boxes, int* records, int* n,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,12 +5,13 @@
 // NOT a port of anything in the reference: demo.py:150-157 ends with draw_boxes and cv2.imwrite, and cv2's rasteriser (Hershey fonts,
 // anti-aliasing, its line joins) is not part of this project; draw_boxes picks random colours besides.  What is drawn is the integer
 // specification of include/lsfa_hip.h, "Detection overlay" (DESIGN.md "Detection overlay"; tests/ref_overlay.py states it in numpy), matched
-// bit for bit.  Out of scope: blending, anti-aliasing, 10-bit / 4:2:2 / 4:4:4 / packed surfaces, masks, tracks.
+// bit for bit.  Out of scope: blending, anti-aliasing, 10-bit / 4:2:2 / 4:4:4 / packed surfaces, masks.
 //
 // overlay_plan_kernel: one workgroup per image.  A prefix of the clamped counts over the classes says where each class's rows start, so only
 // the rows under counts are walked, in draw order, 256 at a time (a frame without detections walks none); the position of a kept row is a
 // prefix again - ballot and popcount inside a wave of 64, four wave counts through LDS - so the order of the records is the draw order by
-// construction and no atomic's arrival order can show.
+// construction and no atomic's arrival order can show.  With ids (lsfa_overlay_plan_ids; the header's "Tracks") a row also needs a track id
+// above 0, its colour is the track's and its label carries "-id" between the name and the score; ids == NULL is lsfa_overlay_plan.
 // overlay_paint_kernel: one 256-lane workgroup per 64 x 16 tile of one frame, a lane owns four adjacent pixels of one row (the tile is
 // even-sized and starts on an even pixel: its chroma samples are its own).  The workgroup first sifts the image's records, with the same
 // prefix, into an LDS list of those that can touch the tile (the first 128 of them with their 16 ints, which the sift has in registers
@@ -18,6 +19,7 @@
 // back to its first hit.  Covered pixels are stored, whole dwords where a lane's four
 // pixels are all covered and the address is aligned, bytes otherwise; an uncovered byte is never stored.
 #include "common.h"
+#include "prefix256.h"
 
 using namespace lsfa;
 
@@ -26,35 +28,17 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kTileW = 64, kTileH = 16;
 constexpr int kRec = LSFA_OVERLAY_REC_INTS;
-constexpr int kMaxChars = LSFA_OVERLAY_NAME_LEN + 6;          // a name and " d.ddd"
+constexpr int kMaxChars = LSFA_OVERLAY_NAME_LEN + 6 + 6;      // a name, "-ddddd" of a track (lsfa_overlay_plan_ids only) and " d.ddd"
 static_assert(10 + (kMaxChars + 3) / 4 <= kRec, "a record holds its characters");
 static_assert(kTileW * kTileH == 4 * kThreads && kTileW % 2 == 0 && kTileH % 2 == 0, "four pixels per lane, even tiles");
 constexpr int kStaged = 128;          // records of a tile's list kept in LDS (8 KiB); a longer list reads the rest from global memory
-constexpr int kGlyphSpace = 0, kGlyphZero = 1, kGlyphDot = 39, kGlyphUnknown = 41;
-
-// the position of this lane's kept item among the kept items of the workgroup's 256, in lane order, and their number: ballot + popcount
-// per wave, the four wave counts through LDS.  Every lane of the workgroup calls it; s_wave is free again when it returns.
-__device__ __forceinline__ int prefix_256(bool keep, int* s_wave, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    const int c = s_wave[w];
-    before += w < wave ? c : 0;
-    all += c;
-  }
-  __syncthreads();
-  *total = all;
-  return before + __popcll(m & ((1ull << lane) - 1ull));
-}
+constexpr int kGlyphSpace = 0, kGlyphZero = 1, kGlyphDash = 38, kGlyphDot = 39, kGlyphUnknown = 41;
 
 __device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }          // false for NaN
 __device__ __forceinline__ int corner(double v) { return (int)fmin(fmax(v, -1073741824.0), 1073741824.0); }  // the cast truncates
 
-__global__ __launch_bounds__(kThreads) void overlay_plan_kernel(const double* __restrict__ dets, const int* __restrict__ counts, int ncls, int R,
+__global__ __launch_bounds__(kThreads) void overlay_plan_kernel(const double* __restrict__ dets, const int* __restrict__ counts,
+                                                                const int* __restrict__ ids /* (N, ncls, R) or NULL */, int ncls, int R,
                                                                 double thresh, int H, int W, int o, int in, int z, int with_score,
                                                                 const unsigned char* __restrict__ names, int max_boxes,
                                                                 int* __restrict__ records, int* __restrict__ n) {
@@ -63,6 +47,7 @@ __global__ __launch_bounds__(kThreads) void overlay_plan_kernel(const double* __
   const int img = blockIdx.x;
   dets += (size_t)img * ncls * R * 5;
   counts += (size_t)img * ncls;
+  if (ids) ids += (size_t)img * ncls * R;
   records += (size_t)img * max_boxes * kRec;
   // the rows to draw, class by class: an exclusive prefix of min(max(counts[j], 0), R) over j = 1 .. ncls-1, 256 classes a round, so that
   // the walk below touches those rows only - a frame without detections has none
@@ -96,7 +81,7 @@ __global__ __launch_bounds__(kThreads) void overlay_plan_kernel(const double* __
   for (int f0 = 0; f0 < total; f0 += kThreads) {
     const int f = f0 + (int)threadIdx.x;
     bool keep = false;
-    int x1 = 0, y1 = 0, x2 = 0, y2 = 0, j = 0;
+    int x1 = 0, y1 = 0, x2 = 0, y2 = 0, j = 0, id = 0;
     double score = 0.0;
     if (f < total) {
       // the class of row f: the last j in 1 .. ncls-1 with s_first[j] <= f (classes without rows share their successor's value)
@@ -114,6 +99,10 @@ __global__ __launch_bounds__(kThreads) void overlay_plan_kernel(const double* __
         if (finite_f64(a) && finite_f64(b) && finite_f64(c) && finite_f64(e) && finite_f64(score) && score >= thresh) {
           x1 = corner(a); y1 = corner(b); x2 = corner(c); y2 = corner(e);
           keep = !(x2 < x1 || y2 < y1 || x2 < 0 || y2 < 0 || x1 > W - 1 || y1 > H - 1);
+          if (ids) {
+            id = ids[(size_t)j * R + r];
+            keep = keep && id > 0;
+          }
         }
       }
     }
@@ -140,6 +129,13 @@ __global__ __launch_bounds__(kThreads) void overlay_plan_kernel(const double* __
           while (j / p >= 10) p *= 10;
           for (; p > 0; p /= 10) ch[L++] = (unsigned char)(kGlyphZero + (j / p) % 10);
         }
+        if (ids) {
+          const int m = id % 100000;
+          ch[L++] = (unsigned char)kGlyphDash;
+          int p = 1;
+          while (m / p >= 10) p *= 10;
+          for (; p > 0; p /= 10) ch[L++] = (unsigned char)(kGlyphZero + (m / p) % 10);
+        }
         if (with_score) {
           const double prod = score * 1000.0;           // rounded to float64 here: the build contracts nothing (-ffp-contract=off)
           const int m = (int)fmin(fmax(floor(prod + 0.5), 0.0), 9999.0);
@@ -161,7 +157,8 @@ __global__ __launch_bounds__(kThreads) void overlay_plan_kernel(const double* __
       }
       rec[0] = x1; rec[1] = y1; rec[2] = x2; rec[3] = y2;
       rec[4] = lx; rec[5] = ly; rec[6] = w; rec[7] = h;
-      rec[8] = j; rec[9] = L;
+      rec[8] = ids ? 1 + (id - 1) % (ncls - 1) : j;
+      rec[9] = L;
     }
   }
   if (threadIdx.x == 0) {
@@ -380,21 +377,35 @@ void launch_paint(const Paint& a, const Surface& s, int N, hipStream_t stream) {
 
 }  // namespace
 
-extern "C" int lsfa_overlay_plan(const double* dets, const int* counts, int N, int ncls, int R, double thresh, int H, int W, int thickness,
-                                 int label_scale, int with_score, const unsigned char* names, int max_boxes, int* records, int* n, void* stream) {
-  LSFA_REQUIRE(dets && counts && records && n, "lsfa_overlay_plan: NULL argument");
+// lsfa_overlay_plan (ids == NULL) and lsfa_overlay_plan_ids
+static int plan(const char* who, const double* dets, const int* counts, const int* ids, int N, int ncls, int R, double thresh, int H, int W, int thickness,
+                int label_scale, int with_score, const unsigned char* names, int max_boxes, int* records, int* n, void* stream) {
+  LSFA_REQUIRE(dets && counts && records && n, "%s: NULL argument", who);
   LSFA_REQUIRE(N > 0 && N <= 65535 && ncls > 0 && ncls <= LSFA_OVERLAY_MAX_CLASSES && R > 0 && (long long)(ncls - 1) * R < (1LL << 31),
-               "lsfa_overlay_plan: bad shape: %d images of %d classes (at most %d) x %d rows", N, ncls, LSFA_OVERLAY_MAX_CLASSES, R);
-  LSFA_REQUIRE(H > 0 && W > 0 && H <= (1 << 16) && W <= (1 << 16), "lsfa_overlay_plan: bad frame: %d x %d", W, H);
-  LSFA_REQUIRE(max_boxes > 0 && max_boxes <= LSFA_OVERLAY_MAX_BOXES, "lsfa_overlay_plan: max_boxes %d is outside 1..%d", max_boxes, LSFA_OVERLAY_MAX_BOXES);
-  LSFA_REQUIRE(thickness >= 1 && thickness <= 8, "lsfa_overlay_plan: thickness %d is outside 1..8", thickness);
-  LSFA_REQUIRE(label_scale >= 0 && label_scale <= 4, "lsfa_overlay_plan: label_scale %d is outside 0..4", label_scale);
+               "%s: bad shape: %d images of %d classes (at most %d) x %d rows", who, N, ncls, LSFA_OVERLAY_MAX_CLASSES, R);
+  LSFA_REQUIRE(H > 0 && W > 0 && H <= (1 << 16) && W <= (1 << 16), "%s: bad frame: %d x %d", who, W, H);
+  LSFA_REQUIRE(max_boxes > 0 && max_boxes <= LSFA_OVERLAY_MAX_BOXES, "%s: max_boxes %d is outside 1..%d", who, max_boxes, LSFA_OVERLAY_MAX_BOXES);
+  LSFA_REQUIRE(thickness >= 1 && thickness <= 8, "%s: thickness %d is outside 1..8", who, thickness);
+  LSFA_REQUIRE(label_scale >= 0 && label_scale <= 4, "%s: label_scale %d is outside 0..4", who, label_scale);
   const int o = (thickness - 1) / 2;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(overlay_plan_kernel, dim3((unsigned)N), dim3(kThreads), 0, s, dets, counts, ncls, R, thresh, H, W, o, thickness - o, label_scale,
+  hipLaunchKernelGGL(overlay_plan_kernel, dim3((unsigned)N), dim3(kThreads), 0, s, dets, counts, ids, ncls, R, thresh, H, W, o, thickness - o, label_scale,
                      with_score ? 1 : 0, names, max_boxes, records, n);
-  LSFA_LAUNCH_CHECK("lsfa_overlay_plan");
+  LSFA_LAUNCH_CHECK(who);
   return LSFA_OK;
+}
+
+extern "C" int lsfa_overlay_plan(const double* dets, const int* counts, int N, int ncls, int R, double thresh, int H, int W, int thickness,
+                                 int label_scale, int with_score, const unsigned char* names, int max_boxes, int* records, int* n, void* stream) {
+  return plan("lsfa_overlay_plan", dets, counts, nullptr, N, ncls, R, thresh, H, W, thickness, label_scale, with_score, names, max_boxes, records, n, stream);
+}
+
+extern "C" int lsfa_overlay_plan_ids(const double* dets, const int* counts, const int* ids, int N, int ncls, int R, double thresh, int H, int W,
+                                     int thickness, int label_scale, int with_score, const unsigned char* names, int max_boxes, int* records, int* n,
+                                     void* stream) {
+  LSFA_REQUIRE(ids, "lsfa_overlay_plan_ids: NULL ids");
+  LSFA_REQUIRE(ncls >= 2, "lsfa_overlay_plan_ids: ncls %d: a track's colour is one of the classes 1..ncls-1", ncls);
+  return plan("lsfa_overlay_plan_ids", dets, counts, ids, N, ncls, R, thresh, H, W, thickness, label_scale, with_score, names, max_boxes, records, n, stream);
 }
 
 extern "C" int lsfa_overlay_paint_bgr(unsigned char* bgr, long long pitch, long long frame_stride, int N, int H, int W, const int* records, const int* n,

@@ -7,6 +7,7 @@ The detections stay where lsfa_det_postprocess(_batch) left them - dets (ncls, R
 batch - and are burnt into a frame that is on the device already: packed BGR (H, W, 3) / (N, H, W, 3) uint8, or the 8-bit 4:2:0 planes
 the YUV intake takes (y and uv of NV12, or y, u and v of I420).  Row views of pitched surfaces are taken as they are: pitch and frame
 stride come from .stride().  Nothing is read back and nothing is allocated by a draw call, so the two launches can be captured in a graph.
+With ids=, the track ids lsfa_amd/tracks.py assigns, the plan is lsfa_overlay_plan_ids: one colour and one number per object.
 
 This is the project's own integer specification (the header; DESIGN.md "Detection overlay"; tests/ref_overlay.py in numpy), not cv2's
 rasteriser: no Hershey fonts, no anti-aliasing, and a fixed palette where the reference's draw_boxes picks random colours."""
@@ -169,21 +170,30 @@ class Overlay(object):
         self.records = torch.zeros((batch, max_boxes, REC_INTS), dtype=torch.int32, device=self.device)
         self.n = torch.zeros((batch, 2), dtype=torch.int32, device=self.device)
 
-    def _plan(self, who, N, batched, H, W, dets, counts, thresh):
-        """validates dets / counts against the frames' N and launches lsfa_overlay_plan"""
+    def _plan(self, who, N, batched, H, W, dets, counts, thresh, ids=None):
+        """validates dets / counts (and ids) against the frames' N and launches lsfa_overlay_plan, or lsfa_overlay_plan_ids with ids"""
         lead = (N,) if batched else ()
         if N > self.batch:
             raise LsfaError("%s: %d frames, this Overlay was made for a batch of %d" % (who, N, self.batch))
         _tensor(who, "dets", dets, torch.float64, lead + (self.ncls, self.R, 5), self.device)
         _tensor(who, "counts", counts, torch.int32, lead + (self.ncls,), self.device)
+        if ids is not None:
+            if self.ncls < 2:
+                raise LsfaError("%s: ids need at least 2 classes: a track's colour is one of the classes 1..ncls-1" % who)
+            _tensor(who, "ids", ids, torch.int32, lead + (self.ncls, self.R), self.device)
+            _check(hip.lib().lsfa_overlay_plan_ids(_ptr(dets), _ptr(counts), _ptr(ids), N, self.ncls, self.R, float(thresh), H, W, self.thickness,
+                                                   self.label_scale, 1 if self.with_score else 0, _ptr(self._names), self.max_boxes,
+                                                   _ptr(self.records), _ptr(self.n), hip._stream()), "lsfa_overlay_plan_ids")
+            return
         _check(hip.lib().lsfa_overlay_plan(_ptr(dets), _ptr(counts), N, self.ncls, self.R, float(thresh), H, W, self.thickness, self.label_scale,
                                            1 if self.with_score else 0, _ptr(self._names), self.max_boxes, _ptr(self.records), _ptr(self.n),
                                            hip._stream()), "lsfa_overlay_plan")
 
     @hip._on_tensor_device
-    def draw_bgr(self, frames, dets, counts, thresh):
+    def draw_bgr(self, frames, dets, counts, thresh, ids=None):
         """frames (H, W, 3) or (N, H, W, 3) uint8, drawn into in place; pixels are packed (strides 3 and 1), rows and frames may be pitched.
-        dets (ncls, R, 5) float64 and counts (ncls) int32 of one frame, (N, ..) of a batch.  Returns frames."""
+        dets (ncls, R, 5) float64 and counts (ncls) int32 of one frame, (N, ..) of a batch.  ids (ncls, R) / (N, ncls, R) int32, a Tracker's:
+        only rows with an id above 0 are drawn, in the track's colour, labelled name-id.  Returns frames."""
         who = "Overlay.draw_bgr"
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.device != self.device or frames.dim() not in (3, 4) or \
                 int(frames.shape[-1]) != 3 or frames.stride(-1) != 1 or frames.stride(-2) != 3 or min(frames.shape) < 1:
@@ -195,21 +205,21 @@ class Overlay(object):
         fs = int(frames.stride(0)) if batched and N > 1 else 0
         if pitch < 3 * W or fs < 0:
             raise LsfaError("%s: a row pitch is below its row: %s strides %s" % (who, tuple(frames.shape), tuple(frames.stride())))
-        self._plan(who, N, batched, H, W, dets, counts, thresh)
+        self._plan(who, N, batched, H, W, dets, counts, thresh, ids)
         _check(hip.lib().lsfa_overlay_paint_bgr(_ptr(frames), pitch, fs, N, H, W, _ptr(self.records), _ptr(self.n), self.max_boxes, self.thickness,
                                                 self.label_scale, _ptr(self._font), _ptr(self._bgr), self.ncls, hip._stream()),
                "lsfa_overlay_paint_bgr")
         return frames
 
     @hip._on_tensor_device
-    def draw_yuv420(self, y, dets, counts, thresh, uv=None, u=None, v=None, matrix='bt601'):
+    def draw_yuv420(self, y, dets, counts, thresh, uv=None, u=None, v=None, matrix='bt601', ids=None):
         """the planes of hip.yuv420_to_bgr_u8 - y and uv (NV12) or y, u and v (I420), one frame or (N, ..) - drawn into in place with the
-        colours converted by `matrix`, the matrix the stream is decoded with.  dets / counts as draw_bgr."""
+        colours converted by `matrix`, the matrix the stream is decoded with.  dets / counts / ids as draw_bgr."""
         who = "Overlay.draw_yuv420"
         args, N, H, W, batched = hip._yuv_planes(who, y, uv, u, v, matrix)
         if y.device != self.device:
             raise LsfaError("%s: the planes are on %s, this Overlay on %s" % (who, y.device, self.device))
-        self._plan(who, N, batched, H, W, dets, counts, thresh)
+        self._plan(who, N, batched, H, W, dets, counts, thresh, ids)
         _check(hip.lib().lsfa_overlay_paint_yuv420(*(args[:10] + (_ptr(self.records), _ptr(self.n), self.max_boxes, self.thickness, self.label_scale,
                                                                   _ptr(self._font), _ptr(self._yuv[matrix]), self.ncls, hip._stream()))),
                "lsfa_overlay_paint_yuv420")
