@@ -695,7 +695,7 @@ int lsfa_mv_key_sad_accu(const unsigned char* luma_cur, const unsigned char* lum
                          int height, int* keysad /* (mbh, mbw) */, void* stream);
 
 /* ------------------------------------------------------------------------ *
- * YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip): the planes a decoder hands over - libav, the VCN decode engines, a raw .yuv dump - straight to
+ * YUV 4:2:0 intake (lsfa_amd/csrc/yuvfmt.hip, the one intake source): the planes a decoder hands over - libav, the VCN decode engines, a raw .yuv dump - straight to
  * the packed BGR frame lsfa_mv_residual / lsfa_luma_u8 / lsfa_image_transform_u8 take, to the luma plane lsfa_mv_estimate searches and to the
  * network's `data`.  Replaces (in function, NOT in arithmetic): the swscale conversion inside the reference's coviar loader
  * (external/data_loader_py2/coviar_data_loader.c), which runs on the CPU.  Neither swscale nor OpenCV is part of this project, and both carry
@@ -726,6 +726,8 @@ int lsfa_mv_key_sad_accu(const unsigned char* luma_cur, const unsigned char* lum
  * lsfa_image_resize_transform_yuv420: lsfa_image_resize_transform with is_u8 = 1 reading its taps from the planes (the converted frame as
  *   float, interpolated in float, padded to `stride`, the float32 / float64 subtraction rule by `stride` stated there); bit-identical to it
  *   on lsfa_yuv420_to_bgr_u8's frame.  h1, w1, out_h, out_w as there - checked.  The fixed-point is_u8 = 2 form is not offered for YUV.
+ * Each of the three equals lsfa_yuv_to_bgr_u8 / lsfa_image_transform_yuv / lsfa_image_resize_transform_yuv ("YUV intake, other chroma
+ * formats" below) with format LSFA_YUV_FORMAT(LSFA_YUV_420, v ? LSFA_YUV_PLANAR : LSFA_YUV_UV, LSFA_YUV_U8): a forward to the same code.
  * ------------------------------------------------------------------------ */
 int lsfa_yuv420_to_bgr_u8(const unsigned char* y, long long y_pitch, long long y_frame_stride, const unsigned char* u_or_uv,
                           const unsigned char* v /* NULL: NV12 */, long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix,
@@ -771,7 +773,7 @@ int lsfa_prof_read(double* ms_host /*LSFA_OP_COUNT*/, int* launches_host /*LSFA_
 const char* lsfa_op_name(int op_id);
 
 /* ------------------------------------------------------------------------ *
- * 10-bit YUV 4:2:0 intake (lsfa_amd/csrc/yuv10.hip): what HEVC Main10, VP9 profile 2 and AV1 10-bit decode to - the VCN engines' P010 /
+ * 10-bit YUV 4:2:0 intake (lsfa_amd/csrc/yuvfmt.hip): what HEVC Main10, VP9 profile 2 and AV1 10-bit decode to - the VCN engines' P010 /
  * P016 surfaces, libav's yuv420p10le - to the same three outputs as the 8-bit intake above, which it mirrors argument for argument with
  * `shift` behind `matrix`.  Everything behind the intake stays 8-bit.  Defined by the specification below (DESIGN.md "YUV intake", "10-bit
  * planes"; restated in numpy as tests/ref_yuv10.py) and bit-exact with THAT; parity with swscale is unpinned and not claimed.
@@ -798,6 +800,8 @@ const char* lsfa_op_name(int op_id);
  *   (subtraction and product in float64, rounded once), without storing the frame.
  * lsfa_image_resize_transform_yuv420p10: lsfa_image_resize_transform with is_u8 = 1 of that frame, bit for bit, reading its taps from the
  *   planes; h1, w1, stride, out_h, out_w as there - checked.
+ * Each of the three, once `shift` is 0 or 6, equals lsfa_yuv_to_bgr_u8 / lsfa_image_transform_yuv / lsfa_image_resize_transform_yuv below with
+ * format LSFA_YUV_FORMAT(LSFA_YUV_420, v ? LSFA_YUV_PLANAR : LSFA_YUV_UV, shift ? LSFA_YUV_HI10 : LSFA_YUV_LO10): a forward to the same code.
  * ------------------------------------------------------------------------ */
 int lsfa_yuv420p10_to_bgr_u8(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v /* NULL: interleaved */,
                              long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int shift, unsigned char* bgr,
@@ -826,7 +830,7 @@ int lsfa_image_resize_transform_yuv420p10(const void* y, long long y_pitch, long
  *   sample: 0: bytes, converted by the 8-bit table ("YUV 4:2:0 intake" above), y_packed = Y   1: 16-bit words with the value in the low ten
  *     bits: the 10-bit specification's conversion, rounding and y_packed rule with shift = 0   2: in the high ten bits: shift = 6.
  *   Packed layouts exist only with sub = 1 and sample = 0; every other combination is valid: 27 + 2 formats.  Matrices 0..2 as above.
- *   The 4:2:0 formats of the two intakes above (layouts 0 and 1) are taken too and give their bytes.
+ *   The 4:2:0 formats of the two intakes above (layouts 0 and 1) are formats like any other: those six exports forward here.
  * Out of scope: interpolated or sited chroma; packed 10-bit (v210, Y210, Y410); 12-bit; 4:1:1 / 4:1:0; YVYU; alpha; BT.2020 / HDR transfer; RGB
  * surfaces.
  * Pitches and frame strides are in BYTES.  LSFA_EINVAL, before anything is launched, for: a format outside the above; a NULL plane or output;

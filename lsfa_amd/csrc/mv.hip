@@ -99,7 +99,7 @@ __global__ __launch_bounds__(kThreads) void mv_residual_kernel(const unsigned ch
 // in float32 (mul, mul, add: the two passes' roundings), everything behind them in float64, one rounding to float32 at the end - instead of
 // materialising three full-resolution maps.  oracle/np_ref.py::transform_mv_res is the same arithmetic statement by statement.
 // (first_resize, MvResArgs, padded_value and second_resize: mv_res_kernels.h, shared with me_segment.hip; ResizeTap, resize_tap, resize_blend and
-// resize_transform_store: resize_kernels.h, shared with yuv.hip)
+// resize_transform_store: resize_kernels.h, shared with yuvfmt.hip)
 template <typename T>
 __global__ __launch_bounds__(kThreads) void transform_mv_res_kernel(const T* __restrict__ mv, const T* __restrict__ res, MvResArgs a,
                                                                     float* __restrict__ out_mv, float* __restrict__ out_res) {

@@ -1,5 +1,5 @@
 // The tap, weight and `transform` arithmetic of the frame intake, stated once for mv.hip (packed BGR / float frames, motion vectors,
-// residuals) and yuv.hip (taps read from YUV 4:2:0 planes).  OpenCV 3.2's HResizeLinear / VResizeLinear<float, float, float> as restated in
+// residuals) and yuvfmt.hip (taps read from YUV planes).  OpenCV 3.2's HResizeLinear / VResizeLinear<float, float, float> as restated in
 // oracle/np_ref.py; the precisions of `transform` follow lib/utils/image.py:296-308 (see lsfa_image_resize_transform in lsfa_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
-// What the YUV 4:2:0 intakes share, stated once for yuv.hip (8-bit planes) and yuv10.hip (10-bit samples in 16-bit words): a converted
-// pixel, the table of the three matrices, and the two output forms of the plane kernels - the packed BGR frame (plus the packed Y plane)
-// and the network's `data`.  A kernel template takes one of the two as `Out` and calls px (one pixel) or quad (four adjacent pixels).
+// What the YUV intake's kernels (yuvfmt.hip) convert into, whatever the format: a converted pixel and its clamp, the table of the three
+// matrices, and the two output forms of the plane kernels - the packed BGR frame (plus the packed Y plane) and the network's `data`.  A
+// kernel template takes one of the two as `Out` and calls px (one pixel) or quad (four adjacent pixels).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,7 +9,13 @@ namespace lsfa {
 
 struct Bgr { int b, g, r; };
 
-__device__ __forceinline__ int clip255(int v) { return min(max(v, 0), 255); }
+// v >> DOWN clipped to 0..255, clamped BEFORE the shift: the same number (v < 0 gives 0, v >= 256 << DOWN gives 255, >> is monotonic), and
+// the ONLY form a channel that reaches BgrOut::quad may be computed in.  Shift-then-saturate, min(max(v >> DOWN, 0), 255), is what the
+// gfx950 back end folds, together with quad's `b | g << 8`, into v_ashr_pk_u8_i32.  That instruction writes the low half of its
+// destination and the back end uses the result as a whole dword: wherever the register held a negative value before (a clipped blue),
+// bytes 2 and 3 of the stored dword came out as 0xFF on the device - DESIGN.md "Other chroma formats".
+template <int DOWN>
+__device__ __forceinline__ int clip_down(int v) { return min(max(v, 0), (256 << DOWN) - 1) >> DOWN; }
 
 // {o, cy, rv, gu, gv, bu} per matrix, in 8-bit units: BT.601 limited, BT.709 limited, BT.601 full range (include/lsfa_hip.h)
 constexpr int kYuvMatrix[3][6] = {{16, 298, 409, 100, 208, 516}, {16, 298, 459, 55, 136, 541}, {0, 256, 359, 88, 183, 454}};

@@ -1,26 +1,37 @@
-// YUV intake for the other chroma formats: 4:2:2 and 4:4:4 beside 4:2:0, chroma interleaved V, U (NV21 / NV61 / NV42) beside U, V, packed
-// 4:2:2 (YUYV / YUY2, UYVY), each of bytes or of 16-bit words holding ten bits - what capture cards, webcams, MJPEG cameras, contribution
-// codecs (ProRes, DNxHR, HEVC 4:2:2 10-bit), screen recorders and Android cameras hand over - to the same three outputs as yuv.hip and
-// yuv10.hip: the packed uint8 BGR frame, the 8-bit luma plane the search reads and the network's `data`.
+// YUV intake: the frames a decoder, a capture card or a camera hands over - libav, the VCN engines, a raw .yuv dump - straight to the packed
+// uint8 BGR frame lsfa_mv_residual reads, to the 8-bit luma plane lsfa_mv_estimate searches and to the network's `data`, without a host-side
+// colour conversion.  ONE conversion and one kernel set behind all nine exports: the three lsfa_*yuv420* (8-bit NV12 / I420) and the three
+// lsfa_*yuv420p10* (P010 / yuv420p10le) are lsfa_yuv_to_bgr_u8, lsfa_image_transform_yuv and lsfa_image_resize_transform_yuv at a format code.
 //
-// NOT a port of anything in the reference.  The conversion is the shipped specification (include/lsfa_hip.h, "YUV 4:2:0 intake" and "10-bit
-// YUV 4:2:0 intake") with the chroma address generalised ("YUV intake, other chroma formats" there; DESIGN.md "Other chroma formats";
-// tests/ref_yuvfmt.py states it in numpy on ref_yuv's and ref_yuv10's conversions).  format = sub | layout << 4 | sample << 8:
+// NOT a port of anything in the reference: there swscale converts inside the coviar loader, on the CPU.  The conversion is DEFINED by the
+// specification (include/lsfa_hip.h, "YUV 4:2:0 intake", "10-bit YUV 4:2:0 intake", "YUV intake, other chroma formats"; DESIGN.md "YUV
+// intake"; tests/ref_yuv.py, ref_yuv10.py and ref_yuvfmt.py state it in numpy) - parity with swscale or OpenCV, which carry options such as
+// chroma siting and bilinear chroma, is unpinned and not claimed.  Integer arithmetic, one answer per input, every byte and word defined input:
+//   C = Y - o, D = U - 128, E = V - 128;  >> is arithmetic;  clip clamps to 0..255;
+//   matrix 0 (BT.601 limited)  o = 16  R = clip((298 C + 409 E + 128) >> 8)  G = clip((298 C - 100 D - 208 E + 128) >> 8)  B = clip((298 C + 516 D + 128) >> 8)
+//   matrix 1 (BT.709 limited)  o = 16  R = clip((298 C + 459 E + 128) >> 8)  G = clip((298 C -  55 D - 136 E + 128) >> 8)  B = clip((298 C + 541 D + 128) >> 8)
+//   matrix 2 (BT.601 full)     o = 0   R = clip((256 C + 359 E + 128) >> 8)  G = clip((256 C -  88 D - 183 E + 128) >> 8)  B = clip((256 C + 454 D + 128) >> 8)
+//   ten-bit samples in 16-bit little-endian words, s = (w >> shift) & 1023: C = Y - 4 o, D = U - 512, E = V - 512, the same coefficients,
+//   rounding constant 512 and >> 10 - converted in ten bits, rounded once, |intermediate| < 2^20; y_packed = min(255, (Y + 2) >> 2).  Planes
+//   that are exactly 4 x an 8-bit plane give the 8-bit BGR and Y bit for bit.
+// format = sub | layout << 4 | sample << 8:
 //   sub     0: 4:2:0 (sx, sy) = (1, 1)   1: 4:2:2 (1, 0)   2: 4:4:4 (0, 0); pixel (x, y) takes Y[y][x] and the chroma sample (x >> sx, y >> sy),
 //           nearest neighbour; chroma planes are ceil(W / 2^sx) x ceil(H / 2^sy)
 //   layout  0: two planes U, V   1: one interleaved plane U, V   2: one interleaved plane V, U   3: packed Y0 U Y1 V   4: packed U Y0 V Y1
 //           (3 and 4: sub = 1, sample = 0 only; the row is ceil(W / 2) four-byte groups in the `y` plane, no chroma planes)
-//   sample  0: bytes, the 8-bit table   1: words, the value in the low ten bits (the 10-bit conversion with shift 0)   2: in the high ten (shift 6)
-// Out of scope: interpolated or sited chroma, packed 10-bit (v210, Y210, Y410), 12-bit, 4:1:1 / 4:1:0, YVYU, alpha, BT.2020 / HDR transfer, RGB.
+//   sample  0: bytes   1: words, the value in the low ten bits (shift 0: yuv420p10le / I010)   2: in the high ten (shift 6: P010 / P016 surfaces)
+// Out of scope: interpolated or sited chroma, packed 10-bit (v210, Y210, Y410), 12-bit and P016's low bits as signal, 4:1:1 / 4:1:0, YVYU,
+// alpha, BT.2020 / HDR transfer, RGB, any binding to rocDecode.
 //
-// Bandwidth kernels in yuv.hip's two-kernel shape; the host picks one per launch.  Every format is reduced on the host to three sample
-// addresses - the first Y, U and V with the bytes from a sample to the next of its kind - so the element-wise kernel (a thread per pixel,
-// one- or two-byte loads) and the resize kernel take layout and subsampling at run time and know nothing of them; only bytes or words is
-// compiled in.  yuvfmt_quad_kernel is compiled
-// per format: a thread takes four horizontally adjacent pixels (of two rows for 4:2:0, of one row otherwise) and reads every chroma
-// sample once - 4:2:2 semi-planar one Y dword and one dword of two pairs, packed one 8-byte load of four whole pixels, 4:4:4 one Y dword and
-// eight chroma bytes, words twice that - and stores through yuv_out.h's quad forms.  It needs W % 4 == 0, for 4:2:0 an even H, and every
-// base, pitch and frame stride a multiple of the load it feeds.
+// Bandwidth kernels, two per output form; the host picks one per launch.  Every format is reduced on the host to three sample addresses -
+// the first Y, U and V with the bytes from a sample to the next of its kind - so the element-wise kernel (a thread per pixel, one- or
+// two-byte loads) and the resize kernel take layout and subsampling at run time and know nothing of them; only bytes or words is compiled
+// in.  yuvfmt_quad_kernel is compiled per format: a thread takes four horizontally adjacent pixels (of two rows for 4:2:0, of one row
+// otherwise) and reads every chroma sample once - 4:2:0 two Y dwords and one dword of two U, V pairs (two half-words for planar chroma),
+// 4:2:2 semi-planar one Y dword and one dword of two pairs, packed one 8-byte load of four whole pixels, 4:4:4 one Y dword and eight chroma
+// bytes, words twice that - and stores through yuv_out.h's quad forms (for `data`, three 16-byte stores a row).  It needs W % 4 == 0, for
+// 4:2:0 an even H, and every base, pitch and frame stride a multiple of the load it feeds.  The resize form gathers and converts its four
+// taps per output pixel like resize_transform_kernel (mv.hip) and shares its tap and weight arithmetic (resize_kernels.h).
 #include "common.h"
 #include "resize_kernels.h"
 #include "yuv_out.h"
@@ -45,13 +56,7 @@ struct FmtPlanes {
   int quad;                     // host only: the geometry allows yuvfmt_quad_kernel (the outputs' alignment is the caller's part)
 };
 
-// clip255(v >> DOWN), clamped BEFORE the shift: the same number (v < 0 gives 0, v >= 256 << DOWN gives 255, >> is monotonic), but not the
-// shift-then-saturate pattern the gfx950 back end folds, together with BgrOut's `b | g << 8`, into v_ashr_pk_u8_i32.  That instruction
-// writes the low half of its destination and the back end uses the result as a whole dword: wherever the register held a negative value
-// before (a clipped blue), bytes 2 and 3 of the stored dword came out as 0xFF on the device - DESIGN.md "Other chroma formats".
-template <int DOWN>
-__device__ __forceinline__ int clip_down(int v) { return min(max(v, 0), (256 << DOWN) - 1) >> DOWN; }
-
+// the one conversion; clip_down (yuv_out.h) and nothing else clamps a channel
 template <bool WORDS>
 __device__ __forceinline__ Bgr fmt_to_bgr(const FmtPlanes& p, int Y, int U, int V) {
   constexpr int half = WORDS ? 512 : 128, down = WORDS ? 10 : 8;
@@ -199,7 +204,8 @@ __global__ __launch_bounds__(kThreads) void resize_transform_yuvfmt_kernel(FmtPl
   resize_transform_store(out + (size_t)n * 3 * plane + r, plane, b, g, rr, m0, m1, m2, pixel_scale, sub_f64);
 }
 
-const char* const kLayoutName[5] = {"planar", "interleaved U, V", "interleaved V, U", "packed YUYV", "packed UYVY"};
+// with the 4:2:0 name of each: what a message of the 8-bit 4:2:0 exports calls its two layouts
+const char* const kLayoutName[5] = {"planar (I420's)", "interleaved U, V (NV12's)", "interleaved V, U (NV21's)", "packed YUYV", "packed UYVY"};
 
 int fill_planes(const char* who, FmtPlanes& p, const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v,
                 long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int format) {
@@ -289,31 +295,29 @@ void launch(const FmtPlanes& p, const Out& out, bool quad, hipStream_t s) {
   }
 }
 
-}  // namespace
-
-extern "C" int lsfa_yuv_to_bgr_u8(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
-                                  long long c_frame_stride, int N, int H, int W, int matrix, int format, unsigned char* bgr, unsigned char* y_packed,
-                                  void* stream) {
+// ---- the three host bodies, one per output form.  `who` is the export that was called: every message names it ---------------------------
+int to_bgr(const char* who, const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
+           long long c_frame_stride, int N, int H, int W, int matrix, int format, unsigned char* bgr, unsigned char* y_packed, void* stream) {
   FmtPlanes p;
-  if (int rc = fill_planes("lsfa_yuv_to_bgr_u8", p, y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format)) return rc;
-  LSFA_REQUIRE(bgr, "lsfa_yuv_to_bgr_u8: NULL output");
+  if (int rc = fill_planes(who, p, y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format)) return rc;
+  LSFA_REQUIRE(bgr, "%s: NULL output", who);
   BgrOut out;
   out.bgr = bgr; out.y_packed = y_packed; out.hw = (long)H * W;
   const bool quad = p.quad && ((reinterpret_cast<uintptr_t>(bgr) | reinterpret_cast<uintptr_t>(y_packed)) & 3u) == 0;
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(LSFA_OP_STEM, s);
   launch(p, out, quad, s);
-  LSFA_LAUNCH_CHECK("lsfa_yuv_to_bgr_u8");
+  LSFA_LAUNCH_CHECK(who);
   return LSFA_OK;
 }
 
-extern "C" int lsfa_image_transform_yuv(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
-                                        long long c_frame_stride, int N, int H, int W, int matrix, int format, const double* pixel_means_bgr_host,
-                                        double pixel_scale, float* data_nchw, void* stream) {
+int transform(const char* who, const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
+              long long c_frame_stride, int N, int H, int W, int matrix, int format, const double* pixel_means_bgr_host, double pixel_scale,
+              float* data_nchw, void* stream) {
   FmtPlanes p;
-  if (int rc = fill_planes("lsfa_image_transform_yuv", p, y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format)) return rc;
-  LSFA_REQUIRE(pixel_means_bgr_host && data_nchw, "lsfa_image_transform_yuv: NULL argument");
-  LSFA_REQUIRE((reinterpret_cast<uintptr_t>(data_nchw) & 3u) == 0, "lsfa_image_transform_yuv: the output is not float aligned");
+  if (int rc = fill_planes(who, p, y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format)) return rc;
+  LSFA_REQUIRE(pixel_means_bgr_host && data_nchw, "%s: NULL argument", who);
+  LSFA_REQUIRE((reinterpret_cast<uintptr_t>(data_nchw) & 3u) == 0, "%s: the output is not float aligned", who);
   DataOut out;
   out.out = data_nchw; out.hw = (long)H * W;
   out.m0 = pixel_means_bgr_host[0]; out.m1 = pixel_means_bgr_host[1]; out.m2 = pixel_means_bgr_host[2];
@@ -322,34 +326,108 @@ extern "C" int lsfa_image_transform_yuv(const void* y, long long y_pitch, long l
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(LSFA_OP_STEM, s);
   launch(p, out, quad, s);
-  LSFA_LAUNCH_CHECK("lsfa_image_transform_yuv");
+  LSFA_LAUNCH_CHECK(who);
   return LSFA_OK;
+}
+
+int resize_transform(const char* who, const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v,
+                     long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int format, double im_scale, int h1, int w1,
+                     int stride, const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw, int out_h, int out_w, void* stream) {
+  FmtPlanes p;
+  if (int rc = fill_planes(who, p, y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format)) return rc;
+  LSFA_REQUIRE(pixel_means_bgr_host && data_nchw, "%s: NULL argument", who);
+  LSFA_REQUIRE((reinterpret_cast<uintptr_t>(data_nchw) & 3u) == 0, "%s: the output is not float aligned", who);
+  LSFA_REQUIRE(h1 > 0 && w1 > 0 && h1 <= (1 << 16) && w1 <= (1 << 16) && stride >= 0 && stride <= (1 << 16) && im_scale > 0.0, "%s: bad shape", who);
+  const int ph = stride > 0 ? (h1 + stride - 1) / stride * stride : h1, pw = stride > 0 ? (w1 + stride - 1) / stride * stride : w1;
+  LSFA_REQUIRE(ph == out_h && pw == out_w, "%s: output is %d x %d, the resized %d x %d frame padded to %d gives %d x %d", who, out_h, out_w, h1, w1,
+               stride, ph, pw);
+  const long total = (long)N * ph * pw;
+  LSFA_REQUIRE(total < (1L << 36), "%s: output too large", who);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope prof(LSFA_OP_STEM, s);
+  auto resize_kernel = p.words ? resize_transform_yuvfmt_kernel<true> : resize_transform_yuvfmt_kernel<false>;
+  hipLaunchKernelGGL(resize_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, p, h1, w1, ph, pw,
+                     1.0 / im_scale, pixel_means_bgr_host[0], pixel_means_bgr_host[1], pixel_means_bgr_host[2], pixel_scale, stride > 0 ? 1 : 0, data_nchw);
+  LSFA_LAUNCH_CHECK(who);
+  return LSFA_OK;
+}
+
+// the 4:2:0 exports say their layout by `v` (NULL: one interleaved U, V plane) and, the 10-bit ones, their sample by `shift`
+int format_420(const void* v, int sample) { return LSFA_YUV_FORMAT(LSFA_YUV_420, v ? LSFA_YUV_PLANAR : LSFA_YUV_UV, sample); }
+int sample_10(int shift) { return shift == 6 ? LSFA_YUV_HI10 : LSFA_YUV_LO10; }
+int check_shift(const char* who, int shift) {
+  LSFA_REQUIRE(shift == 0 || shift == 6, "%s: shift %d is not 6 (P010: the sample in the high ten bits) or 0 (yuv420p10le: in the low ten)", who, shift);
+  return LSFA_OK;
+}
+
+}  // namespace
+
+// ---- the nine exports: the three of a format code, then the 4:2:0 ones as forwards to them -------------------------------------------------
+extern "C" int lsfa_yuv_to_bgr_u8(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
+                                  long long c_frame_stride, int N, int H, int W, int matrix, int format, unsigned char* bgr, unsigned char* y_packed,
+                                  void* stream) {
+  return to_bgr("lsfa_yuv_to_bgr_u8", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format, bgr, y_packed, stream);
+}
+
+extern "C" int lsfa_image_transform_yuv(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
+                                        long long c_frame_stride, int N, int H, int W, int matrix, int format, const double* pixel_means_bgr_host,
+                                        double pixel_scale, float* data_nchw, void* stream) {
+  return transform("lsfa_image_transform_yuv", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format,
+                   pixel_means_bgr_host, pixel_scale, data_nchw, stream);
 }
 
 extern "C" int lsfa_image_resize_transform_yuv(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v,
                                                long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int format, double im_scale,
                                                int h1, int w1, int stride, const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw,
                                                int out_h, int out_w, void* stream) {
-  FmtPlanes p;
-  if (int rc = fill_planes("lsfa_image_resize_transform_yuv", p, y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format))
-    return rc;
-  LSFA_REQUIRE(pixel_means_bgr_host && data_nchw, "lsfa_image_resize_transform_yuv: NULL argument");
-  LSFA_REQUIRE((reinterpret_cast<uintptr_t>(data_nchw) & 3u) == 0, "lsfa_image_resize_transform_yuv: the output is not float aligned");
-  LSFA_REQUIRE(h1 > 0 && w1 > 0 && h1 <= (1 << 16) && w1 <= (1 << 16) && stride >= 0 && stride <= (1 << 16) && im_scale > 0.0,
-               "lsfa_image_resize_transform_yuv: bad shape");
-  const int ph = stride > 0 ? (h1 + stride - 1) / stride * stride : h1, pw = stride > 0 ? (w1 + stride - 1) / stride * stride : w1;
-  if (ph != out_h || pw != out_w) {
-    set_error("lsfa_image_resize_transform_yuv: output is %d x %d, the resized %d x %d frame padded to %d gives %d x %d", out_h, out_w, h1, w1, stride, ph,
-              pw);
-    return LSFA_EINVAL;
-  }
-  const long total = (long)N * ph * pw;
-  LSFA_REQUIRE(total < (1L << 36), "lsfa_image_resize_transform_yuv: output too large");
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope prof(LSFA_OP_STEM, s);
-  auto resize_kernel = p.words ? resize_transform_yuvfmt_kernel<true> : resize_transform_yuvfmt_kernel<false>;
-  hipLaunchKernelGGL(resize_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, p, h1, w1, ph, pw,
-                     1.0 / im_scale, pixel_means_bgr_host[0], pixel_means_bgr_host[1], pixel_means_bgr_host[2], pixel_scale, stride > 0 ? 1 : 0, data_nchw);
-  LSFA_LAUNCH_CHECK("lsfa_image_resize_transform_yuv");
-  return LSFA_OK;
+  return resize_transform("lsfa_image_resize_transform_yuv", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix, format,
+                          im_scale, h1, w1, stride, pixel_means_bgr_host, pixel_scale, data_nchw, out_h, out_w, stream);
 }
+
+extern "C" int lsfa_yuv420_to_bgr_u8(const unsigned char* y, long long y_pitch, long long y_frame_stride, const unsigned char* u_or_uv,
+                                     const unsigned char* v, long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix,
+                                     unsigned char* bgr, unsigned char* y_packed, void* stream) {
+  return to_bgr("lsfa_yuv420_to_bgr_u8", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix,
+                format_420(v, LSFA_YUV_U8), bgr, y_packed, stream);
+}
+
+extern "C" int lsfa_image_transform_yuv420(const unsigned char* y, long long y_pitch, long long y_frame_stride, const unsigned char* u_or_uv,
+                                           const unsigned char* v, long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix,
+                                           const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw, void* stream) {
+  return transform("lsfa_image_transform_yuv420", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix,
+                   format_420(v, LSFA_YUV_U8), pixel_means_bgr_host, pixel_scale, data_nchw, stream);
+}
+
+extern "C" int lsfa_image_resize_transform_yuv420(const unsigned char* y, long long y_pitch, long long y_frame_stride, const unsigned char* u_or_uv,
+                                                  const unsigned char* v, long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix,
+                                                  double im_scale, int h1, int w1, int stride, const double* pixel_means_bgr_host, double pixel_scale,
+                                                  float* data_nchw, int out_h, int out_w, void* stream) {
+  return resize_transform("lsfa_image_resize_transform_yuv420", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix,
+                          format_420(v, LSFA_YUV_U8), im_scale, h1, w1, stride, pixel_means_bgr_host, pixel_scale, data_nchw, out_h, out_w, stream);
+}
+
+extern "C" int lsfa_yuv420p10_to_bgr_u8(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v, long long c_pitch,
+                                        long long c_frame_stride, int N, int H, int W, int matrix, int shift, unsigned char* bgr,
+                                        unsigned char* y_packed, void* stream) {
+  if (int rc = check_shift("lsfa_yuv420p10_to_bgr_u8", shift)) return rc;
+  return to_bgr("lsfa_yuv420p10_to_bgr_u8", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix,
+                format_420(v, sample_10(shift)), bgr, y_packed, stream);
+}
+
+extern "C" int lsfa_image_transform_yuv420p10(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v,
+                                              long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int shift,
+                                              const double* pixel_means_bgr_host, double pixel_scale, float* data_nchw, void* stream) {
+  if (int rc = check_shift("lsfa_image_transform_yuv420p10", shift)) return rc;
+  return transform("lsfa_image_transform_yuv420p10", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix,
+                   format_420(v, sample_10(shift)), pixel_means_bgr_host, pixel_scale, data_nchw, stream);
+}
+
+extern "C" int lsfa_image_resize_transform_yuv420p10(const void* y, long long y_pitch, long long y_frame_stride, const void* u_or_uv, const void* v,
+                                                     long long c_pitch, long long c_frame_stride, int N, int H, int W, int matrix, int shift,
+                                                     double im_scale, int h1, int w1, int stride, const double* pixel_means_bgr_host,
+                                                     double pixel_scale, float* data_nchw, int out_h, int out_w, void* stream) {
+  if (int rc = check_shift("lsfa_image_resize_transform_yuv420p10", shift)) return rc;
+  return resize_transform("lsfa_image_resize_transform_yuv420p10", y, y_pitch, y_frame_stride, u_or_uv, v, c_pitch, c_frame_stride, N, H, W, matrix,
+                          format_420(v, sample_10(shift)), im_scale, h1, w1, stride, pixel_means_bgr_host, pixel_scale, data_nchw, out_h, out_w, stream);
+}
+

@@ -923,54 +923,108 @@ def image_transform_u8(im, pixel_means=(0.0, 0.0, 0.0), pixel_scale=1.0, out=Non
     return out
 
 
-# ---- YUV 4:2:0 intake (lsfa_amd/csrc/yuv.hip) ---------------------------------------------------------------------------------------------
+# ---- YUV intake (lsfa_amd/csrc/yuvfmt.hip): the one plane checker and the one output block behind the wrappers here, in yuv10.py and yuvfmt.py
 YUV_MATRICES = {'bt601': 0, 'bt709': 1, 'jpeg': 2}
 
 
-def _yuv_planes(who, y, uv, u, v, matrix):
-    """The plane arguments of the lsfa_*yuv420* exports from uint8 CUDA tensors: y (H, W) or (N, H, W) and either uv (.., ceil(H/2),
-    2 ceil(W/2)) (NV12) or u, v (.., ceil(H/2), ceil(W/2)) (I420).  Row views of pitched surfaces are taken as they are: pitch and frame
-    stride come from .stride(), only the last dimension must be dense.  Returns (ctypes arguments up to `matrix`, N, H, W, batched)."""
+def _yuv_planes(who, y, uv, u, v, matrix, sub=0, layout=None, words=False, width=None, fmt=None):
+    """The plane arguments of every lsfa_*yuv* export, up to `matrix`, from CUDA tensors: y (H, W) or (N, H, W) and either uv (.., ch, 2 cw) -
+    one interleaved chroma plane - or u, v (.., ch, cw) - two planes - with ch = ceil(H / 2^sy), cw = ceil(W / 2^sx).  sub (0: 4:2:0,
+    1: 4:2:2, 2: 4:4:4), layout (0: planar, 1 / 2: interleaved U, V / V, U, 3 / 4: packed, y the one plane of four-byte groups and `width`
+    the W where it is odd) and words (16-bit samples, else bytes) are the format's fields (include/lsfa_hip.h); layout None takes it from
+    the planes given, as the 4:2:0 exports do; fmt is what a message calls the format.  Row views of pitched surfaces are taken as they
+    are: pitch and frame stride come from .stride(), only the last dimension must be dense.  Returns (ctypes arguments with pitches in
+    bytes, N, H, W, batched); the caller appends its own trailing argument: nothing, `shift` or `format`."""
     def shapes():
-        return ", ".join("%s %s" % (n, (tuple(t.shape), tuple(t.stride())) if isinstance(t, torch.Tensor) else type(t).__name__)
+        return ", ".join("%s %s" % (n, (tuple(t.shape), tuple(t.stride()), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__)
                          for n, t in (("y", y), ("uv", uv), ("u", u), ("v", v)) if t is not None)
     if matrix not in YUV_MATRICES:
         raise LsfaError("%s: matrix %r is not one of %s" % (who, matrix, sorted(YUV_MATRICES)))
-    nv12 = uv is not None
-    if nv12 == (u is not None or v is not None) or (not nv12 and (u is None or v is None)):
-        raise LsfaError("%s: give either uv (NV12) or u and v (I420); got %s" % (who, shapes()))
-    planes = [y, uv] if nv12 else [y, u, v]
+    if layout is None:
+        if (uv is not None) == (u is not None or v is not None) or (uv is None and (u is None or v is None)):
+            raise LsfaError("%s: give either uv (one interleaved plane: NV12, P010) or u and v (two planes: I420); got %s" % (who, shapes()))
+        layout = 1 if uv is not None else 0
+    packed, semi = layout >= 3, layout in (1, 2)
+    if packed:
+        if uv is not None or u is not None or v is not None:
+            raise LsfaError("%s: a packed frame is the one plane y; got %s" % (who, shapes()))
+        planes = [y]
+    elif semi:
+        if uv is None or u is not None or v is not None:
+            raise LsfaError("%s: format %r has one interleaved chroma plane: give uv and neither u nor v; got %s" % (who, fmt, shapes()))
+        planes = [y, uv]
+    else:
+        if uv is not None or u is None or v is None:
+            raise LsfaError("%s: format %r has two chroma planes: give u and v and no uv; got %s" % (who, fmt, shapes()))
+        planes = [y, u, v]
+    dtypes = (torch.int16, torch.uint16) if words else (torch.uint8,)
     for t in planes:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() not in (2, 3) or t.dim() != y.dim() or \
-                t.device != y.device or (t.shape[-1] > 1 and t.stride(-1) != 1):
-            raise LsfaError("%s: 2-D or 3-D uint8 CUDA planes of one device and rank with a dense last dimension expected, got %s" % (who, shapes()))
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or not t.is_cuda or t.dim() not in (2, 3):
+            raise LsfaError("%s: 2-D or 3-D %s CUDA planes expected, got %s" % (who, " / ".join(str(d) for d in dtypes), shapes()))
+    for t in planes:
+        if t.dim() != y.dim() or t.device != y.device or (t.shape[-1] > 1 and t.stride(-1) != 1):
+            raise LsfaError("%s: planes of one device and rank with a dense last dimension expected, got %s" % (who, shapes()))
     batched = y.dim() == 3
     N = int(y.shape[0]) if batched else 1
-    H, W = int(y.shape[-2]), int(y.shape[-1])
-    ch, cw = -(-H // 2), -(-W // 2)
-    want = (ch, 2 * cw) if nv12 else (ch, cw)
+    H, row = int(y.shape[-2]), int(y.shape[-1])
+    if H < 1 or row < 1 or N < 1:
+        raise LsfaError("%s: empty planes: %s" % (who, shapes()))
+    if packed:
+        if row % 4:
+            raise LsfaError("%s: a packed row is ceil(W / 2) groups of four bytes, got %s" % (who, shapes()))
+        W = row // 2 if width is None else width
+        if isinstance(W, bool) or not isinstance(W, int) or -(-W // 2) != row // 4:
+            raise LsfaError("%s: width %r does not give the %d groups of %s" % (who, width, row // 4, shapes()))
+    else:
+        W = row
+        if width is not None and width != W:
+            raise LsfaError("%s: width %r is not the Y plane's: %s" % (who, width, shapes()))
+    b = 2 if words else 1
+    # a plane of one row (or one frame) has no meaningful stride of its own: the row's (the frame's) size serves
+    y_pitch = int(y.stride(-2)) if H > 1 else max(int(y.stride(-2)), row)
+    y_fs = int(y.stride(0)) if batched and N > 1 else 0
+    if y_pitch < row:
+        raise LsfaError("%s: a row pitch is below its row: %s" % (who, shapes()))
+    if packed:
+        return (_ptr(y), y_pitch, y_fs, None, None, 0, 0, N, H, W, YUV_MATRICES[matrix]), N, H, W, batched
+    ch, cw = -(-H // (2 if sub == 0 else 1)), -(-W // (1 if sub == 2 else 2))
+    want = (ch, 2 * cw) if semi else (ch, cw)
     for t in planes[1:]:
         if tuple(t.shape[-2:]) != want or (batched and int(t.shape[0]) != N):
-            raise LsfaError("%s: a %d x %d frame has %s chroma planes of %s%s, got %s" % (who, W, H, "an NV12" if nv12 else "I420", want,
-                                                                                           " per frame, %d frames" % N if batched else "", shapes()))
-    if H < 1 or W < 1 or N < 1:
-        raise LsfaError("%s: empty planes: %s" % (who, shapes()))
+            raise LsfaError("%s: a %d x %d frame%s has %s chroma planes of %s samples%s, got %s" %
+                            (who, W, H, "" if fmt is None else " of format %r" % (fmt,), "an interleaved" if semi else "two", want,
+                             " per frame, %d frames" % N if batched else "", shapes()))
     c = planes[1]
-    if not nv12 and (u.stride() != v.stride()):
+    if not semi and u.stride() != v.stride():
         raise LsfaError("%s: u and v must share one pitch and frame stride, got %s" % (who, shapes()))
-    # a plane of one row (or one frame) has no meaningful stride of its own: the row's (the frame's) size serves
-    y_pitch = int(y.stride(-2)) if H > 1 else max(int(y.stride(-2)), W)
     c_pitch = int(c.stride(-2)) if ch > 1 else max(int(c.stride(-2)), want[1])
-    y_fs = int(y.stride(0)) if batched and N > 1 else 0
     c_fs = int(c.stride(0)) if batched and N > 1 else 0
-    if y_pitch < W or c_pitch < want[1]:
+    if c_pitch < want[1]:
         raise LsfaError("%s: a row pitch is below its row: %s" % (who, shapes()))
-    args = (_ptr(y), y_pitch, y_fs, _ptr(c), _ptr(None if nv12 else v), c_pitch, c_fs, N, H, W, YUV_MATRICES[matrix])
+    args = (_ptr(y), b * y_pitch, b * y_fs, _ptr(c), _ptr(None if semi else v), b * c_pitch, b * c_fs, N, H, W, YUV_MATRICES[matrix])
     return args, N, H, W, batched
 
 
-def _yuv_out(who, name, t, shape, dtype, device):
-    return _tensor(who, name, t, dtype, shape, device)
+def _yuv_out(who, out, shape, dtype, device, name="out"):
+    """the output of an intake wrapper: a new tensor, or the caller's once it is the contiguous `dtype` tensor of `shape` on the planes' device"""
+    return torch.empty(shape, dtype=dtype, device=device) if out is None else _tensor(who, name, out, dtype, shape, device)
+
+
+def _yuv_bgr_out(who, N, H, W, batched, device, out, y_packed):
+    """-> out (H, W, 3) / (N, H, W, 3) uint8; y_packed, where given, is checked as the (.., H, W) uint8 plane"""
+    lead = (N,) if batched else ()
+    if y_packed is not None:
+        _tensor(who, "y_packed", y_packed, torch.uint8, lead + (H, W), device)
+    return _yuv_out(who, out, lead + (H, W, 3), torch.uint8, device)
+
+
+def _yuv_resized_out(who, N, H, W, im_scale, stride, device, out):
+    """-> (stride, h1, w1, ph, pw, out (N, 3, ph, pw) float32) of a resize form: _resized's sizes once im_scale and stride are in range"""
+    if not float(im_scale) > 0.0 or int(stride) < 0:
+        raise LsfaError("%s: im_scale %r must be positive and stride %r non-negative" % (who, im_scale, stride))
+    stride = int(stride)
+    h1, w1, ph, pw = _resized(H, W, im_scale, stride)
+    return stride, h1, w1, ph, pw, _yuv_out(who, out, (N, 3, ph, pw), torch.float32, device)
 
 
 @_on_tensor_device
@@ -983,13 +1037,7 @@ def yuv420_to_bgr_u8(y, uv=None, u=None, v=None, matrix='bt601', out=None, y_pac
     receives the Y plane with the pitch removed (what mv_estimate wants).  One launch."""
     who = "yuv420_to_bgr_u8"
     args, N, H, W, batched = _yuv_planes(who, y, uv, u, v, matrix)
-    lead = (N,) if batched else ()
-    if out is None:
-        out = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=y.device)
-    else:
-        _yuv_out(who, "out", out, lead + (H, W, 3), torch.uint8, y.device)
-    if y_packed is not None:
-        _yuv_out(who, "y_packed", y_packed, lead + (H, W), torch.uint8, y.device)
+    out = _yuv_bgr_out(who, N, H, W, batched, y.device, out, y_packed)
     _check(lib().lsfa_yuv420_to_bgr_u8(*(args + (_ptr(out), _ptr(y_packed), _stream()))), "lsfa_yuv420_to_bgr_u8")
     return out
 
@@ -1001,10 +1049,7 @@ def image_transform_yuv420(y, uv=None, u=None, v=None, matrix='bt601', pixel_mea
     without its H*W % 4 condition.  pixel_means in B, G, R order.  One launch."""
     who = "image_transform_yuv420"
     args, N, H, W, _ = _yuv_planes(who, y, uv, u, v, matrix)
-    if out is None:
-        out = torch.empty((N, 3, H, W), dtype=torch.float32, device=y.device)
-    else:
-        _yuv_out(who, "out", out, (N, 3, H, W), torch.float32, y.device)
+    out = _yuv_out(who, out, (N, 3, H, W), torch.float32, y.device)
     _check(lib().lsfa_image_transform_yuv420(*(args + (_means(pixel_means), float(pixel_scale), _ptr(out), _stream()))),
            "lsfa_image_transform_yuv420")
     return out
@@ -1018,14 +1063,7 @@ def image_resize_transform_yuv420(y, uv=None, u=None, v=None, im_scale=1.0, matr
     planes.  One launch.  The fixed-point uint8 form (u8_fixed_point) is not offered for YUV."""
     who = "image_resize_transform_yuv420"
     args, N, H, W, _ = _yuv_planes(who, y, uv, u, v, matrix)
-    if not float(im_scale) > 0.0 or int(stride) < 0:
-        raise LsfaError("%s: im_scale %r must be positive and stride %r non-negative" % (who, im_scale, stride))
-    stride = int(stride)
-    h1, w1, ph, pw = _resized(H, W, im_scale, stride)
-    if out is None:
-        out = torch.empty((N, 3, ph, pw), dtype=torch.float32, device=y.device)
-    else:
-        _yuv_out(who, "out", out, (N, 3, ph, pw), torch.float32, y.device)
+    stride, h1, w1, ph, pw, out = _yuv_resized_out(who, N, H, W, im_scale, stride, y.device, out)
     _check(lib().lsfa_image_resize_transform_yuv420(*(args + (float(im_scale), h1, w1, stride, _means(pixel_means), float(pixel_scale), _ptr(out),
                                                                ph, pw, _stream()))),
            "lsfa_image_resize_transform_yuv420")

@@ -1,5 +1,5 @@
 """10-bit YUV 4:2:0 intake on torch tensors: the ctypes wrappers of lsfa_yuv420p10_to_bgr_u8, lsfa_image_transform_yuv420p10 and
-lsfa_image_resize_transform_yuv420p10 (lsfa_amd/csrc/yuv10.hip; include/lsfa_hip.h, "10-bit YUV 4:2:0 intake") and the two motion
+lsfa_image_resize_transform_yuv420p10 (lsfa_amd/csrc/yuvfmt.hip; include/lsfa_hip.h, "10-bit YUV 4:2:0 intake") and the two motion
 estimators on such planes.  Built on lsfa_amd/hip.py's binding and checkers and under its rule: every tensor is validated before its pointer
 is taken, and there is no fallback - a missing library or a refused call is an LsfaError.
 
@@ -10,54 +10,15 @@ Row views of pitched surfaces (`y[:, :W]`) are taken as they are: pitch and fram
 import torch
 
 from lsfa_amd import hip
-from lsfa_amd.hip import LsfaError, YUV_MATRICES, _check, _means, _ptr, _resized, _tensor
-
-_WORDS = (torch.int16, torch.uint16)
+from lsfa_amd.hip import LsfaError, _check, _means, _ptr
 
 
 def _planes(who, y, uv, u, v, matrix, msb_aligned):
-    """The plane arguments of the lsfa_*yuv420p10* exports, up to `shift` -> (ctypes arguments, N, H, W, batched); hip._yuv_planes for words"""
-    def shapes():
-        return ", ".join("%s %s" % (n, (tuple(t.shape), tuple(t.stride()), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__)
-                         for n, t in (("y", y), ("uv", uv), ("u", u), ("v", v)) if t is not None)
-    if matrix not in YUV_MATRICES:
-        raise LsfaError("%s: matrix %r is not one of %s" % (who, matrix, sorted(YUV_MATRICES)))
+    """The plane arguments of the lsfa_*yuv420p10* exports: hip._yuv_planes on 16-bit words, then `shift`"""
     if not isinstance(msb_aligned, bool):
         raise LsfaError("%s: msb_aligned must be True (P010: the sample in the high ten bits) or False (yuv420p10le), got %r" % (who, msb_aligned))
-    semi = uv is not None
-    if semi == (u is not None or v is not None) or (not semi and (u is None or v is None)):
-        raise LsfaError("%s: give either uv (interleaved U, V words) or u and v (two planes); got %s" % (who, shapes()))
-    planes = [y, uv] if semi else [y, u, v]
-    for t in planes:
-        if not isinstance(t, torch.Tensor) or t.dtype not in _WORDS or not t.is_cuda or t.dim() not in (2, 3):
-            raise LsfaError("%s: 2-D or 3-D int16 / uint16 CUDA planes expected, got %s" % (who, shapes()))
-    for t in planes:
-        if t.dim() != y.dim() or t.device != y.device or (t.shape[-1] > 1 and t.stride(-1) != 1):
-            raise LsfaError("%s: planes of one device and rank with a dense last dimension expected, got %s" % (who, shapes()))
-    batched = y.dim() == 3
-    N = int(y.shape[0]) if batched else 1
-    H, W = int(y.shape[-2]), int(y.shape[-1])
-    if H < 1 or W < 1 or N < 1:
-        raise LsfaError("%s: empty planes: %s" % (who, shapes()))
-    ch, cw = -(-H // 2), -(-W // 2)
-    want = (ch, 2 * cw) if semi else (ch, cw)
-    for t in planes[1:]:
-        if tuple(t.shape[-2:]) != want or (batched and int(t.shape[0]) != N):
-            raise LsfaError("%s: a %d x %d frame has %s chroma planes of %s words%s, got %s" %
-                            (who, W, H, "an interleaved" if semi else "two", want, " per frame, %d frames" % N if batched else "", shapes()))
-    c = planes[1]
-    if not semi and u.stride() != v.stride():
-        raise LsfaError("%s: u and v must share one pitch and frame stride, got %s" % (who, shapes()))
-    # in words; a plane of one row (or one frame) has no meaningful stride of its own: the row's (the frame's) size serves
-    y_pitch = int(y.stride(-2)) if H > 1 else max(int(y.stride(-2)), W)
-    c_pitch = int(c.stride(-2)) if ch > 1 else max(int(c.stride(-2)), want[1])
-    y_fs = int(y.stride(0)) if batched and N > 1 else 0
-    c_fs = int(c.stride(0)) if batched and N > 1 else 0
-    if y_pitch < W or c_pitch < want[1]:
-        raise LsfaError("%s: a row pitch is below its row: %s" % (who, shapes()))
-    args = (_ptr(y), 2 * y_pitch, 2 * y_fs, _ptr(c), _ptr(None if semi else v), 2 * c_pitch, 2 * c_fs, N, H, W, YUV_MATRICES[matrix],
-            6 if msb_aligned else 0)
-    return args, N, H, W, batched
+    args, N, H, W, batched = hip._yuv_planes(who, y, uv, u, v, matrix, words=True)
+    return args + (6 if msb_aligned else 0,), N, H, W, batched
 
 
 @hip._on_tensor_device
@@ -68,13 +29,7 @@ def yuv420p10_to_bgr_u8(y, uv=None, u=None, v=None, matrix='bt601', msb_aligned=
     uint8 tensor that receives the luma reduced to 8 bits, min(255, (Y + 2) >> 2): what mv_estimate searches.  One launch."""
     who = "yuv420p10_to_bgr_u8"
     args, N, H, W, batched = _planes(who, y, uv, u, v, matrix, msb_aligned)
-    lead = (N,) if batched else ()
-    if out is None:
-        out = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=y.device)
-    else:
-        _tensor(who, "out", out, torch.uint8, lead + (H, W, 3), y.device)
-    if y_packed is not None:
-        _tensor(who, "y_packed", y_packed, torch.uint8, lead + (H, W), y.device)
+    out = hip._yuv_bgr_out(who, N, H, W, batched, y.device, out, y_packed)
     _check(hip.lib().lsfa_yuv420p10_to_bgr_u8(*(args + (_ptr(out), _ptr(y_packed), hip._stream()))), "lsfa_yuv420p10_to_bgr_u8")
     return out
 
@@ -85,10 +40,7 @@ def image_transform_yuv420p10(y, uv=None, u=None, v=None, matrix='bt601', msb_al
     hip.image_transform_u8(yuv420p10_to_bgr_u8(...)) without storing the BGR frame, and without its H*W % 4 condition.  One launch."""
     who = "image_transform_yuv420p10"
     args, N, H, W, _ = _planes(who, y, uv, u, v, matrix, msb_aligned)
-    if out is None:
-        out = torch.empty((N, 3, H, W), dtype=torch.float32, device=y.device)
-    else:
-        _tensor(who, "out", out, torch.float32, (N, 3, H, W), y.device)
+    out = hip._yuv_out(who, out, (N, 3, H, W), torch.float32, y.device)
     _check(hip.lib().lsfa_image_transform_yuv420p10(*(args + (_means(pixel_means), float(pixel_scale), _ptr(out), hip._stream()))),
            "lsfa_image_transform_yuv420p10")
     return out
@@ -101,14 +53,7 @@ def image_resize_transform_yuv420p10(y, uv=None, u=None, v=None, im_scale=1.0, m
     the converted uint8 frame, bit-identical to it, reading the taps from the planes.  One launch."""
     who = "image_resize_transform_yuv420p10"
     args, N, H, W, _ = _planes(who, y, uv, u, v, matrix, msb_aligned)
-    if not float(im_scale) > 0.0 or int(stride) < 0:
-        raise LsfaError("%s: im_scale %r must be positive and stride %r non-negative" % (who, im_scale, stride))
-    stride = int(stride)
-    h1, w1, ph, pw = _resized(H, W, im_scale, stride)
-    if out is None:
-        out = torch.empty((N, 3, ph, pw), dtype=torch.float32, device=y.device)
-    else:
-        _tensor(who, "out", out, torch.float32, (N, 3, ph, pw), y.device)
+    stride, h1, w1, ph, pw, out = hip._yuv_resized_out(who, N, H, W, im_scale, stride, y.device, out)
     _check(hip.lib().lsfa_image_resize_transform_yuv420p10(*(args + (float(im_scale), h1, w1, stride, _means(pixel_means), float(pixel_scale),
                                                                      _ptr(out), ph, pw, hip._stream()))),
            "lsfa_image_resize_transform_yuv420p10")

@@ -12,7 +12,7 @@ taken as they are: pitch and frame stride come from .stride()."""
 import torch
 
 from lsfa_amd import hip
-from lsfa_amd.hip import LsfaError, YUV_MATRICES, _check, _means, _ptr, _resized, _tensor
+from lsfa_amd.hip import LsfaError, _check, _means, _ptr
 
 SUB_420, SUB_422, SUB_444 = 0, 1, 2
 PLANAR, UV, VU, YUYV, UYVY = 0, 1, 2, 3, 4
@@ -65,74 +65,13 @@ def frame_bytes(fmt, width, height):
 
 
 def _planes(who, fmt, y, uv, u, v, matrix, width):
-    """The plane arguments of the lsfa_*_yuv exports, up to `format` -> (ctypes arguments, N, H, W, batched)"""
-    def shapes():
-        return ", ".join("%s %s" % (n, (tuple(t.shape), tuple(t.stride()), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__)
-                         for n, t in (("y", y), ("uv", uv), ("u", u), ("v", v)) if t is not None)
+    """The plane arguments of the lsfa_*_yuv exports: hip._yuv_planes at the format's fields, then `format`"""
     try:
         c, sub, layout, sample = fields(fmt)
     except LsfaError as e:
         raise LsfaError("%s: %s" % (who, e))
-    if matrix not in YUV_MATRICES:
-        raise LsfaError("%s: matrix %r is not one of %s" % (who, matrix, sorted(YUV_MATRICES)))
-    packed, semi = layout >= YUYV, layout in (UV, VU)
-    if packed:
-        if uv is not None or u is not None or v is not None:
-            raise LsfaError("%s: a packed frame is the one plane y; got %s" % (who, shapes()))
-        planes = [y]
-    elif semi:
-        if uv is None or u is not None or v is not None:
-            raise LsfaError("%s: format %r has one interleaved chroma plane: give uv and neither u nor v; got %s" % (who, fmt, shapes()))
-        planes = [y, uv]
-    else:
-        if uv is not None or u is None or v is None:
-            raise LsfaError("%s: format %r has two chroma planes: give u and v and no uv; got %s" % (who, fmt, shapes()))
-        planes = [y, u, v]
-    dtypes = (torch.uint8,) if sample == U8 else (torch.int16, torch.uint16)
-    for t in planes:
-        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or not t.is_cuda or t.dim() not in (2, 3):
-            raise LsfaError("%s: 2-D or 3-D %s CUDA planes expected for format %r, got %s" % (who, " / ".join(str(d) for d in dtypes), fmt, shapes()))
-    for t in planes:
-        if t.dim() != y.dim() or t.device != y.device or (t.shape[-1] > 1 and t.stride(-1) != 1):
-            raise LsfaError("%s: planes of one device and rank with a dense last dimension expected, got %s" % (who, shapes()))
-    batched = y.dim() == 3
-    N = int(y.shape[0]) if batched else 1
-    H, row = int(y.shape[-2]), int(y.shape[-1])
-    if H < 1 or row < 1 or N < 1:
-        raise LsfaError("%s: empty planes: %s" % (who, shapes()))
-    if packed:
-        if row % 4:
-            raise LsfaError("%s: a packed row is ceil(W / 2) groups of four bytes, got %s" % (who, shapes()))
-        W = row // 2 if width is None else width
-        if isinstance(W, bool) or not isinstance(W, int) or -(-W // 2) != row // 4:
-            raise LsfaError("%s: width %r does not give the %d groups of %s" % (who, width, row // 4, shapes()))
-    else:
-        W = row
-        if width is not None and width != W:
-            raise LsfaError("%s: width %r is not the Y plane's: %s" % (who, width, shapes()))
-    b = 1 if sample == U8 else 2
-    y_pitch = int(y.stride(-2)) if H > 1 else max(int(y.stride(-2)), row)
-    y_fs = int(y.stride(0)) if batched and N > 1 else 0
-    if y_pitch < row:
-        raise LsfaError("%s: a row pitch is below its row: %s" % (who, shapes()))
-    if packed:
-        return (_ptr(y), y_pitch, y_fs, None, None, 0, 0, N, H, W, YUV_MATRICES[matrix], c), N, H, W, batched
-    ch, cw = chroma_shape(c, H, W)
-    want = (ch, 2 * cw) if semi else (ch, cw)
-    for t in planes[1:]:
-        if tuple(t.shape[-2:]) != want or (batched and int(t.shape[0]) != N):
-            raise LsfaError("%s: a %d x %d frame of format %r has %s chroma planes of %s samples%s, got %s" %
-                            (who, W, H, fmt, "an interleaved" if semi else "two", want, " per frame, %d frames" % N if batched else "", shapes()))
-    cp = planes[1]
-    if not semi and u.stride() != v.stride():
-        raise LsfaError("%s: u and v must share one pitch and frame stride, got %s" % (who, shapes()))
-    # a plane of one row (or one frame) has no meaningful stride of its own: the row's (the frame's) size serves
-    c_pitch = int(cp.stride(-2)) if ch > 1 else max(int(cp.stride(-2)), want[1])
-    c_fs = int(cp.stride(0)) if batched and N > 1 else 0
-    if c_pitch < want[1]:
-        raise LsfaError("%s: a row pitch is below its row: %s" % (who, shapes()))
-    args = (_ptr(y), b * y_pitch, b * y_fs, _ptr(cp), _ptr(None if semi else v), b * c_pitch, b * c_fs, N, H, W, YUV_MATRICES[matrix], c)
-    return args, N, H, W, batched
+    args, N, H, W, batched = hip._yuv_planes(who, y, uv, u, v, matrix, sub, layout, sample != U8, width, fmt)
+    return args + (c,), N, H, W, batched
 
 
 @hip._on_tensor_device
@@ -143,13 +82,7 @@ def yuv_to_bgr_u8(fmt, y, uv=None, u=None, v=None, matrix='bt601', out=None, y_p
     receives the luma as 8 bits (Y of bytes; min(255, (Y + 2) >> 2) of ten-bit samples): what mv_estimate searches.  One launch."""
     who = "yuv_to_bgr_u8"
     args, N, H, W, batched = _planes(who, fmt, y, uv, u, v, matrix, width)
-    lead = (N,) if batched else ()
-    if out is None:
-        out = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=y.device)
-    else:
-        _tensor(who, "out", out, torch.uint8, lead + (H, W, 3), y.device)
-    if y_packed is not None:
-        _tensor(who, "y_packed", y_packed, torch.uint8, lead + (H, W), y.device)
+    out = hip._yuv_bgr_out(who, N, H, W, batched, y.device, out, y_packed)
     _check(hip.lib().lsfa_yuv_to_bgr_u8(*(args + (_ptr(out), _ptr(y_packed), hip._stream()))), "lsfa_yuv_to_bgr_u8")
     return out
 
@@ -160,10 +93,7 @@ def image_transform_yuv(fmt, y, uv=None, u=None, v=None, matrix='bt601', pixel_m
     hip.image_transform_u8(yuv_to_bgr_u8(...)) without storing the BGR frame, and without its H*W % 4 condition.  One launch."""
     who = "image_transform_yuv"
     args, N, H, W, _ = _planes(who, fmt, y, uv, u, v, matrix, width)
-    if out is None:
-        out = torch.empty((N, 3, H, W), dtype=torch.float32, device=y.device)
-    else:
-        _tensor(who, "out", out, torch.float32, (N, 3, H, W), y.device)
+    out = hip._yuv_out(who, out, (N, 3, H, W), torch.float32, y.device)
     _check(hip.lib().lsfa_image_transform_yuv(*(args + (_means(pixel_means), float(pixel_scale), _ptr(out), hip._stream()))),
            "lsfa_image_transform_yuv")
     return out
@@ -176,14 +106,7 @@ def image_resize_transform_yuv(fmt, y, uv=None, u=None, v=None, im_scale=1.0, ma
     converted uint8 frame, bit-identical to it, reading the taps from the planes.  One launch."""
     who = "image_resize_transform_yuv"
     args, N, H, W, _ = _planes(who, fmt, y, uv, u, v, matrix, width)
-    if not float(im_scale) > 0.0 or int(stride) < 0:
-        raise LsfaError("%s: im_scale %r must be positive and stride %r non-negative" % (who, im_scale, stride))
-    stride = int(stride)
-    h1, w1, ph, pw = _resized(H, W, im_scale, stride)
-    if out is None:
-        out = torch.empty((N, 3, ph, pw), dtype=torch.float32, device=y.device)
-    else:
-        _tensor(who, "out", out, torch.float32, (N, 3, ph, pw), y.device)
+    stride, h1, w1, ph, pw, out = hip._yuv_resized_out(who, N, H, W, im_scale, stride, y.device, out)
     _check(hip.lib().lsfa_image_resize_transform_yuv(*(args + (float(im_scale), h1, w1, stride, _means(pixel_means), float(pixel_scale), _ptr(out),
                                                                ph, pw, hip._stream()))),
            "lsfa_image_resize_transform_yuv")

@@ -1,4 +1,4 @@
-"""lsfa_yuv420p10_to_bgr_u8, lsfa_image_transform_yuv420p10 and lsfa_image_resize_transform_yuv420p10 (lsfa_amd/csrc/yuv10.hip) on the GPU
+"""lsfa_yuv420p10_to_bgr_u8, lsfa_image_transform_yuv420p10 and lsfa_image_resize_transform_yuv420p10 (lsfa_amd/csrc/yuvfmt.hip) on the GPU
 against tests/ref_yuv10.py, against the shipped 8-bit kernels on planes that are 4 x an 8-bit plane and against the packed-BGR entry points
 they fuse, bit for bit (`==` everywhere); yuv10.MotionEstimator10 / SegmentMotionEstimator10 against the 8-bit estimators on the converted
 frames; graph capture; every error path of the C ABI; the demo's 10-bit --yuv input.  tests/test_yuv10_cpu.py pins the reference.

@@ -1,4 +1,4 @@
-"""lsfa_yuv420_to_bgr_u8, lsfa_image_transform_yuv420 and lsfa_image_resize_transform_yuv420 (lsfa_amd/csrc/yuv.hip) on the GPU against
+"""lsfa_yuv420_to_bgr_u8, lsfa_image_transform_yuv420 and lsfa_image_resize_transform_yuv420 (lsfa_amd/csrc/yuvfmt.hip) on the GPU against
 tests/ref_yuv.py and against the packed-BGR entry points they fuse, bit for bit (`==` everywhere); hip.MotionEstimator's *_yuv methods against
 the BGR chain and against ref_me on the Y planes; graph capture; the error paths; the demo's --yuv input.  tests/test_yuv_cpu.py pins the
 reference."""

@@ -325,8 +325,9 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not in this image")
 def test_no_half_register_pack_in_the_format_kernels(tmp_path):
     """v_ashr_pk_u8_i32 writes half of its destination and the back end uses the whole: the four-pixel BGR kernels gave 0xFF in two bytes
-    wherever a blue had clipped to 0 (DESIGN.md "Other chroma formats").  yuvfmt.hip clamps before it shifts so that the instruction is not
-    formed; this looks at what was compiled: the 46 yuvfmt kernels of the library hold none"""
+    wherever a blue had clipped to 0 (DESIGN.md "Other chroma formats").  yuvfmt.hip, the one intake source, clamps before it shifts so that
+    the instruction is not formed; this looks at what was compiled: the 46 yuvfmt kernels are every intake kernel of the library - the
+    4:2:0 exports' own kernels (yuv420_*, yuv420p10_*, resize_transform_yuv420*), which held the instruction, are gone - and hold none"""
     import glob
     import shutil
     import subprocess
@@ -337,13 +338,17 @@ def test_no_half_register_pack_in_the_format_kernels(tmp_path):
     work = tmp_path / "liblsfa_hip.so"
     shutil.copy(lib, work)
     subprocess.run([OBJDUMP, "--offloading", str(work)], check=True, capture_output=True)
-    found, kernels = [], 0
+    found, kernels, old = [], 0, []
     for o in glob.glob(str(work) + ".*gfx950*"):
         asm = subprocess.run([OBJDUMP, "-d", o], check=True, capture_output=True, text=True).stdout
         for body in re.split(r"^[0-9a-f]+ <", asm, flags=re.M)[1:]:
             name = body.split(">:", 1)[0]
-            if "yuvfmt" in name:
+            if "yuv420" in name:
+                old.append(name)
+            if "yuv" in name:          # every intake kernel: they are all yuvfmt's
+                assert "yuvfmt" in name, name
                 kernels += 1
                 found += ["%s: %s" % (name, m) for m in re.findall(r"v_ashr_pk_u8_i32[^\n]*", body)]
+    assert not old, old
     assert kernels == 46, kernels
     assert not found, "%d, e.g. %s" % (len(found), found[0])

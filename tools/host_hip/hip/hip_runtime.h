@@ -1,6 +1,6 @@
 // A stand-in for <hip/hip_runtime.h> that lets a plane kernel's source compile for the HOST with an ordinary C++ compiler: the qualifiers
 // vanish, the built-in indices are thread-local variables, and hipLaunchKernelGGL runs the kernel as nested loops over a grid of up to two
-// dimensions and one-dimensional blocks.  Only what tools/san_yuv10_host.cpp and tools/san_yuvfmt_host.cpp need; vector types keep the device's alignment so that a misaligned wide access is seen by the
+// dimensions and one-dimensional blocks.  Only what tools/san_yuv_host.cpp needs; vector types keep the device's alignment so that a misaligned wide access is seen by the
 // undefined-behaviour sanitiser.  Never part of the library's build.
 #pragma once
 #include <math.h>

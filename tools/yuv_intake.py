@@ -7,10 +7,10 @@ over the rounds, which IS the run-to-run spread to judge a difference by):
                          1.5 B/pixel + lsfa_image_transform_yuv420  and  3 B/pixel (16-bit words) + lsfa_image_transform_yuv420p10
     kernels alone        each intake kernel as a replayed graph of `--iters` launches (no host enqueue between them), with the bytes the
                          algorithm reads and writes over that time: lsfa_image_transform_u8, lsfa_image_transform_yuv420 (NV12, I420),
-                         lsfa_yuv420_to_bgr_u8 (with and without y_packed), lsfa_luma_u8 (what y_packed saves), and the resize forms
-                         lsfa_image_resize_transform (uint8) / lsfa_image_resize_transform_yuv420 at scale 1, stride 16; and the 10-bit legs,
-                         semi-planar (P010) and planar: lsfa_image_transform_yuv420p10, lsfa_yuv420p10_to_bgr_u8 (with and without y_packed)
-                         and lsfa_image_resize_transform_yuv420p10
+                         lsfa_yuv420_to_bgr_u8 (NV12 with and without y_packed, I420), lsfa_luma_u8 (what y_packed saves), and the resize
+                         forms lsfa_image_resize_transform (uint8) / lsfa_image_resize_transform_yuv420 (NV12, I420) at scale 1, stride 16; and
+                         the 10-bit legs, semi-planar (P010) and planar (yuv420p10le): lsfa_image_transform_yuv420p10, lsfa_yuv420p10_to_bgr_u8
+                         (with and without y_packed) and lsfa_image_resize_transform_yuv420p10
 
 The expectations: the NV12 transform kernel is not slower than the u8 one beyond the spread - it writes the same bytes and reads half - and
 neither is the 10-bit transform kernel (either layout), which reads the u8 kernel's 3 B and writes its 12 B per pixel.
@@ -224,22 +224,25 @@ def main():
             'image_transform_yuv420_i420': (lambda: hip.image_transform_yuv420(yi, u=u, v=v, pixel_means=MEANS, pixel_scale=SCALE, out=data), (1.5 + 12) * px * N),
             'yuv420_to_bgr_u8': (lambda: hip.yuv420_to_bgr_u8(y, uv, out=bgr_out), (1.5 + 3) * px * N),
             'yuv420_to_bgr_u8+y_packed': (lambda: hip.yuv420_to_bgr_u8(y, uv, out=bgr_out, y_packed=y_packed), (1.5 + 4) * px * N),
+            'yuv420_to_bgr_u8_i420': (lambda: hip.yuv420_to_bgr_u8(yi, u=u, v=v, out=bgr_out), (1.5 + 3) * px * N),
             'luma_u8(one frame)': (lambda: hip.luma_u8(d_bgr[0], out=luma), (3 + 1) * px),
             'image_resize_transform_u8': (resize_u8, (3 * px + 12 * 608 * 1008) * N),
             'image_resize_transform_yuv420': (lambda: hip.image_resize_transform_yuv420(y, uv, im_scale=1.0, pixel_means=MEANS, pixel_scale=SCALE, stride=16,
                                                                                        out=rdata), (1.5 * px + 12 * 608 * 1008) * N),
+            'image_resize_transform_yuv420_i420': (lambda: hip.image_resize_transform_yuv420(yi, u=u, v=v, im_scale=1.0, pixel_means=MEANS, pixel_scale=SCALE,
+                                                                                            stride=16, out=rdata), (1.5 * px + 12 * 608 * 1008) * N),
             'image_transform_yuv420p10_semi': (lambda: yuv10.image_transform_yuv420p10(y10, uv10, pixel_means=MEANS, pixel_scale=SCALE, out=data),
                                                (3 + 12) * px * N),
-            'image_transform_yuv420p10_planar': (lambda: yuv10.image_transform_yuv420p10(y10p, u=u10, v=v10, pixel_means=MEANS, pixel_scale=SCALE, out=data),
+            'image_transform_yuv420p10_planar': (lambda: yuv10.image_transform_yuv420p10(y10p, u=u10, v=v10, msb_aligned=False, pixel_means=MEANS, pixel_scale=SCALE, out=data),
                                                  (3 + 12) * px * N),
             'yuv420p10_to_bgr_u8_semi': (lambda: yuv10.yuv420p10_to_bgr_u8(y10, uv10, out=bgr_out), (3 + 3) * px * N),
             'yuv420p10_to_bgr_u8_semi+y_packed': (lambda: yuv10.yuv420p10_to_bgr_u8(y10, uv10, out=bgr_out, y_packed=y_packed), (3 + 4) * px * N),
-            'yuv420p10_to_bgr_u8_planar': (lambda: yuv10.yuv420p10_to_bgr_u8(y10p, u=u10, v=v10, out=bgr_out), (3 + 3) * px * N),
-            'yuv420p10_to_bgr_u8_planar+y_packed': (lambda: yuv10.yuv420p10_to_bgr_u8(y10p, u=u10, v=v10, out=bgr_out, y_packed=y_packed), (3 + 4) * px * N),
+            'yuv420p10_to_bgr_u8_planar': (lambda: yuv10.yuv420p10_to_bgr_u8(y10p, u=u10, v=v10, msb_aligned=False, out=bgr_out), (3 + 3) * px * N),
+            'yuv420p10_to_bgr_u8_planar+y_packed': (lambda: yuv10.yuv420p10_to_bgr_u8(y10p, u=u10, v=v10, msb_aligned=False, out=bgr_out, y_packed=y_packed), (3 + 4) * px * N),
             'image_resize_transform_yuv420p10_semi': (lambda: yuv10.image_resize_transform_yuv420p10(y10, uv10, im_scale=1.0, pixel_means=MEANS,
                                                                                                      pixel_scale=SCALE, stride=16, out=rdata),
                                                       (3 * px + 12 * 608 * 1008) * N),
-            'image_resize_transform_yuv420p10_planar': (lambda: yuv10.image_resize_transform_yuv420p10(y10p, u=u10, v=v10, im_scale=1.0, pixel_means=MEANS,
+            'image_resize_transform_yuv420p10_planar': (lambda: yuv10.image_resize_transform_yuv420p10(y10p, u=u10, v=v10, msb_aligned=False, im_scale=1.0, pixel_means=MEANS,
                                                                                                        pixel_scale=SCALE, stride=16, out=rdata),
                                                         (3 * px + 12 * 608 * 1008) * N),
         }
