@@ -191,16 +191,16 @@ int lsfa_aggregate_cosine(const float* a, const float* b, const float* emb_warp,
  * `ws` must hold lsfa_proposal_workspace_bytes(...) bytes.
  * ------------------------------------------------------------------------ */
 size_t lsfa_proposal_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n);
-/* Launch plan (process-wide; results are identical bit for bit): AUTO picks the chip-wide plan (six short
- * kernels spread over the CUs) for count <= 32768 anchors and pre_nms_top_n <= 8192, else the single-workgroup
- * plan (one 16-wave workgroup per image, everything in its CU's LDS).  r6: inside the chip-wide plan AUTO builds the full
- * suppression mask for ONE image (lowest latency) and takes the mask-free box sweep for B >= 2 (a batched pass: one workgroup
- * per image instead of every CU; +2-4 % frames/s in the pipeline).  The workspace size does not depend on it. */
-enum { LSFA_PROPOSAL_PLAN_AUTO = 0, LSFA_PROPOSAL_PLAN_SINGLE_WORKGROUP = 1, LSFA_PROPOSAL_PLAN_CHIP_WIDE = 2,
-       /* the chip-wide plan with a mask-free NMS stage (r3 experiment, same results): only the diagonal tiles of the suppression mask are
-        * built and one 16-wave workgroup decides everything across blocks from the survivors' boxes in LDS.  No dependent trips to
-        * L2, but 64 x (survivors so far) IoU tests per block on ONE CU's four SIMDs: 160 us against 18 + 48 us for mask + sweep on the
-        * benchmark's RPN, so it is not what AUTO picks */
+/* Launch plan (process-wide; results are identical bit for bit).  AUTO picks the chip-wide plan (six short kernels spread over the CUs)
+ * for count <= 32768 anchors and pre_nms_top_n <= 8192, else the single-workgroup plan (one 16-wave workgroup per image, everything in
+ * its CU's LDS).  Inside the chip-wide plan AUTO builds the full suppression mask for ONE image (lowest latency: 18 + 12 us against the
+ * box sweep's 160) and takes the mask-free box sweep for B >= 2, a batched pass of the frame pipeline: one workgroup per image instead
+ * of every CU, +2.2 ... +4.2 % frames/s (profiles/r6/proposal_plan_ab.txt, proposal_plan_ab2.txt).  The workspace size is the same. */
+enum { LSFA_PROPOSAL_PLAN_AUTO = 0, LSFA_PROPOSAL_PLAN_SINGLE_WORKGROUP = 1, LSFA_PROPOSAL_PLAN_CHIP_WIDE = 2 /* full mask for any B */,
+       /* the chip-wide plan with the mask-free NMS stage for any B: what AUTO takes for B >= 2.  Only the diagonal tiles of the suppression
+        * mask are built and one 16-wave workgroup per image decides everything across blocks from the survivors' boxes in LDS.  No
+        * dependent trips to L2, but 64 x (survivors so far) IoU tests per block on ONE CU's four SIMDs: slower alone, cheaper for the
+        * pipeline, whose other streams keep the rest of the chip */
        LSFA_PROPOSAL_PLAN_CHIP_WIDE_BOX_SWEEP = 3,
        /* r6, ABLATION ONLY (tools/lab/tail_ablation.sh, LSFA_LAB_SKIP_TAIL=1): the chip-wide plan WITHOUT its suppression stage - rois and
         * scores are not written.  What the NMS launches cost the frame pipeline is the difference to a normal run; never a product setting. */

@@ -8,7 +8,10 @@
 // Arithmetic is float64 like the numpy reference (fp64 is full rate on CDNA4), following
 // oracle orc_det_postprocess / orc_nms_f64 / orc_bbox_pred_clip operation for operation.
 #include "common.h"
+#include "iou_test.h"
 #include "nms_block.h"
+#include "order_key.h"
+#include "prefix256.h"
 
 using namespace lsfa;
 
@@ -50,33 +53,13 @@ __global__ __launch_bounds__(kThreads) void bbox_pred_clip_kernel(const float* _
 // Phases: threshold + ordered compaction -> rank by (score desc, roi index asc): the m^2 comparisons are
 // split 4 ways per candidate over all 16 waves and summed with LDS atomics -> boxes re-laid in score order
 // -> suppression mask over sorted positions, all 16 waves, WITHOUT the float64 division (exact: see
-// suppresses()) and with the transposed words of the diagonal 64x64 blocks built alongside -> one wave
+// iou_test.h) and with the transposed words of the diagonal 64x64 blocks built alongside -> one wave
 // sweeps the 64-position blocks, each resolved as a ballot fixpoint (a handful of steps) instead of a
 // 64-step scalar loop.
 
 constexpr int kClassThreads = 1024;
 constexpr int kClassWaves = kClassThreads / 64;
 constexpr int kRankSplit = 4;
-
-// numpy keeps `ovr <= thresh` (lib/nms/nms.py:71) with ovr = fl64(inter / uni): the pair suppresses when
-// NOT (ovr <= thresh).  Decided without dividing: v = inter - thresh*uni and d = fma(-thresh, uni, inter)
-// = fl(v) have the same sign; v <= 0 => quotient <= thresh (rounding is monotone); v >= thresh*uni*2^-52
-// => the exact quotient is at least the double after thresh => suppresses; d >= thresh*uni*2^-51
-// implies that.  The sliver in between and non-positive / NaN unions take the division.
-struct NmsTest64 { double thresh, thresh_eps; int fast; };
-
-__device__ __forceinline__ double readlane_f64(double v, int src_lane) {
-  return __longlong_as_double((long long)readlane64((uint64_t)__double_as_longlong(v), src_lane));
-}
-
-__device__ __forceinline__ bool suppresses(double inter, double uni, const NmsTest64& t) {
-  const double d = fma(-t.thresh, uni, inter);
-  const bool pos = d > 0.0, clear = d >= t.thresh_eps * uni;
-  const bool unsure = !t.fast || !(uni > 0.0) || (pos && !clear);
-  bool r = pos && clear;
-  if (__builtin_expect(unsure, 0)) r = !(inter / uni <= t.thresh);
-  return r;
-}
 
 // (second launch bound, minimum waves per SIMD: 4 = one 16-wave workgroup per CU, 72 registers; 8 = two per CU, 63 registers + 8 spilled - an A/B
 //  of tools/lab/build_variant.sh, profiles/r6)
@@ -86,7 +69,7 @@ __device__ __forceinline__ bool suppresses(double inter, double uni, const NmsTe
 __global__ __launch_bounds__(kClassThreads, LSFA_DET_CLASS_MIN_WAVES) void det_class_kernel(
     const float* __restrict__ rois, const float* __restrict__ deltas, const float* __restrict__ probs, int R,
     int ncls, int nreg, int class_agnostic, double im_h, double im_w, double scale, double score_thresh,
-    NmsTest64 nms, double* __restrict__ dets, int* __restrict__ counts, int* __restrict__ keep_idx) {
+    IouTest64 nms, double* __restrict__ dets, int* __restrict__ counts, int* __restrict__ keep_idx) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int j = blockIdx.x;
   const int tid = threadIdx.x;
@@ -108,39 +91,26 @@ __global__ __launch_bounds__(kClassThreads, LSFA_DET_CLASS_MIN_WAVES) void det_c
   int* order = src + R;
   int* rank = order + R;
   int* kept = rank + R;
-  int* misc = kept + R;  // [0] running count, [1..16] wave sums
+  int* misc = kept + R;  // [0] survivors of the sweep, [1..16] wave counts
 
   // 1. threshold + in-order compaction (np.where(scores[:, j] > thresh), tester.py:267)
-  if (tid == 0) misc[0] = 0;
+  //    roi `tid` is this thread's: all R of them in one trip
+  static_assert(kMaxR <= kClassThreads, "det_class_kernel: one roi per thread");
   for (int i = tid; i < R; i += kClassThreads) rank[i] = 0;
-  __syncthreads();
   const int lane = tid & 63, wid = tid >> 6;
-  for (int r0 = 0; r0 < R; r0 += kClassThreads) {
-    const int r = r0 + tid;
-    const double s = r < R ? (double)probs[(size_t)r * ncls + j] : 0.0;
-    const bool flag = r < R && s > score_thresh;
-    const unsigned long long bal = __ballot(flag);
-    if (lane == 0) misc[1 + wid] = __popcll(bal);
-    __syncthreads();
-    int base = misc[0];
-    for (int w = 0; w < wid; ++w) base += misc[1 + w];
-    if (flag) {
-      const int pos = base + __popcll(bal & ((1ULL << lane) - 1ULL));
-      src[pos] = r;
-      score[pos] = s;
-      const int col = class_agnostic ? 1 : j;
-      decode_box(rois + (size_t)r * 5, deltas + ((size_t)r * nreg + col) * 4, im_h, im_w, scale, box + (size_t)pos * 4);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int t = 0;
-      for (int w = 0; w < kClassWaves; ++w) t += misc[1 + w];
-      misc[0] += t;
-    }
-    __syncthreads();
-  }
-  const int m = misc[0];
+  const int r = tid;
+  const double s = r < R ? (double)probs[(size_t)r * ncls + j] : 0.0;
+  const bool flag = r < R && s > score_thresh;
+  int m;
+  const int pos = prefix_block<kClassWaves>(flag, misc + 1, &m);
   if (m == 0) { if (tid == 0) counts[j] = 0; return; }
+  if (flag) {
+    src[pos] = r;
+    score[pos] = s;
+    const int col = class_agnostic ? 1 : j;
+    decode_box(rois + (size_t)r * 5, deltas + ((size_t)r * nreg + col) * 4, im_h, im_w, scale, box + (size_t)pos * 4);
+  }
+  __syncthreads();
 
   // 2. rank: score descending, ties by ascending candidate (= roi) index; candidate i's comparisons are cut
   //    into kRankSplit slices so that m * kRankSplit threads work
@@ -174,13 +144,13 @@ __global__ __launch_bounds__(kClassThreads, LSFA_DET_CLASS_MIN_WAVES) void det_c
   const int nblk = (m + 63) / 64;
   const int ntiles = nblk * (nblk + 1) / 2;
   for (int t = __builtin_amdgcn_readfirstlane(wid); t < ntiles; t += kClassWaves) {
-    int cb = 0;
+    int cb = 0;                                       // nms_tile_decode's enumeration by a plain search: at most 8 column blocks
     while ((cb + 1) * (cb + 2) / 2 <= t) ++cb;
     const int rb = t - cb * (cb + 1) / 2;
     const int a = rb * 64 + lane;
     const bool a_ok = a < m;
     const int ar = a_ok ? a : 0;
-    const double ax1 = sbox[ar * 4], ay1 = sbox[ar * 4 + 1], ax2 = sbox[ar * 4 + 2], ay2 = sbox[ar * 4 + 3];
+    const Box64 abox = {sbox[ar * 4], sbox[ar * 4 + 1], sbox[ar * 4 + 2], sbox[ar * 4 + 3]};
     const double area_a = sarea[ar];
     const int c0 = cb * 64, ncol = min(64, m - c0);
     const bool diag = rb == cb;
@@ -190,23 +160,21 @@ __global__ __launch_bounds__(kClassThreads, LSFA_DET_CLASS_MIN_WAVES) void det_c
     uint64_t bits = 0, tbits = 0;
     bool unsure = !nms.fast;
     for (int c4 = 0; c4 < ncol; c4 += 4) {
-      double bx1[4], by1[4], bx2[4], by2[4], bar[4];
+      Box64 cbox[4];
+      double bar[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int q = min(c0 + c4 + u, m - 1);
-        bx1[u] = sbox[q * 4]; by1[u] = sbox[q * 4 + 1]; bx2[u] = sbox[q * 4 + 2]; by2[u] = sbox[q * 4 + 3];
+        cbox[u] = {sbox[q * 4], sbox[q * 4 + 1], sbox[q * 4 + 2], sbox[q * 4 + 3]};
         bar[u] = sarea[q];
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int c = c4 + u;
-        const double ww = fmax(0.0, fmin(ax2, bx2[u]) - fmax(ax1, bx1[u]) + 1), hh = fmax(0.0, fmin(ay2, by2[u]) - fmax(ay1, by1[u]) + 1);
-        const double inter = ww * hh;
-        const double uni = area_a + bar[u] - inter;
-        const double d = fma(-nms.thresh, uni, inter);
-        const bool pos = d > 0.0, clear = d >= nms.thresh_eps * uni;
-        unsure = unsure || ((!(uni > 0.0) || (pos && !clear)) && c < ncol);
-        const bool p = pos && clear && a_ok && c < ncol && (!diag || c > lane);
+        bool unsure_c = false;
+        const bool over = iou_exceeds_fast(abox, area_a, cbox[u], bar[u], nms, unsure_c);
+        unsure = unsure || (unsure_c && c < ncol);
+        const bool p = over && a_ok && c < ncol && (!diag || c > lane);
         bits |= (uint64_t)p << c;
         if (diag) {
           const uint64_t cw = __ballot(p);
@@ -218,9 +186,8 @@ __global__ __launch_bounds__(kClassThreads, LSFA_DET_CLASS_MIN_WAVES) void det_c
       bits = 0; tbits = 0;
       for (int c = 0; c < ncol; ++c) {
         const double* q = sbox + (size_t)(c0 + c) * 4;
-        const double ww = fmax(0.0, fmin(ax2, q[2]) - fmax(ax1, q[0]) + 1), hh = fmax(0.0, fmin(ay2, q[3]) - fmax(ay1, q[1]) + 1);
-        const double inter = ww * hh;
-        const bool p = !(inter / (area_a + sarea[c0 + c] - inter) <= nms.thresh) && a_ok && (!diag || c > lane);
+        const Box64 cbox = {q[0], q[1], q[2], q[3]};
+        const bool p = iou_exceeds_div(abox, area_a, cbox, sarea[c0 + c], nms) && a_ok && (!diag || c > lane);
         bits |= (uint64_t)p << c;
         if (diag) {
           const uint64_t cw = __ballot(p);
@@ -248,7 +215,7 @@ __global__ __launch_bounds__(kClassThreads, LSFA_DET_CLASS_MIN_WAVES) void det_c
       const uint64_t cur = readlane64(remv, b);
       const bool alive = lane < nb && !((cur >> lane) & 1ULL);
       const uint64_t G = resolve_block(__ballot(alive), alive, cw, rowd, 64);
-      if ((G >> lane) & 1ULL) kept[nk + __popcll(G & ((1ULL << lane) - 1ULL))] = order[base + lane];
+      if ((G >> lane) & 1ULL) kept[nk + lane_rank(G, lane)] = order[base + lane];
       nk += __popcll(G);
       uint64_t rem = G;
       while (rem) {
@@ -279,12 +246,6 @@ __global__ __launch_bounds__(kClassThreads, LSFA_DET_CLASS_MIN_WAVES) void det_c
   }
 }
 
-__device__ __forceinline__ uint32_t desc_key(float score) {
-  const uint32_t u = __float_as_uint(score + 0.0f);
-  const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
-}
-
 // max_per_image cap (tester.py:274-281).  The scores are float32 probabilities widened to float64, so a
 // select on the 32-bit order keys of their float image is exact.  Single workgroup; the keys of all survivors are
 // staged in LDS once (ncls*R <= 16K keys).  image_thresh = the max_per_image-th best key, found in one pass:
@@ -292,22 +253,13 @@ __device__ __forceinline__ uint32_t desc_key(float score) {
 // in, then the exact order inside that bin by pairwise counting among its (few) members.  A bin holding more
 // than kCapListMax keys (thousands of equal scores) falls back to an 8-bit radix select over the staged keys.
 constexpr int kCapMaxKeys = 16384;
-constexpr int kCapBins = 4096;
 constexpr int kCapListMax = 1024;
-
-// monotone 12-bit image of a descending order key: larger score -> larger bin; 128 bins per octave over [2^-32, 1)
-__device__ __forceinline__ int cap_bin(uint32_t key) {
-  const uint32_t asc = ~key;
-  if (!(asc & 0x80000000u)) return 0;
-  const int b = (int)((asc & 0x7fffffffu) >> 16) - ((127 - 32) << 7);
-  return b < 0 ? 0 : (b > kCapBins - 1 ? kCapBins - 1 : b);
-}
 
 __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets, int* __restrict__ counts,
                                                        int* __restrict__ keep_idx, int R, int ncls,
                                                        int max_per_image) {
   __shared__ uint32_t keys[kCapMaxKeys];
-  __shared__ uint32_t hist[kCapBins];
+  __shared__ uint32_t hist[kKeyBins];
   __shared__ uint32_t list[kCapListMax];
   __shared__ int misc[40];
   const int tid = threadIdx.x;
@@ -320,7 +272,7 @@ __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets
     misc[0] = t;
     misc[3] = 0;      // members of the threshold bin collected so far
   }
-  for (int i = tid; i < kCapBins; i += 1024) hist[i] = 0;
+  for (int i = tid; i < kKeyBins; i += 1024) hist[i] = 0;
   __syncthreads();
   const int total = misc[0];
   if (total <= max_per_image) return;
@@ -331,7 +283,7 @@ __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets
     for (int k = lane; k < cj; k += 64) {
       const uint32_t key = desc_key((float)dets[((size_t)j * R + k) * 5 + 4]);
       keys[j * R + k] = key;
-      atomicAdd(&hist[cap_bin(key)], 1u);
+      atomicAdd(&hist[key_bin(key)], 1u);
     }
   }
   __syncthreads();
@@ -340,13 +292,8 @@ __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets
     uint32_t c[4];
     int mine = 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { c[k] = hist[kCapBins - 1 - (4 * tid + k)]; mine += (int)c[k]; }
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += o;
-    }
+    for (int k = 0; k < 4; ++k) { c[k] = hist[kKeyBins - 1 - (4 * tid + k)]; mine += (int)c[k]; }
+    const int incl = wave_inclusive_scan(mine);
     if (lane == 63) misc[8 + wid] = incl;
     __syncthreads();
     int above = incl - mine;
@@ -354,7 +301,7 @@ __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (above < max_per_image && above + (int)c[k] >= max_per_image) {
-        misc[1] = kCapBins - 1 - (4 * tid + k);       // the threshold bin
+        misc[1] = kKeyBins - 1 - (4 * tid + k);       // the threshold bin
         misc[2] = max_per_image - above;              // image_thresh is its misc[2]-th best member (1-based)
         misc[4] = (int)c[k];
       }
@@ -369,7 +316,7 @@ __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets
       const int cj = counts[j];
       for (int k = lane; k < cj; k += 64) {
         const uint32_t key = keys[j * R + k];
-        if (cap_bin(key) == tbin) list[atomicAdd(&misc[3], 1)] = key;
+        if (key_bin(key) == tbin) list[atomicAdd(&misc[3], 1)] = key;
       }
     }
     __syncthreads();
@@ -391,6 +338,7 @@ __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets
       if (!(j >= 1 && k < counts[j])) keys[i] = 0xFFFFFFFFu;
     }
     __syncthreads();
+    // the 8-bit radix select of proposal_select_nms_kernel (proposal.hip) over 4 replicas; written out here too, see there
     uint32_t* rhist = list;       // 1024 words = 4 x 256 replicated radix histograms
     uint32_t prefix = 0;
     int remaining = max_per_image;
@@ -407,12 +355,7 @@ __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets
       int c = 0, incl = 0;
       if (tid < 256) {
         c = (int)(rhist[tid] + rhist[256 + tid] + rhist[512 + tid] + rhist[768 + tid]);
-        incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-          const int o = __shfl_up(incl, d, 64);
-          if (lane >= d) incl += o;
-        }
+        incl = wave_inclusive_scan(c);
         if (lane == 63) misc[8 + wid] = incl;
       }
       __syncthreads();
@@ -444,7 +387,7 @@ __global__ __launch_bounds__(1024) void det_cap_kernel(double* __restrict__ dets
       }
       const unsigned long long bal = __ballot(flag);
       if (flag) {
-        const int pos = m + __popcll(bal & ((1ULL << lane) - 1ULL));
+        const int pos = m + lane_rank(bal, lane);
         double* dst = dets + ((size_t)j * R + pos) * 5;
         dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3]; dst[4] = v[4];
         if (keep_idx) keep_idx[(size_t)j * R + pos] = ki;
@@ -508,12 +451,8 @@ extern "C" int lsfa_det_postprocess_batch(const float* rois, const float* deltas
     (void)hipFuncSetAttribute((const void*)det_class_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   });
   ProfScope prof(LSFA_OP_DET, s);
-  NmsTest64 nms;
-  nms.thresh = nms_thresh;
-  nms.thresh_eps = nms_thresh * 4.440892098500626e-16;   // 2^-51
-  nms.fast = (nms_thresh > 1e-300 && nms_thresh < 1e300) ? 1 : 0;
   hipLaunchKernelGGL(det_class_kernel, dim3(ncls, B), dim3(kClassThreads), lds, s, rois, deltas, probs, R, ncls, nreg,
-                     class_agnostic, im_h, im_w, scale, score_thresh, nms, dets, counts, keep_idx);
+                     class_agnostic, im_h, im_w, scale, score_thresh, make_iou_test64(nms_thresh), dets, counts, keep_idx);
   if (max_per_image > 0)
     hipLaunchKernelGGL(det_cap_kernel, dim3(B), dim3(1024), 0, s, dets, counts, keep_idx, R, ncls, max_per_image);
   LSFA_LAUNCH_CHECK("lsfa_det_postprocess");

@@ -14,6 +14,9 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int src_lane) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+// how many members of `set` sit in lanes below `lane`: a member's position when the set is written out in lane order
+__device__ __forceinline__ int lane_rank(uint64_t set, int lane) { return __popcll(set & ((1ULL << lane) - 1ULL)); }
+
 // Which candidates of a block survive, given for each lane (= candidate, in score order):
 //   alive  the candidate exists and no survivor of an earlier block suppresses it; cand = __ballot(alive)
 //   colw   bit j set <=> candidate j < lane of this block suppresses this lane   (transposed diagonal word)
@@ -50,8 +53,7 @@ __device__ __forceinline__ uint64_t resolve_block(uint64_t cand, bool alive, uin
   if (__popcll(G) > budget) {      // keep the first `budget` survivors
     const int lane = threadIdx.x & 63;
     const bool mine = (G >> lane) & 1ULL;
-    const int rank = __popcll(G & ((1ULL << lane) - 1ULL));
-    G = __ballot(mine && rank < budget);
+    G = __ballot(mine && lane_rank(G, lane) < budget);
   }
   return G;
 }

@@ -2,7 +2,7 @@
 // reference does 4 cudaMalloc/cudaFree, a thrust sort, a 4.5 MB D2H and a serial host loop per call,
 // multi_proposal.cu:454-557).  Two launch plans, same results bit for bit:
 //
-// CHIP-WIDE plan (count <= 32768 anchors, pre_nms_top_n <= 8192: the LSFA shapes), 5 short kernels:
+// CHIP-WIDE plan (count <= 32768 anchors, pre_nms_top_n <= 8192: the LSFA shapes), six short kernels:
 //   proposal_decode_kernel   anchors + decode + clip + filter (ProposalGrid/BBoxPred/FilterBox,
 //                            multi_proposal.cu:47-216) -> float4 boxes + 32-bit order keys, and per
 //                            workgroup a 4096-bin histogram of the keys (128 bins per octave of score)
@@ -14,9 +14,11 @@
 //                            (:517-521) = start of its bin's group + candidates of its own bin ordered
 //                            before it by (key, anchor index) — a handful of compares — then it writes
 //                            its box and key at that position (rank < pre_n: the exact top pre_n, in order)
-//   nms_mask_kernel + nms_sweep_kernel (nms_kernels.h)  64x64 IoU tiles of the upper triangle over the
-//                            chip, then one wave sweeps, stops at post_n survivors and writes the
+//   nms_mask_kernel + nms_sweep_kernel (nms_kernels.h)  one image: 64x64 IoU tiles of the upper triangle
+//                            over the chip, then one wave sweeps, stops at post_n survivors and writes the
 //                            output with the cyclic pad (PrepareOutput, :363-388)
+//   nms_mask_kernel (diagonal tiles) + nms_sweep_iou_kernel (below)  two or more images: one workgroup per
+//                            image decides everything across 64-box blocks from the survivors' boxes
 // SINGLE-WORKGROUP plan (anything larger): proposal_select_nms_kernel, one 16-wave workgroup per
 //   image with everything in its CU's LDS: radix select, stable LSD radix (or bitonic) sort, greedy
 //   NMS with IoUs on the fly against the survivor list.
@@ -25,6 +27,7 @@
 #include <string.h>
 
 #include "nms_kernels.h"
+#include "prefix256.h"
 
 using namespace lsfa;
 
@@ -32,6 +35,7 @@ namespace {
 
 constexpr int kMaxAnchors = 32;
 constexpr int kTopkThreads = 1024;
+constexpr int kTopkWaves = kTopkThreads / 64;
 
 struct Anchors { float v[kMaxAnchors * 4]; };
 
@@ -58,48 +62,22 @@ void generate_anchors(int feature_stride, const float* ratios, int nr, const flo
     }
 }
 
-// ascending-orderable image of a float, complemented: smaller key == larger score
-__device__ __forceinline__ uint32_t desc_key(float score) {
-  score = score + 0.0f;  // -0 -> +0, so that equal scores tie like thrust::greater sees them
-  const uint32_t u = __float_as_uint(score);
-  const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
-}
-__device__ __forceinline__ float key_score(uint32_t key) {
-  const uint32_t asc = ~key;
-  const uint32_t u = (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
-  return __uint_as_float(u);
-}
-
 constexpr int kDecodeThreads = 1024;
-constexpr int kBins = 4096;
-
-// 12-bit monotone image of an order key: 128 bins per octave of score over [2^-32, 1) (7 mantissa
-// bits); everything below (negative scores, the -1 marks) lands in bin 0, everything above in 4095.
-// Monotone in the key, so "key order" never contradicts "bin order"; ties inside a bin are resolved
-// exactly by the rank kernel.
-__device__ __forceinline__ int key_bin(uint32_t key) {
-  const uint32_t asc = ~key;
-  if (!(asc & 0x80000000u)) return 0;                     // negative float
-  const int e7 = (int)((asc & 0x7fffffffu) >> 16);        // exponent + 7 mantissa bits of a positive float
-  const int b = e7 - ((127 - 32) << 7);
-  return b < 0 ? 0 : (b > kBins - 1 ? kBins - 1 : b);
-}
 
 // thread t -> (a, h, w) with w fastest so the five NCHW planes are read coalesced;
 // output position follows the reference's enumeration index = (h*W + w)*A + a.
-// hist_part (images, gridDim.x, kBins) or NULL: histogram of key_bin over THIS workgroup's anchors,
+// hist_part (images, gridDim.x, kKeyBins) or NULL: histogram of key_bin over THIS workgroup's anchors,
 // every bin written (the workspace is not assumed to be zeroed).
 __global__ __launch_bounds__(kDecodeThreads) void proposal_decode_kernel(
     const float* __restrict__ cls_prob, const float* __restrict__ bbox_pred, const float* __restrict__ im_info,
     int A, int H, int W, int feature_stride, int rpn_min_size, Anchors anchors, float4* __restrict__ boxes_all,
     uint32_t* __restrict__ keys_all, uint32_t* __restrict__ hist_part) {
-  __shared__ uint32_t hist[kBins];
+  __shared__ uint32_t hist[kKeyBins];
   const int b = blockIdx.y;
   const int HW = H * W;
   const int t = blockIdx.x * kDecodeThreads + threadIdx.x;
   if (hist_part) {
-    for (int i = threadIdx.x; i < kBins; i += kDecodeThreads) hist[i] = 0;
+    for (int i = threadIdx.x; i < kKeyBins; i += kDecodeThreads) hist[i] = 0;
     __syncthreads();
   }
   if (t < A * HW) {
@@ -151,38 +129,16 @@ __global__ __launch_bounds__(kDecodeThreads) void proposal_decode_kernel(
   }
   if (hist_part) {
     __syncthreads();
-    uint32_t* dst = hist_part + ((size_t)b * gridDim.x + blockIdx.x) * kBins;
-    for (int i = threadIdx.x; i < kBins; i += kDecodeThreads) dst[i] = hist[i];
+    uint32_t* dst = hist_part + ((size_t)b * gridDim.x + blockIdx.x) * kKeyBins;
+    for (int i = threadIdx.x; i < kKeyBins; i += kDecodeThreads) dst[i] = hist[i];
   }
-}
-
-// block-wide exclusive scan of one int per thread (1024 threads = 16 waves)
-__device__ __forceinline__ int block_exclusive_scan(int v, int* wave_sums /*LDS, 16*/, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wave_sums[wid] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int i = 0; i < kTopkThreads / 64; ++i) {
-    const int s = wave_sums[i];
-    if (i < wid) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
 }
 
 // ---- chip-wide plan: compact (grouped by bin) -> rank within the bin + scatter ----------------------
 constexpr int kRankThreads = 256;
 constexpr int kFastMaxCount = 32768;     // anchors per image the chip-wide plan accepts
 
-// info (images, 4) int32: [0] = M, the number of candidates.  bin_start / bin_count (images, kBins): where
+// info (images, 4) int32: [0] = M, the number of candidates.  bin_start / bin_count (images, kKeyBins): where
 // the candidates of a bin sit in the candidate list (bins in DESCENDING order: bin_start[b] = candidates in
 // bins above b) and how many they are — written by workgroup 0, read by the rank kernel.
 // grid (G = decode's gridDim.x, images); block kDecodeThreads.  Every workgroup redoes the small histogram
@@ -192,11 +148,11 @@ __global__ __launch_bounds__(kDecodeThreads) void proposal_compact_kernel(
     uint64_t* __restrict__ cand_all, int* __restrict__ info, int* __restrict__ bin_start, int* __restrict__ bin_count) {
   __shared__ int wave_sums[kDecodeThreads / 64];
   __shared__ int sh[4];
-  __shared__ int slot[kBins];            // next free position of each bin's group, for THIS workgroup's candidates
+  __shared__ int slot[kKeyBins];            // next free position of each bin's group, for THIS workgroup's candidates
   const int img = blockIdx.y, g = blockIdx.x, G = gridDim.x;
   const int tid = threadIdx.x;
   const int N = A * HW;
-  const uint32_t* parts = hist_part + (size_t)img * G * kBins;
+  const uint32_t* parts = hist_part + (size_t)img * G * kKeyBins;
   // this thread's anchor (same chunking as the decode kernel's): its key is needed last, so load it first
   const int t = g * kDecodeThreads + tid;
   uint32_t key = 0, index = 0;
@@ -213,7 +169,7 @@ __global__ __launch_bounds__(kDecodeThreads) void proposal_compact_kernel(
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int q = q0 + u < G ? q0 + u : G - 1;
-      v[u] = *reinterpret_cast<const uint4*>(parts + (size_t)q * kBins + 4 * tid);
+      v[u] = *reinterpret_cast<const uint4*>(parts + (size_t)q * kKeyBins + 4 * tid);
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -226,7 +182,7 @@ __global__ __launch_bounds__(kDecodeThreads) void proposal_compact_kernel(
   }
   const int mine = (int)(c[0] + c[1] + c[2] + c[3]);
   int total;
-  const int below = block_exclusive_scan(mine, wave_sums, &total);     // keys in bins < 4*tid
+  const int below = block_exclusive_scan<kDecodeThreads / 64>(mine, wave_sums, &total);     // keys in bins < 4*tid
   // walk this thread's bins downwards: `above` = keys in bins above the current one.  The bin where the count
   // of keys at or above it first reaches pre_n is the threshold bin (exactly one thread finds it; total >= pre_n)
   int above = total - below - mine;
@@ -234,7 +190,7 @@ __global__ __launch_bounds__(kDecodeThreads) void proposal_compact_kernel(
   for (int k = 3; k >= 0; --k) {
     const int bin = 4 * tid + k;
     slot[bin] = above + (int)before_me[k];
-    if (g == 0) { bin_start[img * kBins + bin] = above; bin_count[img * kBins + bin] = (int)c[k]; }
+    if (g == 0) { bin_start[img * kKeyBins + bin] = above; bin_count[img * kKeyBins + bin] = (int)c[k]; }
     if (above < pre_n && above + (int)c[k] >= pre_n) { sh[0] = bin; sh[1] = above + (int)c[k]; }
     above += (int)c[k];
   }
@@ -266,7 +222,7 @@ __global__ __launch_bounds__(kRankThreads) void proposal_rank_kernel(
   const uint64_t* cand = cand_all + (size_t)img * N;
   const uint64_t e = cand[i];
   const int bin = key_bin((uint32_t)(e >> 32));
-  const int s0 = bin_start[img * kBins + bin], n = bin_count[img * kBins + bin];
+  const int s0 = bin_start[img * kKeyBins + bin], n = bin_count[img * kKeyBins + bin];
   int before = 0;
   {
     const uint64_t* b = cand + s0;
@@ -358,7 +314,7 @@ constexpr int kHistReplicas = 16;
 constexpr size_t kNmsCoreBytes = 1024 * 16 + 1024 * 4 + 64 * 16 + 64 * 8 + 1024 * 4;   // survivors + step scratch
 constexpr size_t kNmsStateBytes = kNmsCoreBytes + 1024 * 16 + 1024 * 4;                 // + alive candidates of a chunk
 
-// devIoU(a, b) > thresh (multi_proposal.cu:252-260, :295): IouTest / iou_exceeds_fast / iou_exceeds_div of nms_kernels.h
+// devIoU(a, b) > thresh (multi_proposal.cu:252-260, :295): IouTest / iou_exceeds_fast / iou_exceeds_div of iou_test.h
 // one pair (used where the loop is short); wave-uniform branch so the division is really skipped
 __device__ __forceinline__ bool iou_exceeds(const float4& a, float Sa, const float4& b, float Sb, const IouTest& t) {
   bool degenerate = !t.fast;
@@ -387,11 +343,8 @@ __device__ __forceinline__ bool suppressed_by(const float4* kept_box, const floa
 template <bool KEYS_LDS, int kPerThread, bool RADIX, bool ALIVE_BOX>
 __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
     const uint32_t* __restrict__ keys_all, const float4* __restrict__ boxes_all, int N, int K, int Kpad,
-    int sort_bytes, IouTest iou, int post_n, float* __restrict__ rois, float* __restrict__ scores,
-    unsigned long long* __restrict__ stamps /* diagnostic: phase timestamps of workgroup 0, or NULL */) {
-#define LSFA_STAMP(i) do { if (stamps && threadIdx.x == 0 && blockIdx.x == 0) stamps[i] = __builtin_readcyclecounter(); } while (0)
+    int sort_bytes, IouTest iou, int post_n, float* __restrict__ rois, float* __restrict__ scores) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  LSFA_STAMP(0);
   uint64_t* sortbuf = reinterpret_cast<uint64_t*>(smem);
   uint32_t* hist = reinterpret_cast<uint32_t*>(smem);
   int* misc = reinterpret_cast<int*>(smem + (size_t)sort_bytes);
@@ -408,9 +361,11 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
   const uint32_t* keys = KEYS_LDS ? lkeys : gkeys;
 
   __syncthreads();
-  LSFA_STAMP(1);
   // ---- radix select: T = K-th smallest key; r_eq = how many keys == T to take ------------
   // replica = lane & 15 spreads same-bucket increments of one wave instruction over 16 words
+  // (det_cap_kernel's fallback in detpost.hip is the same select over 4 replicas, and keeps the bucket's count and scan in registers
+  // across the barrier where this one parks them in the replicas it has read; one routine for both moves det_cap_kernel, which every
+  // frame runs, so the two stay written out - profiles/r19/detection_tail_refactor.txt)
   uint32_t prefix = 0;
   int remaining = K;
   for (int shift = 24; shift >= 0; shift -= 8) {
@@ -428,12 +383,7 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
 #pragma unroll
       for (int r = 0; r < kHistReplicas; ++r) c += hist[r * 256 + tid];
       // inclusive scan over the 256 buckets: 4 waves, wave scan + carry through misc[8..11]
-      int incl = (int)c;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-      }
+      const int incl = wave_inclusive_scan((int)c);
       if (lane == 63) misc[8 + wid] = incl;
       // thread `tid` is the only reader of column `tid` of the replicas, so it may reuse them:
       hist[tid] = (uint32_t)incl;          // replica 0 now holds the per-wave inclusive scan
@@ -458,18 +408,16 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
   }
   const uint32_t T = prefix;
   const int r_eq = remaining;
-  const int n_less = K - r_eq;
 
-  LSFA_STAMP(2);
   // ---- stable compaction (index order): keys < T, and the first r_eq keys == T -------------
   const int chunk = (N + kTopkThreads - 1) / kTopkThreads;
   const int i0 = min(tid * chunk, N), i1 = min(i0 + chunk, N);
   int my_eq = 0, my_less = 0;
   for (int i = i0; i < i1; ++i) { const uint32_t k = keys[i]; my_eq += (k == T); my_less += (k < T); }
   int total_eq, total_sel;
-  const int eq_rank0 = block_exclusive_scan(my_eq, misc + 8, &total_eq);
+  const int eq_rank0 = block_exclusive_scan<kTopkWaves>(my_eq, misc + 8, &total_eq);
   const int my_sel = my_less + min(max(r_eq - eq_rank0, 0), my_eq);
-  int pos = block_exclusive_scan(my_sel, misc + 8, &total_sel);
+  int pos = block_exclusive_scan<kTopkWaves>(my_sel, misc + 8, &total_sel);
   {
     int er = eq_rank0;
     for (int i = i0; i < i1; ++i) {
@@ -479,10 +427,8 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
       if (sel) sortbuf[pos++] = ((uint64_t)k << 32) | (uint32_t)i;
     }
   }
-  (void)n_less;
   __syncthreads();
 
-  LSFA_STAMP(3);
   // ---- sort by key (ascending == score desc); equal keys keep index order -------------------
   if (RADIX) {
     // LSD radix sort, 4-bit digits, stable: thread t owns the contiguous run [c0, c1) of the K
@@ -525,7 +471,7 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
           run += (int)c;
         }
         int tot;
-        const int base = block_exclusive_scan(run, misc + 8, &tot);
+        const int base = block_exclusive_scan<kTopkWaves>(run, misc + 8, &tot);
 #pragma unroll
         for (int e = 0; e < 8; ++e) w[e] = ((ex[2 * e] + base) & 0xffffu) | ((ex[2 * e + 1] + base) << 16);
         p4[0] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -562,7 +508,6 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
     __syncthreads();
   }
 
-  LSFA_STAMP(4);
   // ---- greedy NMS over the sorted candidates, IoU on the fly against the survivors --------
   // (same decisions as nms_kernel + the host sweep, multi_proposal.cu:262-357).  Candidates are
   // taken 1024 at a time: every thread tests ONE candidate against all survivors so far (no
@@ -581,10 +526,7 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
   if (tid == 0) { misc[3] = 0; supp[0] = 0; supp[1] = 0; }
   __syncthreads();
   int num = 0;
-  int dbg_blocks = 0;
-  unsigned long long dbg_a = 0, dbg_b = 0, dbg_c = 0, dbg_t = 0;
   for (int chunk = 0; chunk < K && num < post_n; chunk += kTopkThreads) {
-    if (stamps) dbg_t = __builtin_readcyclecounter();
     // -- filter: one candidate per thread against the survivors so far
     const int ci = chunk + tid;
     const bool valid = ci < K;
@@ -594,14 +536,11 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
     dead = dead || suppressed_by(kept_box, kept_area, 0, num, 1, mybox, myarea, iou);
     // -- ordered compaction of the alive candidates
     int total_alive;
-    const int apos = block_exclusive_scan(dead ? 0 : 1, misc + 8, &total_alive);
+    const int apos = block_exclusive_scan<kTopkWaves>(dead ? 0 : 1, misc + 8, &total_alive);
     if (!dead) { if (ALIVE_BOX) alive_box[apos] = mybox; alive_idx[apos] = ci; }
     __syncthreads();
-    if (stamps) { const unsigned long long t1 = __builtin_readcyclecounter(); dbg_a += t1 - dbg_t; dbg_t = t1; }
     const int m0 = num;   // survivors the filter already accounted for
     for (int base = 0; base < total_alive && num < post_n; base += 64) {
-      ++dbg_blocks;
-      if (stamps) dbg_t = __builtin_readcyclecounter();
       const int nb = min(64, total_alive - base);
       const float4 cb = lane < nb ? (ALIVE_BOX ? alive_box[base + lane] : boxes[(uint32_t)sortbuf[alive_idx[base + lane]]])
                                   : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -645,7 +584,6 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
         }
       }
       __syncthreads();
-      if (stamps) { const unsigned long long t1 = __builtin_readcyclecounter(); dbg_b += t1 - dbg_t; dbg_t = t1; }
       if (wid == 0) {
         // In-block greedy as a fixpoint: G(k) = alive(k) && no earlier j in G suppresses k.  Starting
         // from G = alive, iteration t fixes the first t decisions, so it converges to the serial
@@ -664,11 +602,10 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
         uint64_t kept = G;
         if (__popcll(G) > budget) {
           const bool mine = (G >> lane) & 1ULL;
-          const int rank = __popcll(G & ((1ULL << lane) - 1ULL));
-          kept = __ballot(mine && rank < budget);
+          kept = __ballot(mine && lane_rank(G, lane) < budget);
         }
         if ((kept >> lane) & 1ULL) {
-          const int pos = num + __popcll(kept & ((1ULL << lane) - 1ULL));
+          const int pos = num + lane_rank(kept, lane);
           kept_box[pos] = cb;
           kept_area[pos] = carea;
           kept_idx[pos] = alive_idx[base + lane];
@@ -676,30 +613,104 @@ __global__ __launch_bounds__(kTopkThreads) void proposal_select_nms_kernel(
         if (lane == 0) { misc[3] = num + __popcll(kept); supp[0] = 0; supp[1] = 0; }
       }
       __syncthreads();
-      if (stamps) { const unsigned long long t1 = __builtin_readcyclecounter(); dbg_c += t1 - dbg_t; dbg_t = t1; }
       num = misc[3];
     }
   }
 
-  LSFA_STAMP(5);
-  if (stamps && tid == 0 && blockIdx.x == 0) { stamps[7] = (unsigned long long)num; stamps[8] = (unsigned long long)dbg_blocks; stamps[9] = dbg_a; stamps[10] = dbg_b; stamps[11] = dbg_c; }
-  // ---- PrepareOutput (multi_proposal.cu:363-388): first post_n survivors, cyclic pad ------
-  for (int index = tid; index < post_n; index += kTopkThreads) {
-    const int kpos = index < num ? index : index % num;
-    const float4 bx = kept_box[kpos];
-    float* o = rois + ((size_t)img * post_n + index) * 5;
-    o[0] = (float)img;
-    o[1] = bx.x; o[2] = bx.y; o[3] = bx.z; o[4] = bx.w;
-    if (scores) scores[(size_t)img * post_n + index] = key_score((uint32_t)(sortbuf[kept_idx[kpos]] >> 32));
-  }
-  LSFA_STAMP(6);
-#undef LSFA_STAMP
+  proposal_write_rows(img, tid, kTopkThreads, post_n, num, rois, scores, [&](int k) { return kept_box[k]; },
+                      [&](int k) { return (uint32_t)(sortbuf[kept_idx[k]] >> 32); });
 }
+
+// ---- the box sweep (LSFA_PROPOSAL_PLAN_CHIP_WIDE_BOX_SWEEP; what AUTO takes for B >= 2): the Proposal's sweep without the suppression mask ----
+// nms_sweep_kernel pays one trip to L2 per pair of 64-box blocks for the mask words of the survivors so far: ~0.55 us a block, 70-90
+// blocks on the benchmark's untrained RPN (every anchor regresses to a large box, 3-5 survivors per block) = 48 us, behind an 18 us
+// mask kernel that fills 4465 tiles of which the sweep reads a sliver.  The Proposal keeps at most post_n <= 1024 boxes, so the
+// survivors' boxes fit in LDS and "is candidate j suppressed by an earlier survivor" can be decided from the boxes themselves: one
+// 16-wave workgroup; for block b every wave tests the block's 64 candidates (lane = candidate) against its share of the survivor
+// list (survivor k goes to wave k % 16; its box is a broadcast LDS read), the 16 partial words are ORed, wave 0 resolves the block
+// with resolve_block (the block's own 64 x 64 IoU bits come from nms_mask_kernel run on the DIAGONAL tiles only: 94 tiles instead
+// of 4465) and appends the survivors' boxes.  Nothing the loop loads from global memory depends on the sweep's state (the next
+// block's boxes and diagonal words are requested a block ahead); a block costs two workgroup barriers and ~num/16 IoU tests per
+// lane.  Decisions are the mask kernel's, bit for bit: the same iou_exceeds_fast / iou_exceeds_div, whose value does not depend
+// on which of the two boxes is called the row.
+// What it costs: a wave64 VALU instruction occupies its SIMD for four cycles and a CU has four SIMDs, so the 64 x (survivors so
+// far) IoU tests of a block - ~12 K wave-tests of ~25 instructions over the call - are 150 us of ONE CU's issue slots: 160 us
+// against mask + sweep's 18 + 48 (r3), which spread the same tests over the chip.  Alone it is the slower plan, and one image keeps
+// the mask.  In a batched pass a kernel costs the share of the chip it takes from the other streams, and there one workgroup per
+// image beats every CU: why and by how much is at the launch in lsfa_proposal (r6, profiles/r6/proposal_plan_ab*.txt).
+constexpr int kSweepIouWaves = 16;
+
+__global__ __launch_bounds__(64 * kSweepIouWaves) void nms_sweep_iou_kernel(
+    const float4* __restrict__ sorted_box_all, const uint32_t* __restrict__ sorted_key_all, const uint64_t* __restrict__ mask_all,
+    const uint64_t* __restrict__ diagT_all, int n, int col_blocks, int max_keep, IouTest t, float* __restrict__ rois,
+    float* __restrict__ scores) {
+  __shared__ float4 kbox[kSweepMaxOut];
+  __shared__ float karea[kSweepMaxOut];
+  __shared__ int kept_pos[kSweepMaxOut];
+  __shared__ uint64_t part[kSweepIouWaves];
+  __shared__ int s_num;
+  const int img = blockIdx.x;
+  const float4* sbox = sorted_box_all + (size_t)img * n;
+  const uint64_t* mask = mask_all + (size_t)img * n * col_blocks;
+  const uint64_t* diagT = diagT_all + (size_t)img * n;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (threadIdx.x == 0) s_num = 0;
+  // block 0's operands
+  float4 c_next = lane < n ? sbox[lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+  uint64_t colw_next = 0, rowd_next = 0;
+  if (wave == 0 && lane < n) { colw_next = diagT[lane]; rowd_next = mask[(size_t)lane * col_blocks]; }
+  __syncthreads();
+  int num = 0;
+  for (int b = 0; b < col_blocks && num < max_keep; ++b) {
+    const float4 c = c_next;
+    const uint64_t colw = colw_next, rowd = rowd_next;
+    const int cand = b * 64 + lane;
+    {   // requests for block b + 1: independent of what this block decides
+      const int nc = cand + 64;
+      c_next = nc < n ? sbox[nc] : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (wave == 0) {
+        colw_next = nc < n ? diagT[nc] : 0ULL;
+        rowd_next = nc < n ? mask[(size_t)nc * col_blocks + b + 1] : 0ULL;
+      }
+    }
+    const float Sc = box_area(c);
+    bool sup = false, unsure = !t.fast;
+    for (int k = wave; k < num; k += kSweepIouWaves) sup = sup || iou_exceeds_fast(kbox[k], karea[k], c, Sc, t, unsure);
+    if (__builtin_expect(__any(unsure), 0)) {     // rare: redo this wave's share with the real division
+      sup = false;
+      for (int k = wave; k < num; k += kSweepIouWaves) sup = sup || iou_exceeds_div(kbox[k], karea[k], c, Sc, t);
+    }
+    const uint64_t w = __ballot(sup);
+    if (lane == 0) part[wave] = w;
+    __syncthreads();
+    if (wave == 0) {
+      uint64_t cur = 0;
+#pragma unroll
+      for (int i = 0; i < kSweepIouWaves; ++i) cur |= part[i];
+      const int nb = min(64, n - b * 64);
+      const bool alive = lane < nb && !((cur >> lane) & 1ULL);
+      const uint64_t kept = resolve_block(__ballot(alive), alive, colw, rowd, max_keep - num);
+      if ((kept >> lane) & 1ULL) {
+        const int pos = num + lane_rank(kept, lane);
+        kbox[pos] = c;
+        karea[pos] = Sc;
+        kept_pos[pos] = cand;
+      }
+      if (lane == 0) s_num = num + __popcll(kept);
+    }
+    __syncthreads();
+    num = s_num;
+  }
+  proposal_write_rows(img, (int)threadIdx.x, 64 * kSweepIouWaves, max_keep, num, rois, scores, [&](int k) { return sbox[kept_pos[k]]; },
+                      [&](int k) { return sorted_key_all[(size_t)img * n + kept_pos[k]]; });
+}
+
 
 struct WsLayout {
   size_t boxes, keys, hist, info, bins, cand, sbox, skey, mask, diagT, total;
   int groups;      // decode workgroups per image
-  bool chip_wide, chip_wide_possible;
+  bool chip_wide;
 };
 int clamp_pre_n(int rpn_pre_nms_top_n, int count) {
   int pre_n = rpn_pre_nms_top_n > 0 ? rpn_pre_nms_top_n : count;  // multi_proposal.cu:435-436
@@ -710,15 +721,14 @@ WsLayout ws_layout(int B, int count, int pre_n, int post_n) {
   size_t o = 0;
   l.groups = ceil_div(count, kDecodeThreads);
   l.chip_wide = count <= kFastMaxCount && pre_n <= 8192 && post_n <= kSweepMaxOut;
-  l.chip_wide_possible = l.chip_wide;
   l.boxes = o; o += align_up((size_t)B * count * sizeof(float4), 256);
   l.keys = o; o += align_up((size_t)B * count * sizeof(uint32_t), 256);
   l.hist = l.info = l.bins = l.cand = l.sbox = l.skey = l.mask = l.diagT = o;
   if (l.chip_wide) {
     const size_t col_blocks = (size_t)ceil_div(pre_n, 64);
-    l.hist = o; o += align_up((size_t)B * l.groups * kBins * sizeof(uint32_t), 256);
+    l.hist = o; o += align_up((size_t)B * l.groups * kKeyBins * sizeof(uint32_t), 256);
     l.info = o; o += align_up((size_t)B * 4 * sizeof(int), 256);
-    l.bins = o; o += align_up((size_t)B * 2 * kBins * sizeof(int), 256);
+    l.bins = o; o += align_up((size_t)B * 2 * kKeyBins * sizeof(int), 256);
     l.cand = o; o += align_up((size_t)B * count * sizeof(uint64_t), 256);
     l.sbox = o; o += align_up((size_t)B * pre_n * sizeof(float4), 256);
     l.skey = o; o += align_up((size_t)B * pre_n * sizeof(uint32_t), 256);
@@ -788,7 +798,7 @@ extern "C" int lsfa_proposal(const float* cls_prob, const float* bbox_pred, cons
     int* info = (int*)(base + l.info);
     uint64_t* cand = (uint64_t*)(base + l.cand);
     int* bin_start = (int*)(base + l.bins);
-    int* bin_count = bin_start + (size_t)B * kBins;
+    int* bin_count = bin_start + (size_t)B * kKeyBins;
     float4* sbox = (float4*)(base + l.sbox);
     uint32_t* skey = (uint32_t*)(base + l.skey);
     uint64_t* mask = (uint64_t*)(base + l.mask);
@@ -848,7 +858,7 @@ extern "C" int lsfa_proposal(const float* cls_prob, const float* bbox_pred, cons
 #define LSFA_LAUNCH_SELECT(KL, PER, RAD, AB, LDS, SORTB)                                                     \
   hipLaunchKernelGGL((proposal_select_nms_kernel<KL, PER, RAD, AB>), dim3(B), dim3(kTopkThreads), (LDS), s,   \
                      (const uint32_t*)keys, (const float4*)boxes, count, pre_n, Kpad, (int)(SORTB), iou, post_n, \
-                     rois, scores, (unsigned long long*)nullptr)
+                     rois, scores)
   // 8193..16384 candidates: 128 KB sort buffer, so the alive list keeps indices only (boxes re-read from L2)
   const size_t lds_bitonic16 = (size_t)Kpad * 8 + 256 + kNmsCoreBytes + 1024 * 4;
   if (pre_n <= 8192 && lds_radix_keys <= kLdsMax) LSFA_LAUNCH_SELECT(true, 8, true, true, lds_radix_keys, sortA);

@@ -519,17 +519,23 @@ LAB_SKIP_DET = LAB_SKIP_TAIL or 'det' in LAB_SKIP
 _lab_filled = set()
 
 
-def nms_sorted(boxes, thresh):
-    """boxes (n, >=4) float32 CUDA, sorted by score descending -> (keep int32 (n,), num_keep int32 (1,)) on device."""
-    boxes = _input("nms_sorted", "boxes", boxes, ("n", "d >= 4"))
+def _nms_operands(who, boxes, dtype):
+    """The operands of nms_sorted and nms_sorted_f64: boxes (n, >=4) of `dtype` -> (boxes, n, d, keep, num_keep, workspace)"""
+    boxes = _input(who, "boxes", boxes, ("n", "d >= 4"), dtype=dtype)
     n, d = boxes.shape
     if d < 4:
-        raise LsfaError("nms_sorted: boxes of %d values" % d)
+        raise LsfaError("%s: boxes of %d values" % (who, d))
     keep = torch.empty(max(n, 1), dtype=torch.int32, device=boxes.device)
     num = torch.zeros(1, dtype=torch.int32, device=boxes.device)
-    need = lib().lsfa_nms_workspace_bytes(n)
-    ws = torch.empty(need, dtype=torch.uint8, device=boxes.device)
-    _check(lib().lsfa_nms_sorted(_ptr(boxes), n, d, thresh, _ptr(keep), _ptr(num), _ptr(ws), need, _stream()), "lsfa_nms_sorted")
+    ws = torch.empty(lib().lsfa_nms_workspace_bytes(n), dtype=torch.uint8, device=boxes.device)
+    return boxes, n, d, keep, num, ws
+
+
+@_on_tensor_device
+def nms_sorted(boxes, thresh):
+    """boxes (n, >=4) float32 CUDA, sorted by score descending -> (keep int32 (n,), num_keep int32 (1,)) on device."""
+    boxes, n, d, keep, num, ws = _nms_operands("nms_sorted", boxes, torch.float32)
+    _check(lib().lsfa_nms_sorted(_ptr(boxes), n, d, thresh, _ptr(keep), _ptr(num), _ptr(ws), ws.numel(), _stream()), "lsfa_nms_sorted")
     return keep, num
 
 
@@ -537,15 +543,8 @@ def nms_sorted(boxes, thresh):
 def nms_sorted_f64(boxes, thresh):
     """boxes (n, >=4) float64 CUDA, sorted by score descending -> (keep, num_keep) like nms_sorted; numpy's
     float64 arithmetic and `ovr <= thresh` keep rule (lib/nms/nms.py:47-72)."""
-    boxes = _input("nms_sorted_f64", "boxes", boxes, ("n", "d >= 4"), dtype=torch.float64)
-    n, d = boxes.shape
-    if d < 4:
-        raise LsfaError("nms_sorted_f64: boxes of %d values" % d)
-    keep = torch.empty(max(n, 1), dtype=torch.int32, device=boxes.device)
-    num = torch.zeros(1, dtype=torch.int32, device=boxes.device)
-    need = lib().lsfa_nms_workspace_bytes(n)
-    ws = torch.empty(need, dtype=torch.uint8, device=boxes.device)
-    _check(lib().lsfa_nms_sorted_f64(_ptr(boxes), n, d, thresh, _ptr(keep), _ptr(num), _ptr(ws), need, _stream()), "lsfa_nms_sorted_f64")
+    boxes, n, d, keep, num, ws = _nms_operands("nms_sorted_f64", boxes, torch.float64)
+    _check(lib().lsfa_nms_sorted_f64(_ptr(boxes), n, d, thresh, _ptr(keep), _ptr(num), _ptr(ws), ws.numel(), _stream()), "lsfa_nms_sorted_f64")
     return keep, num
 
 
@@ -570,24 +569,34 @@ def bbox_pred_clip(rois, deltas, im_h, im_w, scale):
     return out
 
 
+def _det_operands(who, rois, deltas, probs, out, batch, B=1):
+    """The operands of det_postprocess (one image, outputs without the image axis, `out` optional) and det_postprocess_batch (`batch`):
+    rois (B*R, 5), deltas (B*R, 4*nreg), probs (B*R, ncls) -> (rois, deltas, probs, R, ncls, nreg, dets, counts, keep_idx)"""
+    rois = _input(who, "rois", rois, ("B R" if batch else "R", 5))
+    BR, dev = int(rois.shape[0]), rois.device
+    if batch and (int(B) < 1 or BR % int(B)):
+        raise LsfaError("%s: %d rois do not divide into B = %r images" % (who, BR, B))
+    deltas = _input(who, "deltas", deltas, (BR, "4 nreg"), dev)
+    probs = _input(who, "probs", probs, (BR, "ncls"), dev)
+    R, ncls = (BR // B if batch else BR), probs.shape[1]
+    nreg = deltas.shape[1] // 4
+    lead = (B,) if batch else ()
+    if out is None and not batch:
+        dets = torch.zeros((ncls, R, 5), dtype=torch.float64, device=dev)
+        counts = torch.zeros(ncls, dtype=torch.int32, device=dev)
+        keep_idx = torch.full((ncls, R), -1, dtype=torch.int32, device=dev)
+    else:
+        out = _given(who, "out", out, 3)
+        dets = _tensor(who, "output buffer out[0] (dets)", out[0], torch.float64, lead + (ncls, R, 5), dev)
+        counts = _tensor(who, "output buffer out[1] (counts)", out[1], torch.int32, lead + (ncls,), dev)
+        keep_idx = _tensor(who, "output buffer out[2] (keep_idx)", out[2], torch.int32, lead + (ncls, R), dev)
+    return rois, deltas, probs, R, ncls, nreg, dets, counts, keep_idx
+
+
 @_on_tensor_device
 def det_postprocess(rois, deltas, probs, im_h, im_w, scale, score_thresh=1e-4, nms_thresh=0.3, max_per_image=300,
                     class_agnostic=True, out=None):
-    rois = _input("det_postprocess", "rois", rois, ("R", 5))
-    R, dev = rois.shape[0], rois.device
-    deltas = _input("det_postprocess", "deltas", deltas, (R, "4 nreg"), dev)
-    probs = _input("det_postprocess", "probs", probs, (R, "ncls"), dev)
-    ncls = probs.shape[1]
-    nreg = deltas.shape[1] // 4
-    if out is None:
-        dets = torch.zeros((ncls, R, 5), dtype=torch.float64, device=rois.device)
-        counts = torch.zeros(ncls, dtype=torch.int32, device=rois.device)
-        keep_idx = torch.full((ncls, R), -1, dtype=torch.int32, device=rois.device)
-    else:
-        out = _given("det_postprocess", "out", out, 3)
-        dets = _tensor("det_postprocess", "output buffer out[0] (dets)", out[0], torch.float64, (ncls, R, 5), dev)
-        counts = _tensor("det_postprocess", "output buffer out[1] (counts)", out[1], torch.int32, (ncls,), dev)
-        keep_idx = _tensor("det_postprocess", "output buffer out[2] (keep_idx)", out[2], torch.int32, (ncls, R), dev)
+    rois, deltas, probs, R, ncls, nreg, dets, counts, keep_idx = _det_operands("det_postprocess", rois, deltas, probs, out, False)
     if LAB_SKIP_DET:
         return dets, counts, keep_idx
     _check(lib().lsfa_det_postprocess(_ptr(rois), _ptr(deltas), _ptr(probs), R, ncls, nreg, int(class_agnostic), im_h, im_w, scale, score_thresh,
@@ -615,19 +624,7 @@ def det_postprocess_batch(rois, deltas, probs, B, im_h, im_w, scale, out, score_
                           class_agnostic=True):
     """lsfa_det_postprocess_batch: det_postprocess for the B images of a batch in one launch pair.  rois (B*R, 5), deltas (B*R, 4*nreg),
     probs (B*R, ncls), image b's rows [b*R, (b+1)*R); out = (dets (B, ncls, R, 5) f64, counts (B, ncls) i32, keep_idx (B, ncls, R) i32)."""
-    who = "det_postprocess_batch"
-    rois = _input(who, "rois", rois, ("B R", 5))
-    BR, dev = int(rois.shape[0]), rois.device
-    if int(B) < 1 or BR % int(B):
-        raise LsfaError("%s: %d rois do not divide into B = %r images" % (who, BR, B))
-    deltas = _input(who, "deltas", deltas, (BR, "4 nreg"), dev)
-    probs = _input(who, "probs", probs, (BR, "ncls"), dev)
-    R, ncls = BR // B, probs.shape[1]
-    nreg = deltas.shape[1] // 4
-    out = _given(who, "out", out, 3)
-    dets = _tensor(who, "output buffer out[0] (dets)", out[0], torch.float64, (B, ncls, R, 5), dev)
-    counts = _tensor(who, "output buffer out[1] (counts)", out[1], torch.int32, (B, ncls), dev)
-    keep_idx = _tensor(who, "output buffer out[2] (keep_idx)", out[2], torch.int32, (B, ncls, R), dev)
+    rois, deltas, probs, R, ncls, nreg, dets, counts, keep_idx = _det_operands("det_postprocess_batch", rois, deltas, probs, out, True, B)
     if LAB_SKIP_DET:
         return dets, counts, keep_idx
     _check(lib().lsfa_det_postprocess_batch(_ptr(rois), _ptr(deltas), _ptr(probs), B, R, ncls, nreg, int(class_agnostic), im_h, im_w, scale,

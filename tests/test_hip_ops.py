@@ -709,6 +709,41 @@ def test_proposal_launch_plans_agree(hip, plan):
     np.testing.assert_array_equal(scores.cpu().numpy(), want_scores)
 
 
+def test_proposal_single_workgroup_radix_sort_keys_in_global_memory(hip):
+    """proposal_select_nms_kernel<false, 8, true, true>: radix sort, order keys read from global memory.  9 * 64 * 64 = 36864 anchors
+    are more than the chip-wide plan's 32768, so 'auto' takes the single-workgroup plan.  Its LDS with the keys staged would be
+    16384 (sort buffer A: the select histograms, > 8 * pre_n) + 256 + 4 * 36864 = 164096 bytes > 160 KB = 163840 (any count > 36800
+    is), without them 16384 + 256 + 46592 (the NMS state, > the radix region's 8000 + 32768) = 63232: the radix sort runs, on
+    global keys."""
+    rs = np.random.RandomState(64)
+    prob, deltas = rpn_inputs(rs, 1, 64, 64)
+    im_info = np.array([[1024, 1024, 1.0]], np.float32)
+    want_rois, want_scores = oracle.proposal(prob, deltas, im_info, rpn_pre_nms_top_n=1000, rpn_post_nms_top_n=100, rpn_min_size=0)
+    op = hip.ProposalOp(rpn_pre_nms_top_n=1000, rpn_post_nms_top_n=100, rpn_min_size=0, output_score=True)
+    rois, scores = op(t(prob), t(deltas), t(im_info))
+    np.testing.assert_array_equal(rois.cpu().numpy(), want_rois)
+    np.testing.assert_array_equal(scores.cpu().numpy(), want_scores)
+
+
+def test_proposal_single_workgroup_bitonic_sort_eight_keys_per_thread(hip):
+    """proposal_select_nms_kernel<false, 8, false, true>: bitonic sort of 8192 keys, eight per thread.  With pre_n = 8192 of the
+    9 * 31 * 31 = 8649 anchors the radix sort's two buffers and counters need 8 * pre_n + 256 + (8 * pre_n + 32768) =
+    16 * pre_n + 33024 = 164096 bytes > 160 KB = 163840 (true from pre_n = 8177 on), with or without the keys in LDS; Kpad = 8192
+    still sorts eight keys per thread, in 65536 + 256 + 46592 = 112384 bytes.  The shape is the chip-wide plan's, hence 'single'."""
+    rs = np.random.RandomState(31)
+    prob, deltas = rpn_inputs(rs, 1, 31, 31)
+    im_info = np.array([[496, 496, 1.0]], np.float32)
+    want_rois, want_scores = oracle.proposal(prob, deltas, im_info, rpn_pre_nms_top_n=8192, rpn_post_nms_top_n=300, rpn_min_size=0)
+    hip.proposal_set_plan('single')
+    try:
+        op = hip.ProposalOp(rpn_pre_nms_top_n=8192, rpn_post_nms_top_n=300, rpn_min_size=0, output_score=True)
+        rois, scores = op(t(prob), t(deltas), t(im_info))
+    finally:
+        hip.proposal_set_plan('auto')
+    np.testing.assert_array_equal(rois.cpu().numpy(), want_rois)
+    np.testing.assert_array_equal(scores.cpu().numpy(), want_scores)
+
+
 def test_proposal_multi_image(hip):
     rs = np.random.RandomState(12)
     prob, deltas = rpn_inputs(rs, 3, 20, 30)

@@ -47,7 +47,7 @@ def main():
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--H', type=int, default=38)
     ap.add_argument('--W', type=int, default=63)
-    ap.add_argument('--proposal-plan', default='auto', choices=['auto', 'single', 'chip'])
+    ap.add_argument('--proposal-plan', default='auto', choices=['auto', 'single', 'chip', 'chip-box-sweep'])
     args = ap.parse_args()
     dev = 'cuda:0'
     hip.proposal_set_plan(args.proposal_plan)
@@ -175,6 +175,11 @@ def main():
         p_, d_ = t(prob), t(deltas)
         us = timeit(lambda: op(p_, d_, im_info), args.iters)
         out[tag] = dict(us=round(us, 2))
+    # the batched pass of the frame pipeline: nine images per launch (the trained-like kind)
+    p9, d9 = [t(np.concatenate(x)) for x in zip(*[rpn_inputs(rs, H, W, trained=True) for _ in range(9)])]
+    im_info9 = im_info.repeat(9, 1)
+    us = timeit(lambda: op(p9, d9, im_info9), args.iters)
+    out['proposal_clustered B=9'] = dict(us=round(us, 2))
     # det post
     R, ncls = 300, 31
     deltas = t((0.15 * rs.randn(R, 8)).astype(np.float32))
@@ -190,6 +195,11 @@ def main():
     sparse[:40, 3] = 0.5
     us = timeit(lambda: hip.det_postprocess(rois, deltas, sparse, H * 16, W * 16, 1.0, out=bufs), args.iters)
     out['det_postprocess(sparse)'] = dict(us=round(us, 2))
+    rois9, deltas9, probs9 = [torch.cat([x.roll(31 * b, 0) for b in range(9)]) for x in (rois, deltas, probs)]
+    bufs9 = (torch.zeros((9, ncls, R, 5), dtype=torch.float64, device=dev), torch.zeros((9, ncls), dtype=torch.int32, device=dev),
+             torch.zeros((9, ncls, R), dtype=torch.int32, device=dev))
+    us = timeit(lambda: hip.det_postprocess_batch(rois9, deltas9, probs9, 9, H * 16, W * 16, 1.0, bufs9), args.iters)
+    out['det_postprocess_batch(all pass thresh) B=9'] = dict(us=round(us, 2))
     # dcn im2col + bn
     x = torch.randn(1, 512, H, W, device=dev)
     off = torch.randn(1, 72, H, W, device=dev)
