@@ -341,6 +341,13 @@ int lsfa_conv_nhwc_fused_fwd(const float* x, int N, int H, int W, int Cin, const
  *               of x, a producing convolution's `amax_out`, or of a map that bounds x); s is the power of two that puts that maximum
  *               into [2^13, 2^14).  An UNDER-estimate makes fp16(x s) overflow: the output turns non-finite and bit 0 of *status is
  *               raised - lsfa_status_check() turns it into an error instead of a silently wrong feature map.
+ *               The exponent rule, for maps and weights alike: e = 13 - floor(log2 max), clamped at 100 (weights: +-100), so that 2^e and
+ *               2^-e are finite normal floats.  A map whose maximum is below 2^-87 is scaled by 2^100 and sits lower in fp16's range: the
+ *               result stays finite with a clear status word, each activation carrying an absolute error of up to 2^-125 (fp16's
+ *               subnormal spacing under that scale) next to the usual relative one.  A zero or subnormal maximum takes e = 13: every
+ *               piece is zero and the output is the bias.  A weight (channel) whose maximum is 2^114 or more is refused where the weights
+ *               are bound (hip.SplitWeight).  The accumulator columns are multiplied back by the single float 2^-(e_map + e_weight): from
+ *               e_map + e_weight = 150 on that float is zero and the channel's output is the bias (tests/test_conv_scale_range_gpu.py).
  *   pieces = 1  one bf16 piece (round to nearest even), one product: the bf16 mode (BASELINE configs[2]).
  * Replaces mx.sym.Convolution (+ the BatchNorm / ReLU / residual add around it) of dff_rfcn/symbols/resnet.py:70-101,
  * sym_common.py:92-135, resnet_v1_101_flownet_rfcn.py:44-55 (feat_conv_3x3), :150-207 (FlowNet), :94-109 (Nq), :209-236 (small net),

@@ -109,7 +109,7 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
   uint4* Sw = &S[wave][0];
   float* Tf = reinterpret_cast<float*>(Sw);
 
-  // the map scale of c2: the rule of scale_finish / amax_exponent_asm, written out (see there)
+  // the map scale of c2: the rule of scale_finish / amax_exponent_asm with its clamp, written out (see kScaleExpMax there)
   const uint32_t* am = reinterpret_cast<const uint32_t*>(a.amax);
   uint32_t mi = max(max(am[lane] & 0x7FFFFFFFu, am[lane + 64] & 0x7FFFFFFFu), max(am[lane + 128] & 0x7FFFFFFFu, am[lane + 192] & 0x7FFFFFFFu));
   // c2: DMA i of chunk c moves pixels 8i .. 8i+7 of the wave's rows, lane -> pixel 8i + (lane >> 3), slot lane & 7
@@ -127,7 +127,7 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
   for (int d = 32; d >= 1; d >>= 1) mi = max(mi, (uint32_t)__shfl_xor((int)mi, d, 64));
   const int ei = (int)((mi >> 23) & 255u);
   if (ei == 255 && a.status && lane == 0) atomicOr(a.status, 2u);      // the INPUT map already holds inf / NaN
-  const int s_in = 13 - ((ei == 0 || ei == 255) ? 0 : __builtin_amdgcn_readfirstlane(ei - 127));
+  const int s_in = 13 - ((ei == 0 || ei == 255) ? 0 : max(__builtin_amdgcn_readfirstlane(ei - 127), 13 - kScaleExpMax));
   const float a_scale = ldexpf(1.f, s_in), inv_in = ldexpf(1.f, -s_in);
 
   int frag[4];
@@ -224,7 +224,7 @@ static __global__ __launch_bounds__(kThreads, (KM == 4 && KN == 4) ? 1 : 2) void
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) mb = max(mb, (uint32_t)__shfl_xor((int)mb, d, 64));
     const int eb = __builtin_amdgcn_readfirstlane((int)((mb >> 23) & 255u));
-    const int s_b = (eb == 0 || eb == 255) ? 0 : min(13 - (eb - 127), 100);
+    const int s_b = (eb == 0 || eb == 255) ? 0 : min(13 - (eb - 127), kScaleExpMax);
     const float b_scale = ldexpf(1.f, s_b), inv_b = ldexpf(1.f, -s_b);
 
     // conv1: per pair of column tiles, the block's four chunks of `a` cut (again: 256 vector instructions against 48 matrix instructions,

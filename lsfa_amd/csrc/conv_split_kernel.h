@@ -338,7 +338,18 @@ __device__ __forceinline__ void scale_loads_wait(ScaleRegs& r) {
                : "+v"(r.m0), "+v"(r.m1), "+v"(r.m2), "+v"(r.m3), "+v"(r.w0), "+v"(r.w1), "+v"(r.w2), "+v"(r.w3) : "n"(N) : "memory");
 }
 
-// -> a_scale = 2^s_exp (the map's maximum into [2^13, 2^14)), os[t] = 2^-(s_exp + w_exp of this lane's column of tile t)
+// THE map rule of the fp16 form, for a map maximum m (the largest amax slot):
+//   s_exp = min(13 - floor(log2 m), kScaleExpMax), and 13 for a zero, subnormal or non-finite m.
+// The scale 2^s_exp puts m into [2^13, 2^14) unless m < 2^-87; there the clamp - the one the weights (hip._fp16_exponent) and the pair
+// kernel's block scale use - keeps 2^s_exp and 2^-s_exp finite normal numbers: the scaled map sits lower in fp16's range, at worst in its
+// subnormals (an absolute error of 2^-25 per scaled value instead of a relative one), never at inf.  Under s_exp = 13 a subnormal
+// maximum scales to less than 2^-112: both fp16 pieces are zero and the output is the bias.  Written out three times (scale_finish,
+// amax_exponent_asm, the pair kernel's s_in - see amax_exponent_asm for why); the clamp is scalar work in the prologue.
+constexpr int kScaleExpMax = 100;
+
+// -> a_scale = 2^s_exp (the map's maximum into [2^13, 2^14)), os[t] = 2^-(s_exp + w_exp of this lane's column of tile t).  The column
+// factor is ONE float: from s_exp + w_exp = 150 on it is zero and the column is flushed to its bias (an output that small is at most
+// 2^(28 - 150) K); up to 149 it is an exact, possibly subnormal, power of two.
 template <int NT>
 __device__ __forceinline__ float scale_finish(const Args& a, const ScaleRegs& r, int lane, float (&os)[NT]) {
   uint32_t m = max(max(r.m0 & 0x7FFFFFFFu, r.m1 & 0x7FFFFFFFu), max(r.m2 & 0x7FFFFFFFu, r.m3 & 0x7FFFFFFFu));
@@ -346,7 +357,7 @@ __device__ __forceinline__ float scale_finish(const Args& a, const ScaleRegs& r,
   for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
   const int e = (int)((m >> 23) & 255u);
   if (e == 255 && a.status && lane == 0) atomicOr(a.status, 2u);      // the INPUT map already holds inf / NaN
-  const int s_exp = 13 - ((e == 0 || e == 255) ? 0 : __builtin_amdgcn_readfirstlane(e - 127));
+  const int s_exp = 13 - ((e == 0 || e == 255) ? 0 : max(__builtin_amdgcn_readfirstlane(e - 127), 13 - kScaleExpMax));
   if (!a.wscale) {
     const float v = ldexpf(1.f, -(s_exp + a.w_exp));
 #pragma unroll
@@ -362,7 +373,7 @@ __device__ __forceinline__ float scale_finish(const Args& a, const ScaleRegs& r,
 
 // the fp16 form's scale from the kAmaxSlots partial maxima (floats or bit patterns of |x|: the same thing for non-negative values),
 // read by inline assembly with its own wait so that no compiler-visible vector load is pending when a DMA ring starts.
-// -> floor(log2(max)), 0 for an all-zero map; an inf / NaN maximum raises bit 1 of *status.  (The rule of scale_finish, which has the loads
+// -> max(floor(log2(max)), 13 - kScaleExpMax), 0 for a zero or subnormal maximum; an inf / NaN maximum raises bit 1 of *status.  (The rule of scale_finish, which has the loads
 // behind it, and of the pair kernel: as ONE function called from the three, all 28 two-piece ring kernels and the 4 pair kernels compile
 // to other code - profiles/r10/conv_kernel_refactor_isa.txt - so it stays written out; change the three together.)
 __device__ __forceinline__ int amax_exponent_asm(const float* amax, int lane, unsigned* status) {
@@ -382,7 +393,7 @@ __device__ __forceinline__ int amax_exponent_asm(const float* amax, int lane, un
   for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
   const int e = (int)((m >> 23) & 255u);
   if (e == 255 && status && lane == 0) atomicOr(status, 2u);      // the INPUT map already holds inf / NaN
-  return (e == 0 || e == 255) ? 0 : __builtin_amdgcn_readfirstlane(e - 127);
+  return (e == 0 || e == 255) ? 0 : max(__builtin_amdgcn_readfirstlane(e - 127), 13 - kScaleExpMax);
 }
 
 // a wave's largest |v| bit pattern -> a slot; non-finite -> status bit 0

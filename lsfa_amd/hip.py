@@ -1304,9 +1304,18 @@ def _fp16_exponent(amax):
     return e.clamp(-100, 100).to(torch.int32)
 
 
+def _fp16_weight_exponent(fn, amax):
+    """_fp16_exponent for a weight at bind time (a host synchronisation is fine here).  A maximum of 2^114 or more is refused: the clamp at
+    -100 would leave the scaled maximum above [2^13, 2^14), towards fp16's overflow - better an error here than a status bit at run time."""
+    if bool((torch.isfinite(amax) & (amax >= 2.0 ** 114)).any()):
+        raise LsfaError("%s: the fp16 two-piece form takes weights below 2^114, the largest here is %g" % (fn, float(amax[torch.isfinite(amax)].max())))
+    return _fp16_exponent(amax)
+
+
 class SplitWeight(object):
     """A convolution weight cut into `pieces` pieces per value and laid out in MFMA fragment order (lsfa_conv_weights); made once per
-    layer at bind time.  pieces = 2: the values are scaled by 2^w_exp so that the largest lands in [2^13, 2^14).
+    layer at bind time.  pieces = 2: the values are scaled by 2^w_exp so that the largest lands in [2^13, 2^14) (_fp16_exponent; a maximum of
+    2^114 or more raises LsfaError).
     Every instance carries pieces, cout, cin, kh, kw, real_cout, real_cin, w_exp (0 unless one exponent scales the whole tensor), w_scale
     (None unless each output channel has its own), frag (None only for pieces == 0) and w_kc (None unless pieces == 0)."""
 
@@ -1338,14 +1347,14 @@ class SplitWeight(object):
             # r5: one power of two per OUTPUT channel, from the channel's own maximum (a BatchNorm folded into trained weights spreads the
             # channels over many octaves: with one scale per tensor the small channels' lo pieces go subnormal).  An all-zero (padding)
             # channel gets exponent 0.
-            e = _fp16_exponent(weight.detach().abs().reshape(self.cout, -1).amax(1).double()).contiguous()
+            e = _fp16_weight_exponent("SplitWeight", weight.detach().abs().reshape(self.cout, -1).amax(1).double()).contiguous()
             self.w_scale = torch.ldexp(torch.ones(self.cout, dtype=torch.float32, device=weight.device), -e).contiguous()
             with torch.cuda.device(weight.device):
                 _check(lib().lsfa_conv_weights_pc(_ptr(w_kc), self.cout, self.kh, self.kw, self.cin, _ptr(e), _ptr(self.frag), _stream()),
                        "lsfa_conv_weights_pc")
             return
         if self.pieces == 2:      # one exponent for the tensor: the caller's, or from its maximum (bind time: a host synchronisation is fine here)
-            self.w_exp = int(_fp16_exponent(weight.detach().abs().max().double()).item() if w_exp is None else w_exp)
+            self.w_exp = int(_fp16_weight_exponent("SplitWeight", weight.detach().abs().max().double()).item() if w_exp is None else w_exp)
         with torch.cuda.device(weight.device):
             _check(lib().lsfa_conv_weights(_ptr(w_kc), self.cout, self.kh, self.kw, self.cin, self.pieces, self.w_exp, _ptr(self.frag), _stream()),
                    "lsfa_conv_weights")
@@ -1638,7 +1647,7 @@ def deconv_phase_weights(wt, cin_pad=None, pieces=None):
     frag4 = torch.empty(4 * per, dtype=torch.uint8, device=wt.device)
     out = PhaseWeights()
     # the four phases together hold every tap of wt exactly once: its maximum is each phase's bound (one host synchronisation)
-    w_exp = int(_fp16_exponent(wt.detach().abs().max().double()).item()) if pieces == 2 else 0
+    w_exp = int(_fp16_weight_exponent("deconv_phase_weights", wt.detach().abs().max().double()).item()) if pieces == 2 else 0
     for py in (0, 1):
         for px in (0, 1):
             kys, kxs = ((3, 1) if py == 0 else (2, 0)), ((3, 1) if px == 0 else (2, 0))
