@@ -346,7 +346,9 @@ void orc_warp_bilinear(const float* feat, int feat_n, const float* flow, int N, 
       float x_real = (gx + 1.0f) * (float)(W - 1) / 2.0f;
       float y_real = (gy + 1.0f) * (float)(H - 1) / 2.0f;
       float fx0 = floorf(x_real), fy0 = floorf(y_real);
-      int x0 = (int)fx0, y0 = (int)fy0;
+      /* clamped to [-2, L] before the conversion, as the kernels do: (int) of a float at or beyond 2^31, of inf or of NaN is undefined,
+       * and an index outside [-1, L - 1] has both of its taps outside the map whatever it is (a NaN fails both compares: -2) */
+      int x0 = (int)fminf_(fmaxf_(fx0, -2.0f), (float)W), y0 = (int)fminf_(fmaxf_(fy0, -2.0f), (float)H);
       float wx0 = 1.0f - (x_real - fx0), wy0 = 1.0f - (y_real - fy0);
       float wx1 = 1.0f - wx0, wy1 = 1.0f - wy0;
       int vx0 = (x0 >= 0 && x0 <= W - 1), vx1 = (x0 + 1 >= 0 && x0 + 1 <= W - 1);
