@@ -75,6 +75,13 @@ __device__ __forceinline__ void scale_of(float m, float& s, float& inv) {
   inv = ok ? __uint_as_float((uint32_t)(be - 13) << 23) : 1.f;
 }
 
+// A non-finite value stays visible (fmaxf / fminf return the other operand for a NaN and would turn it into a clean number): the
+// activation and the maxima below hand a NaN through as it is, by compare-and-select on the value that is stored; finite values keep
+// their bits.  The amax slots take bit patterns of |.| by integer max, where an infinity or a NaN ranks above every finite value.
+__device__ __forceinline__ float keep_nan(float v, float finite_result) { return v != v ? v : finite_result; }
+__device__ __forceinline__ uint32_t abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+__device__ __forceinline__ float max_keep_nan(float m, float v) { return keep_nan(v, keep_nan(m, fmaxf(m, v))); }
+
 // r6: `tbl` (or NULL) = a device table of per-image base pointers: image n is read at tbl[n] instead of x + n * C * H * W, so that frames
 // handed over as separate tensors need no staging copy into one batch (lsfa_avgpool_nchw_tbl; C = channels per image then)
 __global__ __launch_bounds__(256) void avgpool_kernel(const float* __restrict__ x, const float* const* __restrict__ tbl, int C, int NC, int H, int W,
@@ -167,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
     pv[kRowsPerWave] = in ? v * xsc + xsh : 0.f;                                                                          \
   }
 
-  float top = 0.f;                        // max |y| this thread stored
+  uint32_t top = 0;                       // max |y| this thread stored, as its bit pattern
   const float slope = act == 1 ? 0.f : (act == 2 ? 0.1f : 1.f);
   const int abase = half * kRegionD + 2 * mi * kPitchD + px;      // patch row 2 (2 mi + mm) + ky, ky = 2 (s % 4) + half: region half, row 2 mi + mm + s % 4
   const int lo = 4 * half * kStemCout + co;
@@ -274,9 +281,9 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const float o = fmaxf(v[i], 0.f) + slope * fminf(v[i], 0.f);
+          const float o = keep_nan(v[i], fmaxf(v[i], 0.f) + slope * fminf(v[i], 0.f));
           yrow[((i & 3) + 8 * (i >> 2)) * kStemCout] = o;
-          top = fmaxf(top, fabsf(o));
+          top = max(top, abs_bits(o));
         }
       } else {
 #pragma unroll
@@ -284,9 +291,9 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
           const int p = (i & 3) + 8 * (i >> 2);
           if (ox0 + 4 * half + p < Wo) {
             if (arow) v[i] = v[i] + arow[p * kStemCout];
-            const float o = fmaxf(v[i], 0.f) + slope * fminf(v[i], 0.f);
+            const float o = keep_nan(v[i], fmaxf(v[i], 0.f) + slope * fminf(v[i], 0.f));
             yrow[p * kStemCout] = o;
-            top = fmaxf(top, fabsf(o));
+            top = max(top, abs_bits(o));
           }
         }
       }
@@ -297,7 +304,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
 #undef LSFA_STEM_PATCH_CUT
 #undef LSFA_STEM_LOAD_PATCH
   if (amax_out) {      // the slots lsfa_conv_fwd reads as amax_in
-    uint32_t m = __float_as_uint(top);
+    uint32_t m = top;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
     if (lane == 0) atomicMax(amax_out + ((((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + wv) & 255), m);
@@ -311,7 +318,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float4* __restr
                                                            const float4* __restrict__ scale2, const float4* __restrict__ shift2,
                                                            unsigned* __restrict__ amax_out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  float top = 0.f;        // max |.| of what this thread hands to the next convolution (y2 when present, else y)
+  uint32_t top = 0;       // max |.| of what this thread hands to the next convolution (y2 when present, else y), as its bit pattern
   if (i < (long)N * Ho * Wo * C4) {
   const int c = (int)(i % C4);
   long r = i / C4;
@@ -323,19 +330,20 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float4* __restr
   for (int yy = y0; yy < y1; ++yy)
     for (int xx = x0; xx < x1; ++xx) {
       const float4 v = x[(((size_t)n * H + yy) * W + xx) * C4 + c];
-      m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+      m.x = max_keep_nan(m.x, v.x); m.y = max_keep_nan(m.y, v.y); m.z = max_keep_nan(m.z, v.z); m.w = max_keep_nan(m.w, v.w);
     }
   y[i] = m;
   if (y2) {
     const float4 sc = scale2[c], sh = shift2[c];
-    m = make_float4(fmaxf(m.x * sc.x + sh.x, 0.f), fmaxf(m.y * sc.y + sh.y, 0.f), fmaxf(m.z * sc.z + sh.z, 0.f),
-                    fmaxf(m.w * sc.w + sh.w, 0.f));
+    const float4 a = make_float4(m.x * sc.x + sh.x, m.y * sc.y + sh.y, m.z * sc.z + sh.z, m.w * sc.w + sh.w);
+    m = make_float4(keep_nan(a.x, fmaxf(a.x, 0.f)), keep_nan(a.y, fmaxf(a.y, 0.f)), keep_nan(a.z, fmaxf(a.z, 0.f)),
+                    keep_nan(a.w, fmaxf(a.w, 0.f)));
     y2[i] = m;
   }
-  top = fmaxf(fmaxf(fabsf(m.x), fabsf(m.y)), fmaxf(fabsf(m.z), fabsf(m.w)));
+  top = max(max(abs_bits(m.x), abs_bits(m.y)), max(abs_bits(m.z), abs_bits(m.w)));
   }
   if (amax_out) {      // the slots lsfa_conv_fwd reads as amax_in (bit patterns of non-negative floats order like the floats)
-    uint32_t b = __float_as_uint(top);
+    uint32_t b = top;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, d, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(amax_out + ((blockIdx.x * 4 + (threadIdx.x >> 6)) & 255), b);
