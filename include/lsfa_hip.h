@@ -879,8 +879,8 @@ int lsfa_image_resize_transform_yuv(const void* y, long long y_pitch, long long 
 
 /* ------------------------------------------------------------------------ *
  * Detection overlay (lsfa_amd/csrc/overlay.hip): the detections lsfa_det_postprocess(_batch) left on the device, burnt into the frame that is
- * already on the device - a packed BGR frame, or the 8-bit 4:2:0 planes of "YUV 4:2:0 intake" (NV12 / I420), e.g. the surface a hardware
- * encoder takes next.  Nothing is read back and every call can sit inside a captured graph.
+ * already on the device - a packed BGR frame, or the planes of any format the YUV intake reads (NV12 / I420 by lsfa_overlay_paint_yuv420,
+ * all 29 by lsfa_overlay_paint_yuv), e.g. the surface a hardware encoder takes next.  Nothing is read back and every call can sit inside a captured graph.
  * Replaces (in function, NOT in pixels): draw_boxes + cv2.imwrite at the end of the reference's demo.py:150-157.  cv2's rasteriser is not
  * part of this project - no Hershey fonts, no anti-aliasing, none of cv2's line joins - and draw_boxes picks random colours.  The overlay
  * is defined by the integer specification below (DESIGN.md "Detection overlay"; restated in numpy as tests/ref_overlay.py) and is bit-exact
@@ -907,7 +907,22 @@ int lsfa_image_resize_transform_yuv(const void* y, long long y_pitch, long long 
  *   colors: (ncls + 1, 3) uint8 in the component order of the surface: B, G, R or Y, U, V (made on the host, lsfa_amd/overlay.py bgr_to_yuv).
  *   4:2:0 surfaces: Y[y][x] takes component 0 of pixel (x, y)'s result; chroma sample (cx, cy) takes components 1 and 2 of the result of
  *   pixel (2cx, 2cy) and is untouched when that pixel is uncovered - the intake's nearest-neighbour rule.  Odd W, H: chroma is ceil / 2.
- * Out of scope: blending, transparency, anti-aliasing; 10-bit, 4:2:2, 4:4:4 and packed surfaces (draw on their converted BGR frame); masks
+ *   Every YUV surface of the intake (lsfa_overlay_paint_yuv; format = sub | layout << 4 | sample << 8, LSFA_YUV_FORMAT of "YUV intake, other
+ *   chroma formats", the same 27 + 2 codes).  Everything up to a pixel's result is as above; only the samples that take it are new:
+ *     colors: the (ncls + 1, 3) uint8 Y, U, V table of the 4:2:0 surfaces, whatever the sample width: no colour arithmetic on the device.
+ *     Sample value of a colour component c: sample 0: the byte c; 1 (low ten bits): the 16-bit word c << 2; 2 (high ten bits): the word
+ *     c << 8.  The whole word is stored: the bits the intake ignores are written as 0.  (The intake converts planes that are exactly 4 x an
+ *     8-bit plane to the 8-bit BGR bit for bit, so a colour drawn into a 10-bit surface reads back as the same BGR as in 8 bits.)
+ *     Luma: Y[y][x] takes component 0 of pixel (x, y)'s result when the pixel is covered.
+ *     Chroma: with the format's shifts (sx, sy) - 4:2:0 (1, 1), 4:2:2 (1, 0), 4:4:4 (0, 0) - the chroma sample (cx, cy) takes components 1
+ *     and 2 of the result of pixel (cx << sx, cy << sy), the first pixel the intake's nearest-neighbour rule maps to it, which always lies
+ *     inside the frame; the sample is untouched when that pixel is uncovered.  sub = 0 is the (2cx, 2cy) rule above.
+ *     Layouts: 0: two planes U, V; 1: interleaved U, V; 2: interleaved V, U; 3: packed groups Y0 U Y1 V; 4: packed groups U Y0 V Y1.  In
+ *     a packed row group g takes its U and V from pixel 2g and its two Y bytes from pixels 2g and 2g + 1; with odd W the last group's second
+ *     Y byte is never written.
+ *     A sample whose pixel is uncovered is never stored: not rewritten with its own value and not as part of a wider store; for words
+ *     this includes their ignored bits.
+ * Out of scope: blending, transparency, anti-aliasing; packed 10-bit, 12-bit and RGB surfaces (draw on the converted BGR frame); masks
  * and tracks.  (Tracks are drawn by lsfa_overlay_plan_ids, declared under "Tracks" below, from the ids lsfa_track_steps assigns.)
  * A record is LSFA_OVERLAY_REC_INTS ints: x1, y1, x2, y2, lx, ly, w, h, j, L, then the L glyph indices four to an int (character k in bits
  * 8 (k % 4) of int 10 + k / 4), unused bits 0.  The caller sizes the buffers: records (N, max_boxes, LSFA_OVERLAY_REC_INTS) int32 and
@@ -917,11 +932,16 @@ int lsfa_image_resize_transform_yuv(const void* y, long long y_pitch, long long 
  *   walked, so a frame without detections costs the launch - no atomics.  One launch.
  * lsfa_overlay_paint_bgr: bgr (N, H, W, 3) uint8 with a row pitch and a frame stride in BYTES, in place.  One launch for the N frames.
  * lsfa_overlay_paint_yuv420: the planes, pitches and strides of lsfa_yuv420_to_bgr_u8 (v == NULL: NV12), in place.  One launch.
+ * lsfa_overlay_paint_yuv: the planes, pitches and strides of lsfa_yuv_to_bgr_u8 up to W, then `format`, in place.  One launch.  The
+ *   4:2:0 codes of layouts 0 and 1 of bytes leave the bytes lsfa_overlay_paint_yuv420 leaves.
  *   One 256-lane workgroup per 64 x 16 tile; a tile no record can touch leaves before it touches the frame.  thickness and label_scale
  *   must be the plan's.
  * LSFA_EINVAL, before anything is launched, for: a NULL pointer (but names, and v for NV12); N, H, W, R or max_boxes below 1; ncls below 1 or
  * above LSFA_OVERLAY_MAX_CLASSES; H or W above 65536, N above 65535, max_boxes above LSFA_OVERLAY_MAX_BOXES, (ncls - 1) * R at or above 2^31; thickness outside 1..8;
  * label_scale outside 0..4; a pitch below its row (3 W; Y: W; chroma 2 ceil(W / 2) interleaved, ceil(W / 2) planar); a negative frame stride.
+ * lsfa_overlay_paint_yuv refuses besides what the intake refuses of planes: a format outside the 27 + 2; v given with layouts 1 and 2 or
+ * missing with layout 0; a chroma pointer, pitch or stride with a packed layout; for words an odd base, pitch or frame stride; a pitch below
+ * its row (Y: W samples; planar chroma ceil(W / 2^sx) samples, interleaved twice that; packed 4 ceil(W / 2) bytes).
  * On `stream`, no workspace, nothing allocated; not reported under a profiling id.
  * ------------------------------------------------------------------------ */
 #define LSFA_OVERLAY_REC_INTS 16
@@ -940,6 +960,9 @@ int lsfa_overlay_paint_yuv420(unsigned char* y, long long y_pitch, long long y_f
                               unsigned char* v /* NULL: NV12 */, long long c_pitch, long long c_frame_stride, int N, int H, int W,
                               const int* records, const int* n, int max_boxes, int thickness, int label_scale, const unsigned char* font,
                               const unsigned char* colors, int ncls, void* stream);
+int lsfa_overlay_paint_yuv(void* y, long long y_pitch, long long y_frame_stride, void* u_or_uv, void* v /* layout 0 only */, long long c_pitch,
+                           long long c_frame_stride, int N, int H, int W, int format, const int* records, const int* n, int max_boxes,
+                           int thickness, int label_scale, const unsigned char* font, const unsigned char* colors, int ncls, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Tracks (lsfa_amd/csrc/tracks.hip): which detection of frame f is the same object as which detection of frame f - 1, decided on the device

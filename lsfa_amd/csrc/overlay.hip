@@ -1,11 +1,12 @@
 // Detection overlay: the detections lsfa_det_postprocess(_batch) left on the device, burnt into the frame that is already on the device - a
-// packed BGR frame or the 8-bit 4:2:0 planes of the YUV intake (NV12 / I420) - in two launches: a plan kernel that turns dets / counts into
-// an ordered list of records, and a paint kernel per surface form.  Nothing is read back; both can sit inside a captured graph.
+// packed BGR frame or the planes of any of the 29 formats the YUV intake reads (yuvfmt.hip: 4:2:0, 4:2:2 and 4:4:4; planar, interleaved U, V
+// or V, U, packed YUYV / UYVY; bytes or ten-bit words) - in two launches: a plan kernel that turns dets / counts into an ordered list of
+// records, and a paint kernel per surface form.  Nothing is read back; both can sit inside a captured graph.
 //
 // NOT a port of anything in the reference: demo.py:150-157 ends with draw_boxes and cv2.imwrite, and cv2's rasteriser (Hershey fonts,
 // anti-aliasing, its line joins) is not part of this project; draw_boxes picks random colours besides.  What is drawn is the integer
 // specification of include/lsfa_hip.h, "Detection overlay" (DESIGN.md "Detection overlay"; tests/ref_overlay.py states it in numpy), matched
-// bit for bit.  Out of scope: blending, anti-aliasing, 10-bit / 4:2:2 / 4:4:4 / packed surfaces, masks.
+// bit for bit.  Out of scope: blending, anti-aliasing, packed 10-bit, 12-bit and RGB surfaces, masks.
 //
 // overlay_plan_kernel: one workgroup per image.  A prefix of the clamped counts over the classes says where each class's rows start, so only
 // the rows under counts are walked, in draw order, 256 at a time (a frame without detections walks none); the position of a kept row is a
@@ -18,6 +19,12 @@
 // anyway); an empty list - most tiles of most frames - ends it before it touches the frame.  Otherwise each pixel walks the list from the
 // back to its first hit.  Covered pixels are stored, whole dwords where a lane's four
 // pixels are all covered and the address is aligned, bytes otherwise; an uncovered byte is never stored.
+// Surfaces: BgrSurface and Yuv420Surface (lsfa_overlay_paint_bgr, lsfa_overlay_paint_yuv420) and, for lsfa_overlay_paint_yuv, PlanesSurface<SX,
+// SEMI, WORDS> - compiled per horizontal chroma shift, two chroma planes or one interleaved, bytes or words; the vertical shift, V before U
+// and the word's shift (c << 2 or c << 8, the whole word stored) are run-time values - and PackedSurface for YUYV / UYVY: nine
+// instantiations.  The chroma sample (cx, cy) takes pixel (cx << sx, cy << sy): of a lane's four pixels all four or pixels 0 and 2, on every
+// row or the even ones.  A wide store (4 to 16 bytes) is taken only where every sample of it is covered and its address is a multiple of
+// its size; otherwise each covered sample is stored alone, so an uncovered sample - its ignored bits included - is never written.
 #include "common.h"
 #include "prefix256.h"
 
@@ -257,6 +264,150 @@ struct Yuv420Surface {
   }
 };
 
+// ---- every YUV surface of the intake (lsfa_overlay_paint_yuv) ---------------------------------------------------------------------------
+// BYTES (2, 4, 8 or 16, the address a multiple of it) as one store of the dwords r
+template <int BYTES>
+__device__ __forceinline__ void store_raw(unsigned char* a, const uint32_t (&r)[4]) {
+  if constexpr (BYTES == 2) {
+    *reinterpret_cast<uint16_t*>(a) = (uint16_t)r[0];
+  } else if constexpr (BYTES == 4) {
+    *reinterpret_cast<uint32_t*>(a) = r[0];
+  } else if constexpr (BYTES == 8) {
+    *reinterpret_cast<uint2*>(a) = make_uint2(r[0], r[1]);
+  } else {
+    static_assert(BYTES == 16, "a store of 2, 4, 8 or 16 bytes");
+    *reinterpret_cast<uint4*>(a) = make_uint4(r[0], r[1], r[2], r[3]);
+  }
+}
+
+// one sample: the byte c, or the whole 16-bit word c << shl (shl 2: the low ten bits, 8: the high ten; the ignored bits are written as 0)
+template <bool WORDS>
+__device__ __forceinline__ void store_sample(unsigned char* a, uint32_t c, int shl) {
+  if constexpr (WORDS) *reinterpret_cast<uint16_t*>(a) = (uint16_t)(c << shl);
+  else *a = (unsigned char)c;
+}
+
+// sample k (a constant under the unrolled loops) of a wide store's dwords
+template <bool WORDS>
+__device__ __forceinline__ void put_sample(uint32_t (&r)[4], int k, uint32_t c, int shl) {
+  if constexpr (WORDS) r[k >> 1] |= (c << shl) << (16 * (k & 1));
+  else r[k >> 2] |= c << (8 * (k & 3));
+}
+
+// Planes of bytes or words, chroma in two planes (SEMI false: c the U plane, v the V plane) or one interleaved plane (SEMI true: c; vu: V
+// first), subsampled by (SX, sy).  The chroma sample (cx, cy) takes pixel (cx << SX, cy << sy): of this lane's four pixels every one
+// (SX 0) or pixels 0 and 2 (SX 1), on the rows sy allows.  A wide store only where every sample of it is covered and it is aligned.
+template <int SX, bool SEMI, bool WORDS>
+struct PlanesSurface {
+  unsigned char* y;
+  unsigned char* c;
+  unsigned char* v;
+  long long y_pitch, y_stride, c_pitch, c_stride;
+  int sy, vu, shl;
+
+  __device__ __forceinline__ void store(int img, int yy, int x0, const int (&res)[4], const unsigned char* __restrict__ colors) const {
+    constexpr int B = WORDS ? 2 : 1;
+    unsigned char* row = y + (long long)img * y_stride + (long long)yy * y_pitch + (long long)B * x0;
+    const bool all = (res[0] | res[1] | res[2] | res[3]) >= 0;
+    if (all && (reinterpret_cast<uintptr_t>(row) & (uintptr_t)(4 * B - 1)) == 0) {
+      uint32_t r[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) put_sample<WORDS>(r, k, colors[3 * res[k]], shl);
+      store_raw<4 * B>(row, r);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (res[k] >= 0) store_sample<WORDS>(row + B * k, colors[3 * res[k]], shl);
+      }
+    }
+    if (yy & sy) return;
+    constexpr int NC = 4 >> SX;          // this lane's chroma samples of a row
+    bool call = true;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) call = call && res[k << SX] >= 0;
+    const long long co = (long long)img * c_stride + (long long)(yy >> sy) * c_pitch;
+    const int cx = x0 >> SX;
+    if constexpr (SEMI) {
+      constexpr int PAIR = 2 * B;
+      unsigned char* uv = c + co + (long long)PAIR * cx;
+      const int first = 1 + vu, second = 2 - vu;
+      if (call && (reinterpret_cast<uintptr_t>(uv) & (uintptr_t)(NC * PAIR - 1)) == 0) {
+        uint32_t r[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          put_sample<WORDS>(r, 2 * k, colors[3 * res[k << SX] + first], shl);
+          put_sample<WORDS>(r, 2 * k + 1, colors[3 * res[k << SX] + second], shl);
+        }
+        store_raw<NC * PAIR>(uv, r);
+        return;
+      }
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        if (res[k << SX] >= 0) {
+          store_sample<WORDS>(uv + PAIR * k, colors[3 * res[k << SX] + first], shl);
+          store_sample<WORDS>(uv + PAIR * k + B, colors[3 * res[k << SX] + second], shl);
+        }
+      }
+    } else {
+      unsigned char* up = c + co + (long long)B * cx;
+      unsigned char* vp = v + co + (long long)B * cx;
+      if (call && ((reinterpret_cast<uintptr_t>(up) | reinterpret_cast<uintptr_t>(vp)) & (uintptr_t)(NC * B - 1)) == 0) {
+        uint32_t ru[4] = {0, 0, 0, 0}, rv[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          put_sample<WORDS>(ru, k, colors[3 * res[k << SX] + 1], shl);
+          put_sample<WORDS>(rv, k, colors[3 * res[k << SX] + 2], shl);
+        }
+        store_raw<NC * B>(up, ru);
+        store_raw<NC * B>(vp, rv);
+        return;
+      }
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        if (res[k << SX] >= 0) {
+          store_sample<WORDS>(up + B * k, colors[3 * res[k << SX] + 1], shl);
+          store_sample<WORDS>(vp + B * k, colors[3 * res[k << SX] + 2], shl);
+        }
+      }
+    }
+  }
+};
+
+// packed 4:2:2 of bytes: a row is four-byte groups Y0 U Y1 V (uyvy 0) or U Y0 V Y1 (uyvy 1); group g takes U and V from pixel 2g and its Y
+// bytes from pixels 2g and 2g + 1.  This lane's four pixels are two whole groups: one 8-byte store where all four are covered
+struct PackedSurface {
+  unsigned char* p;
+  long long pitch, stride;
+  int uyvy;
+
+  __device__ __forceinline__ void store(int img, int yy, int x0, const int (&res)[4], const unsigned char* __restrict__ colors) const {
+    unsigned char* row = p + (long long)img * stride + (long long)yy * pitch + 2LL * x0;
+    const bool all = (res[0] | res[1] | res[2] | res[3]) >= 0;
+    if (all && (reinterpret_cast<uintptr_t>(row) & 7u) == 0) {
+      uint32_t r[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        const uint32_t y0 = colors[3 * res[2 * g]], y1 = colors[3 * res[2 * g + 1]], u = colors[3 * res[2 * g] + 1], vv = colors[3 * res[2 * g] + 2];
+        r[g] = uyvy ? (u | y0 << 8 | vv << 16 | y1 << 24) : (y0 | u << 8 | y1 << 16 | vv << 24);
+      }
+      store_raw<8>(row, r);
+      return;
+    }
+    const int yo = uyvy ? 1 : 0, uo = 1 - yo;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (res[k] >= 0) {
+        unsigned char* g = row + 4 * (k >> 1);
+        g[yo + 2 * (k & 1)] = colors[3 * res[k]];
+        if ((k & 1) == 0) {
+          g[uo] = colors[3 * res[k] + 1];
+          g[uo + 2] = colors[3 * res[k] + 2];
+        }
+      }
+    }
+  }
+};
+
 template <class Surface>
 __global__ __launch_bounds__(kThreads) void overlay_paint_kernel(Paint a, Surface s) {
   __shared__ unsigned short s_list[LSFA_OVERLAY_MAX_BOXES];
@@ -440,5 +591,81 @@ extern "C" int lsfa_overlay_paint_yuv420(unsigned char* y, long long y_pitch, lo
   s.y_pitch = y_pitch; s.y_stride = y_frame_stride; s.c_pitch = c_pitch; s.c_stride = c_frame_stride;
   launch_paint(a, s, N, (hipStream_t)stream);
   LSFA_LAUNCH_CHECK("lsfa_overlay_paint_yuv420");
+  return LSFA_OK;
+}
+
+namespace {
+
+template <int SX, bool SEMI, bool WORDS>
+void launch_planes(const Paint& a, unsigned char* y, unsigned char* c, unsigned char* v, long long y_pitch, long long y_stride, long long c_pitch,
+                   long long c_stride, int sy, int vu, int shl, int N, hipStream_t stream) {
+  PlanesSurface<SX, SEMI, WORDS> s;
+  s.y = y; s.c = c; s.v = v;
+  s.y_pitch = y_pitch; s.y_stride = y_stride; s.c_pitch = c_pitch; s.c_stride = c_stride;
+  s.sy = sy; s.vu = vu; s.shl = shl;
+  launch_paint(a, s, N, stream);
+}
+
+}  // namespace
+
+// the intake's refusals of planes (yuvfmt.hip fill_planes) and the overlay's own of everything else; nine instantiations of the paint kernel:
+// (4:4:4 | 4:2:0 and 4:2:2) x (two chroma planes | one interleaved) x (bytes | words), and the packed rows
+extern "C" int lsfa_overlay_paint_yuv(void* y, long long y_pitch, long long y_frame_stride, void* u_or_uv, void* v, long long c_pitch,
+                                      long long c_frame_stride, int N, int H, int W, int format, const int* records, const int* n, int max_boxes,
+                                      int thickness, int label_scale, const unsigned char* font, const unsigned char* colors, int ncls, void* stream) {
+  const char* who = "lsfa_overlay_paint_yuv";
+  Paint a;
+  if (int rc = fill_paint(who, a, N, H, W, records, n, max_boxes, thickness, label_scale, font, colors, ncls)) return rc;
+  const int sub = format & 15, layout = (format >> 4) & 15, sample = (format >> 8) & 15;
+  LSFA_REQUIRE(format >= 0 && format < (1 << 12) && sub <= LSFA_YUV_444 && layout <= LSFA_YUV_UYVY && sample <= LSFA_YUV_HI10,
+               "%s: format 0x%x is not sub (0..2) | layout (0..4) << 4 | sample (0..2) << 8", who, (unsigned)format);
+  const bool packed = layout >= LSFA_YUV_YUYV, words = sample != LSFA_YUV_U8, planar = layout == LSFA_YUV_PLANAR;
+  LSFA_REQUIRE(!packed || (sub == LSFA_YUV_422 && !words), "%s: format 0x%x: the packed layouts exist only as 4:2:2 of bytes", who, (unsigned)format);
+  LSFA_REQUIRE(y, "%s: NULL plane", who);
+  if (packed) {
+    LSFA_REQUIRE(!u_or_uv && !v && c_pitch == 0 && c_frame_stride == 0,
+                 "%s: a packed frame is one plane: both chroma pointers must be NULL and the chroma pitch %lld and frame stride %lld zero", who, c_pitch,
+                 c_frame_stride);
+  } else {
+    LSFA_REQUIRE(u_or_uv, "%s: NULL plane", who);
+    LSFA_REQUIRE(planar == (v != nullptr), "%s: layout %d goes with %s", who, layout,
+                 planar ? "two chroma planes: v is NULL" : "one chroma plane: v must be NULL");
+  }
+  const int B = words ? 2 : 1;
+  if (words) {
+    LSFA_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(u_or_uv) | reinterpret_cast<uintptr_t>(v)) & 1u) == 0,
+                 "%s: a plane of 16-bit words starts at an odd address", who);
+    LSFA_REQUIRE((((unsigned long long)y_pitch | (unsigned long long)y_frame_stride | (unsigned long long)c_pitch | (unsigned long long)c_frame_stride) & 1u) == 0,
+                 "%s: pitches and frame strides are bytes between 16-bit words and must be even: Y %lld / %lld, chroma %lld / %lld", who, y_pitch,
+                 y_frame_stride, c_pitch, c_frame_stride);
+  }
+  const int sx = sub == LSFA_YUV_444 ? 0 : 1, sy = sub == LSFA_YUV_420 ? 1 : 0;
+  const int cw = (W + (1 << sx) - 1) >> sx;
+  const long long y_row = packed ? 4LL * cw : (long long)B * W;
+  LSFA_REQUIRE(y_pitch >= y_row, "%s: %s pitch %lld is below the row's %lld bytes", who, packed ? "packed" : "Y", y_pitch, y_row);
+  const long long c_row = packed ? 0 : (long long)(planar ? 1 : 2) * B * cw;
+  LSFA_REQUIRE(c_pitch >= c_row, "%s: chroma pitch %lld is below the row's %lld bytes", who, c_pitch, c_row);
+  LSFA_REQUIRE(y_frame_stride >= 0 && c_frame_stride >= 0, "%s: frame strides %lld / %lld: negative", who, y_frame_stride, c_frame_stride);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* yb = static_cast<unsigned char*>(y);
+  unsigned char* cb = static_cast<unsigned char*>(u_or_uv);
+  unsigned char* vb = static_cast<unsigned char*>(v);
+  if (packed) {
+    PackedSurface s;
+    s.p = yb; s.pitch = y_pitch; s.stride = y_frame_stride; s.uyvy = layout == LSFA_YUV_UYVY ? 1 : 0;
+    launch_paint(a, s, N, st);
+  } else {
+    const int vu = layout == LSFA_YUV_VU ? 1 : 0, shl = sample == LSFA_YUV_U8 ? 0 : sample == LSFA_YUV_LO10 ? 2 : 8;
+    switch (sx | (planar ? 0 : 2) | (words ? 4 : 0)) {
+#define LSFA_SURF(SX, SEMI, WORDS)                                                                                                       \
+  case SX | (SEMI ? 2 : 0) | (WORDS ? 4 : 0):                                                                                            \
+    launch_planes<SX, SEMI, WORDS>(a, yb, cb, vb, y_pitch, y_frame_stride, c_pitch, c_frame_stride, sy, vu, shl, N, st);                 \
+    break;
+      LSFA_SURF(0, false, false) LSFA_SURF(1, false, false) LSFA_SURF(0, true, false) LSFA_SURF(1, true, false)
+      LSFA_SURF(0, false, true) LSFA_SURF(1, false, true) LSFA_SURF(0, true, true) LSFA_SURF(1, true, true)
+#undef LSFA_SURF
+    }
+  }
+  LSFA_LAUNCH_CHECK(who);
   return LSFA_OK;
 }

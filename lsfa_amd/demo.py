@@ -40,13 +40,16 @@ through lsfa_amd/yuvfmt.py (image_resize_transform_yuv, MotionEstimatorYuv).
 BGR frame (a --yuv frame converted by the shipped *_to_bgr_u8) by lsfa_amd/overlay.py and the frame is written as DIR/<frame stem>.png
 with PIL.  --draw-yuv FILE (--yuv-format nv12 | i420 only): the detections are drawn into a COPY of the frame's planes - the motion
 estimator still needs the pristine frames - and the annotated raw stream is written in the input's layout, e.g. for an encoder.
+--draw-raw FILE (every --yuv-format of lsfa_amd.yuvfmt.FORMATS: p010, yuyv422, nv21, yuv444p10le, ...): the same for any input layout -
+each frame's annotated planes back to back, yuvfmt.frame_bytes per frame, drawn by Overlay.draw_yuv; a ten-bit surface takes the 8-bit
+colour in its ten bits, so the stream reads back through the intake as the same BGR.
 --classes FILE: one class name per line (the foreground classes, or all with the background first); without it a label is the class
 id.  --draw-thickness / --draw-scale: the outline's thickness and the label's scale (0: no label).  The drawing is this project's own
 integer specification (DESIGN.md "Detection overlay"), not cv2's, and runs outside the timed region like the reference's.
 --track [--track-iou X --track-max-age N --track-min-hits N --track-slots T]: every detection gets a track id on the device, frame by
 frame (lsfa_amd/tracks.py; DESIGN.md "Tracks" - the reference has no tracker).  Under --estimate-mv the estimator's block rows of the frame
 predict where last frame's boxes went; a key frame that restarts the chain has none, and without --estimate-mv there is no prediction.
-With --draw / --draw-yuv a track keeps one colour and one number (labels read name-id); otherwise the id is the `track` of every
+With --draw / --draw-yuv / --draw-raw a track keeps one colour and one number (labels read name-id); otherwise the id is the `track` of every
 detection of --out (-1: below --score, 0: not reported yet or dropped).
 """
 import argparse
@@ -343,9 +346,10 @@ def parse_args(argv=None):
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--draw', default=None, help='a directory that receives every frame with its detections drawn in, as <frame stem>.png')
     ap.add_argument('--draw-yuv', default=None, help='--yuv with --yuv-format nv12 | i420: write the annotated raw stream, in the input\'s layout, here')
-    ap.add_argument('--classes', default=None, help='--draw / --draw-yuv: a file of class names, one per line; the default labels are class ids')
-    ap.add_argument('--draw-thickness', type=int, default=None, help='--draw / --draw-yuv: the outline\'s thickness in pixels, 1..8 (default 3, the reference\'s)')
-    ap.add_argument('--draw-scale', type=int, default=None, help='--draw / --draw-yuv: the label\'s scale, 1..4, or 0 for no label (default 2)')
+    ap.add_argument('--draw-raw', default=None, help='--yuv with any --yuv-format: write the annotated raw stream, in the input\'s layout, here')
+    ap.add_argument('--classes', default=None, help='--draw / --draw-yuv / --draw-raw: a file of class names, one per line; the default labels are class ids')
+    ap.add_argument('--draw-thickness', type=int, default=None, help='--draw / --draw-yuv / --draw-raw: the outline\'s thickness in pixels, 1..8 (default 3, the reference\'s)')
+    ap.add_argument('--draw-scale', type=int, default=None, help='--draw / --draw-yuv / --draw-raw: the label\'s scale, 1..4, or 0 for no label (default 2)')
     ap.add_argument('--track', action='store_true', help='give every detection a track id on the device (lsfa_amd.tracks); with --estimate-mv the '
                                                          'estimator\'s block rows predict where last frame\'s boxes went')
     ap.add_argument('--track-iou', type=float, default=None, help='--track: the least IoU of a match (default 0.3; not a tuned value)')
@@ -357,10 +361,16 @@ def parse_args(argv=None):
         ap.error('--draw-yuv writes the input\'s own layout and needs --yuv with --yuv-format nv12 or i420; draw any other input with --draw')
     if args.draw_yuv and os.path.abspath(args.draw_yuv) == os.path.abspath(args.yuv):
         ap.error('--draw-yuv would overwrite its input %s' % args.yuv)
-    drawing = bool(args.draw or args.draw_yuv)
+    if args.draw_raw and not args.yuv:
+        ap.error('--draw-raw writes the input\'s own layout and needs --yuv')
+    if args.draw_raw and os.path.abspath(args.draw_raw) == os.path.abspath(args.yuv):
+        ap.error('--draw-raw would overwrite its input %s' % args.yuv)
+    if args.draw_raw and args.draw_yuv and os.path.abspath(args.draw_raw) == os.path.abspath(args.draw_yuv):
+        ap.error('--draw-raw and --draw-yuv name one file: %s' % args.draw_raw)
+    drawing = bool(args.draw or args.draw_yuv or args.draw_raw)
     for name, v in (('--classes', args.classes), ('--draw-thickness', args.draw_thickness), ('--draw-scale', args.draw_scale)):
         if v is not None and not drawing:
-            ap.error('%s belongs to --draw / --draw-yuv' % name)
+            ap.error('%s belongs to --draw / --draw-yuv / --draw-raw' % name)
     if args.draw_thickness is not None and not 1 <= args.draw_thickness <= 8:
         ap.error('--draw-thickness %d is outside 1..8' % args.draw_thickness)
     if args.draw_scale is not None and not 0 <= args.draw_scale <= 4:
@@ -424,14 +434,16 @@ def class_names(path, ncls):
 
 
 class _Drawer(object):
-    """--draw / --draw-yuv: one overlay.Overlay for the clip, made at the first frame from the detection buffers' shape"""
+    """--draw / --draw-yuv / --draw-raw: one overlay.Overlay for the clip, made at the first frame from the detection buffers' shape"""
 
     def __init__(self, args, clip):
-        self.args, self.clip, self.ov, self.yuv_out = args, clip, None, None
+        self.args, self.clip, self.ov, self.yuv_out, self.raw_out = args, clip, None, None, None
         if args.draw:
             os.makedirs(args.draw, exist_ok=True)
         if args.draw_yuv:
             self.yuv_out = open(args.draw_yuv, 'wb')
+        if args.draw_raw:
+            self.raw_out = open(args.draw_raw, 'wb')
 
     def frame(self, idx, dets, counts, ids=None):
         """draws frame idx's detections (the device buffers fg.*_frame returned; ids: --track's, one colour and one number per object) and
@@ -451,10 +463,15 @@ class _Drawer(object):
             buf, planes = clip.planes_copy(idx)
             self.ov.draw_yuv420(planes.pop('y'), dets, counts, args.score, matrix=clip.matrix, ids=ids, **planes)
             self.yuv_out.write(buf.cpu().numpy().tobytes())
+        if self.raw_out is not None:
+            buf, planes = clip.planes_copy(idx)
+            self.ov.draw_yuv(clip.fmt, planes.pop('y'), dets, counts, args.score, matrix=clip.matrix, ids=ids, width=clip.src_w, **planes)
+            self.raw_out.write(buf.cpu().numpy().tobytes())
 
     def close(self):
-        if self.yuv_out is not None:
-            self.yuv_out.close()
+        for f in (self.yuv_out, self.raw_out):
+            if f is not None:
+                f.close()
 
 
 def main(argv=None):
@@ -482,7 +499,7 @@ def main(argv=None):
     fg.scale = float(clip.im_scale)
     fg.im_info[0, 2] = fg.scale
     classes = None       # class names live in the dataset (imdb.classes); ids are reported without one
-    drawer = _Drawer(args, clip) if args.draw or args.draw_yuv else None
+    drawer = _Drawer(args, clip) if args.draw or args.draw_yuv or args.draw_raw else None
     tracker = None       # --track: made at the first frame from the detection buffers' shape
 
     results, total, count = [], 0.0, 0

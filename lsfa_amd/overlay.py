@@ -1,11 +1,12 @@
-"""Detection overlay on torch tensors: the ctypes wrappers of lsfa_overlay_plan, lsfa_overlay_paint_bgr and lsfa_overlay_paint_yuv420
-(lsfa_amd/csrc/overlay.hip; include/lsfa_hip.h, "Detection overlay"), the glyphs they draw with, the palette and the YUV colour rows.  Built
-on lsfa_amd/hip.py's binding and checkers and under its rule: every tensor is validated before its pointer is taken, and there is no
+"""Detection overlay on torch tensors: the ctypes wrappers of lsfa_overlay_plan, lsfa_overlay_paint_bgr, lsfa_overlay_paint_yuv420 and
+lsfa_overlay_paint_yuv (lsfa_amd/csrc/overlay.hip; include/lsfa_hip.h, "Detection overlay"), the glyphs they draw with, the palette and
+the YUV colour rows.  Built on lsfa_amd/hip.py's binding and checkers and under its rule: every tensor is validated before its pointer is taken, and there is no
 fallback - a missing library or a refused call is an LsfaError.
 
 The detections stay where lsfa_det_postprocess(_batch) left them - dets (ncls, R, 5) float64 and counts (ncls) int32, or (N, ..) of a
 batch - and are burnt into a frame that is on the device already: packed BGR (H, W, 3) / (N, H, W, 3) uint8, or the 8-bit 4:2:0 planes
-the YUV intake takes (y and uv of NV12, or y, u and v of I420).  Row views of pitched surfaces are taken as they are: pitch and frame
+the YUV intake takes (y and uv of NV12, or y, u and v of I420), or - draw_yuv - the planes of any format of lsfa_amd/yuvfmt.py: 4:2:2,
+4:4:4, V before U, packed YUYV / UYVY, ten-bit words.  Row views of pitched surfaces are taken as they are: pitch and frame
 stride come from .stride().  Nothing is read back and nothing is allocated by a draw call, so the two launches can be captured in a graph.
 With ids=, the track ids lsfa_amd/tracks.py assigns, the plan is lsfa_overlay_plan_ids: one colour and one number per object.
 
@@ -14,7 +15,7 @@ rasteriser: no Hershey fonts, no anti-aliasing, and a fixed palette where the re
 import numpy as np
 import torch
 
-from lsfa_amd import hip
+from lsfa_amd import hip, yuvfmt
 from lsfa_amd.hip import LsfaError, _check, _ptr, _tensor
 
 REC_INTS = 16               # LSFA_OVERLAY_REC_INTS
@@ -223,6 +224,23 @@ class Overlay(object):
         _check(hip.lib().lsfa_overlay_paint_yuv420(*(args[:10] + (_ptr(self.records), _ptr(self.n), self.max_boxes, self.thickness, self.label_scale,
                                                                   _ptr(self._font), _ptr(self._yuv[matrix]), self.ncls, hip._stream()))),
                "lsfa_overlay_paint_yuv420")
+        return y
+
+    @hip._on_tensor_device
+    def draw_yuv(self, fmt, y, dets, counts, thresh, uv=None, u=None, v=None, matrix='bt601', ids=None, width=None):
+        """the planes of yuvfmt.yuv_to_bgr_u8 in any of its formats - `fmt` a name of yuvfmt.FORMATS or a code; uint8 planes, or int16 /
+        uint16 words of ten bits; a packed format's one plane as y, with `width` where W is odd - drawn into in place with the colours
+        converted by `matrix`.  A ten-bit surface takes the 8-bit colour as c << 2 (low ten bits) or c << 8 (high ten), the whole word
+        stored, so it reads back through the intake as the same BGR.  dets / counts / ids as draw_bgr.  Returns y."""
+        who = "Overlay.draw_yuv"
+        args, N, H, W, batched = yuvfmt._planes(who, fmt, y, uv, u, v, matrix, width)
+        if y.device != self.device:
+            raise LsfaError("%s: the planes are on %s, this Overlay on %s" % (who, y.device, self.device))
+        self._plan(who, N, batched, H, W, dets, counts, thresh, ids)
+        _check(hip.lib().lsfa_overlay_paint_yuv(*(args[:10] + (args[11], _ptr(self.records), _ptr(self.n), self.max_boxes, self.thickness,
+                                                               self.label_scale, _ptr(self._font), _ptr(self._yuv[matrix]), self.ncls,
+                                                               hip._stream()))),
+               "lsfa_overlay_paint_yuv")
         return y
 
     def drawn(self):

@@ -4,6 +4,8 @@ events, same process; profiles/r16/overlay_frontend.txt):
 
     plan + paint                   for BGR and NV12 at 1000x600 and 1920x1080 with 0, 30 and 300 recorded detections of 30 classes,
                                    launched eagerly and as a replayed graph of `reps` calls
+    plan + paint, other surfaces   Overlay.draw_yuv (lsfa_overlay_paint_yuv) for p010, yuyv422 and yuv444p - and for nv12, the same surface
+                                   through the new export - with the same detections, beside draw_yuv420's NV12 of the same run
     yuv420_to_bgr_u8               the shipped conversion at the same size: one full-frame pass to hold the overlay against
     one non-key frame              tools/me_frontend.py's non_key_frame at 1000x600, eager
 
@@ -23,12 +25,13 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from lsfa_amd import hip, overlay
+from lsfa_amd import hip, overlay, yuvfmt
 
 DEV = 'cuda:0'
 NCLS, ROWS = 31, 300
 SIZES = ((1000, 600), (1920, 1080))
 DETECTIONS = (0, 30, 300)
+OTHER_SURFACES = ('nv12', 'p010', 'yuyv422', 'yuv444p')          # through Overlay.draw_yuv
 
 
 def detections(n, W, H, seed=0):
@@ -44,6 +47,22 @@ def detections(n, W, H, seed=0):
     return torch.from_numpy(dets).to(DEV), torch.from_numpy(counts).to(DEV)
 
 
+def surface(fmt, W, H):
+    """the planes of one frame of format fmt as draw_yuv's keyword arguments, random samples"""
+    _, _, layout, sample = yuvfmt.fields(fmt)
+    ch, cw = yuvfmt.chroma_shape(fmt, H, W)
+
+    def plane(rows, cols):
+        if sample == yuvfmt.U8:
+            return torch.randint(0, 256, (rows, cols), dtype=torch.uint8, device=DEV)
+        return (torch.randint(0, 1024, (rows, cols), dtype=torch.int16, device=DEV) << (6 if sample == yuvfmt.HI10 else 0))
+    if layout >= yuvfmt.YUYV:
+        return dict(y=plane(H, 4 * cw), width=W)
+    if layout == yuvfmt.PLANAR:
+        return dict(y=plane(H, W), u=plane(ch, cw), v=plane(ch, cw))
+    return dict(y=plane(H, W), uv=plane(ch, 2 * cw))
+
+
 def forms(W, H):
     """[(name, fn)] of one size: the overlay per surface and detection count, and the conversion"""
     ch, cw = -(-H // 2), -(-W // 2)
@@ -52,6 +71,7 @@ def forms(W, H):
     bgr = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device=DEV)
     converted = torch.empty((H, W, 3), dtype=torch.uint8, device=DEV)
     out = [('yuv420_to_bgr_u8', lambda: hip.yuv420_to_bgr_u8(y, uv=uv, out=converted))]
+    others = {fmt: surface(fmt, W, H) for fmt in OTHER_SURFACES}
     for n in DETECTIONS:
         ov = overlay.Overlay(NCLS, ROWS, max_boxes=512, device=DEV)
         dets, counts = detections(n, W, H)
@@ -59,6 +79,9 @@ def forms(W, H):
         out.append(('nv12_%d' % n, lambda ov=ov, dets=dets, counts=counts: ov.draw_yuv420(y, dets, counts, 0.7, uv=uv)))
         out[-1][1]()
         assert int(ov.drawn()[0, 0]) == n, (n, ov.drawn())
+        for fmt in OTHER_SURFACES:
+            out.append(('%s_yuv_%d' % (fmt, n), lambda ov=ov, dets=dets, counts=counts, fmt=fmt, kw=others[fmt]: ov.draw_yuv(fmt, kw['y'], dets, counts, 0.7, **{
+                k: v for k, v in kw.items() if k != 'y'})))
     return out
 
 
@@ -132,6 +155,11 @@ def main():
                 goal['%s %s %s' % (size, k, how)] = dict(us=r[k][how]['median'], full_pass_us=full[how]['median'], spread_us=round(spread, 2),
                                                          met=bool(r[k][how]['median'] <= full[how]['median'] + spread))
     out['goal_no_detections_not_above_the_full_frame_pass_beyond_spread'] = goal
+    # every other surface over draw_yuv420's NV12 of this run (the paint kernel of lsfa_overlay_paint_yuv420 is untouched by the new export)
+    out['other_surfaces_over_nv12'] = {
+        size: {'%s_yuv_%d' % (fmt, n): {how: round(out[size]['%s_yuv_%d' % (fmt, n)][how]['median'] / out[size]['nv12_%d' % n][how]['median'], 3)
+                                        for how in ('graph', 'eager')} for fmt in OTHER_SURFACES for n in DETECTIONS}
+        for size in ('%dx%d' % s for s in SIZES)}
     print(json.dumps(out, indent=1))
 
 
